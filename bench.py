@@ -2,6 +2,8 @@
 """Headline benchmark: warped+composited frames/sec at 256x512, 8 layers, fwd+bwd.
 
     python bench.py --gpus 1 --steps 100 --warmup 10           # config C3, the headline
+    python bench.py --gpus 1 --steps 100 --warmup 10 --full    # ... with roofline, variants and CPU baseline
+    python bench.py --steps 20 --warmup 5 --dump-outputs DIR   # ... and the last step's outputs as DIR/*.npy
     python bench.py --config C5                                # the other BASELINE.json configs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -30,14 +32,22 @@ metric string:
   (--pipeline with C4 / C5: Synthesizer.predict's hot-path calls on whole clips instead of the synthetic forward)
 
 Timing protocol of every workload: a time-based settle (>= 0.3 s of the step, `settle_ms`) before the --warmup steps,
-then FIVE blocks of exactly --steps steps, each bracketed by barrier + synchronize; `ms_per_step` is the MEDIAN block
-(`ms_per_step_blocks` lists all five, max over ranks each); the per-kernel event pairs are taken in a separate pass
-afterwards, so the timed blocks carry no events.
+then ONE block of exactly --steps steps, bracketed by barrier + synchronize; `ms_per_step` is that block's time per
+step (max over ranks).  A plain run does nothing else: it sets up, warms up, times the --steps steps, writes the outputs
+(--dump-outputs) and prints the headline line.
 
-With --gpus N > 1 and the default workload the line carries a `north_star` object (the RCCL all-gather of composited
-frames, the C5 pipeline as ONE job split over the N ranks, a cross-rank bit-equality check): see north_star_block.
+--full adds everything beyond the headline, as before: FIVE blocks of exactly --steps steps, `ms_per_step` the MEDIAN
+block (`ms_per_step_blocks` lists all five, max over ranks each), and the figures that take passes of their own -- the
+per-kernel event pairs (taken in a separate pass afterwards, so the timed blocks carry no events), the roofline, the
+HIP-graph / loss-gradient / decode variants beside the headline, the CPU baseline and, with --gpus N > 1 and the
+default workload, a `north_star` object (the RCCL all-gather of composited frames, the C5 pipeline as ONE job split over
+the N ranks, a cross-rank bit-equality check): see north_star_block.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+--dump-outputs DIR writes what the timed path handed its caller in the LAST timed step (the composited frames, the
+loss and the gradients of a training step) as DIR/<name>.npy in float32, at most 64 MB in all (dump_outputs: a fixed,
+seeded sample of a larger array).  The inputs are seeded: the same arguments give the same inputs on every run.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it carries two extra objects:
   roofline      dominant kernel, algorithmic bytes per launch / mean launch duration measured live
                 with events on the launch stream, against the 8 TB/s HBM3E peak
   cpu_baseline  the oracle (a PyTorch-CPU restatement of the reference path, oracle/wif_oracle.py)
@@ -315,8 +325,36 @@ CONFIGS = {
     "WIF": (2, 5, 17, 512, 1024, "wif"),
 }
 
-TIMED_BLOCKS = 5       # blocks of --steps steps; the median block is the line's ms_per_step
+TIMED_BLOCKS = 5       # --full: blocks of --steps steps; the median block is the line's ms_per_step
 SETTLE_SECONDS = 0.3   # of the step itself, before the --warmup steps (a cold box: clocks, caches, allocator)
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: every array of the dump together, .npy headers included
+
+
+def timed_block_count(args):
+    """A plain run times ONE block of exactly --steps steps; --full the median of TIMED_BLOCKS."""
+    return TIMED_BLOCKS if args.full else 1
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> tensor: what the timed path handed its caller in its last step) as
+    out_dir/<name>.npy, float32 (float64 stays float64).  Each array gets an equal share of DUMP_BYTES; one larger than
+    its share is written as a fixed sample -- its elements at flat indices drawn, sorted, from a CPU generator seeded
+    with 0 -- so that the same arguments sample the same elements on every run and two builds compare element for
+    element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BYTES - 4096 * len(arrays)) // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            arr = t.reshape(-1)[idx.to(t.device)].cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def settle_interpreter():
@@ -369,6 +407,10 @@ def median_block(blocks):
 
 
 def block_fields(blocks, steps, settle_ms):
+    if len(blocks) == 1:  # a plain run
+        return {"settle_ms": settle_ms,
+                "timing": f"one block of {steps} steps (bracketed by barrier + synchronize, max over ranks), after "
+                          f"{settle_ms} ms of settling and the warm-up steps"}
     return {"ms_per_step_blocks": [round(b / steps * 1e3, 4) for b in blocks], "settle_ms": settle_ms,
             "timing": f"median of {len(blocks)} blocks of {steps} steps (each bracketed by barrier + synchronize, max over "
                       f"ranks), after {settle_ms} ms of settling and the warm-up steps; per-kernel events in a separate pass"}
@@ -436,8 +478,8 @@ def main():
     ap.add_argument("--lib", default=None, help="A/B timing: another build of the library (tools_dev/build_variant.py)")
     ap.add_argument("--north-star", choices=["auto", "on", "off"], default="auto",
                     help="append the `north_star` object (all-gather of composited frames over the ranks, the C5 pipeline "
-                         "as ONE job split over them, cross-rank bit-equality) to the default workload's line; auto: when "
-                         "--gpus > 1")
+                         "as ONE job split over them, cross-rank bit-equality) to the default workload's line; auto: with "
+                         "--full and --gpus > 1")
     ap.add_argument("--north-star-config", choices=["C4", "C5"], default="C5",
                     help="recipe of the north_star block's pipeline job (C5 = Cityscapes 512x1024, the north star's)")
     ap.add_argument("--fresh-inputs-per-block", action="store_true",
@@ -449,6 +491,13 @@ def main():
                          "runs of this command (FETCH_SIZE, WRITE_SIZE: ~40 s)")
     ap.add_argument("--cpu-frames", type=int, default=28)
     ap.add_argument("--cpu-reps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: five timed blocks (median), per-kernel table, roofline, the "
+                         "variants beside the headline, CPU baseline, north_star (--gpus > 1); a plain run times one "
+                         "block of --steps steps and prints the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32, at most "
+                         "64 MB in all: a fixed, seeded sample of a larger output)")
     args = ap.parse_args()
     c_clips, c_fpc, c_nl, c_h, c_w, c_mode = CONFIGS[args.config]
     clips = args.clips if args.clips is not None else c_clips
@@ -525,10 +574,12 @@ def main():
     def square_mean(rgb):  # the loss exactly as SURVEY 8(d) writes it: autograd's own gradient chain
         return rgb.square().mean()
 
+    last = {}  # what the last step handed its caller (--dump-outputs)
+
     def step(loss=None):
         if mode == "fwd":
             with torch.no_grad():
-                graphed(*graphed.inputs)  # the graph's own static buffers: no input copy in the step
+                last["rgb"] = graphed(*graphed.inputs)  # the graph's own static buffers: no input copy in the step
             return
         if mode == "infer":
             with torch.no_grad():
@@ -536,11 +587,14 @@ def main():
                 prev, pending[0] = pending[0], all_gather_frames_async(rgb, frames * world)
                 if prev is not None:
                     prev.wait()
+            last["rgb"] = rgb
             return
         layers.grad = None
         pts.grad = None
         rgb = WF.warp_composite(layers, pts, occ, tps.inverse_kernel, tps.basis_t)
-        (loss or square_mean)(rgb).backward()
+        out = (loss or square_mean)(rgb)
+        out.backward()
+        last["rgb"], last["loss"] = rgb.detach(), out.detach()
 
     def fence():
         if pending[0] is not None:  # every gather started inside a timed region ends inside it
@@ -579,62 +633,67 @@ def main():
     settle_ms = settle_gpu(step, fence)
     for _ in range(args.warmup):
         step()
-    blocks = timed_blocks(step, fence, args.steps, dist, device, args.dist_backend,
+    blocks = timed_blocks(step, fence, args.steps, dist, device, args.dist_backend, nblocks=timed_block_count(args),
                           between=fresh_inputs if args.fresh_inputs_per_block else None)
     elapsed = median_block(blocks)
-    # the same step with the loss gradient 2 * rgb / N written as ONE elementwise kernel (_SquareMean) instead of
-    # autograd's four-pass chain: reported next to the headline, never as it
-    loss_variants = None
-    if mode == "train" and world == 1:
-        n = max(5, min(args.steps, 20))
-        for _ in range(2):
-            step(loss=_SquareMean.apply)
-        one_pass = sorted(timed(n, loss=_SquareMean.apply) / n for _ in range(3))[1]
-        loss_variants = {"autograd_loss_ms_per_step": round(elapsed / args.steps * 1e3, 4),
-                         "one_pass_loss_gradient_ms_per_step": round(one_pass * 1e3, 4),
-                         "note": "value / ms_per_step use out.square().mean().backward() as it is written in SURVEY "
-                                 "8(d); the second line is the same step with the loss gradient 2*rgb/N in one "
-                                 "elementwise pass (bench.py:_SquareMean, same numbers; median of 3 short blocks)"}
-    # per-entry-point device times from a SEPARATE pass (event pairs on the launch stream around every C-ABI call):
-    # the timed blocks above carry no events
-    n_events = max(5, min(args.steps, 20))
-    with _lib.KernelTimer() as kt:
-        timed(n_events)
+    if args.dump_outputs and rank == 0:
+        outputs = dict(last)
+        if mode == "train":
+            outputs.update(grad_layers=layers.grad, grad_pts=pts.grad)
+        dump_outputs(args.dump_outputs, outputs)
+    loss_variants = launch_split = None
+    if args.full:
+        # the same step with the loss gradient 2 * rgb / N written as ONE elementwise kernel (_SquareMean) instead of
+        # autograd's four-pass chain: reported next to the headline, never as it
+        if mode == "train" and world == 1:
+            n = max(5, min(args.steps, 20))
+            for _ in range(2):
+                step(loss=_SquareMean.apply)
+            one_pass = sorted(timed(n, loss=_SquareMean.apply) / n for _ in range(3))[1]
+            loss_variants = {"autograd_loss_ms_per_step": round(elapsed / args.steps * 1e3, 4),
+                             "one_pass_loss_gradient_ms_per_step": round(one_pass * 1e3, 4),
+                             "note": "value / ms_per_step use out.square().mean().backward() as it is written in SURVEY "
+                                     "8(d); the second line is the same step with the loss gradient 2*rgb/N in one "
+                                     "elementwise pass (bench.py:_SquareMean, same numbers; median of 3 short blocks)"}
+        # per-entry-point device times from a SEPARATE pass (event pairs on the launch stream around every C-ABI call):
+        # the timed blocks above carry no events
+        n_events = max(5, min(args.steps, 20))
+        with _lib.KernelTimer() as kt:
+            timed(n_events)
 
-    # launch-bound shapes: what part of a replay is kernel, what part the floor of launching a graph
-    launch_split = None
-    if mode == "fwd" and world == 1:
-        n = max(args.steps, 50)
-        tiny = GraphedCall(lambda t: t.add_(1.0), torch.zeros(64, device=device))
-        tiny(*tiny.inputs)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(n):
+        # launch-bound shapes: what part of a replay is kernel, what part the floor of launching a graph
+        if mode == "fwd" and world == 1:
+            n = max(args.steps, 50)
+            tiny = GraphedCall(lambda t: t.add_(1.0), torch.zeros(64, device=device))
             tiny(*tiny.inputs)
-        fence()
-        floor_us = (time.perf_counter() - t0) / n * 1e6
-        reps_in_graph = 16
-        many = GraphedCall(lambda l, p, o: [WF.warp_composite(l, p, o, tps.inverse_kernel, tps.basis_t)
-                                            for _ in range(reps_in_graph)][-1], layers, pts, occ)
-        many(*many.inputs)
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(n):
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                tiny(*tiny.inputs)
+            fence()
+            floor_us = (time.perf_counter() - t0) / n * 1e6
+            reps_in_graph = 16
+            many = GraphedCall(lambda l, p, o: [WF.warp_composite(l, p, o, tps.inverse_kernel, tps.basis_t)
+                                                for _ in range(reps_in_graph)][-1], layers, pts, occ)
             many(*many.inputs)
-        fence()
-        many_us = (time.perf_counter() - t0) / n * 1e6
-        kernel_us = (many_us - floor_us) / reps_in_graph
-        alg_fwd = (16 * nl + 12) * h * w * frames
-        launch_split = {"replay_us": round(elapsed / args.steps * 1e6, 2),
-                        "empty_graph_replay_us": round(floor_us, 2),
-                        "kernel_us": round(kernel_us, 2),
-                        # the roofline fraction on either clock: a whole replay (what `roofline.frac` uses) and the
-                        # kernel without the per-replay launch floor
-                        "frac_replay": round(alg_fwd / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                        "frac_kernel": round(alg_fwd / (kernel_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
-                        "note": f"empty graph = one 64-element add; kernel_us = (replay of a graph of {reps_in_graph} "
-                                "forwards - empty-graph replay) / 16: the forward kernel with its in-graph dependency "
-                                "boundary, without the per-replay launch floor"}
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                many(*many.inputs)
+            fence()
+            many_us = (time.perf_counter() - t0) / n * 1e6
+            kernel_us = (many_us - floor_us) / reps_in_graph
+            alg_fwd = (16 * nl + 12) * h * w * frames
+            launch_split = {"replay_us": round(elapsed / args.steps * 1e6, 2),
+                            "empty_graph_replay_us": round(floor_us, 2),
+                            "kernel_us": round(kernel_us, 2),
+                            # the roofline fraction on either clock: a whole replay (what `roofline.frac` uses) and the
+                            # kernel without the per-replay launch floor
+                            "frac_replay": round(alg_fwd / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                            "frac_kernel": round(alg_fwd / (kernel_us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4),
+                            "note": f"empty graph = one 64-element add; kernel_us = (replay of a graph of {reps_in_graph} "
+                                    "forwards - empty-graph replay) / 16: the forward kernel with its in-graph dependency "
+                                    "boundary, without the per-replay launch floor"}
 
     out = None
     if rank == 0:
@@ -642,63 +701,67 @@ def main():
         total_frames = frames * world
         value = total_frames / (elapsed / args.steps)
         hw = h * w
-        alg = {"waldo_warp_composite_fwd": (16 * nl + 12) * hw * frames,
-               "waldo_warp_composite_bwd": (32 * nl + 12) * hw * frames}
-        if mode != "train":
-            alg.pop("waldo_warp_composite_bwd")
-        if mode == "fwd":
-            # inside a graph the per-call events are not recorded: the replay time is the kernel
-            # time plus the graph's launch floor
-            ks = {"waldo_warp_composite_fwd": (args.steps, ms_per_step)}
-        else:
-            ks = kt.summary()  # (from the separate events pass)
-            # without autograd the forward is the one-launch entry point from the control points
-            # (same kernel, mapping folded in): reported under the forward's name
-            if "waldo_warp_composite_pts_fwd" in ks and "waldo_warp_composite_fwd" not in ks:
-                ks["waldo_warp_composite_fwd"] = ks.pop("waldo_warp_composite_pts_fwd")
-        dom = max(alg, key=lambda k: ks[k][1])
-        kern = {}
-        for k in alg:
-            gbs = alg[k] / (ks[k][1] * 1e-3) / 1e9
-            kern[k] = {"launches": ks[k][0], "ms": round(ks[k][1], 4), "alg_bytes": alg[k],
-                       "GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
-        # HBM-side bytes per launch: measured by two rocprofv3 --pmc children of this very command (the default workload
-        # on one GPU), else from the committed passes of the same command (profiles/traffic.json)
-        live, live_note = None, None
-        if args.config == "C3" and not custom and world == 1 and not args.no_live_traffic:
-            try:
-                live = live_traffic(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic"])
-            except Exception as exc:  # (the line stands on the committed passes)
-                live_note = f"live passes failed ({type(exc).__name__}: {str(exc)[:200]})"
+        roof = None
+        if args.full:
+            alg = {"waldo_warp_composite_fwd": (16 * nl + 12) * hw * frames,
+                   "waldo_warp_composite_bwd": (32 * nl + 12) * hw * frames}
+            if mode != "train":
+                alg.pop("waldo_warp_composite_bwd")
+            if mode == "fwd":
+                # inside a graph the per-call events are not recorded: the replay time is the kernel
+                # time plus the graph's launch floor
+                ks = {"waldo_warp_composite_fwd": (args.steps, ms_per_step)}
+            else:
+                ks = kt.summary()  # (from the separate events pass)
+                # without autograd the forward is the one-launch entry point from the control points
+                # (same kernel, mapping folded in): reported under the forward's name
+                if "waldo_warp_composite_pts_fwd" in ks and "waldo_warp_composite_fwd" not in ks:
+                    ks["waldo_warp_composite_fwd"] = ks.pop("waldo_warp_composite_pts_fwd")
+            dom = max(alg, key=lambda k: ks[k][1])
+            kern = {}
+            for k in alg:
+                gbs = alg[k] / (ks[k][1] * 1e-3) / 1e9
+                kern[k] = {"launches": ks[k][0], "ms": round(ks[k][1], 4), "alg_bytes": alg[k],
+                           "GBps": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4)}
+            # HBM-side bytes per launch: measured by two rocprofv3 --pmc children of this very command (the default
+            # workload on one GPU), else from the committed passes of the same command (profiles/traffic.json)
+            live, live_note = None, None
+            if args.config == "C3" and not custom and world == 1 and not args.no_live_traffic:
+                try:
+                    live = live_traffic(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic"])
+                except Exception as exc:  # (the line stands on the committed passes)
+                    live_note = f"live passes failed ({type(exc).__name__}: {str(exc)[:200]})"
 
-        def moved_bytes(k):
-            return live[k] if live and live.get(k) else measured_traffic(k, frames, nl, h, w)
+            def moved_bytes(k):
+                return live[k] if live and live.get(k) else measured_traffic(k, frames, nl, h, w)
 
-        traffic = moved_bytes(dom)
-        copy_gbs = copy_bandwidth(device)  # measured D2D copy rate of this box (read + write bytes per second)
-        for k in kern:
-            # next to the fraction of the 8 TB/s spec: the fraction of what a copy kernel reaches on THIS box, and what
-            # the entry point really moved
-            kern[k]["frac_of_copy"] = round(kern[k]["GBps"] / copy_gbs, 4)
-            moved = moved_bytes(k)
-            if moved:
-                kern[k]["moved_bytes"] = int(moved)
-                kern[k]["moved_over_alg"] = round(moved / alg[k], 3)
-                kern[k]["moved_GBps"] = round(moved / (kern[k]["ms"] * 1e-3) / 1e9, 1)
-                kern[k]["moved_frac_of_copy"] = round(kern[k]["moved_GBps"] / copy_gbs, 4)
-        roof = {"bound": "hbm", "kernel": dom, "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": kern[dom]["frac"], "traffic": traffic,
-                "traffic_source": (("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE, two child runs of this "
-                                    "command in this run (FETCH_SIZE x2: gfx950 tallies 128-byte requests at 64 bytes; "
-                                    "KiB -> bytes), mean per dispatch, summed over the entry point's kernels") if live else
-                                   ("profiles/traffic.json: rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this workload, "
-                                    "committed; not re-measured in this run" + (": " + live_note if live_note else "")))
-                if traffic else None,
-                "ms_per_launch": kern[dom]["ms"], "alg_bytes_per_launch": alg[dom],
-                "kernels": kern}
-        roof["copy_GBps"] = round(copy_gbs, 1)
-        roof["frac_of_copy"] = kern[dom]["frac_of_copy"]
-        roof["guide_copy_GBps"] = 6290.0  # MI355X_MICROARCH.md: float4 device copy; this pool's boxes reach 4.7-5.1 TB/s
+            traffic = moved_bytes(dom)
+            copy_gbs = copy_bandwidth(device)  # measured D2D copy rate of this box (read + write bytes per second)
+            for k in kern:
+                # next to the fraction of the 8 TB/s spec: the fraction of what a copy kernel reaches on THIS box, and
+                # what the entry point really moved
+                kern[k]["frac_of_copy"] = round(kern[k]["GBps"] / copy_gbs, 4)
+                moved = moved_bytes(k)
+                if moved:
+                    kern[k]["moved_bytes"] = int(moved)
+                    kern[k]["moved_over_alg"] = round(moved / alg[k], 3)
+                    kern[k]["moved_GBps"] = round(moved / (kern[k]["ms"] * 1e-3) / 1e9, 1)
+                    kern[k]["moved_frac_of_copy"] = round(kern[k]["moved_GBps"] / copy_gbs, 4)
+            roof = {"bound": "hbm", "kernel": dom, "achieved": kern[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": kern[dom]["frac"], "traffic": traffic,
+                    "traffic_source": (("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE, two child runs of "
+                                        "this command in this run (FETCH_SIZE x2: gfx950 tallies 128-byte requests at "
+                                        "64 bytes; KiB -> bytes), mean per dispatch, summed over the entry point's "
+                                        "kernels") if live else
+                                       ("profiles/traffic.json: rocprofv3 FETCH_SIZE / WRITE_SIZE passes of this "
+                                        "workload, committed; not re-measured in this run"
+                                        + (": " + live_note if live_note else "")))
+                    if traffic else None,
+                    "ms_per_launch": kern[dom]["ms"], "alg_bytes_per_launch": alg[dom],
+                    "kernels": kern}
+            roof["copy_GBps"] = round(copy_gbs, 1)
+            roof["frac_of_copy"] = kern[dom]["frac_of_copy"]
+            roof["guide_copy_GBps"] = 6290.0  # the MI355X float4 device-copy figure; measured boxes reach 4.7-5.1 TB/s
         what = {"train": "fwd+bwd", "infer": "fwd only + all-gather", "fwd": "fwd only (HIP-graph replay)"}[mode]
         if args.config == "C3" and not custom:
             metric = "warped+composited frames/sec at 256x512, 8 layers; fwd+bwd"
@@ -718,8 +781,9 @@ def main():
                                       + ("one all-gather of the composited frames per step, overlapped with the next "
                                          "step's kernels" if mode == "infer"
                                          else "no data-path collective")},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         out.update(block_fields(blocks, args.steps, settle_ms))
         if loss_variants is not None:
             out["loss_variants"] = loss_variants
@@ -727,8 +791,9 @@ def main():
                 total_frames / (loss_variants["one_pass_loss_gradient_ms_per_step"] * 1e-3), 2)
         if launch_split is not None:
             out["launch_split"] = launch_split
-    # the north star's multi-GPU evidence rides on the default command's line (the driver's scaling run passes no flags)
-    want_ns = args.north_star == "on" or (args.north_star == "auto" and world > 1 and args.config == "C3" and not custom)
+    # the north star's multi-GPU evidence rides on the default workload's --full line
+    want_ns = args.north_star == "on" or (args.north_star == "auto" and args.full and world > 1 and args.config == "C3"
+                                           and not custom)
     if want_ns and dist is not None:
         del layers, pts, occ
         torch.cuda.empty_cache()
@@ -738,7 +803,7 @@ def main():
         if rank == 0:
             out["north_star"] = ns
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nl, h, w, min(args.cpu_frames, max(1, 28 * 131072 // hw)),
                                                args.cpu_reps)
         print(json.dumps(out), flush=True)
@@ -921,13 +986,29 @@ def run_lvd(args, clips, world, rank, device, dist):
             dist.barrier()
         torch.cuda.synchronize()
 
+    names = ("raw", "pose_o", "pose_b", "score", "cls_logit")  # step.leaves, in order
+    last = {}
+
+    def run():  # the step, keeping the loss it hands its caller (--dump-outputs); detached: a loss that kept the
+        last["loss"] = step().detach()  # autograd graph alive would keep its AccumulateGrad nodes on this stream
+
+    def dump():  # what the headline's last timed step computed: the loss and the leaves' gradients
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, dict(loss=last["loss"], **{"grad_" + n: x.grad
+                                                                       for n, x in zip(names, step.leaves)}))
+
     for _ in range(3):  # (the interpreter settles first: its full collection is a pause of the launch queue)
         step()
     settle_interpreter()
     settle_ms = settle_gpu(step, fence)
     for _ in range(args.warmup):
         step()
-    blocks_eager = timed_blocks(step, fence, args.steps, dist, device, args.dist_backend)
+    nblocks = timed_block_count(args)
+    blocks_eager = None
+    if args.full or not args.graph:
+        blocks_eager = timed_blocks(run, fence, args.steps, dist, device, args.dist_backend, nblocks=nblocks)
+        if not args.graph:
+            dump()
     # forward, loss and backward captured ONCE and replayed (the library launches on the current stream and never
     # synchronises; the frame indices are validated by the kernels, in a replay as in an eager call).  The step is ~90
     # short launches behind ~1.6 ms of interpreter and autograd-engine time per step: eager, it runs at the speed of the
@@ -935,44 +1016,48 @@ def run_lvd(args, clips, world, rank, device, dist):
     # them.  A capture that fails leaves the eager line standing (`--graph` then reports the failure as its ms_per_step
     # note); a hard GPU fault is not catchable in-process: the eager blocks above have been timed by then.
     blocks_graph, graph_note = None, None
-    try:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            step()
-        settle_gpu(graph.replay, fence)
-        blocks_graph = timed_blocks(graph.replay, fence, args.steps, dist, device, args.dist_backend)
-        _lib.IndexStatus.check_all(sync=True)
-    except Exception as exc:
-        graph_note = f"capture failed: {type(exc).__name__}: {exc}"
+    if args.full or args.graph:
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    step()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                graph_loss = step()
+            settle_gpu(graph.replay, fence)
+            blocks_graph = timed_blocks(graph.replay, fence, args.steps, dist, device, args.dist_backend,
+                                        nblocks=nblocks)
+            _lib.IndexStatus.check_all(sync=True)
+            if args.graph:
+                last["loss"] = graph_loss.detach()
+                dump()
+        except Exception as exc:
+            graph_note = f"capture failed: {type(exc).__name__}: {exc}"
+    if blocks_eager is None and blocks_graph is None:  # a plain --graph run whose capture failed: the eager line
+        blocks_eager = timed_blocks(run, fence, args.steps, dist, device, args.dist_backend, nblocks=nblocks)
+        dump()
     use_graph = args.graph and blocks_graph is not None
     blocks = blocks_graph if use_graph else blocks_eager
     elapsed = median_block(blocks)
-    elapsed_eager = median_block(blocks_eager)
-    elapsed_graph = median_block(blocks_graph) if blocks_graph is not None else None
-    grads_ok = step.grads_finite()
-    # the per-entry-point table from a SECOND, untimed pass: a step is ~250 short launches queued ahead of the GPU,
-    # and two event records around each of its ~70 library calls make the host the bottleneck (3.7 ms against 2.1)
-    n_table = max(3, min(args.steps, 10))
-    with _lib.KernelTimer() as kt:
-        for _ in range(n_table):
-            step()
-        fence()
+    if args.full:
+        elapsed_eager = median_block(blocks_eager)
+        elapsed_graph = median_block(blocks_graph) if blocks_graph is not None else None
+        grads_ok = step.grads_finite()
+        # the per-entry-point table from a SECOND, untimed pass: a step is ~250 short launches queued ahead of the GPU,
+        # and two event records around each of its ~70 library calls make the host the bottleneck (3.7 ms against 2.1)
+        n_table = max(3, min(args.steps, 10))
+        with _lib.KernelTimer() as kt:
+            for _ in range(n_table):
+                step()
+            fence()
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        table = {}
-        for name, (n, ms) in sorted(kt.summary().items(), key=lambda kv: -kv[1][0] * kv[1][1]):
-            table[name] = {"launches_per_step": round(n / n_table, 2), "ms_per_step": round(n * ms / n_table, 4)}
-        in_lib = sum(r["ms_per_step"] for r in table.values())
         o, t = step.opt, step.frames
         h, w = o.dim, int(o.dim * o.aspect_ratio)
-        dom = next(iter(table))
         out = {
             "metric": f"LVD training-step frames/sec through the warp path at {h}x{w}, {o.num_obj + 1} layers, "
                       f"{t}-frame clips; fwd+bwd (the reference's live backward path; not the headline metric)",
@@ -985,21 +1070,31 @@ def run_lvd(args, clips, world, rank, device, dist):
                                    f"-> loss -> backward; the networks outside the path replaced by seeded leaves",
                        "frames_per_gpu": clips * t, "layers": o.num_obj + 1, "height": h, "width": w,
                        "parallelism": f"clips sharded x{world}, no data-path collective"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": None, "traffic": None,
-                         "note": "a chain of ~35 latency- and atomics-bound launches on 63 MB of grids and 22 MB of "
-                                 "alphas: no single kernel's algorithmic bytes describe it; per-kernel counters in "
-                                 "profiles/r04_lvd_step_counters.txt", "ms_per_launch": table[dom]["ms_per_step"]},
-            "pipeline": {"ms_in_library_calls": round(in_lib, 4), "ms_outside": round(ms_per_step - in_lib, 4),
-                         "note": "per C-ABI entry point, event pairs on the launch stream, from a second untimed pass; "
-                                 "ms_outside = autograd's own kernels (gradient accumulation, fills, the loss) and "
-                                 "launch gaps",
-                         "entry_points": table},
-            "grads_finite": grads_ok,
-            "launch": "the whole step (forward, loss, backward) replayed from one HIP graph" if use_graph else "eager",
-            "ms_per_step_eager": round(elapsed_eager / args.steps * 1e3, 4),
-            "ms_per_step_graph_replay": round(elapsed_graph / args.steps * 1e3, 4) if elapsed_graph is not None else graph_note,
         }
+        if args.full:
+            table = {}
+            for name, (n, ms) in sorted(kt.summary().items(), key=lambda kv: -kv[1][0] * kv[1][1]):
+                table[name] = {"launches_per_step": round(n / n_table, 2), "ms_per_step": round(n * ms / n_table, 4)}
+            in_lib = sum(r["ms_per_step"] for r in table.values())
+            dom = next(iter(table))
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": None, "traffic": None,
+                             "note": "a chain of ~35 latency- and atomics-bound launches on 63 MB of grids and 22 MB of "
+                                     "alphas: no single kernel's algorithmic bytes describe it; per-kernel counters in "
+                                     "profiles/r04_lvd_step_counters.txt", "ms_per_launch": table[dom]["ms_per_step"]},
+                "pipeline": {"ms_in_library_calls": round(in_lib, 4), "ms_outside": round(ms_per_step - in_lib, 4),
+                             "note": "per C-ABI entry point, event pairs on the launch stream, from a second untimed "
+                                     "pass; ms_outside = autograd's own kernels (gradient accumulation, fills, the loss) "
+                                     "and launch gaps",
+                             "entry_points": table},
+                "grads_finite": grads_ok})
+        out["launch"] = ("the whole step (forward, loss, backward) replayed from one HIP graph" if use_graph
+                         else "eager" + (f" ({graph_note})" if args.graph and graph_note else ""))
+        if args.full:
+            out["ms_per_step_eager"] = round(elapsed_eager / args.steps * 1e3, 4)
+            out["ms_per_step_graph_replay"] = (round(elapsed_graph / args.steps * 1e3, 4) if elapsed_graph is not None
+                                               else graph_note)
         out.update(block_fields(blocks, args.steps, settle_ms))
         print(json.dumps(out), flush=True)
     if dist is not None:
@@ -1025,40 +1120,39 @@ def run_wif(args, clips, world, rank, device, dist):
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = {}
+
+    def run():  # the step, keeping the loss it hands its caller (--dump-outputs); detached: a loss that kept the
+        last["loss"] = step().detach()  # autograd graph alive would keep its AccumulateGrad nodes on this stream
+
     for _ in range(3):  # (the interpreter settles first: its full collection is a pause of the launch queue)
         step()
     settle_interpreter()
     settle_ms = settle_gpu(step, fence)
     for _ in range(args.warmup):
         step()
-    blocks = timed_blocks(step, fence, args.steps, dist, device, args.dist_backend)
+    blocks = timed_blocks(run, fence, args.steps, dist, device, args.dist_backend, nblocks=timed_block_count(args))
     elapsed = median_block(blocks)
-    # the no-grad half alone (what `inpaint` computes before net_ii): its share of the step
-    decode_blocks = timed_blocks(step.decode, fence, max(3, args.steps // 2), dist, device, args.dist_backend, nblocks=3)
-    decode_ms = median_block(decode_blocks) / max(3, args.steps // 2) * 1e3
-    grads_ok = step.grads_finite()
+    if args.dump_outputs and rank == 0:  # the loss, the stand-in network's gradients and the decode WIF fused
+        outputs = {"loss": last["loss"], "raw_output": step.raw_output}
+        outputs.update({"grad_unet_" + n.replace(".", "_"): p.grad for n, p in step.unet.named_parameters()})
+        dump_outputs(args.dump_outputs, outputs)
     step.warper.check_time_indices()
-    n_table = max(3, min(args.steps, 10))
-    with _lib.KernelTimer() as kt:
-        for _ in range(n_table):
-            step()
-        fence()
+    if args.full:
+        # the no-grad half alone (what `inpaint` computes before net_ii): its share of the step
+        decode_blocks = timed_blocks(step.decode, fence, max(3, args.steps // 2), dist, device, args.dist_backend,
+                                     nblocks=3)
+        decode_ms = median_block(decode_blocks) / max(3, args.steps // 2) * 1e3
+        grads_ok = step.grads_finite()
+        n_table = max(3, min(args.steps, 10))
+        with _lib.KernelTimer() as kt:
+            for _ in range(n_table):
+                step()
+            fence()
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        alg = step.hd_algorithmic_bytes()
-        table = {}
-        for name, (n, ms) in sorted(kt.summary().items(), key=lambda kv: -kv[1][0] * kv[1][1]):
-            per_step = n * ms / n_table
-            row = {"launches_per_step": round(n / n_table, 2), "ms_per_step": round(per_step, 4)}
-            if name in alg:
-                row["alg_bytes_per_step"] = alg[name]
-                row["GBps"] = round(alg[name] / (per_step * 1e-3) / 1e9, 1)
-                row["frac"] = round(row["GBps"] / HBM_PEAK_GBS, 4)
-            table[name] = row
-        in_lib = sum(r["ms_per_step"] for r in table.values())
         o, t = step.opt, step.frames
         hd, wd = step.vid.shape[-2:]
-        dom = max((k for k in alg if k in table), key=lambda k: table[k]["ms_per_step"])
         out = {
             "metric": f"WIF training-step frames/sec at {hd}x{wd}, {o.num_obj + 1} layers, {t}-frame clips ({step.ctx_len} "
                       f"context + {t - step.ctx_len} predicted); warp path forward under no_grad + WIF.forward/backward, as "
@@ -1075,18 +1169,32 @@ def run_wif(args, clips, world, rank, device, dist):
                                    f"background motion '{args.motion}'",
                        "frames_per_gpu": clips * t, "layers": o.num_obj + 1, "height": hd, "width": wd,
                        "parallelism": f"clips sharded x{world}, no data-path collective"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": table[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": table[dom]["frac"], "traffic": None,
-                         "alg_bytes_per_launch": alg[dom], "ms_per_launch": table[dom]["ms_per_step"]},
-            "pipeline": {"ms_in_library_calls": round(in_lib, 4), "ms_outside": round(ms_per_step - in_lib, 4),
-                         "ms_no_grad_decode": round(decode_ms, 4),
-                         "note": "per C-ABI entry point, event pairs on the launch stream, from a second untimed pass; "
-                                 "ms_outside = framework kernels (the cat of frames and layouts, the stand-in "
-                                 "convolution forward + weight gradient, the loss) and launch gaps; ms_no_grad_decode = "
-                                 "the step's first half alone (everything before net_ii)",
-                         "entry_points": table},
-            "grads_finite": grads_ok,
         }
+        if args.full:
+            alg = step.hd_algorithmic_bytes()
+            table = {}
+            for name, (n, ms) in sorted(kt.summary().items(), key=lambda kv: -kv[1][0] * kv[1][1]):
+                per_step = n * ms / n_table
+                row = {"launches_per_step": round(n / n_table, 2), "ms_per_step": round(per_step, 4)}
+                if name in alg:
+                    row["alg_bytes_per_step"] = alg[name]
+                    row["GBps"] = round(alg[name] / (per_step * 1e-3) / 1e9, 1)
+                    row["frac"] = round(row["GBps"] / HBM_PEAK_GBS, 4)
+                table[name] = row
+            in_lib = sum(r["ms_per_step"] for r in table.values())
+            dom = max((k for k in alg if k in table), key=lambda k: table[k]["ms_per_step"])
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": table[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": table[dom]["frac"], "traffic": None,
+                             "alg_bytes_per_launch": alg[dom], "ms_per_launch": table[dom]["ms_per_step"]},
+                "pipeline": {"ms_in_library_calls": round(in_lib, 4), "ms_outside": round(ms_per_step - in_lib, 4),
+                             "ms_no_grad_decode": round(decode_ms, 4),
+                             "note": "per C-ABI entry point, event pairs on the launch stream, from a second untimed "
+                                     "pass; ms_outside = framework kernels (the cat of frames and layouts, the stand-in "
+                                     "convolution forward + weight gradient, the loss) and launch gaps; "
+                                     "ms_no_grad_decode = the step's first half alone (everything before net_ii)",
+                             "entry_points": table},
+                "grads_finite": grads_ok})
         out.update(block_fields(blocks, args.steps, settle_ms))
         print(json.dumps(out), flush=True)
     if dist is not None:
@@ -1122,6 +1230,7 @@ def run_pipeline(args, clips, world, rank, device, dist):
     pending = [None]  # the previous step's all-gather: over xGMI while this step's kernels run
 
     graph_box = [pipe.graphed() if args.graph else None]
+    last = {}  # what the last step handed its caller: this rank's inpainted predicted frames (--dump-outputs)
 
     def step():
         graph = graph_box[0]
@@ -1131,6 +1240,7 @@ def run_pipeline(args, clips, world, rank, device, dist):
                 out = out.clone()  # the graph's static buffer: the next replay overwrites it while the gather runs
         else:
             out = pipe()["inp_pred_vid"]
+        last["inp_pred_vid"] = out
         if strong:  # out: this rank's block of the B * Tp predicted frames
             if emulated is not None:
                 return
@@ -1154,48 +1264,57 @@ def run_pipeline(args, clips, world, rank, device, dist):
     settle_ms = settle_gpu(step, fence)
     for _ in range(args.warmup):
         step()
-    blocks = timed_blocks(step, fence, args.steps, dist, device, args.dist_backend)
+    blocks = timed_blocks(step, fence, args.steps, dist, device, args.dist_backend, nblocks=timed_block_count(args))
     elapsed = median_block(blocks)
-    # one GPU, eager line: the same step replayed from ONE HIP graph beside it (the GPU's time without the launch
-    # gaps; what `--graph` makes the line's ms_per_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last))
     graph_ms = None
-    if dist is None and graph_box[0] is None and emulated is None:
-        try:
-            graph_box[0] = pipe.graphed()
-            for _ in range(max(args.warmup, 1)):
+    if args.full:
+        # one GPU, eager line: the same step replayed from ONE HIP graph beside it (the GPU's time without the launch
+        # gaps; what `--graph` makes the line's ms_per_step)
+        if dist is None and graph_box[0] is None and emulated is None:
+            try:
+                graph_box[0] = pipe.graphed()
+                for _ in range(max(args.warmup, 1)):
+                    step()
+                gb = timed_blocks(step, fence, args.steps, nblocks=3)  # (the same step, its hand-over of the frames included)
+                graph_ms = round(median_block(gb) / args.steps * 1e3, 4)
+            except Exception as exc:  # (the eager line stands on its own)
+                graph_ms = f"capture failed: {exc}"
+            graph_box[0] = None
+        # the per-entry-point table from a SEPARATE pass (event pairs around every C-ABI call; none inside a HIP graph)
+        n_table = max(3, min(args.steps, 10))
+        with _lib.KernelTimer() as kt:
+            for _ in range(n_table):
                 step()
-            gb = timed_blocks(step, fence, args.steps, nblocks=3)  # (the same step, its hand-over of the frames included)
-            graph_ms = round(median_block(gb) / args.steps * 1e3, 4)
-        except Exception as exc:  # (the eager line stands on its own)
-            graph_ms = f"capture failed: {exc}"
-        graph_box[0] = None
-    # the per-entry-point table from a SEPARATE pass (event pairs around every C-ABI call; none inside a HIP graph)
-    n_table = max(3, min(args.steps, 10))
-    with _lib.KernelTimer() as kt:
-        for _ in range(n_table):
-            step()
-        fence()
+            fence()
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        table = {}
-        alg = {} if strong else pipe.hd_algorithmic_bytes()  # (a rank's share of a split job: no per-kernel roofline)
-        for name, (n, ms) in sorted(kt.summary().items(), key=lambda kv: -kv[1][0] * kv[1][1]):
-            per_step = n * ms / n_table
-            row = {"launches_per_step": round(n / n_table, 2), "ms_per_step": round(per_step, 4)}
-            if name in alg:
-                row["alg_bytes_per_step"] = alg[name]
-                row["GBps"] = round(alg[name] / (per_step * 1e-3) / 1e9, 1)
-                row["frac"] = round(row["GBps"] / HBM_PEAK_GBS, 4)
-            table[name] = row
-        in_lib = sum(r["ms_per_step"] for r in table.values())
         o = pipe.opt
-        if strong or not table:  # (inside a HIP graph the per-call events are not recorded: no table)
-            dom = max(table, key=lambda k: table[k]["ms_per_step"]) if table else None
-            roof = {"bound": "hbm", "kernel": dom, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
-                    "traffic": None, "ms_per_launch": table[dom]["ms_per_step"] if table else None,
-                    "note": ("rank 0's share of a split job; the per-kernel roofline of the whole job is the weak-scaling "
-                             "line's (same kernels, same shapes per unit)") if strong else
-                            "replayed from one HIP graph: no per-call events; the eager line has the per-kernel table"}
+        if args.full:
+            table = {}
+            alg = {} if strong else pipe.hd_algorithmic_bytes()  # (a rank's share of a split job: no per-kernel roofline)
+            for name, (n, ms) in sorted(kt.summary().items(), key=lambda kv: -kv[1][0] * kv[1][1]):
+                per_step = n * ms / n_table
+                row = {"launches_per_step": round(n / n_table, 2), "ms_per_step": round(per_step, 4)}
+                if name in alg:
+                    row["alg_bytes_per_step"] = alg[name]
+                    row["GBps"] = round(alg[name] / (per_step * 1e-3) / 1e9, 1)
+                    row["frac"] = round(row["GBps"] / HBM_PEAK_GBS, 4)
+                table[name] = row
+            in_lib = sum(r["ms_per_step"] for r in table.values())
+            if strong or not table:  # (inside a HIP graph the per-call events are not recorded: no table)
+                dom = max(table, key=lambda k: table[k]["ms_per_step"]) if table else None
+                roof = {"bound": "hbm", "kernel": dom, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
+                        "traffic": None, "ms_per_launch": table[dom]["ms_per_step"] if table else None,
+                        "note": ("rank 0's share of a split job; the per-kernel roofline of the whole job is the weak-scaling "
+                                 "line's (same kernels, same shapes per unit)") if strong else
+                                "replayed from one HIP graph: no per-call events; the eager line has the per-kernel table"}
+            else:
+                dom = max((k for k in alg if k in table), key=lambda k: table[k]["ms_per_step"])
+                roof = {"bound": "hbm", "kernel": dom, "achieved": table[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": table[dom]["frac"], "traffic": None,
+                        "alg_bytes_per_launch": alg[dom], "ms_per_launch": table[dom]["ms_per_step"]}
         if strong:
             u0, u1 = pipe.local_units("pred")
             r0, r1 = pipe.local_units("rec")
@@ -1210,11 +1329,6 @@ def run_pipeline(args, clips, world, rank, device, dist):
                    + ("NO collective (one emulated rank on one GPU)" if emulated else
                       "one all-gather of the inpainted predicted frames per step, overlapped with the next step's kernels"))
         else:
-            if table:
-                dom = max((k for k in alg if k in table), key=lambda k: table[k]["ms_per_step"])
-                roof = {"bound": "hbm", "kernel": dom, "achieved": table[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": table[dom]["frac"], "traffic": None,
-                        "alg_bytes_per_launch": alg[dom], "ms_per_launch": table[dom]["ms_per_step"]}
             total_frames = clips * t * world
             workload = f"{args.config} pipeline: {clips} clips x {t} frames per GPU ({pipe.ctx_len} context)"
             par = (f"clips sharded x{world}, one all-gather of the inpainted predicted frames per step, "
@@ -1235,14 +1349,15 @@ def run_pipeline(args, clips, world, rank, device, dist):
                                    f"{'written' if getattr(o, 'use_inpainter', False) else 'NOT produced (use_inpainter off)'}",
                        "frames_per_gpu": clips * t if not strong else round(clips * t / (emulated[1] if emulated else world), 2),
                        "layers": o.num_obj + 1, "height": hd, "width": wd, "parallelism": par},
-            "roofline": roof,
-            "pipeline": {"ms_in_library_calls": round(in_lib, 4),
-                         "ms_outside": round(ms_per_step - in_lib, 4),
-                         "note": "per C-ABI entry point, event pairs on the launch stream, from a separate untimed pass; "
-                                 "ms_outside = framework kernels and launch gaps between the calls (indexing, permutes, "
-                                 "the stand-ins)",
-                         "entry_points": table},
         }
+        if args.full:
+            out["roofline"] = roof
+            out["pipeline"] = {"ms_in_library_calls": round(in_lib, 4),
+                               "ms_outside": round(ms_per_step - in_lib, 4),
+                               "note": "per C-ABI entry point, event pairs on the launch stream, from a separate "
+                                       "untimed pass; ms_outside = framework kernels and launch gaps between the "
+                                       "calls (indexing, permutes, the stand-ins)",
+                               "entry_points": table}
         out.update(block_fields(blocks, args.steps, settle_ms))
         if graph_ms is not None:
             out["ms_per_step_graph_replay"] = graph_ms

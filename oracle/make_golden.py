@@ -434,16 +434,242 @@ def gen_demo_clip():
     print(f"demo_clip: {len(names)} frames + layouts, {total / 1024:.1f} KiB")
 
 
+def flat(prefix, value, out):
+    """A tensor, None or a (nested) tuple of them as npz entries: `prefix`, `prefix.none`, `prefix.len` + `prefix.<i>`
+    (tests/test_oracle_live.py:unflat reads them back)."""
+    if value is None:
+        out[prefix + ".none"] = np.array(1)
+    elif isinstance(value, (tuple, list)):
+        out[prefix + ".len"] = np.array(len(value))
+        for i, v in enumerate(value):
+            flat(f"{prefix}.{i}", v, out)
+    else:
+        out[prefix] = value.detach().cpu().numpy()
+    return out
+
+
+class record_primitives:
+    """Context manager: records, in call order, the input and output of every ``log`` and ``torch.inverse`` call made
+    inside it.  These are the two steps of the TPS buffers whose last bits depend on the CPU (ATen's float ``log``
+    and the matrix inverse both go through MKL, which rounds differently per instruction set); the test replays the
+    recorded outputs to the oracle after checking that it asks for them with bit-identical inputs."""
+
+    def __enter__(self):
+        self.calls, self._orig = [], (torch.Tensor.log, torch.log, torch.inverse)
+        t_log, f_log, inv = self._orig
+
+        def wrap(op, fn):
+            def call(x, *a, **k):
+                y = fn(x, *a, **k)
+                self.calls.append((op, x.detach().clone(), y.detach().clone()))
+                return y
+            return call
+        torch.Tensor.log, torch.log, torch.inverse = wrap(0, t_log), wrap(0, f_log), wrap(1, inv)
+        return self
+
+    def __exit__(self, *exc):
+        torch.Tensor.log, torch.log, torch.inverse = self._orig
+        return False
+
+
+def gen_live_buffers(ns):
+    """tests/test_oracle_live.py::test_buffers_bit_equal: the reference's grid / Gaussian / TPS buffers, and the
+    CPU-dependent primitive calls inside the TPS constructor (record_primitives)."""
+    out = {}
+    for h, w in [(4, 4), (8, 16), (128, 256), (3, 7)]:
+        flat(f"grid_{h}_{w}", ns.get_grid(h, w), out)
+    flat("gaussian_3", ns.get_gaussian_kernel(3), out)
+    with record_primitives() as rec:
+        ref = ns.TPSWarp(16, 32, ns.get_grid(4, 4).view(-1, 2))
+    for i, (op, x, y) in enumerate(rec.calls):
+        out[f"tps_call.{i}.op"], out[f"tps_call.{i}.in"], out[f"tps_call.{i}.out"] = np.array(op), x.numpy(), y.numpy()
+    flat("tps_inverse_kernel", ref.inverse_kernel, out)
+    flat("tps_tgt_grid_repr", ref.tgt_grid_repr, out)
+    save("live_buffers", **out)
+
+
+def gen_live_inverse_warp(ns):
+    """tests/test_oracle_live.py::test_inverse_warp_random: InverseWarp on TPS grids of seeded control points (stable
+    sort, see ref_import.stable_sort)."""
+    for seed in range(3):
+        torch.manual_seed(seed)
+        ctrl = ns.get_grid(4, 4).view(-1, 2)
+        hs, ws, ht, wt = [(8, 8, 16, 32), (16, 32, 16, 32), (12, 20, 24, 40)][seed]
+        inv = ns.InverseWarp(hs, ws, ht, wt)
+        sg = ns.TPSWarp(hs, ws, ctrl)(ctrl.view(1, 16, 2) * 0.7 + 0.1 * torch.randn(3, 16, 2))
+        out = flat("sg", sg, {"target": np.array([ht, wt])})
+        for erode in (True, False):
+            with R.stable_sort():
+                flat(f"erode_{int(erode)}", inv(sg, erode=erode), out)
+        save(f"live_inverse_warp_{seed}", **out)
+
+
+# layers at 4x8 and frames at 8x16 (load_dim = 2 x dim: the HD path), so that each case's file stays small
+LIVE_WARPER_SIZE = dict(dim=4, load_dim=8)
+LIVE_WARPER_OVER = [dict(), dict(weight_cls=True, min_cls=0.1), dict(load_dim=0),
+                    dict(allow_ghost=True, include_self=True), dict(no_filter=True)]
+
+
+def gen_live_warper(ns):
+    """tests/test_oracle_live.py::test_warper_against_reference: Warper's grids, grid_to_flow[_ctx], input_to_output,
+    alpha_to_alpha, layer_from_input and the flow helpers on seeded inputs, one file per option set."""
+    from oracle import warper_oracle as WO
+    from oracle import wif_oracle as O
+    for case, over in enumerate(LIVE_WARPER_OVER):
+        torch.manual_seed(0)
+        opt = R.warper_opt(num_obj=3, **{**LIVE_WARPER_SIZE, **over})
+        ref = ns.Warper(opt)
+        b, t, no, nl = 2, 4, 3, 5
+        obj_pose = ns.get_grid(2, 2).view(1, 1, 1, 4, 2) * 0.5 + 0.15 * torch.randn(b, t, no, 4, 2)
+        bg_pose = ns.get_grid(2, 4).view(1, 1, 1, 8, 2) + 0.05 * torch.randn(b, t, 1, 8, 2)
+        with R.stable_sort():
+            grid = ref(obj_pose, bg_pose)
+        cfg = WO.WarperCfg.from_opt(opt)
+        (hd, wd), (h, w), (ho, wo) = cfg.src_shape_hd, cfg.src_shape, cfg.tgt_shape
+        out = {"size." + k: np.array(v) for k, v in LIVE_WARPER_SIZE.items()}
+        for k, v in dict(obj_pose=obj_pose, bg_pose=bg_pose, grid=grid).items():
+            flat(k, v, out)
+        inp = torch.randn(b, t, 3 + nl, hd, wd)
+        occ = O.compute_occ(torch.randn(b, t, no))
+        obj_alpha = torch.rand(b, no, 1, ho, wo) * 2 - 1
+        bg_alpha = torch.ones(b, 1, h, w)
+        cls = torch.rand(b, no, nl).softmax(-1)
+        ctx_ts = torch.tensor([[[0, 1], [1, 0]], [[1, 1], [0, 0]]])
+        pred_ts = torch.tensor([2, 3])
+        for k, v in dict(inp=inp, occ=occ, obj_alpha=obj_alpha, bg_alpha=bg_alpha, cls=cls, ctx_ts=ctx_ts,
+                         pred_ts=pred_ts).items():
+            flat(k, v, out)
+        for name in ("grid_to_flow_ctx", "grid_to_flow"):
+            for i, c in enumerate((cls,) if opt.weight_cls else (cls, None)):
+                r = getattr(ref, name)(inp, grid, occ, obj_alpha, bg_alpha, c, ctx_ts, pred_ts)
+                flat(f"{name}.cls{i}", r, out)
+        flat("input_to_output", ref.input_to_output(inp, r[3], r[0], ctx_ts), out)
+        if opt.include_self:  # needs Tp == T
+            ctx2 = torch.roll(torch.arange(t), 1).view(1, 1, t).expand(b, 1, t)
+            pr2 = torch.arange(t)
+            r2 = ref.grid_to_flow(inp, grid, occ, obj_alpha, bg_alpha, cls, ctx2, pr2)  # LVD training path
+            flat("self.grid_to_flow", r2, out)
+            flat("self.input_to_output", ref.input_to_output(inp, r2[3], r2[0], ctx2), out)
+        flat("alpha_to_alpha", ref.alpha_to_alpha(obj_alpha, bg_alpha, grid, occ), out)
+        x5 = torch.randn(b, t, 4, h, w)
+        flat("x5", x5, out)
+        flat("layer_from_input", ref.layer_from_input(x5, grid), out)
+        flat("bg_flow_ref_to_pred", ref.grid_to_bg_flow_from_ref_to_pred(grid, 2, 1), out)
+        flat("obj_flow_ref_to_pred", ref.grid_to_obj_flow_from_ref_to_pred(grid, 2, 1, 2), out)
+        flat("bg_flow_ctx_to_ref", ref.grid_to_bg_flow_from_ctx_to_ref(grid, 2, 3), out)
+        save(f"live_warper_{case}", **out)
+
+
+def gen_live_wif_forward(ns):
+    """tests/test_oracle_live.py::test_wif_forward_against_reference: WIF.forward around a 1 x 1 convolution."""
+    torch.manual_seed(0)
+    b, tc, t, c, h, w = 2, 3, 2, 12, 8, 16
+    vid = torch.randn(b, tc, t, c, h, w)
+    wif = ns.WIF.__new__(ns.WIF)
+    torch.nn.Module.__init__(wif)
+    wif.score, wif.ab = True, True
+    lin = torch.nn.Conv2d(c, 5, 1)
+    wif.unet = lin
+    save("live_wif_forward", vid=vid, weight=lin.weight, bias=lin.bias, out=ns.WIF.forward(wif, vid))
+
+
+def gen_live_expand(ns):
+    """tests/test_oracle_live.py::test_expand_equals_reference_bit_for_bit: tools/utils.py:expand on hard and soft
+    masks, every `dir`, several rounds."""
+    torch.manual_seed(5)
+    hard = (torch.rand(2, 3, 17, 23) > 0.9).float()
+    soft = torch.rand(2, 1, 19, 21) * (torch.rand(2, 1, 19, 21) > 0.8)
+    out = {"hard": hard, "soft": soft}
+    for d in (None, "south", "north", "east", "west"):
+        for num in (1, 2, 5):
+            out[f"hard_{d}_{num}"] = ns.expand(hard.clone(), num, dir=d)
+            out[f"soft_{d}_{num}"] = ns.expand(soft.clone(), num, dir=d, soft=True)
+    save("live_expand", **out)
+
+
+def gen_io_formats():
+    """tests/test_io_formats.py::test_formats_against_reference_loader: the reference's own loader methods
+    (data/base_dataset.py, executed where it lies under stubbed torchvision / tools.utils parents) on the committed
+    demo files.  The outputs are large and compared bit for bit, so their SHA-256 digests (of the float32 bytes) are
+    stored with their shapes."""
+    import hashlib
+    import importlib.util
+    golden = OUT
+    flo = os.path.join(golden, "demo_flow.flo")
+    clip = os.path.join(golden, "demo_clip", "leftImg8bit_sequence_512", "val", "munster")
+    lyt_dir = clip.replace("_512", "_deeplabv3_512")
+
+    class ToTensor:
+        def __call__(self, img):
+            a = np.asarray(img)
+            a = a[None] if a.ndim == 2 else a.transpose(2, 0, 1)
+            return torch.from_numpy(a.copy()).float() / 255
+
+    class Compose:
+        def __init__(self, ts):
+            self.ts = ts
+
+        def __call__(self, x):
+            for t in self.ts:
+                x = t(x)
+            return x
+
+    stubs = {k: types.ModuleType(k) for k in ("torchvision", "torchvision.transforms", "torchvision.datasets",
+                                              "torchvision.datasets.video_utils", "tools", "tools.utils")}
+    tv = stubs["torchvision.transforms"]
+    tv.ToTensor = ToTensor
+    tv.Resize = lambda size, method: (lambda img: img.resize((size[1], size[0]), method))
+    tv.Normalize = lambda mean, std: (lambda x: (x - torch.tensor(mean).view(-1, 1, 1)) / torch.tensor(std).view(-1, 1, 1))
+    tv.Compose = Compose
+    stubs["torchvision"].transforms = tv
+    stubs["torchvision.datasets.video_utils"].VideoClips = object
+    for name in ("get_vprint", "serialize", "deserialize"):
+        setattr(stubs["tools.utils"], name, lambda *a, **k: None)
+    saved = {k: sys.modules.get(k) for k in stubs}
+    sys.modules.update(stubs)
+    sys.dont_write_bytecode = True
+    out = {}
+
+    def record(key, t):
+        t = t.contiguous()
+        assert t.dtype == torch.float32
+        out[key + ".sha256"] = np.frombuffer(hashlib.sha256(t.numpy().tobytes()).digest(), dtype=np.uint8)
+        out[key + ".shape"] = np.array(t.shape)
+
+    try:
+        spec = importlib.util.spec_from_file_location("ref_base_dataset",
+                                                      os.path.join(R.REF_ROOT, "data", "base_dataset.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        ds = object.__new__(mod.BaseDataset)
+        ds.opt = types.SimpleNamespace(remap_lyt=[], num_lyt=20, flow_dim=0)
+        record("flow", ds.load_flow_path(flo))
+        record("layout", ds.load_layout_path(os.path.join(lyt_dir, sorted(os.listdir(lyt_dir))[0])))
+        pi = os.path.join(clip, sorted(os.listdir(clip))[0])
+        for dim, ar in ((128, 1.0), (128, 2.0), (512, 2.0)):
+            record(f"rgb_{dim}_{int(dim * ar)}", ds.load_rgb_path(pi, mod.get_transform(dim, aspect_ratio=ar)))
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+    save("io_formats_reference_loader", **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ns = R.load()
     only = set(sys.argv[1:])  # e.g. `make_golden.py inverse_warp_perm`; none = all
     for fn in (gen_tps, gen_grid_sample, gen_occ_comp, gen_warp_composite, gen_warp_composite_delta, gen_inverse_warp,
-               gen_inverse_warp_kernel_size, gen_inverse_warp_perm, gen_warper, gen_inpaint, gen_producers, gen_pose_affine):
+               gen_inverse_warp_kernel_size, gen_inverse_warp_perm, gen_warper, gen_inpaint, gen_producers, gen_pose_affine,
+               gen_live_buffers, gen_live_inverse_warp, gen_live_warper, gen_live_wif_forward, gen_live_expand):
         if not only or fn.__name__[4:] in only:
             fn(ns)
     if not only or "demo_clip" in only:
         gen_demo_clip()
+    if not only or "io_formats" in only:
+        gen_io_formats()
 
 
 if __name__ == "__main__":

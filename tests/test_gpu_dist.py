@@ -199,8 +199,8 @@ def test_bench_strong_scaling_line():
 
 
 def test_default_multi_gpu_line_carries_the_north_star_block():
-    """`bench.py --gpus 2` with NO other workload flag -- the one multi-GPU command the driver's scaling run issues (here
-    with `--dist-backend gloo`: the two ranks share this box's GPU) -- prints ONE line: the C3 headline loop (no data-path
+    """`bench.py --gpus 2 --full` with NO other workload flag (here with `--dist-backend gloo`: the two ranks share this
+    box's GPU) prints ONE line: the C3 headline loop (no data-path
     collective) and, behind it, the `north_star` object: the all-gather of composited frames at C4 and C5 (bytes, the
     collective alone, exposed time with the overlap off and on), the C5 pipeline as one job split over the ranks
     (ms_per_step, per-rank compute, speed-up over rank 0 running the whole job) and the cross-rank bit-equality check.
@@ -211,7 +211,7 @@ def test_default_multi_gpu_line_carries_the_north_star_block():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -235,7 +235,7 @@ def test_default_multi_gpu_line_carries_the_north_star_block():
 
 
 def test_bench_wif_line():
-    """`bench.py --config WIF`: the reference's WIF training step (Synthesizer.inpaint's call order at the
+    """`bench.py --config WIF --full`: the reference's WIF training step (Synthesizer.inpaint's call order at the
     train_wif.sh recipe) as one JSON line with the per-entry-point table -- the unrestricted flow passes, the frame
     warp and BOTH directions of the fusion kernel in it."""
     import json
@@ -243,7 +243,7 @@ def test_bench_wif_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", "WIF", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", "WIF", "--steps", "2", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -258,7 +258,7 @@ def test_bench_wif_line():
 
 
 def test_default_line_measures_its_hbm_traffic_in_the_run():
-    """The default one-GPU command (what the driver runs) collects ``roofline.traffic`` itself: two rocprofv3 --pmc child
+    """The default one-GPU command with --full collects ``roofline.traffic`` itself: two rocprofv3 --pmc child
     runs of the same command (bench.py::live_traffic), and the bytes they report per backward launch lie between the
     algorithmic bytes and three times them (the K1 -> K2 records are real traffic of this design: 2.2 x)."""
     import json
@@ -269,7 +269,7 @@ def test_default_line_measures_its_hbm_traffic_in_the_run():
         pytest.skip("no rocprofv3 on this box")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -282,3 +282,51 @@ def test_default_line_measures_its_hbm_traffic_in_the_run():
     assert roof["alg_bytes_per_launch"] < roof["traffic"] < 3 * roof["alg_bytes_per_launch"]
     fwd = roof["kernels"]["waldo_warp_composite_fwd"]
     assert fwd["alg_bytes"] < fwd["moved_bytes"] < 2 * fwd["alg_bytes"]
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps N --warmup W` without --full: ONE line with the headline fields only, timed over one block of
+    exactly N steps; --dump-outputs writes what the last step handed its caller (composited frames, loss, gradients) as
+    float32 .npy files of at most 64 MB together -- the same values the fused path computes from the same seeded inputs
+    in this process, sampled at the same indices."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    import waldo_amd
+    from waldo_amd import functional as WF
+    from waldo_amd.tools.utils import get_grid
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    got_dir, want_dir = tmp_path / "bench", tmp_path / "here"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--clips", "1",
+           "--frames-per-clip", "2", "--dump-outputs", str(got_dir)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "frames/s" and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["ms_per_step"] > 0 and out["metric"].startswith("warped+composited")
+    assert abs(out["value"] - 2 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert not {"roofline", "cpu_baseline", "loss_variants", "ms_per_step_blocks", "north_star"} & set(out), sorted(out)
+
+    names = ["grad_layers", "grad_pts", "loss", "rgb"]
+    assert sorted(p.stem for p in got_dir.iterdir()) == names
+    assert sum(p.stat().st_size for p in got_dir.iterdir()) <= 64 * 10 ** 6
+    dev = torch.device("cuda:0")
+    tps = waldo_amd.TPSWarp(256, 512, get_grid(4, 4).view(-1, 2)).to(dev)
+    layers, pts, occ = bench.synth(2, 8, 256, 512, dev, seed=0)
+    layers.requires_grad_()
+    pts.requires_grad_()
+    rgb = WF.warp_composite(layers, pts, occ, tps.inverse_kernel, tps.basis_t)
+    loss = rgb.square().mean()
+    loss.backward()
+    bench.dump_outputs(str(want_dir), {"rgb": rgb, "loss": loss, "grad_layers": layers.grad, "grad_pts": pts.grad})
+    for name in names:
+        a, b = np.load(got_dir / (name + ".npy")), np.load(want_dir / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == b.shape, (name, a.dtype, a.shape, b.shape)
+        tol = 1e-6 if name in ("rgb", "loss") else 1e-5 * float(np.abs(b).max())  # (gradients: atomics' order)
+        assert float(np.abs(a - b).max()) <= tol, name
+    assert np.load(got_dir / "grad_layers.npy").size < layers.numel()  # (a sample: the whole gradient is 34 MB)

@@ -1,7 +1,5 @@
 """Row f4: on-disk formats of the demo clips (host logic; no GPU)."""
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ from waldo_amd.tools import io as wio
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEMO = os.path.join(HERE, "golden", "demo_flow.flo")  # a data file of the reference's demo set
-REF = "/root/reference"
 
 
 def test_read_flo_demo_file():
@@ -48,76 +45,29 @@ def test_layout_to_logits():
     assert set(lg.unique().tolist()) == {-5.0, 5.0} and torch.equal((lg > 0).sum(0), torch.ones(2, 3, dtype=torch.long))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 def test_formats_against_reference_loader():
-    """The reference's own loader methods (data/base_dataset.py, executed from where it lies under
-    stubbed torchvision / tools.utils parents) on the same files."""
-    import importlib.util
+    """The reference's own loader methods (data/base_dataset.py) on the committed demo files, recorded by
+    oracle/make_golden.py:gen_io_formats as the SHA-256 of their float32 bytes: the product's readers give the same
+    tensors bit for bit -- the flow file, the first layout map, the first frame at three sizes."""
+    import hashlib
+    ref = np.load(os.path.join(HERE, "golden", "io_formats_reference_loader.npz"))
+
+    def check(key, t):
+        t = t.contiguous()
+        assert t.dtype == torch.float32 and tuple(t.shape) == tuple(ref[key + ".shape"]), (key, t.shape)
+        assert hashlib.sha256(t.numpy().tobytes()).digest() == ref[key + ".sha256"].tobytes(), key
+
+    check("flow", wio.read_flo(DEMO))
+    clip = os.path.join(HERE, "golden", "demo_clip", "leftImg8bit_sequence_512", "val", "munster")
+    lyt_dir = clip.replace("_512", "_deeplabv3_512")
+    p = os.path.join(lyt_dir, sorted(os.listdir(lyt_dir))[0])
     import PIL.Image
-
-    class ToTensor:
-        def __call__(self, img):
-            a = np.asarray(img)
-            a = a[None] if a.ndim == 2 else a.transpose(2, 0, 1)
-            return torch.from_numpy(a.copy()).float() / 255
-
-    stubs = {
-        "torchvision": types.ModuleType("torchvision"),
-        "torchvision.transforms": types.ModuleType("torchvision.transforms"),
-        "torchvision.datasets": types.ModuleType("torchvision.datasets"),
-        "torchvision.datasets.video_utils": types.ModuleType("torchvision.datasets.video_utils"),
-        "tools": types.ModuleType("tools"),
-        "tools.utils": types.ModuleType("tools.utils"),
-    }
-    stubs["torchvision.transforms"].ToTensor = ToTensor
-    stubs["torchvision"].transforms = stubs["torchvision.transforms"]
-    stubs["torchvision.datasets.video_utils"].VideoClips = object
-    for name in ("get_vprint", "serialize", "deserialize"):
-        setattr(stubs["tools.utils"], name, lambda *a, **k: None)
-    saved = {k: sys.modules.get(k) for k in stubs}
-    sys.modules.update(stubs)
-    sys.dont_write_bytecode = True
-    try:
-        spec = importlib.util.spec_from_file_location("ref_base_dataset", os.path.join(REF, "data", "base_dataset.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        ds = object.__new__(mod.BaseDataset)
-        ds.opt = types.SimpleNamespace(remap_lyt=[], num_lyt=20, flow_dim=0)
-        ref_flow = ds.load_flow_path(DEMO)
-        assert torch.equal(wio.read_flo(DEMO), ref_flow)
-        lyt_dir = os.path.join(REF, "datasets", "demo_cityscapes", "leftImg8bit_sequence_deeplabv3_512", "val", "munster")
-        p = os.path.join(lyt_dir, sorted(os.listdir(lyt_dir))[0])
-        ref_lyt = ds.load_layout_path(p)
-        ids = torch.from_numpy(np.asarray(PIL.Image.open(p)).copy()).long()
-        assert torch.equal(wio.layout_to_logits(ids, 20), ref_lyt)
-        assert torch.equal(wio.read_layout(p, 20), ref_lyt)
-        # frames: load_rgb_path + the inference transform of get_transform (Resize on the PIL image,
-        # ToTensor, Normalize(0.5, 0.5)) with stand-ins for the three torchvision classes it composes
-        tv = stubs["torchvision.transforms"]
-        tv.Resize = lambda size, method: (lambda img: img.resize((size[1], size[0]), method))
-        tv.Normalize = lambda mean, std: (lambda x: (x - torch.tensor(mean).view(-1, 1, 1)) / torch.tensor(std).view(-1, 1, 1))
-
-        class Compose:
-            def __init__(self, ts):
-                self.ts = ts
-
-            def __call__(self, x):
-                for t in self.ts:
-                    x = t(x)
-                return x
-
-        tv.Compose = Compose
-        img_dir = lyt_dir.replace("_deeplabv3_512", "_512")
-        pi = os.path.join(img_dir, sorted(os.listdir(img_dir))[0])
-        for dim, ar in ((128, 1.0), (128, 2.0), (512, 2.0)):
-            ref_img = ds.load_rgb_path(pi, mod.get_transform(dim, aspect_ratio=ar))
-            assert torch.equal(wio.read_rgb(pi, (dim, int(dim * ar))), ref_img), (dim, ar)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
+    ids = torch.from_numpy(np.asarray(PIL.Image.open(p)).copy()).long()
+    check("layout", wio.layout_to_logits(ids, 20))
+    check("layout", wio.read_layout(p, 20))
+    pi = os.path.join(clip, sorted(os.listdir(clip))[0])
+    for dim, ar in ((128, 1.0), (128, 2.0), (512, 2.0)):
+        check(f"rgb_{dim}_{int(dim * ar)}", wio.read_rgb(pi, (dim, int(dim * ar))))
 
 
 CLIP = os.path.join(HERE, "golden", "demo_clip", "leftImg8bit_sequence_512", "val", "munster")

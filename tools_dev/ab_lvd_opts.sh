@@ -4,7 +4,7 @@ set -e
 mkdir -p gpurun_out/ab_lvd
 for i in 1 2; do
   for opt in "" "$@"; do
-    python bench.py --config LVD --steps 200 --warmup 20 --no-cpu-baseline $opt 2>/dev/null | python -c "
+    python bench.py --config LVD --steps 200 --warmup 20 --full --no-cpu-baseline $opt 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['pipeline']['entry_points']
 g=lambda k: e.get(k,{}).get('ms_per_step')

@@ -6,7 +6,7 @@ for i in 1 2; do
   for lib in "" "$@"; do
     opt=""; [ -n "$lib" ] && opt="--lib $lib"
     for cfg in C5 C4; do
-    python bench.py --config $cfg --pipeline --steps 10 --warmup 2 --no-cpu-baseline $opt 2>/dev/null | python -c "
+    python bench.py --config $cfg --pipeline --steps 10 --warmup 2 --full $opt 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); e=d['pipeline']['entry_points']
 g=lambda k: e.get(k,{}).get('ms_per_step')
