@@ -42,7 +42,7 @@ int waldo_max_layers(void);
 /* Test-only switches between kernel variants that compute the same thing (A/B parity tests of the
  * fast paths against the plain ones).  THE ONE PIECE OF PROCESS-GLOBAL STATE of the library: process-wide,
  * off by default, relaxed atomics; nothing reads the environment.  Kernel variants that were measured and
- * rejected are NOT in the library (tools_dev/dropped/, buildable with tools_dev/build_variant.py). */
+ * rejected are NOT in the library, nor in its sources: DESIGN.md records them and where git history keeps them. */
 #define WALDO_DEBUG_FWD_PLAIN 0   /* fused forward: gather kernel instead of the LDS-staged one */
 #define WALDO_DEBUG_IW_PASSES 1   /* grid inversion: one kernel per fill / erosion pass */
 #define WALDO_DEBUG_BWD_GENERIC 2 /* fused backward: the generic per-tap-atomics kernel for every shape

@@ -122,40 +122,38 @@ def test_only_the_checker_legs_touch_the_oracle():
     assert hits and all(entry[entry.rfind("\ndef ", 0, h):].lstrip().startswith("def smoke") for h in hits)
 
 
-def test_timing_only_ablations_cannot_reach_a_product_build(tmp_path):
-    """A WALDO_ABL_* switch (timing-only, may compute wrong values) without -DWALDO_TIMING_ONLY_BUILD does not get
-    past the preprocessor; with it, the library reports version 0."""
-    import subprocess
+def test_product_sources_hold_no_ablation_variant_or_stamp_hooks():
+    """No timing-only ablation (wrong values on purpose), rejected-variant switch or diagnostic stamp build can reach a
+    product library: the sources it is compiled from contain none."""
     from waldo_amd import build
-    src = os.path.join(build.CSRC, "runtime.hip")
-    base = [build.HIPCC, "-E", "--offload-arch=gfx950", "--cuda-host-only", f"-I{build.INCLUDE}"]
-    bad = subprocess.run(base + ["-DWALDO_ABL_REC_ALIAS=2", src], capture_output=True, text=True)
-    assert bad.returncode != 0 and "WALDO_TIMING_ONLY_BUILD" in bad.stderr
-    ok = subprocess.run(base + ["-DWALDO_ABL_REC_ALIAS=2", "-DWALDO_TIMING_ONLY_BUILD", src], capture_output=True,
-                        text=True)
-    assert ok.returncode == 0, ok.stderr[-500:]
-    assert re.search(r"waldo_version\(void\)\s*\{\s*return 0;", ok.stdout)
-    assert not re.search(r"waldo_version\(void\)\s*\{\s*return 1\d\d\d;", ok.stdout)
+    files = build.sources() + build._deps()
+    assert any(f.endswith("runtime.hip") for f in files) and any(f.endswith("waldo_hip.h") for f in files)
+    for src in files:
+        text = open(src).read()
+        for token in ("WALDO_ABL_", "WALDO_VARIANT_", "WALDO_TIMING_ONLY_BUILD", "_STAMPS"):
+            assert token not in text, (src, token)
 
 
-def test_binding_refuses_a_version_0_library_unless_named_explicitly(tmp_path):
-    """What a timing-only build looks like to the binding: waldo_version() == 0.  The default path refuses it."""
+def test_binding_refuses_a_version_0_library(tmp_path):
+    """A library of another ABI version -- here waldo_version() == 0 -- is refused, whether it sits at the default path or
+    was named with use_library() (bench.py --lib, pytest --waldo-lib)."""
     import subprocess
     import sys
     csrc = tmp_path / "v0.c"
     csrc.write_text("int waldo_version(void) { return 0; }\n")
     so = tmp_path / "libwaldo_hip.so"
     subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(so), str(csrc)], check=True)
-    code = ("import sys; sys.path.insert(0, %r)\n"
-            "from waldo_amd import _lib\n"
-            "_lib.LIB_PATH = %r\n"
-            "try:\n"
-            "    _lib.load()\n"
-            "except _lib.WaldoHipError as e:\n"
-            "    assert 'ABI version 0' in str(e), e\n"
-            "    print('refused')\n") % (ROOT, str(so))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "refused" in r.stdout, (r.stdout, r.stderr[-800:])
+    for bind in ("_lib.LIB_PATH = %r" % str(so), "_lib.use_library(%r)" % str(so)):
+        code = ("import sys; sys.path.insert(0, %r)\n"
+                "from waldo_amd import _lib\n"
+                "%s\n"
+                "try:\n"
+                "    _lib.load()\n"
+                "except _lib.WaldoHipError as e:\n"
+                "    assert 'ABI version 0' in str(e), e\n"
+                "    print('refused')\n") % (ROOT, bind)
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "refused" in r.stdout, (bind, r.stdout, r.stderr[-800:])
 
 
 def test_entry_points_issue_no_memset_or_memcpy_nodes():

@@ -1,4 +1,4 @@
-# dev: LVD-recipe step, product kernels against a debug option (or a variant library: tools_dev/dropped/README.md), interleaved on one box
+# dev: LVD-recipe step, product kernels against a debug option (or a variant library: tools_dev/build_variant.py), interleaved on one box
 set -e
 OPT=${1:---lib tools_dev/_variants/rows.so}
 mkdir -p gpurun_out/ab_lvd

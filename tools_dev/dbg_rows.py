@@ -14,7 +14,7 @@ dist = torch.softmax(torch.randn(b, nl - 1, ncls, device=dev), -1)
 occ = torch.rand(b, t, nl, nl, device=dev) * 0.8
 res = {}
 for px in (0, 1):
-    pass  # (round 6: the lane-layer kernels are a VARIANT build, tools_dev/dropped/README.md; run this once per library with --lib)
+    pass  # (round 6: the lane-layer kernels were a variant build, since dropped; run this once per library with --lib)
     a, d, o = alpha_lr.clone().requires_grad_(), dist.clone().requires_grad_(), occ.clone().requires_grad_()
     a01, alpha = WF.flow_ctx_alpha(a, inp, d, o, tw, 3, s)
     torch.manual_seed(1)

@@ -27,18 +27,6 @@
 
 namespace waldo {
 
-#ifndef WALDO_FCW_SPARSE
-#define WALDO_FCW_SPARSE 1  // wave-uniform skipping of absent layers (flow_ctx_warp_kernel); 0: every layer, every factor
-#endif
-#ifndef WALDO_FCW_MASK_FIRST
-#define WALDO_FCW_MASK_FIRST 1  // 0: whole records of every layer; 1: a layer's mask first, its flow record if wanted;
-                                // 2: the masks of ALL layers up front (one LDS round trip), records of wanted layers.
-                                // C5 pipeline, A/B on one box (tools_dev/ab_pipeline.sh): 7.67 / 7.55 / 7.80 ms per step
-#endif
-#ifndef WALDO_FCW_CONST_OUT
-#define WALDO_FCW_CONST_OUT 0   // 1: outputs of layers outside the active set as constants, behind a wave-uniform branch
-                                // -- measured SLOWER (8.1 against 7.6 ms: twelve more branches cut the store stream up)
-#endif
 template <int LP, int NCP>
 __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
     const float* __restrict__ alpha_lr, const float* __restrict__ input,
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
   if (dist != nullptr) tab_bad = dist_stage<LP>(sdist, dist + (int64_t)b * (L - 1) * Nl, L, Nl);
   tab_bad |= occ_stage<LP>(occm, occ + ((int64_t)b * T + t) * L * L, L);
   // (the barrier doubles as the vote on non-finite entries of the two tables: see the short cuts below)
-  const bool dense = WALDO_FCW_SPARSE ? __syncthreads_or(tab_bad) != 0 : (__syncthreads(), true);
+  const bool dense = __syncthreads_or(tab_bad) != 0;
   if (x >= Wd || y >= Hd) return;
   const UpTaps ut = up_taps(y, x, 1.0f / (float)scale, H, W);
 
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
     if (__ballot(a[l] != 0.0f) != 0ull) active |= 1u << l;
     wild |= __ballot(!(fabsf(a[l]) <= 3.0e38f)) != 0ull;
   }
-  if (!WALDO_FCW_SPARSE || dense || wild) active = LP >= 32 ? 0xffffffffu : (1u << LP) - 1u;
+  if (dense || wild) active = LP >= 32 ? 0xffffffffu : (1u << LP) - 1u;
 
   if (dist != nullptr) {
     // softmax over the Nl layout logits of this pixel (held in registers)
@@ -159,13 +147,6 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
                            // step, 3.45 -> 3.01 at C4; at 6, which 24 KB of LDS allow, the same 5.5 ms:
                            // profiles/r04_ab_flow_ctx_warp_reflow_*.txt)
 #endif
-#ifndef WALDO_FCW_TP_INNER
-#define WALDO_FCW_TP_INNER 0  // the Tp units of a (clip, context) innermost in an XCD's tile walk (hd_pixel_rows_grouped)
-#endif
-#ifndef WALDO_FCW_REFLOW
-#define WALDO_FCW_REFLOW 1  // the upsampled flow of a layer is taken AGAIN where its composited alpha is known (active layers only)
-                            // instead of kept per layer: 2 LP registers fewer across the occlusion product
-#endif
 #ifndef WALDO_FCW_ROWS
 #define WALDO_FCW_ROWS 4  // pixels per thread of flow_ctx_warp_kernel at scale >= 2 (tile = 4 WALDO_FCW_ROWS x 64 pixels)
 #endif
@@ -176,11 +157,8 @@ constexpr int kFcwRows = WALDO_FCW_ROWS;
 // floats of LDS for the staged low-resolution records of a tile with `rows` pixels per thread: 136 cells (4 x 64 tile
 // at x 2) up to L = 12; L <= 8: 204 cells (8 x 64 tile at x 2).  The 16 x 64 tile at 9-12 layers only ever fits at
 // x 4 and up (6 x 18 cells): sized for exactly that, 24 KB with the order, six workgroups per CU
-#ifndef WALDO_FCW_SMALL_LDS
-#define WALDO_FCW_SMALL_LDS 1
-#endif
 constexpr int fcw_cap(int lp, int rows) {
-  return lp <= 8 ? 7680 : (lp <= 12 ? ((WALDO_FCW_SMALL_LDS && rows == kFcwRows && kFcwRows == 4) ? 5632 : 7168) : 8192);
+  return lp <= 8 ? 7680 : (lp <= 12 ? ((rows == kFcwRows && kFcwRows == 4) ? 5632 : 7168) : 8192);
 }
 template <int LP, int R>
 struct FcwLds {
@@ -208,14 +186,9 @@ __device__ __forceinline__ float nan_max(float a, float b) { return __builtin_el
 // paid per 256 pixels; timing-only ablations put everything but the gathers, the product and the stores at 5 of the
 // kernel's 7.8 ms per C5 pipeline step.  With R = 4 a 16 x 64 tile stages 6 x 18 cells where four 4 x 64 tiles staged
 // 4 x (3 x 18).
-#ifndef WALDO_FCW_COMPACT_CHUNK
-#define WALDO_FCW_COMPACT_CHUNK 4  // slots whose loads are in flight together
-#endif
-#ifndef WALDO_FCW_COMPACT
-#define WALDO_FCW_COMPACT 0  // > 0 (variant builds only): slots of the per-TILE compact layer list, round 6's bounded experiment --
-                             // bit-identical and 8-13 % SLOWER (tools_dev/dropped/flow_ctx_warp_compact.hip.h); 0: not compiled
-#endif
-template <int LP, bool SCORE, int R, int KS = 0>
+// (Round 6 tried a per-TILE compact list of the layers present: bit-identical and 8-13 % SLOWER; git show
+// 93480c2:tools_dev/dropped/flow_ctx_warp_compact.hip.h.)
+template <int LP, bool SCORE, int R>
 __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R > 1 && LP <= 17) ? 4 : 1)) void flow_ctx_warp_kernel(
     const float* __restrict__ flow_lr, const float* __restrict__ isobj_lr,
     const float* __restrict__ a01, const int64_t* __restrict__ ctx_ts,
@@ -228,11 +201,7 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
   const int Hd = H * scale, Wd = W * scale;
   const int64_t HWd = (int64_t)Hd * Wd, HW = (int64_t)H * W;
   int m, x, y_first;  // m = (b, tc, tp)
-#if WALDO_FCW_TP_INNER
-  if (!hd_pixel_rows_grouped<R>(units / Tp, Tp, Hd, Wd, tiles, nbands, m, x, y_first)) return;
-#else
   if (!hd_pixel_rows<R>(units, Hd, Wd, tiles, nbands, m, x, y_first)) return;
-#endif
   const int tp = m % Tp, b = m / (Tc * Tp);
   const float rscale = 1.0f / (float)scale;
   // frame of the context alpha (clamped: the index comes from device memory; an index outside the window is reported
@@ -268,10 +237,6 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
   float fx_lo = INFINITY, fx_hi = -INFINITY, fy_lo = INFINITY, fy_hi = -INFINITY;
   __shared__ float wave_box[kBlock / kWave][4];
   __shared__ unsigned wave_seen[kBlock / kWave];
-#if WALDO_FCW_COMPACT
-  unsigned mine = 0;  // bit l: this thread staged a cell of layer l whose object mask may pass the ghost test
-  __shared__ unsigned wave_bits[kBlock / kWave];
-#endif
   if (staged) {
     // thread = (cell, layer group): kBlock / area groups share the layers of a cell
     const int ngrp = kBlock / area;
@@ -287,11 +252,6 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
         const float* fl = flow_lr + (((int64_t)m * L + lc) * 2) * HW + off;
         f32x4 rec = {fl[0], fl[HW], 0.0f, 0.0f};
         if (nob && lc >= 1) rec[2] = isobj_lr[((int64_t)m * (L - 1) + (lc - 1)) * HW + off];
-#if WALDO_FCW_COMPACT
-        // (a pixel's mask is a convex combination of four cells, rounded: 0.8999 keeps a margin below the test's 0.9;
-        // a NaN cell counts as present)
-        if (KS > 0 && l < L && !(rec[2] <= 0.8999f)) mine |= 1u << l;
-#endif
         flow_bad |= !(fabsf(rec[0]) <= 3.0e38f) | !(fabsf(rec[1]) <= 3.0e38f);
         if (layer_bits != nullptr) {  // (uniform)
           fx_lo = fminf(fx_lo, rec[0]), fx_hi = fmaxf(fx_hi, rec[0]);
@@ -311,16 +271,9 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
       wb[0] = fx_lo, wb[1] = fx_hi, wb[2] = fy_lo, wb[3] = fy_hi;
     }
   }
-#if WALDO_FCW_COMPACT
-  if (KS > 0) {  // the wavefront's OR of `mine`, one word per wavefront (read behind the barrier below)
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine |= (unsigned)__shfl_xor((int)mine, d, kWave);
-    if ((threadIdx.x & (kWave - 1)) == 0) wave_bits[threadIdx.x >> 6] = mine;
-  }
-#endif
   // (the barrier doubles as the vote: a non-finite entry anywhere in the order or in the tile's low-resolution flows
   // switches the skipping below off; a tile whose patch is not staged is not examined: dense)
-  const bool dense = WALDO_FCW_SPARSE ? (__syncthreads_or(occ_bad | flow_bad | !staged) != 0) : (__syncthreads(), true);
+  const bool dense = __syncthreads_or(occ_bad | flow_bad | !staged) != 0;
   // ---- the layers PRESENT around this tile's samples (no ghost mask: Warper.grid_to_flow, lvd.py:602-705).  The
   // first pass left one word per (frame, row, 64-pixel segment) of the context frame's composited alphas: bit l = layer
   // l is non-zero somewhere in the segment (`layer_bits`).  A sample of this tile lands at pixel + flow with the flow
@@ -365,14 +318,9 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
     __syncthreads();
     present = (unsigned)__builtin_amdgcn_readfirstlane((int)(wave_seen[0] | wave_seen[1] | wave_seen[2] | wave_seen[3]));
   }
-  int rr_first = 0;
-#if WALDO_FCW_COMPACT  // (variant builds only: round 6's rejected experiment, tools_dev/dropped/)
-#include "flow_ctx_warp_compact.hip.h"
-#else
   if (x >= Wd) return;
-#endif
 #pragma unroll 1
-  for (int rr = rr_first; rr < R; ++rr) {
+  for (int rr = 0; rr < R; ++rr) {
   const int y = y_first + kHdRows * rr;
   if (y >= Hd) break;
   const int64_t p = (int64_t)y * Wd + x;
@@ -403,28 +351,14 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
   // below) switches everything back to all L layers and all L x L factors, so NaNs propagate exactly as before.
   // (the tall tiles only: at one pixel per thread the low-resolution taps may come from memory -- the LVD recipe, where
   // every layer is active -- and taking them twice costs 34 more loads per pixel: 55 -> 71 us per call there)
-  constexpr bool kReflow = WALDO_FCW_REFLOW && R > 1;
+  // (the tall tiles take the upsampled flow of a layer AGAIN where its composited alpha is known -- active layers only --
+  // instead of keeping it per layer: 2 LP registers fewer across the occlusion product)
+  constexpr bool kReflow = R > 1;
   float a[LP], fx[kReflow ? 1 : LP], fy[kReflow ? 1 : LP];
   float dis = -INFINITY;
   const float* ap0 = a01 + (((int64_t)b * Tw + ts) * L) * HWd;  // plane of layer l: + min(l, L - 1) * HWd
   unsigned active = 0;  // wave-uniform: bit l = some lane has a[l] != 0
   bool wild = false;    // some lane sampled a non-finite alpha
-  // the object masks of all layers up front (staged tiles): 4 (L - 1) four-byte LDS reads in flight together, one
-  // wait; bit l of keep_bits (per lane) = layer l is visible here, bit l of want_bits (wave-uniform) = in some lane
-  unsigned keep_bits = 0xffffffffu, want_bits = 0xffffffffu;
-  if (WALDO_FCW_MASK_FIRST == 2 && staged && nob) {
-    float g[LP];
-#pragma unroll
-    for (int l = 1; l < LP; ++l)
-      g[l] = up_blend(ut, lrimg[lt.o00 + 4 * l + 2], lrimg[lt.o01 + 4 * l + 2], lrimg[lt.o10 + 4 * l + 2],
-                      lrimg[lt.o11 + 4 * l + 2]);
-#pragma unroll
-    for (int l = 1; l < LP; ++l) {
-      const bool kp = g[l] > 0.9f;
-      if (!kp) keep_bits &= ~(1u << l);
-      if (__ballot(kp) == 0ull) want_bits &= ~(1u << l);
-    }
-  }
   auto layers = [&](auto from_lds) {
     constexpr bool LDS = decltype(from_lds)::value;
     constexpr int CH = LP < WALDO_FCW_CHUNK ? LP : WALDO_FCW_CHUNK;  // layers whose loads are in flight together
@@ -440,25 +374,21 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
         if (l >= LP) break;
         float fxl = 0.0f, fyl = 0.0f, g = 1.0f;
         const bool masked = l >= 1 && nob;  // uniform: this layer has an object mask
-        bool want;
-        if (WALDO_FCW_MASK_FIRST == 2 && LDS) {
-          keep[k] = (keep_bits >> l) & 1u;
-          want = l < L && (WALDO_FCW_SPARSE ? ((want_bits & present) >> l & 1u) != 0 : true);
-        } else {
-          if (LDS) {
-            // the mask alone first (four 4-byte reads): most layers stop here
-            if (masked)
-              g = up_blend(ut, lrimg[lt.o00 + 4 * l + 2], lrimg[lt.o01 + 4 * l + 2], lrimg[lt.o10 + 4 * l + 2],
-                           lrimg[lt.o11 + 4 * l + 2]);
-          } else if (masked) {
-            g = up_sample(isobj_lr + ((int64_t)m * (L - 1) + max(min(l, L - 1) - 1, 0)) * HW, ut);
-          }
-          keep[k] = !(masked && !(g > 0.9f));
-          // a padding layer (l >= L) is never sampled: its alpha is 0 by definition; nor is a layer that is absent from
-          // every segment this tile's samples can reach (`present`)
-          want = l < L && (WALDO_FCW_SPARSE ? (__ballot(keep[k]) != 0ull && ((present >> l) & 1u) != 0) : true);
+        if (LDS) {
+          // the mask alone first (four 4-byte reads), the flow record only if the layer is wanted: most layers stop
+          // here.  C5 pipeline, A/B on one box (tools_dev/ab_pipeline.sh): 7.55 ms per step against 7.67 with whole
+          // records of every layer and 7.80 with the masks of ALL layers up front (one LDS round trip)
+          if (masked)
+            g = up_blend(ut, lrimg[lt.o00 + 4 * l + 2], lrimg[lt.o01 + 4 * l + 2], lrimg[lt.o10 + 4 * l + 2],
+                         lrimg[lt.o11 + 4 * l + 2]);
+        } else if (masked) {
+          g = up_sample(isobj_lr + ((int64_t)m * (L - 1) + max(min(l, L - 1) - 1, 0)) * HW, ut);
         }
-        if (want || ((dense || WALDO_FCW_MASK_FIRST == 0) && l < L)) {  // (dense: the flow of every layer, its product with alpha 0 may be NaN)
+        keep[k] = !(masked && !(g > 0.9f));
+        // a padding layer (l >= L) is never sampled: its alpha is 0 by definition; nor is a layer that is absent from
+        // every segment this tile's samples can reach (`present`)
+        const bool want = l < L && __ballot(keep[k]) != 0ull && ((present >> l) & 1u) != 0;
+        if (want || (dense && l < L)) {  // (dense: the flow of every layer, its product with alpha 0 may be NaN)
           if (LDS) {
             const f32x2_p v00 = *reinterpret_cast<const f32x2_p*>(lrimg + lt.o00 + 4 * l);
             const f32x2_p v01 = *reinterpret_cast<const f32x2_p*>(lrimg + lt.o01 + 4 * l);
@@ -476,11 +406,7 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
         if (want) {
           need |= 1u << k;
           pt[k] = pair_taps(gx0 + fxl, gy0 + fyl, Hd, Wd, inter[k]);
-#ifdef WALDO_ABL_FCW_NOGATHER  // timing-only ablation: one coalesced load instead of the taps
-          ra[k] = rb[k] = (f32x2_p){ap0[p], fxl};
-#else
           pair_load(ap0 + (int64_t)min(l, L - 1) * HWd, pt[k], ra[k], rb[k]);
-#endif
         }
         if (k & 1) __builtin_amdgcn_sched_barrier(0);  // the LDS records of two layers at a time (32 registers)
       }
@@ -507,7 +433,7 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
   };
   if (R > 1 || staged) layers(std::true_type{});
   else layers(std::false_type{});
-  if (!WALDO_FCW_SPARSE || dense || wild) active = L >= 32 ? 0xffffffffu : (1u << L) - 1u;
+  if (dense || wild) active = L >= 32 ? 0xffffffffu : (1u << L) - 1u;
   disocc[(int64_t)m * HWd + p] = dis;
   float ox = 0.0f, oy = 0.0f;
   float amax = -INFINITY;  // max over the layers of the composited alpha (Synthesizer.predict's disocclusion test)
@@ -519,9 +445,6 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
 #pragma unroll
   for (int j = 0; j < LP; j += 4) {
     f32x2_w prd[2] = {{1.0f, 1.0f}, {1.0f, 1.0f}};
-#ifdef WALDO_ABL_FCW_NOOCC  // timing-only ablation: without the L x L products
-    prd[0][0] = occm[j];
-#else
     if ((active >> j) & 0xfu) {  // wave-uniform
 #pragma unroll
       for (int i = 0; i < LP; ++i) {
@@ -538,11 +461,12 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
         }
       }
     }
-#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (j + k >= LP) break;
-      if (!(WALDO_FCW_CONST_OUT || kReflow) || (active & (1u << (j + k)))) {  // wave-uniform
+      // (without the reflow every layer's outputs are computed: writing those outside the active set as constants
+      // behind a wave-uniform branch measured SLOWER, 8.1 against 7.6 ms: twelve more branches cut the store stream up)
+      if (!kReflow || (active & (1u << (j + k)))) {  // wave-uniform
         const float v = a[j + k] * prd[k >> 1][k & 1];
         if (kReflow) {
           // the layer's upsampled flow again (the same expressions as in the sampling loop: the same bits), for the
@@ -568,20 +492,16 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
           ox += v * fx[j + k];
           oy += v * fy[j + k];
         }
-#ifndef WALDO_ABL_FCW_NOSTORE
         if (j + k < L) {
           const float av = v * 2.0f - 1.0f;
           ac[p] = av;
           amax = nan_max(amax, av);
           if (SCORE) ssum += (av + 1.0f) / 2.0f;
         }
-#endif
       } else if (j + k < L) {
         // alpha 0 in every lane (all operands finite): 2 * 0 - 1, + 0 to the score and to the flow
-#ifndef WALDO_ABL_FCW_NOSTORE
         ac[p] = -1.0f;
         amax = nan_max(amax, -1.0f);
-#endif
       }
       if (j + k < L) ac += HWd;
     }
@@ -611,19 +531,8 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
 #ifndef WALDO_FWF_BANDS
 #define WALDO_FWF_BANDS 8
 #endif
-#ifndef WALDO_FWF_TP_INNER
-#define WALDO_FWF_TP_INNER 1  // the Tp predicted frames of a clip innermost in an XCD's tile walk (HdTile::pixel_grouped)
-#endif
-#ifndef WALDO_FWF_NT
-#define WALDO_FWF_NT 1  // non-temporal stores for out / raw (read next by another kernel, far larger than any cache): -3.5 %
-#endif
-__device__ __forceinline__ void fwf_store(float* p, float v) {
-#if WALDO_FWF_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+// non-temporal stores for out / raw (read next by another kernel, far larger than any cache): -3.5 %
+__device__ __forceinline__ void fwf_store(float* p, float v) { __builtin_nontemporal_store(v, p); }
 
 // Tile shape (tools_dev/ab_hd.py --amp, C5 size, ms at flow amplitudes of 10 / 25 / 50 / 150 px over 32-pixel
 // cells): 4 x 64 (a wavefront = one 64-pixel row segment, as the other kernels of this file) 3.86 / 4.89 / 6.53
@@ -638,12 +547,8 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
     float* __restrict__ raw, int* __restrict__ status, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
     float eps, int units, int tiles, int nbands) {
   const int64_t HWd = (int64_t)Hd * Wd;
-  int n, x, y;  // n = (b, tp)
-#if WALDO_FWF_TP_INNER
+  int n, x, y;  // n = (b, tp); the Tp predicted frames of a clip innermost in an XCD's tile walk
   if (!HdTile<WALDO_FWF_TILE_COLS>::pixel_grouped(units / Tp, Tp, Hd, Wd, tiles, nbands, n, x, y) || x >= Wd || y >= Hd) return;
-#else
-  if (!HdTile<WALDO_FWF_TILE_COLS>::pixel(units, Hd, Wd, tiles, nbands, n, x, y) || x >= Wd || y >= Hd) return;
-#endif
   const int b = n / Tp, tp = n % Tp;
   const int64_t p = (int64_t)y * Wd + x;
   float gx0, gy0;
@@ -727,16 +632,12 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
       const float* plane = frame[tc] + (int64_t)c * HWd;
-#ifdef WALDO_ABL_FWF_NOGATHER  // timing-only ablation: one coalesced load instead of the four taps
-      v[tc][0] = v[tc][1] = v[tc][2] = v[tc][3] = plane[p];
-#else
       const f32x2_fw top = *reinterpret_cast<const f32x2_fw*>(reinterpret_cast<const char*>(plane) + ob0[tc]);
       const f32x2_fw bot = *reinterpret_cast<const f32x2_fw*>(reinterpret_cast<const char*>(plane) + ob1[tc]);
       v[tc][0] = top[0];
       v[tc][1] = top[1];
       v[tc][2] = bot[0];
       v[tc][3] = bot[1];
-#endif
     }
   };
   // corners of the footprint from the pair elements (see above); a no-op for interior wavefronts
@@ -762,9 +663,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
       const float v = fmaf(tv[tc][3], w11[tc], fmaf(tv[tc][2], w10[tc], fmaf(tv[tc][1], w01[tc], tv[tc][0] * w00[tc])));
-#ifndef WALDO_ABL_FWF_NORAW  // timing-only ablation: without the per-context stores
       if (tc < Tc) fwf_store(rbase + ((int64_t)tc * (C + L) + c) * HWd, v);
-#endif
       acc += v * wt[tc];
     }
     if (include_self) {
@@ -797,9 +696,6 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
 // reads the taps from there -- four coalesced loads per thread and channel instead of eight gathers, every line
 // requested once per tile.  Channel c + 1's loads are in flight while channel c is sampled and stored; two LDS-only
 // barriers per channel (no vmcnt wait: the stores keep draining).  Same taps, weights and arithmetic: same bits.
-#ifndef WALDO_FWF_LDS
-#define WALDO_FWF_LDS 1
-#endif
 constexpr int kFwfCap = 1024;  // texels of one context's staged box = one float4 per thread
 // FULL: Tc == TCP and no `include_self` -- every vector-memory operation of the channel loop is then unconditional,
 // and the wait for channel c + 1's box can leave channel c's stores in flight (with a store behind a branch the
@@ -807,13 +703,6 @@ constexpr int kFwfCap = 1024;  // texels of one context's staged box = one float
 #ifndef WALDO_FWF_LDS_WAVES
 #define WALDO_FWF_LDS_WAVES 4  // 116 VGPRs, NO scratch.  (Five waves -- 96 VGPRs -- measured the same speed in round 4 and spilled two
                                // dwords: a kernel with scratch inside a replayed HIP graph faulted on this stack)
-#endif
-#ifndef WALDO_FWF_PER_CONTEXT
-#define WALDO_FWF_PER_CONTEXT 1  // Tc = 4: a context whose box does not fit gathers ALONE (0: the whole tile, as in round 4)
-#endif
-#ifndef WALDO_FWF_LDS_DB
-#define WALDO_FWF_LDS_DB 0  // 1: two sets of images, alternating by channel: one barrier per channel instead of two, 33 KB and four
-                            // waves per SIMD -- 9.17-9.42 against 9.09-9.19 ms per C5 step with one set at five waves (A/B)
 #endif
 template <int TCP, bool FULL>
 __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_lds_kernel(
@@ -839,7 +728,9 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   const int t = (int)threadIdx.x, lane = t & (kWave - 1), wave = t >> 6;
   float gx0, gy0;
   identity_grid(x, y, Wd, Hd, gx0, gy0);
-  __shared__ __attribute__((aligned(16))) float img[WALDO_FWF_LDS_DB ? 2 : 1][TCP][kFwfCap];
+  // (one image per context.  Two sets alternating by channel -- one barrier per channel instead of two, 33 KB and four
+  // waves per SIMD -- measured 9.17-9.42 against 9.09-9.19 ms per C5 step with one set at five waves, A/B)
+  __shared__ __attribute__((aligned(16))) float img[TCP][kFwfCap];
   __shared__ int wbox[kBlock / kWave][TCP][2];
 
   const int Tcx = Tc + (include_self ? 1 : 0);
@@ -956,9 +847,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
       const float v = fmaf(v4[tc][3], w11[tc], fmaf(v4[tc][2], w10[tc], fmaf(v4[tc][1], w01[tc], v4[tc][0] * w00[tc])));
-#ifndef WALDO_ABL_FWF_NORAW
       if (FULL || tc < Tc) fwf_store(rbase + ((int64_t)tc * (C + L) + c) * HWd, v);
-#endif
       acc += v * wt[tc];
     }
     if (include_self) {
@@ -967,9 +856,6 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     }
     fwf_store(obase + (int64_t)c * HWd, acc);
   };
-#ifdef WALDO_ABL_FWF_ALLSTAGED  // timing-only ablation: no tile gathers (wrong values where a box does not fit)
-  stage_mask = (1u << TCP) - 1u;
-#endif
   // The channel loop for a compile-time set of staged contexts (bit tc of MASK): a staged context's taps come from
   // its LDS image (one float4 of its box per thread and channel, loaded a channel ahead), the others' straight from
   // memory as two 8-byte pairs, also a channel ahead.  Round 4 had two loops -- every context staged, or the WHOLE
@@ -1004,10 +890,10 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
         }
       }
     };
-    auto park = [&](int set) {
+    auto park = [&]() {
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc)
-        if (((MASK >> tc) & 1u) && ((mine >> tc) & 1u)) *reinterpret_cast<f32x4*>(&img[set][tc][4 * t]) = box4[tc];
+        if (((MASK >> tc) & 1u) && ((mine >> tc) & 1u)) *reinterpret_cast<f32x4*>(&img[tc][4 * t]) = box4[tc];
     };
     auto take = [&]() {  // the pairs loaded a channel ahead become this channel's
 #pragma unroll
@@ -1018,17 +904,16 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
         }
     };
     issue(0);
-    park(0);
+    park();
     take();
     if (kAny) lds_barrier();
     for (int c = 0; c < C; ++c) {
       issue(min(c + 1, C - 1));  // in flight while channel c is sampled and stored (the last trip re-reads its own)
-      const int set = WALDO_FWF_LDS_DB ? (c & 1) : 0;
       float tv[TCP][4];
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc) {
         if ((MASK >> tc) & 1u) {
-          const char* im = reinterpret_cast<const char*>(&img[set][tc][0]);
+          const char* im = reinterpret_cast<const char*>(&img[tc][0]);
           tv[tc][0] = *reinterpret_cast<const float*>(im + ob0[tc]);
           tv[tc][1] = *reinterpret_cast<const float*>(im + ob0[tc] + 4);
           tv[tc][2] = *reinterpret_cast<const float*>(im + ob1[tc]);
@@ -1040,15 +925,15 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
       }
       assign(tv);
       fuse_store(c, tv);
-      if (kAny && !WALDO_FWF_LDS_DB) lds_barrier();  // every thread has read channel c's taps
-      park(WALDO_FWF_LDS_DB ? (set ^ 1) : 0);  // (waits for the boxes of channel c + 1, not for channel c's stores; the other
-                                               // set was last read before the previous trip's barrier)
+      if (kAny) lds_barrier();  // every thread has read channel c's taps
+      park();  // (waits for the boxes of channel c + 1, not for channel c's stores)
       take();
       if (kAny) lds_barrier();
     }
   };
-  // (uniform dispatch; a context beyond Tc repeats context Tc - 1: same box, same bit)
-  if (FULL && TCP == 4 && WALDO_FWF_PER_CONTEXT) {
+  // (uniform dispatch; a context beyond Tc repeats context Tc - 1: same box, same bit.  Tc = 4: a context whose box
+  // does not fit gathers ALONE, where round 4 gathered for the whole tile)
+  if (FULL && TCP == 4) {
     switch (stage_mask & 15u) {
 #define WALDO_FWF_CASE(M) case M: channel_loop(std::integral_constant<unsigned, M>{}); break;
       WALDO_FWF_CASE(0) WALDO_FWF_CASE(1) WALDO_FWF_CASE(2) WALDO_FWF_CASE(3) WALDO_FWF_CASE(4) WALDO_FWF_CASE(5)
@@ -1138,8 +1023,7 @@ extern "C" int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* inpu
 }
 
 #define WALDO_FCW_LAUNCH(LPV, SC, RV)                                                                          \
-  hipLaunchKernelGGL((flow_ctx_warp_kernel<LPV, SC, RV, (RV == kFcwRows && kFcwRows > 1 && LPV >= 8 && LPV <= 17) ? WALDO_FCW_COMPACT : 0>), \
-                     dim3((unsigned)fcw_grid), dim3(kBlock), 0, st,                                           \
+  hipLaunchKernelGGL((flow_ctx_warp_kernel<LPV, SC, RV>), dim3((unsigned)fcw_grid), dim3(kBlock), 0, st,      \
                      flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, alpha_ctx, lay, score, disocc, alpha_max, \
                      layer_bits, status, T, Tw, Tc, Tp, L, H, W, scale, (int)N, geom.tiles, geom.nbands)
 #define WALDO_FCW_CASE(LPV)                                        \
@@ -1186,12 +1070,7 @@ static int flow_ctx_warp_launch(const char* fn, const float* flow_lr, const floa
   };
   const int rows = scale < 2 ? 1 : (fits(kFcwRows) ? kFcwRows : (fits(2) ? 2 : 1));
   HdGeom geom = hd_geom_rows(N, H * scale, W * scale, rows);
-#if WALDO_FCW_TP_INNER
-  geom.nbands = 8;
-  const int64_t fcw_grid = xcd_grid_banded((int64_t)B * Tc, geom.nbands, geom.tiles, Tp);
-#else
   const int64_t fcw_grid = hd_grid(N, geom);
-#endif
   if (fcw_grid > 2147483647) {
     set_error("%s: problem too large for one launch", fn);
     return WALDO_EINVAL;
@@ -1268,12 +1147,8 @@ static int frame_warp_fuse_launch(const char* fn, const float* input, const floa
     set_error("%s: null pointer", fn);
     return WALDO_EINVAL;
   }
-#if WALDO_FWF_TP_INNER
   const dim3 grid((unsigned)xcd_grid_banded(B, geom.nbands, geom.tiles, Tp));
-#else
-  const dim3 grid((unsigned)hd_grid(units, geom));
-#endif
-#if WALDO_FWF_LDS && WALDO_FWF_TP_INNER && WALDO_FWF_TILE_COLS == 32
+#if WALDO_FWF_TILE_COLS == 32
   // (16-byte loads of the boxes: rows that start on a multiple of four texels from a 16-byte aligned base)
   if (Wd % 4 == 0 && (reinterpret_cast<uintptr_t>(input) & 15) == 0 && Tc <= 4) {
     // (the context count is a template parameter: a padding context repeats the last real one -- its taps, its box, its

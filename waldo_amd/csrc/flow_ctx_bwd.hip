@@ -339,14 +339,10 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bw
               const float wx0 = 1.0f - t.fx, wy0 = 1.0f - t.fy;
               const float w00 = wx0 * wy0 * (t.vx0 * t.vy0), w01 = t.fx * wy0 * (t.vx1 * t.vy0);
               const float w10 = wx0 * t.fy * (t.vx0 * t.vy1), w11 = t.fx * t.fy * (t.vx1 * t.vy1);
-#ifndef WALDO_ABL_FCB_NOATOMIC  // timing-only ablation: without the scatter
               if (w00 != 0.0f) atomicAdd(gp + (t.o00 >> 2), gsg * w00);
               if (w01 != 0.0f) atomicAdd(gp + (t.o01 >> 2), gsg * w01);
               if (w10 != 0.0f) atomicAdd(gp + (t.o10 >> 2), gsg * w10);
               if (w11 != 0.0f) atomicAdd(gp + (t.o11 >> 2), gsg * w11);
-#else
-              if (w00 + w01 + w10 + w11 == 123.0f) gp[0] = gsg;
-#endif
             }
           }
         }
@@ -510,19 +506,10 @@ static int acc_tiles(int64_t units, int64_t tiles) {  // tiles per workgroup: ke
   return (int)min((int64_t)kAccTilesMax, max((int64_t)1, units * tiles / WALDO_FCB_MIN_WGS));
 }
 
-// the lane-layer kernels (tools_dev/dropped/flow_ctx_bwd_rows.hip.h: round 5's experiment) serve 9 .. 17 layers; measured
-// no faster than the per-pixel ones at the LVD recipe (warp 0.210 against 0.217 ms, alpha 0.206 against 0.165): they
-// exist in VARIANT builds only (tools_dev/build_variant.py NAME -DWALDO_VARIANT_FCB_ROWS), where they take every
-// launch they can serve
-#ifdef WALDO_VARIANT_FCB_ROWS
-static bool rows_kernels(int L) { return L >= 9 && L <= 17; }
-#endif
+// Round 5's lane-layer kernels for 9 .. 17 layers were no faster than the per-pixel ones at the LVD recipe (warp 0.210
+// against 0.217 ms, alpha 0.206 against 0.165) and were dropped (git show 93480c2:tools_dev/dropped/flow_ctx_bwd_rows.hip.h).
 
 }  // namespace waldo
-
-#ifdef WALDO_VARIANT_FCB_ROWS
-#include "flow_ctx_bwd_rows.hip.h"
-#endif
 
 using namespace waldo;
 
@@ -561,20 +548,7 @@ extern "C" int waldo_flow_ctx_alpha_bwd(const float* alpha_lr, const float* inpu
   const int tiles = (int)(((int64_t)H * scale * W * scale + kBlock - 1) / kBlock);
   const int tpb = acc_tiles(N, tiles), groups = (tiles + tpb - 1) / tpb;
   float* gup = scale > 1 ? workspace : grad_alpha_lr;
-#ifdef WALDO_VARIANT_FCB_ROWS
-  if (rows_kernels(L)) {
-    if (dist == nullptr || Nl <= 20)
-      hipLaunchKernelGGL(flow_ctx_alpha_bwd_rows_kernel<20>, dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, alpha_lr,
-                         input, dist, occ, grad_a01, grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, chan_off, H, W,
-                         scale, tiles, tpb, groups);
-    else
-      hipLaunchKernelGGL(flow_ctx_alpha_bwd_rows_kernel<32>, dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, alpha_lr,
-                         input, dist, occ, grad_a01, grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, chan_off, H, W,
-                         scale, tiles, tpb, groups);
-  } else
-#endif
-  {
-    // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
+  // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
 #define WALDO_FCAB_CASE(LPV)                                                                                             \
   case LPV:                                                                                                              \
     if (dist == nullptr || Nl <= kFewCls)                                                                                \
@@ -586,16 +560,15 @@ extern "C" int waldo_flow_ctx_alpha_bwd(const float* alpha_lr, const float* inpu
                          alpha_lr, input, dist, occ, grad_a01, grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, \
                          chan_off, H, W, scale, tiles, tpb, groups);                                                     \
     break;
-    switch (flow_ctx_pad_l(L)) {
-      WALDO_FCAB_CASE(4)
-      WALDO_FCAB_CASE(8)
-      WALDO_FCAB_CASE(12)
-      WALDO_FCAB_CASE(17)
-      WALDO_FCAB_CASE(24)
-      WALDO_FCAB_CASE(32)
-    }
-#undef WALDO_FCAB_CASE
+  switch (flow_ctx_pad_l(L)) {
+    WALDO_FCAB_CASE(4)
+    WALDO_FCAB_CASE(8)
+    WALDO_FCAB_CASE(12)
+    WALDO_FCAB_CASE(17)
+    WALDO_FCAB_CASE(24)
+    WALDO_FCAB_CASE(32)
   }
+#undef WALDO_FCAB_CASE
   if (scale > 1) {
     const int64_t P = N * L;
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -625,13 +598,6 @@ extern "C" int waldo_flow_ctx_warp_bwd(const float* flow_lr, const float* isobj_
   const int tiles = (int)(((int64_t)H * scale * W * scale + kBlock - 1) / kBlock);
   const int tpb = acc_tiles(N, tiles), groups = (tiles + tpb - 1) / tpb;
   float* gup = scale > 1 ? workspace : grad_flow_lr;
-#ifdef WALDO_VARIANT_FCB_ROWS
-  if (rows_kernels(L))
-    hipLaunchKernelGGL(flow_ctx_warp_bwd_rows_kernel, dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, flow_lr, isobj_lr,
-                       a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw,
-                       Tc, Tp, L, H, W, scale, tiles, tpb, groups);
-  else
-#endif
   switch (flow_ctx_pad_l(L)) {
     WALDO_FCB_CASE(4, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
     WALDO_FCB_CASE(8, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)

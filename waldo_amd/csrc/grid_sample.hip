@@ -61,20 +61,16 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_fwd_kernel(
 // Sum of v over the lanes from this one to the end of its RUN (consecutive lanes with the same scatter address;
 // `stop`: the run ends at this lane).  After the step of distance d a lane that has not met its run's end has summed d
 // more lanes, all of its run, so lane + d exists: no range check.
-// Runs end at the 16-lane ROW boundaries (WALDO_GS_RUN_ROWS): the four steps are DPP row shifts -- two VALU operations
+// Runs end at the 16-lane ROW boundaries: the four steps are DPP row shifts -- two VALU operations
 // each, no LDS crossbar -- where six steps of two ds_bpermute round trips each made the hot wavefronts (the few whose
 // pixels land inside the object's canvas) crawl; a run cut by a row boundary costs one more atomic.  The runs are
 // 2 - 4 lanes long where a 64 x 64 canvas covers ~100 frame pixels.
-#ifndef WALDO_GS_RUN_ROWS
-#define WALDO_GS_RUN_ROWS 1
-#endif
-constexpr int kRunSpan = WALDO_GS_RUN_ROWS ? 16 : kWave;
+constexpr int kRunSpan = 16;
 template <int D>
 __device__ __forceinline__ int row_from_above(int v) {  // lane i <- lane i + D of its row (row_shl:D; past the row: 0)
   return __builtin_amdgcn_update_dpp(0, v, 0x100 + D, 0xf, 0xf, true);
 }
 __device__ __forceinline__ float run_sum(float v, bool stop) {
-#if WALDO_GS_RUN_ROWS
   int st = stop ? 1 : 0;
 #define WALDO_GS_STEP(D)                                                         \
   {                                                                              \
@@ -88,23 +84,8 @@ __device__ __forceinline__ float run_sum(float v, bool stop) {
   WALDO_GS_STEP(1) WALDO_GS_STEP(2) WALDO_GS_STEP(4) WALDO_GS_STEP(8)
 #undef WALDO_GS_STEP
   return v;
-#else
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const float vo = __shfl_down(v, d, kWave);
-    const int so = __shfl_down((int)stop, d, kWave);
-    if (!stop) {
-      v += vo;
-      stop = so != 0;
-    }
-  }
-  return v;
-#endif
 }
 
-#ifndef WALDO_GS_RUNS
-#define WALDO_GS_RUNS 1  // the scatter of grad_input summed over runs of equal addresses inside a wavefront first
-#endif
 __global__ __launch_bounds__(kBlock) void grid_sample2d_bwd_kernel(
     const float* __restrict__ input, const float* __restrict__ grid,
     const float* __restrict__ grad_output, float* __restrict__ grad_input,
@@ -114,7 +95,6 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_bwd_kernel(
   const int64_t p_ = (int64_t)(blockIdx.x % tiles) * kBlock + threadIdx.x;
   // (a thread past the last pixel works on the last one with zero weights: it takes part in the wavefront's sums)
   const bool live = p_ < HWo;
-  if (!WALDO_GS_RUNS && !live) return;
   const int64_t p = live ? p_ : HWo - 1;
   const float2 g = *reinterpret_cast<const float2*>(grid + (n * HWo + p) * 2);
   const Taps t = make_taps(g.x, g.y, Hi, Wi);
@@ -136,16 +116,13 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_bwd_kernel(
   const float wq[4] = {live ? t.w00 : 0.0f, live ? t.w01 : 0.0f, live ? t.w10 : 0.0f, live ? t.w11 : 0.0f};
   bool stop[4], head[4];
   const bool scatter = grad_input != nullptr &&
-                       (!WALDO_GS_RUNS || __ballot(wq[0] != 0.0f || wq[1] != 0.0f || wq[2] != 0.0f || wq[3] != 0.0f) != 0ull);
-  if (WALDO_GS_RUNS && scatter) {
+                       __ballot(wq[0] != 0.0f || wq[1] != 0.0f || wq[2] != 0.0f || wq[3] != 0.0f) != 0ull;
+  if (scatter) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-#if WALDO_GS_RUN_ROWS  // (the neighbours inside the row; the row's first / last lane starts / ends a run whatever they hold)
+      // (the neighbours inside the row; the row's first / last lane starts / ends a run whatever they hold)
       const uint32_t nxt = (uint32_t)row_from_above<1>((int)key[q]);
       const uint32_t prv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)key[q], 0x111, 0xf, 0xf, true);  // row_shr:1
-#else
-      const uint32_t nxt = (uint32_t)__shfl_down((int)key[q], 1, kWave), prv = (uint32_t)__shfl_up((int)key[q], 1, kWave);
-#endif
       stop[q] = (lane & (kRunSpan - 1)) == kRunSpan - 1 || nxt != key[q];
       head[q] = (lane & (kRunSpan - 1)) == 0 || prv != key[q];
     }
@@ -163,20 +140,14 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_bwd_kernel(
       gix = fmaf(gv, ddx, gix);
       giy = fmaf(gv, bot - top, giy);
     }
-#ifndef WALDO_ABL_GS_NOATOMIC  // timing-only ablation: without the scatter
     if (scatter) {  // (wave-uniform)
       float* gp = grad_input + (nin * C + c) * HWi;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        if (WALDO_GS_RUNS) {
-          const float sum = run_sum(gvs * wq[q], stop[q]);
-          if (head[q] && sum != 0.0f) atomicAdd(gp + (key[q] >> 2), sum);
-        } else if (wq[q] != 0.0f) {
-          atomicAdd(gp + (key[q] >> 2), gvs * wq[q]);
-        }
+        const float sum = run_sum(gvs * wq[q], stop[q]);
+        if (head[q] && sum != 0.0f) atomicAdd(gp + (key[q] >> 2), sum);
       }
     }
-#endif
   }
   if (grad_grid != nullptr && live) {
     float2* o = reinterpret_cast<float2*>(grad_grid + (n * HWo + p) * 2);
@@ -185,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_bwd_kernel(
 }
 
 // Measured and dropped in round 4: the scatter summed in LDS first.  The kernel above is bound by its global atomics
-// (at the LVD recipe 58 us per call against 18 us with the scatter compiled out, -DWALDO_ABL_GS_NOATOMIC), so a
+// (at the LVD recipe 58 us per call against 18 us with the scatter compiled out), so a
 // variant gave every workgroup a BAND of output rows of one map, an LDS window of the input rows the band's taps
 // reach (ds_add_f32), and one coalesced global atomic per non-zero texel of the window at the end -- correct (it
 // passed the parity tests against the per-tap form and the oracle) and SLOWER: 84 / 74 / 77 / 72 us per call with
@@ -210,9 +181,6 @@ typedef float f32x2_gs __attribute__((ext_vector_type(2)));
 // none of whose 256 pixels has a corner inside the input -- object canvases warped into the frame cover a part of it
 // -- loads nothing: zeros-padding gives exactly `- delta` there.  At the KITTI recipe the warp of the object flows
 // writes 1.3 GB per call and took 0.55 ms.
-#ifndef WALDO_GS_PAIRS
-#define WALDO_GS_PAIRS 1
-#endif
 struct PairOff {
   uint32_t ob0, ob1;
   int shift;  // x0 - xb: -1 / 0 / +1 (beyond that every corner is invalid)
@@ -262,8 +230,8 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_fwd4_kernel(
     shift[q] = fmaf(delta + pre.bias, wsum, -delta);
     touches |= (t[q].vx0 + t[q].vx1) * (t[q].vy0 + t[q].vy1) != 0.0f;
   }
-  const bool pairs = WALDO_GS_PAIRS && Wi >= 2;  // (uniform)
-  if (pairs && __ballot(touches) == 0ull) {      // (wave-uniform) every corner outside: 0 * texel + shift
+  const bool pairs = Wi >= 2;  // (uniform)
+  if (pairs && __ballot(touches) == 0ull) {  // (wave-uniform) every corner outside: 0 * texel + shift
     for (int c = 0; c < C; ++c)
       *reinterpret_cast<f32x4_gs*>(out + (int64_t)c * HWo) = (f32x4_gs){shift[0], shift[1], shift[2], shift[3]};
     if (mask_out != nullptr) *reinterpret_cast<f32x4_gs*>(mask_out + n * HWo + p) = (f32x4_gs){0.0f, 0.0f, 0.0f, 0.0f};

@@ -67,13 +67,7 @@ bool debug_option(int option) {
 
 }  // namespace waldo
 
-// A timing-only ablation build (waldo_common.hip.h) reports version 0: no binding written against a real ABI
-// version accepts it by accident.
-#ifdef WALDO_TIMING_ONLY_BUILD
-extern "C" int waldo_version(void) { return 0; }
-#else
 extern "C" int waldo_version(void) { return 1019; }
-#endif
 
 extern "C" int waldo_set_debug_option(int option, int value) {
   if (option < 0 || option >= WALDO_DEBUG_COUNT) {

@@ -9,20 +9,6 @@
 #include "../../include/waldo_hip.h"
 #include "warp_composite_layout.hip.h"
 
-// The WALDO_ABL_* switches below and in the kernels are TIMING-ONLY ablations: several of them compute wrong values
-// on purpose (aliased frames, stores or gathers compiled out).  None of them may reach a product build: a translation
-// unit compiled with one of them and without -DWALDO_TIMING_ONLY_BUILD does not compile, and a library built with
-// that flag reports waldo_version() == 0 (csrc/runtime.hip), which waldo_amd._lib.load() refuses unless the library
-// was named explicitly (use_library / bench.py --lib).  tools_dev/build_variant.py passes the flag by itself.
-#if (defined(WALDO_ABL_NOFALLBACK) || defined(WALDO_ABL_FPB) || defined(WALDO_ABL_FCW_NOGATHER) ||              \
-     defined(WALDO_ABL_FCW_NOOCC) || defined(WALDO_ABL_FCW_NOSTORE) || defined(WALDO_ABL_FWF_NOGATHER) ||       \
-     defined(WALDO_ABL_FWF_NORAW) || defined(WALDO_ABL_FWF_ALLSTAGED) || defined(WALDO_ABL_FCB_NOATOMIC) ||     \
-     defined(WALDO_ABL_GS_NOATOMIC) || defined(WALDO_ABL_REC_ALIAS) || defined(WALDO_ABL_LAYER_ALIAS) ||        \
-     defined(WALDO_ABL_K1_LDS_PAD) || defined(WALDO_ABL_NO_REC_STORE) || defined(WALDO_ABL_ROWS_NOP2)) &&                                       \
-    !defined(WALDO_TIMING_ONLY_BUILD)
-#error "WALDO_ABL_* timing-only ablations need -DWALDO_TIMING_ONLY_BUILD (tools_dev/build_variant.py): not a product build"
-#endif
-
 namespace waldo {
 
 void set_error(const char* fmt, ...);
@@ -342,26 +328,9 @@ __device__ __forceinline__ void stream_store16(float* uniform_base, uint32_t byt
 }
 
 // measured at the headline shape (backward 2.247 ms with plain stores): records nt 2.210, sc1 2.236;
-// gradient planes nt 2.218; both nt 2.193; nt LOADS of the records in K2 2.267 (worse)
-// timing-only ablation (-DWALDO_ABL_REC_ALIAS=n, wrong values): every frame's records alias those of
-// frame f % n, i.e. the records stay resident in the Infinity Cache
-#ifdef WALDO_ABL_REC_ALIAS
-#define WALDO_REC_FRAME(f) ((f) % WALDO_ABL_REC_ALIAS)
-#else
-#define WALDO_REC_FRAME(f) (f)
-#endif
-// timing-only ablation (-DWALDO_ABL_LAYER_ALIAS=n, wrong values): the staged boxes of every frame are read
-// from frame f % n, i.e. the layer reads are served by the caches instead of HBM
-#ifdef WALDO_ABL_LAYER_ALIAS
-#define WALDO_LAYER_FRAME(f) ((f) % WALDO_ABL_LAYER_ALIAS)
-#else
-#define WALDO_LAYER_FRAME(f) (f)
-#endif
+// gradient planes nt 2.218; both nt 2.193; nt LOADS of the records in K2 2.267 (worse, so K2 loads them plainly)
 #ifndef WALDO_REC_STORE_POLICY
 #define WALDO_REC_STORE_POLICY 2
-#endif
-#ifndef WALDO_REC_LOAD_NT
-#define WALDO_REC_LOAD_NT 0
 #endif
 #ifndef WALDO_GRAD_STORE_POLICY
 #define WALDO_GRAD_STORE_POLICY 0  // K2's gradient planes: plain stores.  (Non-temporal was 2 % faster at three

@@ -82,21 +82,6 @@ struct Px16Cfg {
   static constexpr int kWavesPerSimd = LP <= 8 ? 3 : 2;
 };
 
-// Diagnostic build only (-DWALDO_K1_STAMPS): s_memtime stamps of wave 0 at the phase boundaries of
-// the LAST frame of a workgroup's chunk, into a buffer of the code object that no kernel reads
-// (tools_dev/k1_stamps.py); never compiled into the product library.
-#ifdef WALDO_K1_STAMPS
-constexpr int kStampSlots = 24, kStampBlocks = 8192;
-__device__ unsigned long long waldo_k1_stamps[kStampBlocks * kStampSlots];
-#define WALDO_STAMP(i)                                                                            \
-  do {                                                                                            \
-    if (threadIdx.x == 0 && f == f1 - 1 && blockIdx.x < kStampBlocks)                             \
-      waldo_k1_stamps[blockIdx.x * kStampSlots + (i)] = __builtin_amdgcn_s_memtime();             \
-  } while (0)
-#else
-#define WALDO_STAMP(i) do { } while (0)
-#endif
-
 template <int LP, bool EXL, bool GOCC>
 __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) void warp_composite_bwd_px16_kernel(
     const float* __restrict__ layers, const float* __restrict__ basis_t,
@@ -123,10 +108,7 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
   //   stage  per frame, in turn: the transposition slices of the grid, the staged layer image (two
   //          buffers), the transposed basis of phase (H) -- and, without parking, gg in front of it;
   //   boxred coordinate ranges per wave; wbound contribution-bound exponents per wave.
-#ifndef WALDO_ABL_K1_LDS_PAD  // timing-only ablation: extra LDS floats per workgroup (occupancy sweep)
-#define WALDO_ABL_K1_LDS_PAD 0
-#endif
-  __shared__ __attribute__((aligned(16))) float lds[C::kLdsFloats + WALDO_ABL_K1_LDS_PAD];
+  __shared__ __attribute__((aligned(16))) float lds[C::kLdsFloats];
   float* park = lds;
   float* img = lds + C::kParkFloats;
   float* gg = kPark ? park : img;
@@ -173,7 +155,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
     int lane = lane_k, arow = arow_k, kk = kk_k, pix = pix_k;
     asm volatile("" : "+v"(lane), "+v"(arow), "+v"(kk), "+v"(pix));
     const float* oc = occ + (int64_t)f * L * L;
-    WALDO_STAMP(0);
     // ---- (A) TPS grid of every layer on the matrix pipe, in pixel units (see
     // warp_composite_fwd_lds_kernel):
     // D[pixel][(layer, xy)] = sum_k basis[pixel][k] * mapping[k][(layer, xy)]
@@ -252,7 +233,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
       }
     }
     __syncthreads();  // ranges of all waves visible; the slices (inside the image) are free again
-    WALDO_STAMP(1);
     // ---- (D) box of the 2x2 blocks of every layer: lanes 0..15 turn the range of "their" column
     // (layer, xy) into block origins -- per cell of the footprint table (this tile owns its cells:
     // plain stores in the splat kernel's format (min x, -max x, min y, -max y)) and for the whole
@@ -297,10 +277,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
         by0[l] = ymin;
         bw[l] = ((xmax - bx0[l] + 1) + 3) & ~3;
         bh[l] = ymax - ymin + 1;
-#ifdef WALDO_ABL_NOFALLBACK  // timing-only ablation: oversize boxes are cut to the cap (wrong values)
-        bw[l] = min(bw[l], 128);
-        bh[l] = min(bh[l], kStageCap / bw[l]);
-#endif
         fits[l] = bh[l] * bw[l] <= kStageCap;  // block-uniform
       }
     }
@@ -324,7 +300,7 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
     StageRegs stg[LP];  // fully unrolled: a layer's registers live from its load to its LDS store
     auto issue = [&](int l) {
       const int lc = EXL ? l : min(l, L - 1);
-      const float* src = layers + ((int64_t)WALDO_LAYER_FRAME(f) * L + lc) * 4 * HW;
+      const float* src = layers + ((int64_t)f * L + lc) * 4 * HW;
       // unconditional loads (items past the box re-read its last item; a box that does not fit
       // reads texel 0): no exec-mask branches, so the loads are issued back to back
       const int bw2 = bw[l] >> 1, n = fits[l] ? bh[l] * bw2 : 1;
@@ -343,7 +319,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
 #pragma unroll
     for (int l = 0; l < kAhead; ++l) issue(l);
     WALDO_PRIO_OFF(WALDO_K1_PRIO_MASK, 2);
-    WALDO_STAMP(2);
     {
 #pragma unroll
       for (int l = 0; l < LP; ++l) {
@@ -371,7 +346,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
         float gal = 0.0f;
         if (grad_alpha != nullptr) gal = grad_alpha[((int64_t)f * L + l) * HW + p];
         __syncthreads();  // buffer l&1 complete; buffer (l+1)&1 no longer read by anyone
-        if (l < 8) WALDO_STAMP(3 + l);
         const TapCore tc = tap_core_px(gxs[l], gys[l], H, W);
         const float* b0 = img + (l & 1) * kImgBufFloats;
         float sv[4], sx[4], sy[4];
@@ -444,7 +418,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
       }
     }
 
-    WALDO_STAMP(11);
     // ---- (F) composite backward (lvd.py:100-114): a'_j = a_j prod_i (1 - a_i occ[i][j]).
     // Two layers j per step on the packed-fp32 pipe (v_pk_mul_f32 / v_pk_fma_f32: two lanes' worth of
     // work per VALU issue slot -- this kernel is issue bound); the contributions of even and odd j
@@ -511,20 +484,15 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
 #pragma unroll
       for (int l = 0; l < LP; ++l) ga[l] += ga2[l][0] + ga2[l][1];
     }
-    WALDO_STAMP(12);
     // ---- (G) a_m = (s_m3 + 1)/2 for m >= 1; a_0 is the constant 1.  Records, contribution bounds
     // and the grid gradient of every layer.  The records go out FIRST: the stores get the rest of
     // this phase to drain.
     WALDO_PRIO_ON(WALDO_K1_PRIO_MASK, 4);
-#ifndef WALDO_ABL_NO_REC_STORE  // timing-only ablation: K1 without its record stores (wrong gradients)
     if (live) {
-#else
-    if (live && H < 0) {
-#endif
 #pragma unroll
       for (int l = 0; l < LP; ++l)
         if (EXL || l < L)
-          stream_store16<WALDO_REC_STORE_POLICY>(reinterpret_cast<float*>(rec + ((int64_t)WALDO_REC_FRAME(f) * L + l) * HW),
+          stream_store16<WALDO_REC_STORE_POLICY>(reinterpret_cast<float*>(rec + ((int64_t)f * L + l) * HW),
                                                  (uint32_t)p * 16u, HW * 16,
                                                  (f32x4){gxs[l], gys[l], ap[l], l >= 1 ? 0.5f * ga[l] : 0.0f});
     }
@@ -584,7 +552,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
       for (int c = 2 * LP; c < GGC; ++c) ggw[c * OP] = 0.0f;
     }
     __syncthreads();  // gg rows and the waves' bounds are complete
-    WALDO_STAMP(13);
     {
       constexpr int kCellsPerTile = kLdsTile / kCellRows, kWavesPerCell = 4 / kCellsPerTile;
       if (threadIdx.x < kCellsPerTile * LP) {
@@ -654,7 +621,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
         }
       }
       WALDO_PRIO_OFF(WALDO_K1_PRIO_MASK, 8);
-      WALDO_STAMP(14);
       __syncthreads();  // every wave is done reading gg: reuse its bytes for the accumulators
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
@@ -680,7 +646,6 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
       }
     }
     __syncthreads();  // the stage region, boxred and wbound are re-used by the next frame
-    WALDO_STAMP(15);
   }
 }
 

@@ -45,42 +45,25 @@ namespace waldo {
 #ifndef WALDO_FWD8_WAVES
 #define WALDO_FWD8_WAVES 3   // register cap of the L <= 8 forward (it needs 109: four waves per SIMD)
 #endif
-// Wave priority (s_setprio) around the phases that ISSUE memory operations, so that a wavefront about to put loads or
-// stores in flight does not queue behind the other workgroups' tap arithmetic.  Level 0: off.  The masks pick the
-// phases: bit 0 a layer's staging stores + the next box loads, bit 1 a frame's first box loads (and K1's output-gradient
+// Wave priority (s_setprio 1) around the phases that ISSUE memory operations, so that a wavefront about to put loads or
+// stores in flight does not queue behind the other workgroups' tap arithmetic.  The masks pick the phases (0: none):
+// bit 0 a layer's staging stores + the next box loads, bit 1 a frame's first box loads (and K1's output-gradient
 // loads), bit 2 the output stores (K1: the records), bit 3 K1's MFMA contraction.
 // Measured (round 5, tools_dev/ab_bench.py, three boxes, same bits): K1 with bits 0 + 1: backward 2.050 -> 2.005 ms on
 // one box, 2.045 -> 2.035 and 2.060 -> 2.047 on two others (levels 1 / 2 / 3 alike); with the record stores or the MFMA
 // phase as well: nothing more; the forward: no change with any of its bits (+1 % with bit 2); K2 around its candidate
 // loads: +2.5 % (worse).  So: K1 alone, its loads alone.
-#ifndef WALDO_STAGE_PRIO
-#define WALDO_STAGE_PRIO 1
-#endif
 #ifndef WALDO_FWD_PRIO_MASK
 #define WALDO_FWD_PRIO_MASK 0
 #endif
 #ifndef WALDO_K1_PRIO_MASK
 #define WALDO_K1_PRIO_MASK 3
 #endif
-#define WALDO_PRIO_ON(mask, bit) do { if (WALDO_STAGE_PRIO && ((mask) & (bit))) __builtin_amdgcn_s_setprio(WALDO_STAGE_PRIO); } while (0)
-#define WALDO_PRIO_OFF(mask, bit) do { if (WALDO_STAGE_PRIO && ((mask) & (bit))) __builtin_amdgcn_s_setprio(0); } while (0)
+#define WALDO_PRIO_ON(mask, bit) do { if ((mask) & (bit)) __builtin_amdgcn_s_setprio(1); } while (0)
+#define WALDO_PRIO_OFF(mask, bit) do { if ((mask) & (bit)) __builtin_amdgcn_s_setprio(0); } while (0)
 #ifndef WALDO_STAGE_AHEAD
 #define WALDO_STAGE_AHEAD 2  // layers whose box loads are in flight at a time (measured 2 / 3 / 4 / 6 / 8:
                              // fwd 0.726 / 0.728 / 0.736 / 0.836 / 0.990 ms, bwd 2.222 / 2.225 / 2.242 / 2.58 / 2.59)
-#endif
-
-// Diagnostic build only (-DWALDO_FWD_STAMPS): s_memtime stamps of wave 0 at the phase boundaries of the first
-// frame of a workgroup's chunk (tools_dev/fwd_stamps.py); never compiled into the product library.
-#ifdef WALDO_FWD_STAMPS
-constexpr int kFwdStampSlots = 16, kFwdStampBlocks = 4096;
-__device__ unsigned long long waldo_fwd_stamps[kFwdStampBlocks * kFwdStampSlots];
-#define WALDO_FSTAMP(i)                                                                  \
-  do {                                                                                   \
-    if (threadIdx.x == 0 && blockIdx.x < kFwdStampBlocks)                                \
-      waldo_fwd_stamps[blockIdx.x * kFwdStampSlots + (i)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define WALDO_FSTAMP(i) do { } while (0)
 #endif
 
 struct BoxTaps {
@@ -210,7 +193,7 @@ __device__ __forceinline__ f32x2_t lerp2(const f32x2_t p00, const f32x2_t p01, c
 // its launch gap were a quarter of the call).
 // Measured and dropped in round 4 ("all layers staged" for short launches: every layer's box loads issued at once,
 // LP images in LDS, ONE barrier per tile-frame instead of L): bit-identical, and no faster -- 12.2 us against 11.8 at
-// BASELINE config C2.  tools_dev/fwd_stamps.py shows why: of a C2 tile-frame's ~10 us a third is the first memory
+// BASELINE config C2.  Phase timestamps (s_memtime) showed why: of a C2 tile-frame's ~10 us a third is the first memory
 // round trip (basis operand, mapping fold), a sixth the MFMA grid + transposition, and the L staged layer steps cost
 // 4.4 us rolling against 3.1 + 1.8 (issue) all at once.  DESIGN.md section 4c.
 // NW: wavefronts per workgroup.  4: a 16 x 16 tile (wave w = rows 4w .. 4w+3).  8: a 16 x 32 tile, waves 4 .. 7 on its
@@ -238,7 +221,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
   const int arow = lane & 15, kk = lane >> 4;
   int chunk, tile, rest_;
   if (!xcd_decode_banded(blockIdx.x, nchunks, nbands, ntiles, 1, chunk, tile, rest_)) return;
-  WALDO_FSTAMP(0);
   const int col0 = (tile % ntx) * (kLdsTile * NW / 4) + (wave >> 2) * kLdsTile;
   const int row0 = (tile / ntx) * kLdsTile + (wave & 3) * 4;
   // 16 x 16 tile: wave w covers rows 4w .. 4w+3, lane -> (row 4w + lane / 16, column lane % 16)
@@ -322,7 +304,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
   const int f1 = min(F, f0 + frames_per_block);
   if (f0 < f1) fold_first(f0);
   __syncthreads();
-  WALDO_FSTAMP(1);  // LDS cleared, basis operand loaded, first mapping folded
 
   // pixel-unit grid: the MFMA column of this lane is an x column (even) or a y column (odd)
   const float half_size = 0.5f * (float)((arow & 1) ? H : W);
@@ -334,7 +315,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
     // base + constant that it then keeps live across the whole frame loop, or spills).
     int lane = lane_k, arow = arow_k, kk = kk_k;
     asm volatile("" : "+v"(lane), "+v"(arow), "+v"(kk));
-    if (f == f0 + 1) WALDO_FSTAMP(8);  // (stamps 8 .. 12: the SECOND frame of the chunk, the loop's steady state)
     // ---- (A) TPS grid of every layer on the matrix pipe, in pixel units (scaled_map):
     // D[pixel][(layer, xy)] = sum_k basis[pixel][k] * mapping[k][(layer, xy)]
     f32x4 acc[4][NT];
@@ -418,8 +398,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
       }
     }
     __syncthreads();  // ranges of all waves visible; the slices (inside the image) are free again
-    if (f == f0) WALDO_FSTAMP(2);  // grid on MFMA, ranges, transposition
-    if (f == f0 + 1) WALDO_FSTAMP(9);
     // ---- (D) box of the 2x2 blocks of every layer: lanes 0..15 of every wave turn the range of
     // "their" column into block origins, then the corners go to SGPRs
     int lo_t[NT], hi_t[NT];
@@ -445,10 +423,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
       by0[l] = ymin;
       bw[l] = ((xmax - bx0[l] + 1) + 3) & ~3;
       bh[l] = ymax - ymin + 1;
-#ifdef WALDO_ABL_NOFALLBACK  // timing-only ablation: oversize boxes are cut to the cap (wrong values)
-      bw[l] = min(bw[l], 128);
-      bh[l] = min(bh[l], kCap / bw[l]);
-#endif
     }
 
     // ---- (E) staging: every lane moves one item (two texels, four planes) of a layer's box.  A
@@ -463,7 +437,7 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
     StageRegs stg[LP];  // fully unrolled: a layer's registers live from its load to its LDS store
     auto issue = [&](int l) {
       const int lc = EXL ? l : min(l, L - 1);
-      const float* src = layers + ((int64_t)WALDO_LAYER_FRAME(f) * L + lc) * 4 * HW;
+      const float* src = layers + ((int64_t)f * L + lc) * 4 * HW;
       // unconditional loads (items past the box re-read its last item; a box that does not fit
       // reads texel 0): no exec-mask branches, so the loads are issued back to back
       const bool fits = bh[l] * bw[l] <= kCap;
@@ -484,8 +458,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
 #pragma unroll
     for (int l = 0; l < kAhead; ++l) issue(l);
     WALDO_PRIO_OFF(WALDO_FWD_PRIO_MASK, 2);
-    if (f == f0) WALDO_FSTAMP(3);  // boxes, first loads issued
-    if (f == f0 + 1) WALDO_FSTAMP(10);
     {
 #pragma unroll
       for (int l = 0; l < LP; ++l) {
@@ -539,8 +511,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
       }
     }
 
-    if (f == f0) WALDO_FSTAMP(5);  // every layer sampled
-    if (f == f0 + 1) WALDO_FSTAMP(11);
     // ---- composite: a_0 = 1 (lvd.py:105), a_l = (s_l3 + 1) / 2
     float a[LP];
 #pragma unroll
@@ -585,8 +555,6 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
     }
     WALDO_PRIO_OFF(WALDO_FWD_PRIO_MASK, 4);
     __syncthreads();  // boxred and the image buffers are re-used by the next frame
-    if (f == f0) WALDO_FSTAMP(6);  // composite, stores issued, closing barrier
-    if (f == f0 + 1) WALDO_FSTAMP(12);
   }
 }
 

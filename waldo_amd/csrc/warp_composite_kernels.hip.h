@@ -368,9 +368,6 @@ void launch_splat(const float* rec, const float* grad_rgb, const int* cellbox,
 }  // namespace waldo
 
 #include "warp_composite_fwd_lds.hip.h"
-#ifdef WALDO_VARIANT_FWD_PIPE  // tools_dev/build_variant.py only: round 5's rejected experiment (tools_dev/dropped/)
-#include "warp_composite_fwd_pipe.hip.h"
-#endif
 #include "warp_composite_bwd_px16.hip.h"
 
 namespace waldo {
@@ -382,9 +379,6 @@ namespace waldo {
 // prefer a chunk count divisible by the 8 XCDs (each chunk is pinned to one) while keeping enough
 // workgroups to fill the chip several times over
 static inline int chunk_frames(int F, int64_t ntiles) {
-#ifdef WALDO_ABL_FPB  // timing-only sweep of the frames per workgroup
-  return WALDO_ABL_FPB < F ? WALDO_ABL_FPB : F;
-#endif
   for (int c = 8; c >= 2; --c) {
     const int chunks = (F + c - 1) / c;
     if (chunks % kXcds == 0 && (int64_t)chunks * ntiles >= 2048) return c;
@@ -437,24 +431,6 @@ static void launch_fwd(const float* layers, const float* basis_t, const float* m
       };
       using T = std::true_type;
       using N = std::false_type;
-#ifdef WALDO_VARIANT_FWD_PIPE
-      if constexpr (NW == 4 && LP >= 2 && LP <= 8) {
-        // a VARIANT build (tools_dev/build_variant.py NAME -DWALDO_VARIANT_FWD_PIPE): round 5's software-pipelined frame
-        // loop (tools_dev/dropped/warp_composite_fwd_pipe.hip.h; same bits, 2.5 % slower at the headline shape) takes
-        // every launch it can serve -- the product library does not contain it
-        if (L == LP) {
-          if (src_pts != nullptr)
-            hipLaunchKernelGGL((warp_composite_fwd_pipe_kernel<LP, true>), grid16, dim3(NW * kWave), 0, st, layers,
-                               basis_t, mapping, inv_kernel, src_pts, occ, rgb, alpha, F, H, W, fpb, ntx16, nt16,
-                               nchunks, nbands, delta);
-          else
-            hipLaunchKernelGGL((warp_composite_fwd_pipe_kernel<LP, false>), grid16, dim3(NW * kWave), 0, st, layers,
-                               basis_t, mapping, inv_kernel, src_pts, occ, rgb, alpha, F, H, W, fpb, ntx16, nt16,
-                               nchunks, nbands, delta);
-          return;
-        }
-      }
-#endif
       if (src_pts != nullptr) {
         if (L == LP) go(T{}, T{}); else go(N{}, T{});
       } else {

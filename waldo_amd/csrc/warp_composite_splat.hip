@@ -81,14 +81,12 @@ constexpr int kPitch = WALDO_K2_PITCH;
 constexpr int kImgWords = kSrcRows * kPitch;           // image words per channel
 constexpr int kPlane = kImgWords + kWave;              // + the dump words
 constexpr int kDump = kImgWords;                       // + lane
-// WALDO_K2_PK64: two channel planes share a 64-bit word per texel (lo = plane 2q, hi = plane 2q + 1) and a
-// tap is added with ONE ds_add_u64 per pair: 8 LDS atomics per pixel instead of 16 (tools_dev/r3_micro.hip:
-// 52.8 vs 69.1 LDS cycles per pixel-wave).  The signed 32-bit sums decode exactly from the 64-bit total: the
-// low half is the low sum modulo 2^32 (no overflow: the scale guarantees it), and the high half carries the
-// high sum plus the borrows of negative low halves, -1 per addend, i.e. minus [low sum < 0] in the end.
-#ifndef WALDO_K2_PK64
-#define WALDO_K2_PK64 1  // measured: backward 2.133 -> 2.092 ms at the headline shape, bit-identical sums
-#endif
+// Two channel planes share a 64-bit word per texel (lo = plane 2q, hi = plane 2q + 1) and a tap is added
+// with ONE ds_add_u64 per pair: 8 LDS atomics per pixel instead of 16 (tools_dev/r3_micro.hip: 52.8 vs 69.1
+// LDS cycles per pixel-wave; measured: backward 2.133 -> 2.092 ms at the headline shape, bit-identical sums).
+// The signed 32-bit sums decode exactly from the 64-bit total: the low half is the low sum modulo 2^32 (no
+// overflow: the scale guarantees it), and the high half carries the high sum plus the borrows of negative low
+// halves, -1 per addend, i.e. minus [low sum < 0] in the end.
 
 // taps of one candidate pixel into the S image.  Branch-free: a tap outside S adds to the lane's
 // own dump word -- never to a shared address, where same-address adds would serialise.  (A corner
@@ -145,7 +143,6 @@ __device__ __forceinline__ void splat_pixel(int* img, int lane, bool on, const T
     gv[2] = as * g2;
     gv[3] = rec.y * tile_scale[1];
   }
-#if WALDO_K2_PK64
   // the 64-bit image: pair q of texel word w at 8 * (q * kPlane + w); a00 .. a11 hold 4 * w
   auto add2 = [&](int* a, int q, float vlo, float vhi) {
     const int lo = cvt_round(vlo), hi = cvt_round(vhi);
@@ -162,17 +159,6 @@ __device__ __forceinline__ void splat_pixel(int* img, int lane, bool on, const T
     add2(a10, q, pb0[0], pb1[0]);
     add2(a11, q, pb0[1], pb1[1]);
   }
-#else
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const f32x2 gs = {gv[c], gv[c]};
-    const f32x2 pt = gs * (c < 3 ? wt_rgb : wt_a), pb = gs * (c < 3 ? wb_rgb : wb_a);
-    atomicAdd(a00 + c * kPlane, cvt_round(pt[0]));
-    atomicAdd(a01 + c * kPlane, cvt_round(pt[1]));
-    atomicAdd(a10 + c * kPlane, cvt_round(pb[0]));
-    atomicAdd(a11 + c * kPlane, cvt_round(pb[1]));
-  }
-#endif
 }
 
 // does any tap of this pixel fall into S?
@@ -339,7 +325,7 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
   const f32x2_k2 tile_scale = {__uint_as_float((unsigned)(127 - 200 + (verdict[3] & 0xffff)) << 23),
                                __uint_as_float((unsigned)(127 - 200 + ((verdict[3] >> 16) & 0xffff)) << 23)};
   const float* gplane = grad_rgb + f * 3 * HW;
-  const float4* rcp = rec + ((int64_t)WALDO_REC_FRAME(f) * L + layer) * HW;
+  const float4* rcp = rec + ((int64_t)f * L + layer) * HW;
 
   if ((bsum_rgb > 0.0f || bsum_a > 0.0f) && !poison) {
     if (nhit <= kMaxHit) {
@@ -364,15 +350,7 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
         k.livep = i < total && py < H && px < W;
         k.p = (unsigned)(__mul24(min(py, H - 1), W) + min(px, W - 1));
         // 32-bit byte offsets from uniform bases (HW * 8 < 2^32 is implied by the launcher's check)
-#if WALDO_REC_LOAD_NT
-        {
-          typedef float f32x4 __attribute__((ext_vector_type(4)));
-          const f32x4 r = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(rcp) + k.p * 16u));
-          k.rc = make_float4(r[0], r[1], r[2], r[3]);
-        }
-#else
         k.rc = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(rcp) + k.p * 16u);
-#endif
         k.g0 = ldb(gplane, k.p * 4u);
         k.g1 = ldb(gplane + HW, k.p * 4u);
         k.g2 = ldb(gplane + 2 * HW, k.p * 4u);
@@ -470,14 +448,10 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
         const float inv_a = __uint_as_float(0x7f000000u - __float_as_uint(sc[1]));
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-#if WALDO_K2_PK64
           const i32x4* w64 = reinterpret_cast<const i32x4*>(reinterpret_cast<const long long*>(img) + (c >> 1) * kPlane + li);
           const i32x4 wa = w64[0], wb = w64[1];  // (lo, hi) of texels li .. li + 3
           const i32x4 los = {wa[0], wa[2], wb[0], wb[2]}, his = {wa[1], wa[3], wb[1], wb[3]};
           const i32x4 v = (c & 1) ? his - (los >> 31) : los;
-#else
-          const i32x4 v = *reinterpret_cast<const i32x4*>(img + c * kPlane + li);
-#endif
           const float inv = c < 3 ? inv_rgb : inv_a;
           stream_store16<WALDO_GRAD_STORE_POLICY>(gbase + c * HW, doff * 4u, HW * 4,
                                                   (f32x4){(float)v[0] * inv, (float)v[1] * inv, (float)v[2] * inv, (float)v[3] * inv});
@@ -494,12 +468,8 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
       const f32x2_k2 sc = sbscale[((y - sy0) >> 3) * kSubX + ((x - sx0) >> 4)];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-#if WALDO_K2_PK64
         const int lo = img[2 * ((c >> 1) * kPlane + li)], hi = img[2 * ((c >> 1) * kPlane + li) + 1];
         const int v = (c & 1) ? hi - (lo >> 31) : lo;
-#else
-        const int v = img[c * kPlane + li];
-#endif
         (gbase + c * HW)[doff] = (float)v * __uint_as_float(0x7f000000u - __float_as_uint(sc[c < 3 ? 0 : 1]));
       }
     }
