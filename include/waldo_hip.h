@@ -33,6 +33,11 @@ extern "C" {
 
 typedef void* waldo_stream_t; /* hipStream_t */
 
+/* Element type of a retyped buffer of the *_dt entry points (the 16-bit WIF path).  The arithmetic stays fp32; a
+ * 16-bit result is the fp32 result rounded to nearest-even (the bits of torch's `.to(dtype)`), a 16-bit input is
+ * widened to fp32 on load.  Any other code: WALDO_EINVAL with a message, before any launch. */
+enum waldo_dtype { WALDO_DTYPE_F32 = 0, WALDO_DTYPE_F16 = 1, WALDO_DTYPE_BF16 = 2 };
+
 /* ABI version: major*1000 + minor. */
 int waldo_version(void);
 const char* waldo_last_error_string(void);
@@ -287,6 +292,15 @@ int waldo_flow_ctx_warp_raw_fwd(const float* flow_lr, const float* isobj_lr, con
                                 float* raw, float* score, float* disocc, float* alpha_max,
                                 const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp, int L,
                                 int H, int W, int scale, int C, int Tcx, waldo_stream_t stream);
+/* The same with `raw` of element type raw_dtype (enum waldo_dtype): a 16-bit raw gets the alpha slots rounded to
+ * nearest-even; flow, score, disocc and alpha_max stay fp32 (score is summed from the fp32 values, so nothing reads
+ * the rounded alphas back).  WALDO_DTYPE_F32 = waldo_flow_ctx_warp_raw_fwd. */
+int waldo_flow_ctx_warp_raw_fwd_dt(const float* flow_lr, const float* isobj_lr, const float* a01,
+                                   const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ, float* flow,
+                                   void* raw, float* score, float* disocc, float* alpha_max,
+                                   const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp,
+                                   int L, int H, int W, int scale, int C, int Tcx, int raw_dtype,
+                                   waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * A10: Warper.input_to_output (models/nets/lvd.py:830-853): warp of the context frames
@@ -315,6 +329,12 @@ int waldo_frame_warp_fuse_raw_fwd(const float* input, const float* flow, const f
                                   const int64_t* ctx_ts, float* out, float* raw, int* status, int B, int T, int Tc,
                                   int Tp, int C, int L, int Hd, int Wd, int include_self, float eps,
                                   waldo_stream_t stream);
+/* The same with `raw` of element type raw_dtype (the type waldo_flow_ctx_warp_raw_fwd_dt filled it in): a 16-bit raw
+ * gets the warped channels (and the self slot) rounded to nearest-even; `out` stays fp32 and has the fp32 call's bits. */
+int waldo_frame_warp_fuse_raw_fwd_dt(const float* input, const float* flow, const float* score,
+                                     const int64_t* ctx_ts, float* out, void* raw, int* status, int B, int T, int Tc,
+                                     int Tp, int C, int L, int Hd, int Wd, int include_self, float eps, int raw_dtype,
+                                     waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Backward of A9 / A10 (csrc/flow_ctx_bwd.hip): the reference's live backward path in LVD training
@@ -458,6 +478,14 @@ int waldo_wif_fuse_fwd(const float* vid, const float* net, float* out, int64_t N
 int waldo_wif_fuse_bwd(const float* vid, const float* net, const float* out, const float* grad_out,
                        float* grad_vid, float* grad_net, int64_t N, int Tc, int C, int Co,
                        int64_t HW, int ab, waldo_stream_t stream);
+/* The same with vid / net each of element type vid_dtype / net_dtype (enum waldo_dtype), widened to fp32 on load;
+ * out and grad_out stay fp32; grad_vid is written in vid's type and grad_net in net's (rounded to nearest-even), with
+ * the same overwrite / zero contract per channel. */
+int waldo_wif_fuse_fwd_dt(const void* vid, const void* net, float* out, int64_t N, int Tc, int C, int Co,
+                          int64_t HW, int ab, int vid_dtype, int net_dtype, waldo_stream_t stream);
+int waldo_wif_fuse_bwd_dt(const void* vid, const void* net, const float* out, const float* grad_out,
+                          void* grad_vid, void* grad_net, int64_t N, int Tc, int C, int Co, int64_t HW, int ab,
+                          int vid_dtype, int net_dtype, waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f3. The mask dilation of WIF.inpaint: expand() (tools/utils.py:300-323; called at models/nets/wif.py:77,

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libwaldo_hip.so")
 # ABI this binding was written against (include/waldo_hip.h: waldo_version() = major * 1000 + minor); a
 # library of another version has other prototypes behind the same names and is refused by load()
-ABI_VERSION = 1019
+ABI_VERSION = 1020
 
 _c_f = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
@@ -54,6 +54,9 @@ SIGNATURES = {
     "waldo_frame_warp_fuse_fwd": [_c_f] * 7 + [_int] * 9 + [_flt, _stream],
     "waldo_flow_ctx_warp_raw_fwd": [_c_f] * 13 + [_int] * 11 + [_stream],
     "waldo_frame_warp_fuse_raw_fwd": [_c_f] * 7 + [_int] * 9 + [_flt, _stream],
+    # the *_dt forms: the retyped buffers as void* plus WALDO_DTYPE_* codes (include/waldo_hip.h: enum waldo_dtype)
+    "waldo_flow_ctx_warp_raw_fwd_dt": [_c_f] * 13 + [_int] * 12 + [_stream],
+    "waldo_frame_warp_fuse_raw_fwd_dt": [_c_f] * 7 + [_int] * 9 + [_flt, _int, _stream],
     "waldo_flow_ctx_alpha_bwd": [_c_f] * 10 + [_int] * 10 + [_stream],
     "waldo_flow_ctx_warp_bwd": [_c_f] * 13 + [_int] * 9 + [_stream],
     "waldo_frame_warp_fuse_bwd": [_c_f] * 8 + [_int] * 9 + [_flt, _stream],
@@ -62,6 +65,9 @@ SIGNATURES = {
     "waldo_wif_fuse_fwd": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _stream],
     "waldo_wif_fuse_bwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int,
                            _stream],
+    "waldo_wif_fuse_fwd_dt": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _int, _int, _stream],
+    "waldo_wif_fuse_bwd_dt": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _int, _int,
+                              _stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],
@@ -214,14 +220,15 @@ def ptr(t):
     return t.data_ptr()
 
 
-def check_cuda(*tensors):
+def check_cuda(*tensors, half=False):
+    """GPU tensors of fp32 -- or, with ``half`` (the entry points with a dtype code), of fp32, fp16 or bf16."""
     for t in tensors:
         if t is None:
             continue
         if not t.is_cuda:
             raise WaldoHipError("waldo_amd ops need tensors on the GPU (cuda device); "
                                 "there is no CPU fallback")
-        if t.dtype != torch.float32:
+        if t.dtype != torch.float32 and not (half and t.dtype in (torch.float16, torch.bfloat16)):
             raise WaldoHipError(f"waldo_amd ops are fp32-only, got {t.dtype}")
 
 

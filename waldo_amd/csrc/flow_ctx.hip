@@ -188,15 +188,20 @@ __device__ __forceinline__ float nan_max(float a, float b) { return __builtin_el
 // 4 x (3 x 18).
 // (Round 6 tried a per-TILE compact list of the layers present: bit-identical and 8-13 % SLOWER; git show
 // 93480c2:tools_dev/dropped/flow_ctx_warp_compact.hip.h.)
-template <int LP, bool SCORE, int R>
-__global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R > 1 && LP <= 17) ? 4 : 1)) void flow_ctx_warp_kernel(
+// AT: the element type of alpha_ctx -- float, or __bf16 / _Float16 for the alpha slots of a 16-bit `raw` (store_pair16:
+// two pixels per 4-byte store where Wd is even).
+// (the 16-bit R = 2 instances at up to 12 layers: four waves -- at five they spilled)
+template <int LP, bool SCORE, int R, typename AT = float>
+__global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? ((R == 2 && !std::is_same<AT, float>::value) ? 4 : WALDO_FCW_WAVES)
+                                                         : ((R > 1 && LP <= 17) ? 4 : 1)) void flow_ctx_warp_kernel(
     const float* __restrict__ flow_lr, const float* __restrict__ isobj_lr,
     const float* __restrict__ a01, const int64_t* __restrict__ ctx_ts,
     const int64_t* __restrict__ pred_ts, const float* __restrict__ occ, float* __restrict__ flow,
-    float* __restrict__ alpha_ctx, ActxLayout lay, float* __restrict__ score, float* __restrict__ disocc,
+    AT* __restrict__ alpha_ctx, ActxLayout lay, float* __restrict__ score, float* __restrict__ disocc,
     float* __restrict__ alpha_max, const unsigned* __restrict__ layer_bits, int* __restrict__ status, int T, int Tw, int Tc,
     int Tp, int L, int H, int W, int scale, int units, int tiles, int nbands) {
   using G = FcwLds<LP, R>;
+  constexpr bool kF32 = std::is_same<AT, float>::value;
   typedef float f32x2_w __attribute__((ext_vector_type(2)));
   const int Hd = H * scale, Wd = W * scale;
   const int64_t HWd = (int64_t)Hd * Wd, HW = (int64_t)H * W;
@@ -437,7 +442,19 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
   disocc[(int64_t)m * HWd + p] = dis;
   float ox = 0.0f, oy = 0.0f;
   float amax = -INFINITY;  // max over the layers of the composited alpha (Synthesizer.predict's disocclusion test)
-  float* ac = alpha_ctx + b * lay.sb + ((m / Tp) % Tc) * lay.stc + tp * lay.stp;
+  AT* ac = alpha_ctx + b * lay.sb + ((m / Tp) % Tc) * lay.stc + tp * lay.stp;
+  // (16-bit: a lane pair = two adjacent pixels of one row, 64-pixel segments from a multiple of 64.  The tall tiles
+  // store pairs only -- the launcher takes R = 1 for an odd Wd -- and R = 1 stores pixel by pixel where Wd is odd: a
+  // run-time choice in the tall tiles cost registers the 5-wave bound does not have, and scratch)
+  const bool pair16 = R > 1 || (Wd & 1) == 0;  // (uniform)
+  auto put = [&](float v) {
+    if constexpr (kF32) {
+      ac[p] = v;
+    } else {
+      if (pair16) store_pair16<false>(ac + (p - (x & 1)), (x & 1) != 0, v);
+      else store_px16<false>(ac + p, v);
+    }
+  };
   float ssum = 0.0f;
   // four columns j of the order per step, two and two on the packed-fp32 pipe (the product of every column
   // runs over i in the same order as in the other kernels of the path); rows and column quads outside the active
@@ -494,13 +511,13 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
         }
         if (j + k < L) {
           const float av = v * 2.0f - 1.0f;
-          ac[p] = av;
+          put(av);
           amax = nan_max(amax, av);
           if (SCORE) ssum += (av + 1.0f) / 2.0f;
         }
       } else if (j + k < L) {
         // alpha 0 in every lane (all operands finite): 2 * 0 - 1, + 0 to the score and to the flow
-        ac[p] = -1.0f;
+        put(-1.0f);
         amax = nan_max(amax, -1.0f);
       }
       if (j + k < L) ac += HWd;
@@ -533,6 +550,16 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? WALDO_FCW_WAVES : ((R
 #endif
 // non-temporal stores for out / raw (read next by another kernel, far larger than any cache): -3.5 %
 __device__ __forceinline__ void fwf_store(float* p, float v) { __builtin_nontemporal_store(v, p); }
+// a 16-bit `raw` (the raw path only: waldo_frame_warp_fuse_raw_fwd_dt): PAIR -- the LDS kernel's 64-column tiles, lane
+// pairs of adjacent pixels, one 4-byte store per lane (store_pair16; `at` is then the pair's first pixel); otherwise
+// one 2-byte store per pixel
+template <bool PAIR>
+__device__ __forceinline__ void fwf_put(float* at, bool, float v) { fwf_store(at, v); }
+template <bool PAIR, typename T>
+__device__ __forceinline__ void fwf_put(T* at, bool odd, float v) {
+  if (PAIR) store_pair16<true>(at, odd, v);
+  else store_px16<true>(at, v);
+}
 
 // Tile shape (tools_dev/ab_hd.py --amp, C5 size, ms at flow amplitudes of 10 / 25 / 50 / 150 px over 32-pixel
 // cells): 4 x 64 (a wavefront = one 64-pixel row segment, as the other kernels of this file) 3.86 / 4.89 / 6.53
@@ -540,11 +567,12 @@ __device__ __forceinline__ void fwf_store(float* p, float v) { __builtin_nontemp
 // Under a sheared flow the footprint of a long row segment crosses many image rows and every 8-byte pair
 // pulls a line of its own; the squarer wavefront keeps the footprint compact, and at 32 columns the stores
 // are still whole 128-byte lines.
-template <int TCP>
+// RT: the element type of `raw` (16-bit: the raw path only -- `alpha` is then NULL -- one 2-byte store per pixel).
+template <int TCP, typename RT = float>
 __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
     const float* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
     const float* __restrict__ score, const int64_t* __restrict__ ctx_ts, float* __restrict__ out,
-    float* __restrict__ raw, int* __restrict__ status, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
+    RT* __restrict__ raw, int* __restrict__ status, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
     float eps, int units, int tiles, int nbands) {
   const int64_t HWd = (int64_t)Hd * Wd;
   int n, x, y;  // n = (b, tp); the Tp predicted frames of a clip innermost in an XCD's tile walk
@@ -595,7 +623,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
       // the alphas already sit in `raw` (waldo_flow_ctx_warp_raw_fwd wrote them there) and their sum came with
       // them: one plane per context instead of L read and L copied
       s = score[m * HWd + p];
-    } else {
+    } else if constexpr (std::is_same<RT, float>::value) {
       const float* al = alpha + m * L * HWd + p;
       float* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + tcc) * (C + L) + C) * HWd + p;
       for (int l = 0; l < L; ++l) {
@@ -608,8 +636,8 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
     ssum += real ? fabsf(s + eps) : 0.0f;
   }
   if (include_self) {
-    float* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + p;
-    for (int l = 0; l < L; ++l) fwf_store(rw + (int64_t)l * HWd, 1.0f);
+    RT* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + p;
+    for (int l = 0; l < L; ++l) fwf_put<false>(rw + (int64_t)l * HWd, false, 1.0f);
     ssum += fabsf(1.0f + eps);
   }
   const float den = fmaxf(ssum, 1e-12f);
@@ -618,7 +646,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
 #pragma unroll
   for (int tc = 0; tc < TCP; ++tc) wt[tc] = (tc < Tc) ? (sc[tc] + eps) / den : 0.0f;
   const float* self = input + ((int64_t)b * T + min(tp, T - 1)) * C * HWd + p;
-  float* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + p;  // context tc: + tc * (C+L) * HWd
+  RT* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + p;  // context tc: + tc * (C+L) * HWd
   float* obase = out + ((int64_t)b * Tp + tp) * (C + 1) * HWd + p;
   // Channel loop, software-pipelined by hand: the sixteen tap loads of channel c + 1 are issued BEFORE the
   // stores of channel c.  Vector-memory operations retire in issue order (loads, stores: one counter), so
@@ -663,11 +691,11 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
       const float v = fmaf(tv[tc][3], w11[tc], fmaf(tv[tc][2], w10[tc], fmaf(tv[tc][1], w01[tc], tv[tc][0] * w00[tc])));
-      if (tc < Tc) fwf_store(rbase + ((int64_t)tc * (C + L) + c) * HWd, v);
+      if (tc < Tc) fwf_put<false>(rbase + ((int64_t)tc * (C + L) + c) * HWd, false, v);
       acc += v * wt[tc];
     }
     if (include_self) {
-      fwf_store(rbase + ((int64_t)Tc * (C + L) + c) * HWd, vself);
+      fwf_put<false>(rbase + ((int64_t)Tc * (C + L) + c) * HWd, false, vself);
       acc += vself * wself;
     }
     fwf_store(obase + (int64_t)c * HWd, acc);
@@ -704,11 +732,16 @@ constexpr int kFwfCap = 1024;  // texels of one context's staged box = one float
 #define WALDO_FWF_LDS_WAVES 4  // 116 VGPRs, NO scratch.  (Five waves -- 96 VGPRs -- measured the same speed in round 4 and spilled two
                                // dwords: a kernel with scratch inside a replayed HIP graph faulted on this stack)
 #endif
-template <int TCP, bool FULL>
+// RT 16-bit (the raw path only: `alpha` is NULL): 4 x 64 tiles instead of 8 x 32, a wavefront = one 64-pixel row
+// segment, so that the lane pairs of store_pair16 write every 128-byte line of `raw` whole (fwf_kcols).
+// (8 x 32 tiles with the same lane pairs write half lines: 8.66 against 7.33 ms per C5 step, profiles/r07_raw_dtype_*)
+template <typename RT>
+constexpr int fwf_kcols() { return std::is_same<RT, float>::value ? 32 : 64; }
+template <int TCP, bool FULL, typename RT = float>
 __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_lds_kernel(
     const float* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
     const float* __restrict__ score, const int64_t* __restrict__ ctx_ts, float* __restrict__ out,
-    float* __restrict__ raw, int* __restrict__ status, int T, int Tc_, int Tp, int C, int L, int Hd, int Wd, int include_self_,
+    RT* __restrict__ raw, int* __restrict__ status, int T, int Tc_, int Tp, int C, int L, int Hd, int Wd, int include_self_,
     float eps, int units, int tiles, int nbands) {
   typedef float f32x2_fw __attribute__((ext_vector_type(2)));
   typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -717,14 +750,19 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   const bool include_self = FULL ? false : include_self_ != 0;
   const int64_t HWd = (int64_t)Hd * Wd;
   int n, x, y;  // n = (b, tp)
-  if (!HdTile<32>::pixel_grouped(units / Tp, Tp, Hd, Wd, tiles, nbands, n, x, y)) return;  // (uniform)
+  constexpr bool kF32 = std::is_same<RT, float>::value;
+  if (!HdTile<fwf_kcols<RT>()>::pixel_grouped(units / Tp, Tp, Hd, Wd, tiles, nbands, n, x, y)) return;  // (uniform)
   // a thread beyond the right / bottom edge works on the tile's last pixel of its row / column: it computes and
   // stores the same values to the same addresses as that pixel's own thread (no branch around the stores, every
-  // thread reaches the barriers, the box is that of the live pixels)
-  x = min(x, Wd - 1);
+  // thread reaches the barriers, the box is that of the live pixels).  16-bit: on the last PAIR of its row (Wd % 4 ==
+  // 0), so that a lane pair stays two adjacent pixels, x even in the even lane
+  if constexpr (kF32) x = min(x, Wd - 1);
+  else x = min(x, Wd - 2 + (x & 1));
   y = min(y, Hd - 1);
   const int b = n / Tp, tp = n % Tp;
   const int64_t p = (int64_t)y * Wd + x;
+  const bool odd = (x & 1) != 0;
+  const int64_t pr = kF32 ? p : p - (odd ? 1 : 0);  // where this thread's stores to `raw` go (16-bit: its pair's)
   const int t = (int)threadIdx.x, lane = t & (kWave - 1), wave = t >> 6;
   float gx0, gy0;
   identity_grid(x, y, Wd, Hd, gx0, gy0);
@@ -775,7 +813,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     float sv = 0.0f;
     if (score != nullptr) {
       sv = score[m * HWd + p];
-    } else {
+    } else if constexpr (kF32) {
       const float* al = alpha + m * L * HWd + p;
       float* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + tcc) * (C + L) + C) * HWd + p;
       for (int l = 0; l < L; ++l) {
@@ -788,8 +826,8 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     ssum += real ? fabsf(sv + eps) : 0.0f;
   }
   if (include_self) {
-    float* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + p;
-    for (int l = 0; l < L; ++l) fwf_store(rw + (int64_t)l * HWd, 1.0f);
+    RT* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + pr;
+    for (int l = 0; l < L; ++l) fwf_put<true>(rw + (int64_t)l * HWd, odd, 1.0f);
     ssum += fabsf(1.0f + eps);
   }
   lds_barrier();
@@ -825,7 +863,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
 #pragma unroll
   for (int tc = 0; tc < TCP; ++tc) wt[tc] = (tc < Tc) ? (sc[tc] + eps) / den : 0.0f;
   const float* self = input + ((int64_t)b * T + min(tp, T - 1)) * C * HWd + p;
-  float* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + p;  // context tc: + tc * (C+L) * HWd
+  RT* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + pr;  // context tc: + tc * (C+L) * HWd
   float* obase = out + ((int64_t)b * Tp + tp) * (C + 1) * HWd + p;
   const bool any_shift = __ballot(shifted) != 0ull;  // wave-uniform
   // corners of the footprint from the pair elements (see the kernel above); a no-op for interior wavefronts
@@ -847,11 +885,11 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
       const float v = fmaf(v4[tc][3], w11[tc], fmaf(v4[tc][2], w10[tc], fmaf(v4[tc][1], w01[tc], v4[tc][0] * w00[tc])));
-      if (FULL || tc < Tc) fwf_store(rbase + ((int64_t)tc * (C + L) + c) * HWd, v);
+      if (FULL || tc < Tc) fwf_put<true>(rbase + ((int64_t)tc * (C + L) + c) * HWd, odd, v);
       acc += v * wt[tc];
     }
     if (include_self) {
-      fwf_store(rbase + ((int64_t)Tc * (C + L) + c) * HWd, vself);
+      fwf_put<true>(rbase + ((int64_t)Tc * (C + L) + c) * HWd, odd, vself);
       acc += vself * wself;
     }
     fwf_store(obase + (int64_t)c * HWd, acc);
@@ -972,6 +1010,7 @@ static int check_flow_ctx(const char* fn, int64_t N, int L, int H, int W, int sc
 
 using namespace waldo;
 
+#ifndef WALDO_FC_RAW_HALF  // (the fp32 unit; flow_ctx_raw_bf16.hip / _f16.hip compile the 16-bit raw path: end of file)
 #define WALDO_FC_CASE(LPV, KERNEL, ...)                                                      \
   case LPV:                                                                                  \
     hipLaunchKernelGGL((KERNEL<LPV>), dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0, st, \
@@ -1021,28 +1060,31 @@ extern "C" int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* inpu
 #undef WALDO_FCA_CASE
   return launch_status("waldo_flow_ctx_alpha_fwd");
 }
+#endif  // !WALDO_FC_RAW_HALF
 
 #define WALDO_FCW_LAUNCH(LPV, SC, RV)                                                                          \
-  hipLaunchKernelGGL((flow_ctx_warp_kernel<LPV, SC, RV>), dim3((unsigned)fcw_grid), dim3(kBlock), 0, st,      \
+  hipLaunchKernelGGL((flow_ctx_warp_kernel<LPV, SC, RV, AT>), dim3((unsigned)fcw_grid), dim3(kBlock), 0, st,  \
                      flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, alpha_ctx, lay, score, disocc, alpha_max, \
                      layer_bits, status, T, Tw, Tc, Tp, L, H, W, scale, (int)N, geom.tiles, geom.nbands)
-#define WALDO_FCW_CASE(LPV)                                        \
-  case LPV:                                                       \
-    if (rows == 1) {                                              \
-      if (score != nullptr) WALDO_FCW_LAUNCH(LPV, true, 1);       \
-      else WALDO_FCW_LAUNCH(LPV, false, 1);                       \
-    } else if (rows == 2) {                                       \
-      if (score != nullptr) WALDO_FCW_LAUNCH(LPV, true, 2);       \
-      else WALDO_FCW_LAUNCH(LPV, false, 2);                       \
-    } else {                                                      \
-      if (score != nullptr) WALDO_FCW_LAUNCH(LPV, true, kFcwRows); \
-      else WALDO_FCW_LAUNCH(LPV, false, kFcwRows);                \
-    }                                                             \
+// (a 16-bit alpha_ctx is the raw path's, which always writes the score: no instances without it)
+#define WALDO_FCW_CASE(LPV)                                                       \
+  case LPV:                                                                      \
+    if (rows == 1) {                                                             \
+      if (score != nullptr) WALDO_FCW_LAUNCH(LPV, true, 1);                      \
+      else if constexpr (std::is_same<AT, float>::value) WALDO_FCW_LAUNCH(LPV, false, 1);        \
+    } else if (rows == 2) {                                                      \
+      if (score != nullptr) WALDO_FCW_LAUNCH(LPV, true, 2);                      \
+      else if constexpr (std::is_same<AT, float>::value) WALDO_FCW_LAUNCH(LPV, false, 2);        \
+    } else {                                                                     \
+      if (score != nullptr) WALDO_FCW_LAUNCH(LPV, true, kFcwRows);               \
+      else if constexpr (std::is_same<AT, float>::value) WALDO_FCW_LAUNCH(LPV, false, kFcwRows); \
+    }                                                                            \
     break;
 
+template <typename AT>
 static int flow_ctx_warp_launch(const char* fn, const float* flow_lr, const float* isobj_lr, const float* a01,
                                 const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ, float* flow,
-                                float* alpha_ctx, ActxLayout lay, float* score, float* disocc, float* alpha_max,
+                                AT* alpha_ctx, ActxLayout lay, float* score, float* disocc, float* alpha_max,
                                 const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp, int L,
                                 int H, int W, int scale, waldo_stream_t stream) {
   const int64_t N = (int64_t)B * Tc * Tp;
@@ -1068,7 +1110,9 @@ static int flow_ctx_warp_launch(const char* fn, const float* flow_lr, const floa
     const int cells = ((kHdRows * r + scale - 1) / scale + 2) * ((kHdCols + scale - 1) / scale + 2);
     return cells <= kBlock && cells * cell_floats <= fcw_cap(lp, r);
   };
-  const int rows = scale < 2 ? 1 : (fits(kFcwRows) ? kFcwRows : (fits(2) ? 2 : 1));
+  // (a 16-bit alpha_ctx with an odd Wd: R = 1, the one form that stores pixel by pixel -- flow_ctx_warp_kernel)
+  const bool one_row = scale < 2 || (!std::is_same<AT, float>::value && (W * scale) % 2 != 0);
+  const int rows = one_row ? 1 : (fits(kFcwRows) ? kFcwRows : (fits(2) ? 2 : 1));
   HdGeom geom = hd_geom_rows(N, H * scale, W * scale, rows);
   const int64_t fcw_grid = hd_grid(N, geom);
   if (fcw_grid > 2147483647) {
@@ -1086,38 +1130,27 @@ static int flow_ctx_warp_launch(const char* fn, const float* flow_lr, const floa
   return launch_status(fn);
 }
 
-extern "C" int waldo_flow_ctx_warp_fwd(const float* flow_lr, const float* isobj_lr, const float* a01,
-                                       const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ,
-                                       float* flow, float* alpha_ctx, float* disocc, float* alpha_max,
-                                       const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp,
-                                       int L, int H, int W, int scale, waldo_stream_t stream) {
-  const int64_t plane = (int64_t)H * scale * W * scale;
-  const ActxLayout lay = {(int64_t)Tc * Tp * L * plane, (int64_t)Tp * L * plane, (int64_t)L * plane};
-  return flow_ctx_warp_launch("waldo_flow_ctx_warp_fwd", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow,
-                              alpha_ctx, lay, nullptr, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W,
-                              scale, stream);
-}
-
-extern "C" int waldo_flow_ctx_warp_raw_fwd(const float* flow_lr, const float* isobj_lr, const float* a01,
-                                           const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ,
-                                           float* flow, float* raw, float* score, float* disocc,
-                                           float* alpha_max, const unsigned* layer_bits, int* status, int B, int T,
-                                           int Tw, int Tc, int Tp, int L, int H, int W, int scale, int C, int Tcx,
-                                           waldo_stream_t stream) {
+// the raw path (LVD.forward(mode="decode_output")): alpha_ctx into the alpha slots of `raw`, of element type AT
+template <typename AT>
+static int flow_ctx_warp_raw(const char* fn, const float* flow_lr, const float* isobj_lr, const float* a01,
+                             const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ, float* flow, AT* raw,
+                             float* score, float* disocc, float* alpha_max, const unsigned* layer_bits, int* status,
+                             int B, int T, int Tw, int Tc, int Tp, int L, int H, int W, int scale, int C, int Tcx,
+                             waldo_stream_t stream) {
   if (C < 1 || Tcx < Tc || Tcx > Tc + 1 || !raw || !score) {
-    set_error("waldo_flow_ctx_warp_raw_fwd: bad raw layout C=%d Tc'=%d for Tc=%d (need C >= 1, Tc <= Tc' <= Tc + 1, "
-              "raw and score)", C, Tcx, Tc);
+    set_error("%s: bad raw layout C=%d Tc'=%d for Tc=%d (need C >= 1, Tc <= Tc' <= Tc + 1, raw and score)", fn, C, Tcx,
+              Tc);
     return WALDO_EINVAL;
   }
   const int64_t plane = (int64_t)H * scale * W * scale, ctx = (int64_t)(C + L) * plane;
   const ActxLayout lay = {(int64_t)Tp * Tcx * ctx, ctx, (int64_t)Tcx * ctx};
-  return flow_ctx_warp_launch("waldo_flow_ctx_warp_raw_fwd", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow,
-                              raw + (int64_t)C * plane, lay, score, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc,
-                              Tp, L, H, W, scale, stream);
+  return flow_ctx_warp_launch(fn, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, raw + (int64_t)C * plane, lay,
+                              score, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, stream);
 }
 
+template <typename RT>
 static int frame_warp_fuse_launch(const char* fn, const float* input, const float* flow, const float* alpha,
-                                  const float* score, const int64_t* ctx_ts, float* out, float* raw, int* status,
+                                  const float* score, const int64_t* ctx_ts, float* out, RT* raw, int* status,
                                   int B, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
                                   float eps, waldo_stream_t stream) {
   if (B < 0 || T < 1 || Tc < 1 || Tc + (include_self ? 1 : 0) > kFwMaxCtx || Tp < 1 || C < 1 || L < 1 ||
@@ -1151,12 +1184,19 @@ static int frame_warp_fuse_launch(const char* fn, const float* input, const floa
 #if WALDO_FWF_TILE_COLS == 32
   // (16-byte loads of the boxes: rows that start on a multiple of four texels from a 16-byte aligned base)
   if (Wd % 4 == 0 && (reinterpret_cast<uintptr_t>(input) & 15) == 0 && Tc <= 4) {
+    HdGeom lgeom = HdTile<fwf_kcols<RT>()>::geom(units, Hd, Wd);  // (16-bit `raw`: 4 x 64 tiles)
+    lgeom.nbands = WALDO_FWF_BANDS;
+    if (xcd_grid_banded(B, lgeom.nbands, lgeom.tiles, Tp) > 2147483647) {
+      set_error("%s: problem too large for one launch", fn);
+      return WALDO_EINVAL;
+    }
+    const dim3 lgrid((unsigned)xcd_grid_banded(B, lgeom.nbands, lgeom.tiles, Tp));
     // (the context count is a template parameter: a padding context repeats the last real one -- its taps, its box, its
     // loads -- so one context compiled for four did four contexts' work: the LVD recipe's "prev" mode, 114 us per call)
 #define WALDO_FWF_LAUNCH(TCPV, FULLV)                                                                                   \
-  hipLaunchKernelGGL((frame_warp_fuse_lds_kernel<TCPV, FULLV>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow, \
-                     alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units,     \
-                     geom.tiles, geom.nbands)
+  hipLaunchKernelGGL((frame_warp_fuse_lds_kernel<TCPV, FULLV, RT>), lgrid, dim3(kBlock), 0, (hipStream_t)stream, input,   \
+                     flow, alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, \
+                     lgeom.tiles, lgeom.nbands)
     if (Tc == 4 && !include_self) WALDO_FWF_LAUNCH(4, true);
     else if (Tc == 1) WALDO_FWF_LAUNCH(1, false);
     else if (Tc == 2) WALDO_FWF_LAUNCH(2, false);
@@ -1166,15 +1206,114 @@ static int frame_warp_fuse_launch(const char* fn, const float* input, const floa
   }
 #endif
   if (Tc == 1)
-    hipLaunchKernelGGL(frame_warp_fuse_kernel<1>, grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
+    hipLaunchKernelGGL((frame_warp_fuse_kernel<1, RT>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
                        alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles, geom.nbands);
   else if (Tc <= 4)
-    hipLaunchKernelGGL(frame_warp_fuse_kernel<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
+    hipLaunchKernelGGL((frame_warp_fuse_kernel<4, RT>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
                        alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles, geom.nbands);
   else
-    hipLaunchKernelGGL(frame_warp_fuse_kernel<8>, grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
+    hipLaunchKernelGGL((frame_warp_fuse_kernel<8, RT>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
                        alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles, geom.nbands);
   return launch_status(fn);
+}
+
+template <typename RT>
+static int frame_warp_fuse_raw(const char* fn, const float* input, const float* flow, const float* score,
+                               const int64_t* ctx_ts, float* out, RT* raw, int* status, int B, int T, int Tc, int Tp,
+                               int C, int L, int Hd, int Wd, int include_self, float eps, waldo_stream_t stream) {
+  if (B > 0 && !score) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  return frame_warp_fuse_launch(fn, input, flow, nullptr, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd, Wd,
+                                include_self, eps, stream);
+}
+
+// The 16-bit raw path, one compile unit per element type (flow_ctx_raw_bf16.hip, flow_ctx_raw_f16.hip: this file with
+// WALDO_FC_RAW_HALF / WALDO_FC_RAW_SUFFIX defined) -- they double the flow_ctx_warp instances.
+#define WALDO_FC_CAT_(a, b) a##b
+#define WALDO_FC_CAT(a, b) WALDO_FC_CAT_(a, b)
+#define WALDO_FC_RAW_PROTOS(SUFFIX)                                                                                     \
+  int WALDO_FC_CAT(flow_ctx_warp_raw_, SUFFIX)(                                                                         \
+      const char* fn, const float* flow_lr, const float* isobj_lr, const float* a01, const int64_t* ctx_ts,             \
+      const int64_t* pred_ts, const float* occ, float* flow, void* raw, float* score, float* disocc, float* alpha_max, \
+      const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp, int L, int H, int W, int scale,   \
+      int C, int Tcx, waldo_stream_t stream);                                                                           \
+  int WALDO_FC_CAT(frame_warp_fuse_raw_, SUFFIX)(const char* fn, const float* input, const float* flow,                 \
+                                                 const float* score, const int64_t* ctx_ts, float* out, void* raw,      \
+                                                 int* status, int B, int T, int Tc, int Tp, int C, int L, int Hd,       \
+                                                 int Wd, int include_self, float eps, waldo_stream_t stream);
+
+#ifdef WALDO_FC_RAW_HALF
+namespace waldo {
+WALDO_FC_RAW_PROTOS(WALDO_FC_RAW_SUFFIX)
+
+int WALDO_FC_CAT(flow_ctx_warp_raw_, WALDO_FC_RAW_SUFFIX)(
+    const char* fn, const float* flow_lr, const float* isobj_lr, const float* a01, const int64_t* ctx_ts,
+    const int64_t* pred_ts, const float* occ, float* flow, void* raw, float* score, float* disocc, float* alpha_max,
+    const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp, int L, int H, int W, int scale,
+    int C, int Tcx, waldo_stream_t stream) {
+  return flow_ctx_warp_raw(fn, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, static_cast<WALDO_FC_RAW_HALF*>(raw),
+                           score, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, C, Tcx, stream);
+}
+
+int WALDO_FC_CAT(frame_warp_fuse_raw_, WALDO_FC_RAW_SUFFIX)(const char* fn, const float* input, const float* flow,
+                                                            const float* score, const int64_t* ctx_ts, float* out,
+                                                            void* raw, int* status, int B, int T, int Tc, int Tp, int C,
+                                                            int L, int Hd, int Wd, int include_self, float eps,
+                                                            waldo_stream_t stream) {
+  return frame_warp_fuse_raw(fn, input, flow, score, ctx_ts, out, static_cast<WALDO_FC_RAW_HALF*>(raw), status, B, T, Tc,
+                             Tp, C, L, Hd, Wd, include_self, eps, stream);
+}
+}  // namespace waldo
+#else
+namespace waldo {
+WALDO_FC_RAW_PROTOS(bf16)
+WALDO_FC_RAW_PROTOS(f16)
+}  // namespace waldo
+
+extern "C" int waldo_flow_ctx_warp_fwd(const float* flow_lr, const float* isobj_lr, const float* a01,
+                                       const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ,
+                                       float* flow, float* alpha_ctx, float* disocc, float* alpha_max,
+                                       const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc, int Tp,
+                                       int L, int H, int W, int scale, waldo_stream_t stream) {
+  const int64_t plane = (int64_t)H * scale * W * scale;
+  const ActxLayout lay = {(int64_t)Tc * Tp * L * plane, (int64_t)Tp * L * plane, (int64_t)L * plane};
+  return flow_ctx_warp_launch("waldo_flow_ctx_warp_fwd", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow,
+                              alpha_ctx, lay, nullptr, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W,
+                              scale, stream);
+}
+
+extern "C" int waldo_flow_ctx_warp_raw_fwd(const float* flow_lr, const float* isobj_lr, const float* a01,
+                                           const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ,
+                                           float* flow, float* raw, float* score, float* disocc,
+                                           float* alpha_max, const unsigned* layer_bits, int* status, int B, int T,
+                                           int Tw, int Tc, int Tp, int L, int H, int W, int scale, int C, int Tcx,
+                                           waldo_stream_t stream) {
+  return flow_ctx_warp_raw("waldo_flow_ctx_warp_raw_fwd", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, raw, score,
+                           disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, C, Tcx, stream);
+}
+
+extern "C" int waldo_flow_ctx_warp_raw_fwd_dt(const float* flow_lr, const float* isobj_lr, const float* a01,
+                                              const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ,
+                                              float* flow, void* raw, float* score, float* disocc, float* alpha_max,
+                                              const unsigned* layer_bits, int* status, int B, int T, int Tw, int Tc,
+                                              int Tp, int L, int H, int W, int scale, int C, int Tcx, int raw_dtype,
+                                              waldo_stream_t stream) {
+  const char* fn = "waldo_flow_ctx_warp_raw_fwd_dt";
+  switch (raw_dtype) {
+    case WALDO_DTYPE_F32:
+      return flow_ctx_warp_raw(fn, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, static_cast<float*>(raw), score,
+                               disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, C, Tcx, stream);
+    case WALDO_DTYPE_BF16:
+      return flow_ctx_warp_raw_bf16(fn, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, raw, score, disocc,
+                                    alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, C, Tcx, stream);
+    case WALDO_DTYPE_F16:
+      return flow_ctx_warp_raw_f16(fn, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, raw, score, disocc,
+                                   alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, C, Tcx, stream);
+  }
+  set_error("%s: unknown raw dtype %d (WALDO_DTYPE_F32 / _F16 / _BF16)", fn, raw_dtype);
+  return WALDO_EINVAL;
 }
 
 extern "C" int waldo_frame_warp_fuse_fwd(const float* input, const float* flow, const float* alpha,
@@ -1193,10 +1332,27 @@ extern "C" int waldo_frame_warp_fuse_raw_fwd(const float* input, const float* fl
                                              const int64_t* ctx_ts, float* out, float* raw, int* status, int B, int T,
                                              int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self, float eps,
                                              waldo_stream_t stream) {
-  if (B > 0 && !score) {
-    set_error("waldo_frame_warp_fuse_raw_fwd: null pointer");
-    return WALDO_EINVAL;
-  }
-  return frame_warp_fuse_launch("waldo_frame_warp_fuse_raw_fwd", input, flow, nullptr, score, ctx_ts, out, raw, status,
-                                B, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, stream);
+  return frame_warp_fuse_raw("waldo_frame_warp_fuse_raw_fwd", input, flow, score, ctx_ts, out, raw, status, B, T, Tc, Tp,
+                             C, L, Hd, Wd, include_self, eps, stream);
 }
+
+extern "C" int waldo_frame_warp_fuse_raw_fwd_dt(const float* input, const float* flow, const float* score,
+                                                const int64_t* ctx_ts, float* out, void* raw, int* status, int B, int T,
+                                                int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
+                                                float eps, int raw_dtype, waldo_stream_t stream) {
+  const char* fn = "waldo_frame_warp_fuse_raw_fwd_dt";
+  switch (raw_dtype) {
+    case WALDO_DTYPE_F32:
+      return frame_warp_fuse_raw(fn, input, flow, score, ctx_ts, out, static_cast<float*>(raw), status, B, T, Tc, Tp, C,
+                                 L, Hd, Wd, include_self, eps, stream);
+    case WALDO_DTYPE_BF16:
+      return frame_warp_fuse_raw_bf16(fn, input, flow, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd, Wd,
+                                      include_self, eps, stream);
+    case WALDO_DTYPE_F16:
+      return frame_warp_fuse_raw_f16(fn, input, flow, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd, Wd,
+                                     include_self, eps, stream);
+  }
+  set_error("%s: unknown raw dtype %d (WALDO_DTYPE_F32 / _F16 / _BF16)", fn, raw_dtype);
+  return WALDO_EINVAL;
+}
+#endif  // WALDO_FC_RAW_HALF

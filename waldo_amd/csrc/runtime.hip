@@ -67,7 +67,7 @@ bool debug_option(int option) {
 
 }  // namespace waldo
 
-extern "C" int waldo_version(void) { return 1019; }
+extern "C" int waldo_version(void) { return 1020; }
 
 extern "C" int waldo_set_debug_option(int option, int value) {
   if (option < 0 || option >= WALDO_DEBUG_COUNT) {

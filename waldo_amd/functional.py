@@ -633,16 +633,21 @@ def pose_affine(pose, mul6, bias6, base_pts, mul_delta=1.0, pts_mul=1.0):
 class _WifFuse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vid, net, ab):
-        _lib.check_cuda(vid, net)
+        _lib.check_cuda(vid, net, half=True)  # (fp16 / bf16 too: a UNet under autocast)
         vid, net = _c(vid), _c(net)
         b, t, tc, c, h, w = vid.shape
         co = net.shape[3]
         if tuple(net.shape) != (b, t, tc, co, h, w):
             raise _lib.WaldoHipError(f"wif_fuse: shapes {tuple(vid.shape)} vs {tuple(net.shape)}")
-        out = vid.new_empty(b, t, 3, h, w)
+        out = vid.new_empty(b, t, 3, h, w, dtype=torch.float32)
         with _lib.on_device(vid.device):
-            _lib.call("waldo_wif_fuse_fwd", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out), b * t, tc,
-                      c, co, h * w, int(bool(ab)), _lib.current_stream(vid.device))
+            if vid.dtype == torch.float32 and net.dtype == torch.float32:
+                _lib.call("waldo_wif_fuse_fwd", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out), b * t, tc,
+                          c, co, h * w, int(bool(ab)), _lib.current_stream(vid.device))
+            else:
+                _lib.call("waldo_wif_fuse_fwd_dt", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out), b * t, tc,
+                          c, co, h * w, int(bool(ab)), _DTYPE_CODE[vid.dtype], _DTYPE_CODE[net.dtype],
+                          _lib.current_stream(vid.device))
         ctx.save_for_backward(vid, net, out)
         ctx.ab = int(bool(ab))
         return out
@@ -656,15 +661,22 @@ class _WifFuse(torch.autograd.Function):
         gv = torch.empty_like(vid) if ctx.needs_input_grad[0] else None
         gn = torch.empty_like(net) if ctx.needs_input_grad[1] else None
         with _lib.on_device(vid.device):
-            _lib.call("waldo_wif_fuse_bwd", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
-                      _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w,
-                      ctx.ab, _lib.current_stream(vid.device))
+            if vid.dtype == torch.float32 and net.dtype == torch.float32:
+                _lib.call("waldo_wif_fuse_bwd", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
+                          _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w,
+                          ctx.ab, _lib.current_stream(vid.device))
+            else:
+                _lib.call("waldo_wif_fuse_bwd_dt", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
+                          _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w,
+                          ctx.ab, _DTYPE_CODE[vid.dtype], _DTYPE_CODE[net.dtype], _lib.current_stream(vid.device))
         return gv, gn, None
 
 
 def wif_fuse(vid, net_out, ab=True):
     """Fusion epilogue of WIF.forward with ii_score (models/nets/wif.py:49-54).
-    vid (B, T, Tc, C, H, W): the UNet input after the permute; net_out (B, T, Tc, 4|5, H, W)."""
+    vid (B, T, Tc, C, H, W): the UNet input after the permute; net_out (B, T, Tc, 4|5, H, W).  Each of them fp32, fp16
+    or bf16 (a 16-bit raw_output, a UNet under autocast): widened to fp32 on load, the arithmetic is the fp32 one.
+    The result is fp32; the gradients come back in their inputs' types (the fp32 gradients rounded to nearest-even)."""
     return _WifFuse.apply(vid, net_out, ab)
 
 
@@ -918,23 +930,33 @@ def flow_ctx_warp(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, scale, layer
     return (flow, alpha_ctx, disocc, amax) if layer_max else (flow, alpha_ctx, disocc)
 
 
+# element types of the *_dt entry points (include/waldo_hip.h: enum waldo_dtype)
+_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
 class RawSlots:
     """What ``flow_ctx_warp_into_raw`` leaves for ``frame_warp_fuse_raw``: the ``raw`` tensor of
     Warper.input_to_output, (B, Tp, Tc', C + L, Hd, Wd), with the alpha slots of its Tc contexts filled, and
-    ``score`` (B, Tc, Tp, Hd, Wd) = the per-context sums of (alpha + 1) / 2 (lvd.py:841)."""
+    ``score`` (B, Tc, Tp, Hd, Wd) = the per-context sums of (alpha + 1) / 2 (lvd.py:841).  ``raw`` is fp32, bf16 or
+    fp16 (``raw.dtype``); ``score`` is fp32 in every case."""
 
     def __init__(self, raw, score, channels, include_self):
         self.raw, self.score, self.channels, self.include_self = raw, score, channels, include_self
 
 
 def flow_ctx_warp_into_raw(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, scale, channels, include_self,
-                           layer_max=False, status=None, layer_bits=None):
+                           layer_max=False, status=None, layer_bits=None, raw_dtype=torch.float32):
     """``flow_ctx_warp`` for the caller that runs ``frame_warp_fuse_raw`` on the result next
     (LVD.forward(mode="decode_output"), lvd.py:141-153), WITHOUT autograd: ``alpha_ctx`` is written straight
     into the alpha slots of input_to_output's ``raw`` tensor (lvd.py:846) and returned as a strided
     (B*Tc*Tp -> B, Tc, Tp, L, Hd, Wd) view of it.  ``channels`` = C of the frames that will be warped,
     ``include_self``: whether ``raw`` gets the extra self context.  Returns (flow, alpha_ctx view (B, Tc, Tp, L,
-    Hd, Wd), disocc, amax or None, slots): ``slots`` (a ``RawSlots``) goes to ``frame_warp_fuse_raw``."""
+    Hd, Wd), disocc, amax or None, slots): ``slots`` (a ``RawSlots``) goes to ``frame_warp_fuse_raw``.
+    ``raw_dtype``: the element type ``raw`` is allocated in -- fp32, or bf16 / fp16 for a UNet under autocast: the alpha
+    slots (and later the warped channels) are the fp32 values rounded to nearest-even, ``.to(raw_dtype)``'s bits; flow,
+    disocc, amax and the score stay fp32."""
+    if raw_dtype not in _DTYPE_CODE:
+        raise _lib.WaldoHipError(f"flow_ctx_warp_into_raw: raw_dtype must be fp32, bf16 or fp16, got {raw_dtype}")
     if torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (flow_lr, a01, occ)):
         raise _lib.WaldoHipError("flow_ctx_warp_into_raw: no gradient flows through the raw-slot path; use flow_ctx_warp")
     flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ = _flow_ctx_warp_args("flow_ctx_warp_into_raw", flow_lr, isobj_lr, a01,
@@ -947,16 +969,23 @@ def flow_ctx_warp_into_raw(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, sca
     st, strict = _status(status)
     with torch.no_grad():
         flow = flow_lr.new_empty(m, 2, hd, wd)
-        raw = flow_lr.new_empty(b, tp, tcx, channels + nl, hd, wd)
+        raw = flow_lr.new_empty(b, tp, tcx, channels + nl, hd, wd, dtype=raw_dtype)
         score = flow_lr.new_empty(b, tc, tp, hd, wd)
         disocc = flow_lr.new_empty(m, hd, wd)
         amax = flow_lr.new_empty(m, hd, wd) if layer_max else None
         with _lib.on_device(flow_lr.device):
-            _lib.call("waldo_flow_ctx_warp_raw_fwd", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
-                      _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
-                      _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
-                      _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h, w,
-                      scale, int(channels), tcx, _lib.current_stream(flow_lr.device))
+            if raw_dtype == torch.float32:
+                _lib.call("waldo_flow_ctx_warp_raw_fwd", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
+                          _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
+                          _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
+                          _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h,
+                          w, scale, int(channels), tcx, _lib.current_stream(flow_lr.device))
+            else:
+                _lib.call("waldo_flow_ctx_warp_raw_fwd_dt", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
+                          _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
+                          _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
+                          _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h,
+                          w, scale, int(channels), tcx, _DTYPE_CODE[raw_dtype], _lib.current_stream(flow_lr.device))
         alpha_ctx = raw[:, :, :tc, channels:].permute(0, 2, 1, 3, 4, 5)  # (B, Tc, Tp, L, Hd, Wd), strided
     if strict:
         st.check(sync=True)
@@ -1034,7 +1063,9 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
     """``frame_warp_fuse`` behind ``flow_ctx_warp_into_raw`` (no autograd): the context alphas already sit in
     ``slots.raw`` and their per-context sums in ``slots.score``, so they are neither read nor copied -- one score
     plane per context instead of L alpha planes.  The same bits as ``frame_warp_fuse`` on the alpha view
-    (tests/test_gpu_warper.py::test_alpha_ctx_written_into_raw_slots).  Returns (out, raw as (B, Tc', Tp, ...))."""
+    (tests/test_gpu_warper.py::test_alpha_ctx_written_into_raw_slots).  Returns (out, raw as (B, Tc', Tp, ...)).
+    A 16-bit ``slots.raw`` (``flow_ctx_warp_into_raw(..., raw_dtype=...)``) gets the warped channels rounded to
+    nearest-even; ``out`` is fp32 either way."""
     _lib.check_cuda(input, flow)
     if not ctx_ts.is_cuda:
         raise _lib.WaldoHipError("frame_warp_fuse_raw: ctx_ts must be on the GPU")
@@ -1055,9 +1086,15 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
     st, strict = _status(status)
     out = input.new_empty(b, tp, c + 1, hd, wd)
     with torch.no_grad(), _lib.on_device(input.device):
-        _lib.call("waldo_frame_warp_fuse_raw_fwd", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
-                  _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
-                  1 if slots.include_self else 0, float(eps), _lib.current_stream(input.device))
+        if raw.dtype == torch.float32:
+            _lib.call("waldo_frame_warp_fuse_raw_fwd", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
+                      _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
+                      1 if slots.include_self else 0, float(eps), _lib.current_stream(input.device))
+        else:
+            _lib.call("waldo_frame_warp_fuse_raw_fwd_dt", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
+                      _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
+                      1 if slots.include_self else 0, float(eps), _DTYPE_CODE[raw.dtype],
+                      _lib.current_stream(input.device))
     if strict:
         st.check(sync=True)
     return out, raw.permute(0, 2, 1, 3, 4, 5)

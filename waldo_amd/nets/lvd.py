@@ -457,13 +457,14 @@ class Warper(nn.Module):
                                            bool(self.allow_ghost and self.layer_occupancy))
 
     def _flow_fused(self, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts, ctx_only, into_raw=None,
-                    ctx_products=None):
+                    ctx_products=None, raw_dtype=torch.float32):
         """_flow_common with the two full-resolution passes fused (csrc/flow_ctx.hip); everything at
         the low resolution goes through the same per-op kernels as the unfused path.  ``into_raw``
         (decode_output, no autograd; a list): alpha_ctx is written into the slots it will occupy in
         input_to_output's ``raw`` tensor and comes back as a view of it; the list receives the ``WF.RawSlots``
         that ``WF.frame_warp_fuse_raw`` takes (WF.flow_ctx_warp_into_raw).  ``ctx_products``: ``context_products``'
-        result for the same context (``ctx_only``): the first half is not run again."""
+        result for the same context (``ctx_only``): the first half is not run again.  ``raw_dtype``: the element type
+        of that ``raw`` tensor (fp32, bf16 or fp16; ``into_raw`` only)."""
         tgt_grid_obj, src_grid_obj, tgt_grid_bg, src_grid_bg = grid
         b, _, no = src_grid_obj.shape[:3]
         tc, tp = ctx_ts.size(1), pred_ts.size(0)
@@ -506,7 +507,7 @@ class Warper(nn.Module):
             res = WF.flow_ctx_warp_into_raw(flow_lr.reshape(b * tc * tp, nl, 2, h, w), is_obj, a01, ctx_ts, pred_ts,
                                             occ, tw, s, input.size(2), self.include_self and tp == t,
                                             layer_max=self.keep_alpha_ctx_max, status=self.index_status,
-                                            layer_bits=layer_bits if is_obj is None else None)
+                                            layer_bits=layer_bits if is_obj is None else None, raw_dtype=raw_dtype)
             into_raw.append(res[4])
         else:
             res = WF.flow_ctx_warp(flow_lr.reshape(b * tc * tp, nl, 2, h, w), is_obj, a01, ctx_ts, pred_ts, occ, tw, s,
@@ -521,7 +522,7 @@ class Warper(nn.Module):
                 disocc.view(b, tc, tp, 1, hd, wd))
 
     def _flow_common(self, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts, ctx_only, into_raw=None,
-                     ctx_products=None):
+                     ctx_products=None, raw_dtype=torch.float32):
         # int64 + contiguous ONCE for every op below; what earlier launches reported about their indices surfaces here
         ctx_ts, pred_ts = WF.normalise_time_index(ctx_ts), WF.normalise_time_index(pred_ts)
         self.index_status.check()
@@ -532,7 +533,8 @@ class Warper(nn.Module):
             raw_ok = into_raw is not None and self.raw_slots and no_grad and \
                 self._frame_warp_fused(input, ctx_ts.size(1), pred_ts.size(0))
             return self._flow_fused(input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts, ctx_only,
-                                    into_raw=into_raw if raw_ok else None, ctx_products=ctx_products if no_grad else None)
+                                    into_raw=into_raw if raw_ok else None, ctx_products=ctx_products if no_grad else None,
+                                    raw_dtype=raw_dtype)
         self.alpha_ctx_max = None  # (only the fused pass produces it)
         tgt_grid_obj, src_grid_obj, tgt_grid_bg, src_grid_bg = grid
         b, _, no = src_grid_obj.shape[:3]
@@ -658,7 +660,7 @@ def estimate_alpha_grid_occ(warper, obj_alpha, bg_alpha, obj_pose, bg_pose, occ_
 
 
 def decode_output(warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts, restrict_to_ctx=True,
-                  use_disocc=False, ctx_products=None):
+                  use_disocc=False, ctx_products=None, raw_dtype=None):
     """``LVD.forward(mode="decode_output")`` (lvd.py:141-153): flow / alpha synthesis, frame warp and
     temporal fusion, the ``use_disocc`` concatenation (lvd.py:148-151) and the split of the score
     channel.  Returns ``(output, flow, alpha_unflt, alpha, raw_alpha, raw_output, alpha_ctx)``.
@@ -668,18 +670,30 @@ def decode_output(warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pr
     is a strided VIEW into ``raw_output``'s storage (the reference returns two tensors; the values are the same): an
     in-place write to either shows in the other, and the view keeps the whole buffer alive -- clone it to detach.
     ``ctx_products``: ``Warper.context_products`` of the same context frames (``restrict_to_ctx``, no autograd), computed
-    once by a caller that decodes that context more than once."""
+    once by a caller that decodes that context more than once.
+    ``raw_dtype`` (None = fp32, torch.bfloat16, torch.float16): the element type of ``raw_output`` and ``alpha_ctx``, the
+    input of a UNet that runs under autocast.  The arithmetic stays fp32: a 16-bit result has the bits of the fp32
+    result's ``.to(raw_dtype)``.  On the raw-slot path the kernels store 16 bits themselves (``alpha_ctx`` stays a view of
+    ``raw_output``); on every other path (autograd, the unfused fallback) the fp32 tensors are cast once, differentiably.
+    ``output``, ``flow``, ``alpha``, ``alpha_unflt`` and ``raw_alpha`` stay fp32."""
+    raw_dtype = _raw_dtype(raw_dtype)
     ctx_ts, pred_ts = WF.normalise_time_index(ctx_ts), WF.normalise_time_index(pred_ts)  # shared by both calls
     # (without autograd the context alphas are composited straight into raw_output's slots: `slots` receives what
     # the frame warp needs to know about them)
     slots = []
     flow, alpha_unflt, alpha, alpha_ctx, disocc = warper._flow_common(input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts,
                                                                       pred_ts, restrict_to_ctx, into_raw=slots,
-                                                                      ctx_products=ctx_products)
+                                                                      ctx_products=ctx_products, raw_dtype=raw_dtype)
     if slots:
         output, raw_output = WF.frame_warp_fuse_raw(input, flow, slots[0], ctx_ts, status=warper.index_status)
     else:
         output, raw_output = warper.input_to_output(input, alpha_ctx, flow, ctx_ts)
+        if raw_dtype != torch.float32:
+            if warper.keep_alpha_ctx_max and warper.alpha_ctx_max is None:
+                # (the layer max of the fp32 alphas, what the fused pass hands out: a caller's disocclusion test must not
+                # depend on which path ran, nor see the rounded alphas)
+                warper.alpha_ctx_max = alpha_ctx.detach().amax(dim=3)
+            raw_output, alpha_ctx = raw_output.to(raw_dtype), alpha_ctx.to(raw_dtype)
     warper.index_status.check()  # (no synchronisation: whatever has been reported by now)
     # (ONE split instead of two slices of `output`: backward is a concatenation of the two gradients, where two
     # SliceBackward nodes each zero-fill a buffer of the full size and autograd adds them)
@@ -687,5 +701,15 @@ def decode_output(warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pr
     if use_disocc:
         if warper.include_self:
             disocc = torch.cat([disocc, torch.ones_like(disocc[:, :1])], dim=1)
-        raw_output = torch.cat([raw_output, disocc], dim=3)
+        # (in raw_output's type: torch.cat would promote a 16-bit raw_output back to fp32)
+        raw_output = torch.cat([raw_output, disocc.to(raw_output.dtype)], dim=3)
     return output, flow, alpha_unflt, alpha, raw_alpha, raw_output, alpha_ctx
+
+
+def _raw_dtype(raw_dtype):
+    """``decode_output``'s ``raw_dtype``: None -> fp32; fp32, bf16 and fp16 only."""
+    if raw_dtype is None:
+        return torch.float32
+    if raw_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"raw_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {raw_dtype}")
+    return raw_dtype

@@ -151,7 +151,7 @@ class WIF(nn.Module):
             else:
                 corners = [(ox0, oy0), (ox0, oy1), (w - 1, by1), (w - 1, by0)]
             region = point_in_polygon(orig_px, corners).float()
-            look = inpainter((1 - region) * raw_output[:, -1, -1, :3], region)
+            look = inpainter((1 - region) * raw_output[:, -1, -1, :3].float(), region)  # (fp32: a 16-bit raw_output too)
             out.append((region, look, warper.grid_to_obj_flow_from_ref_to_pred(grid, ctx_len, ref, obj_id)))
         return out
 
@@ -160,10 +160,15 @@ class WIF(nn.Module):
         background ONCE in a reference frame (the last prediction) and propagate it to the other
         predicted frames along the background flow.  `inpainter(img, mask, ...)` is the external
         MAT network (out of scope: any callable with the reference's signature).
-        Returns (B, ctx_len + Tp, 3, H, W)."""
+        Returns (B, ctx_len + Tp, 3, H, W).
+        A 16-bit ``raw_output`` / ``alpha_ctx`` (``decode_output(..., raw_dtype=...)``): ``forward`` fuses the 16-bit
+        tensor itself; the mask and propagation passes (``inpaint_holes``, the border objects) are fp32-only and get
+        an fp32 copy of ``alpha_ctx`` and of the 3-channel slice of ``raw_output`` the border objects read -- the same
+        values, so the same result as on the fp32-cast tensors."""
         o = self.opt
         if o.use_inpainter:
-            mask, obj_mask = self._holes(alpha_ctx)
+            alpha_ctx32 = alpha_ctx.float()  # (a no-op for fp32)
+            mask, obj_mask = self._holes(alpha_ctx32)
         if not o.loop_ii:
             vid = self.forward(raw_output)
             if o.use_inpainter:
@@ -186,7 +191,7 @@ class WIF(nn.Module):
             ref_to_pred = warper.grid_to_bg_flow_from_ref_to_pred(grid, ctx_len, ref)
             ref_img, ref_mask, shadow = self._reference_background(inpainter, frames, mask, obj_mask, alpha,
                                                                    real_vid, ctx_len, warper, grid, ref)
-            entering = self._border_objects(inpainter, raw_output, alpha_ctx, pred_flow, ctx_len, warper, grid,
+            entering = self._border_objects(inpainter, raw_output, alpha_ctx32, pred_flow, ctx_len, warper, grid,
                                             ref) if o.propagate_obj else []
             # (the kernels carry no gradient: under autograd with a differentiable frame the spelled-out loop runs)
             fused = (self.fuse_propagate and len(entering) <= 2 and all(x.dtype == torch.float32 for x in (ref_img, mask))

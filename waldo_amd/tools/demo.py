@@ -221,7 +221,7 @@ def _points_grids_occ(opt, warper, net, nb, nt):
 
 
 def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, shared=None, shared_key=None,
-                  out_alpha=None):
+                  out_alpha=None, raw_dtype=None):
     """One decode of predict() (estimate_alpha_grid_occ -> decode_output -> disocclusion test -> WIF fusion,
     synthesizer.py:434-460 / 464-484) for ``nb`` clips on the compact time axis ``sel`` (frame numbers: the context
     frames 0 .. ctx_len - 1, then the other frames whose poses the decode needs -- a frame may stand there twice, with
@@ -232,7 +232,8 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
     vouches for it, when ``net`` is a per-block copy of them).  Returns (output (nb, n, 3, Hd, Wd), disocc
     (nb, n, 1, Hd, Wd), inpainted (nb, n, 3, Hd, Wd), flow (nb, Tc, n, 2, Hd, Wd)).  Every kernel of the chain works
     per (b, t) unit (the layout filter's class distribution per clip, over its context frames), so the bits of a frame
-    do not depend on which other frames or clips are decoded beside it (tests/test_gpu_pipeline.py)."""
+    do not depend on which other frames or clips are decoded beside it (tests/test_gpu_pipeline.py).  ``raw_dtype``:
+    decode_output's (None = fp32; bf16 / fp16: the WIF input in 16 bits, fused by the 16-bit wif_fuse)."""
     no = opt.num_obj
     dev = real_input.device
     nt, n = len(sel), len(where)
@@ -318,7 +319,8 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
     warper.return_alpha = want_alpha
     try:
         output, flow, _, alpha, _, raw_output, alpha_ctx = decode_output(warper, real_input, grid, occ, obj_alpha, bga,
-                                                                         net["cls"], ctx_ts, pred_ts, ctx_products=products)
+                                                                         net["cls"], ctx_ts, pred_ts, ctx_products=products,
+                                                                         raw_dtype=raw_dtype)
         mx = warper.alpha_ctx_max
     finally:
         warper.keep_alpha_ctx_max, warper.return_alpha = prev, prev_alpha
@@ -334,10 +336,11 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
 
 
 @torch.no_grad()
-def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len):
+def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None):
     """The hot-path part of Synthesizer.predict (models/synthesizer.py:434-480).  real_vid
     (B, T, 3, H, W), real_lyt (B, T, Nl, H, W); ``net`` = synthetic_network_outputs(...).
-    Returns a dict of the tensors predict produces."""
+    ``raw_dtype``: the element type of the WIF input ``raw_output`` (None = fp32; torch.bfloat16 / torch.float16 for a
+    UNet under autocast -- decode_output).  Returns a dict of the tensors predict produces."""
     b, t = real_vid.shape[:2]
     every = list(range(t))
     out = {}
@@ -351,18 +354,21 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len):
     if getattr(opt, "include_self", False) or not MERGE_DECODES or opt.no_future:
         # the reference's two calls, one after the other (include_self: every frame is a context of itself)
         shared = SharedContext() if not getattr(opt, "include_self", False) else None
-        rec, dis, inp, _ = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every, every, shared=shared)
+        rec, dis, inp, _ = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every, every, shared=shared,
+                                         raw_dtype=raw_dtype)
         out["rec_vid"], out["rec_disocc"], out["inp_rec_vid"] = rec, dis, inp
         if not opt.no_future:
             alpha = []
             pred, dis, inp, flow = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every,
-                                                 list(range(ctx_len, t)), shared=shared, out_alpha=alpha)
+                                                 list(range(ctx_len, t)), shared=shared, out_alpha=alpha,
+                                                 raw_dtype=raw_dtype)
     else:
         # ONE decode for the reconstruction's and the prediction's units (see decode_units): the context's products once,
         # every full-resolution pass launched once with T + Tp units per clip
         alpha = []
         (rec, dis, inp, _), (pred, dis_p, inp_p, flow) = decode_units(
-            opt, warper, wif, real_input, net, ctx_len, b, t, 0, b, every, list(range(ctx_len, t)), out_alpha=alpha)
+            opt, warper, wif, real_input, net, ctx_len, b, t, 0, b, every, list(range(ctx_len, t)), out_alpha=alpha,
+            raw_dtype=raw_dtype)
         out["rec_vid"], out["rec_disocc"], out["inp_rec_vid"] = rec, dis, inp
         dis, inp = dis_p, inp_p
     if not opt.no_future:
@@ -388,17 +394,19 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len):
 MERGE_DECODES = True
 
 
-def decode_units(opt, warper, wif, real_input, net, ctx_len, b, t, b0, b1, rec_frames, pred_frames, out_alpha=None):
+def decode_units(opt, warper, wif, real_input, net, ctx_len, b, t, b0, b1, rec_frames, pred_frames, out_alpha=None,
+                 raw_dtype=None):
     """The reconstruction's frames ``rec_frames`` and the prediction's frames ``pred_frames`` (clip-relative frame numbers,
     ascending) of clips b0:b1 in ONE decode.  Returns the two 4-tuples of ``_decode_block`` (either may be None when its
-    list is empty)."""
+    list is empty).  ``raw_dtype``: see ``_decode_block``."""
     dev = real_input.device
     rec_new = [f for f in rec_frames if f >= ctx_len]
     sel = list(range(ctx_len)) + rec_new + list(pred_frames)
     where = [f if f < ctx_len else ctx_len + rec_new.index(f) for f in rec_frames] + \
             [ctx_len + len(rec_new) + i for i in range(len(pred_frames))]
     blk = _block_net(opt, net, b, t, b0, b1, sel, dev)
-    vid, dis, inp, flow = _decode_block(opt, warper, wif, real_input, blk, ctx_len, b1 - b0, sel, where, out_alpha=out_alpha)
+    vid, dis, inp, flow = _decode_block(opt, warper, wif, real_input, blk, ctx_len, b1 - b0, sel, where, out_alpha=out_alpha,
+                                        raw_dtype=raw_dtype)
     nr = len(rec_frames)
 
     def part(lo, hi):
@@ -469,7 +477,8 @@ UNIT_KEYS = {"rec": ("rec_vid", "rec_disocc", "inp_rec_vid"), "pred": ("pred_vid
 
 
 @torch.no_grad()
-def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, world, phases=("rec", "pred")):
+def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, world, phases=("rec", "pred"),
+                    raw_dtype=None):
     """This rank's share of predict() when ONE job (B clips) is split over ``world`` ranks: the
     (b, t) output units of each decode -- B * T reconstructed frames, B * (T - Tc) predicted ones -- are dealt in
     contiguous blocks of the phase's dealing order (dist.shard_range over ``phase_order``: the reconstruction's spreads
@@ -481,7 +490,7 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
     Returns {key: (units, C, Hd, Wd)} with the rank's units in the order of ``local_unit_ids``, for the keys of UNIT_KEYS
     (``pred_vid`` / ``inp_pred_vid``: the predicted frames only; ``pred_flow``: Tc * 2 channels); ``gather_predict`` puts
     the ranks' blocks together into predict()'s dict.  Reference: the data-parallel split of tools/engine.py:63-64, here
-    over frames instead of clips so that one clip can use every GPU."""
+    over frames instead of clips so that one clip can use every GPU.  ``raw_dtype``: see ``predict``."""
     from ..dist import shard_range
     if opt.include_self:
         raise ValueError("predict_sharded: include_self appends the predicted frame itself as a context "
@@ -523,7 +532,7 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
         # this rank's reconstruction and prediction units belong to the same clips: ONE decode for both (decode_units)
         b0, b1, rec_frames = segs["rec"][0]
         rec, pred = decode_units(opt, warper, wif, clip_input(b0, b1), net, ctx_len, b, t, b0, b1, rec_frames,
-                                 segs["pred"][0][2])
+                                 segs["pred"][0][2], raw_dtype=raw_dtype)
         keep("rec", b1 - b0, rec)
         keep("pred", b1 - b0, pred)
     else:
@@ -533,7 +542,7 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
                 blk = _block_net(opt, net, b, t, b0, b1, sel, dev)
                 res = _decode_block(opt, warper, wif, clip_input(b0, b1), blk, ctx_len, b1 - b0, sel,
                                     [sel.index(f) for f in frames], shared=shared[(b0, b1)],
-                                    shared_key=job + (inputs[(b0, b1)],))
+                                    shared_key=job + (inputs[(b0, b1)],), raw_dtype=raw_dtype)
                 keep(phase, b1 - b0, res)
     for k, v in parts.items():
         if v:
@@ -581,8 +590,11 @@ def gather_predict(local, real_vid, ctx_len, keys=None, group=None):
     return {k: units_to_clips(k, pending[k].wait(), b, t, ctx_len, world, real_vid) for k in keys}
 
 
+RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --raw-dtype
+
+
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
-        device="cuda:0"):
+        device="cuda:0", raw_dtype=None):
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt)
     size = (dim, int(dim * aspect_ratio))
     clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames)
@@ -591,7 +603,7 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
     warper = Warper(opt).to(dev)
     wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     net = synthetic_network_outputs(opt, 1, vid.shape[1], ctx_len, seed=seed, device=dev)
-    res = predict(opt, warper, wif, vid, lyt, net, ctx_len)
+    res = predict(opt, warper, wif, vid, lyt, net, ctx_len, raw_dtype=raw_dtype)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         for key in ("rec_vid", "inp_rec_vid", "pred_vid", "inp_pred_vid"):
@@ -614,9 +626,11 @@ def main():
     ap.add_argument("--frames", type=int, default=6)
     ap.add_argument("--ctx-len", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--raw-dtype", choices=sorted(RAW_DTYPES), default="fp32",
+                    help="element type of the WIF input raw_output (bf16 / fp16: what a UNet under autocast takes)")
     args = ap.parse_args()
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
-              ctx_len=args.ctx_len, seed=args.seed)
+              ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype])
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "
               f"finite={bool(torch.isfinite(v).all())}")
