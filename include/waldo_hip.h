@@ -38,6 +38,16 @@ typedef void* waldo_stream_t; /* hipStream_t */
  * widened to fp32 on load.  Any other code: WALDO_EINVAL with a message, before any launch. */
 enum waldo_dtype { WALDO_DTYPE_F32 = 0, WALDO_DTYPE_F16 = 1, WALDO_DTYPE_BF16 = 2 };
 
+/* Packed clip (waldo_amd.functional.PackedClip).  The clip that A9 / A10 read, (B,T,3+Nl,Hd,Wd) fp32 = three RGB planes
+ * and Nl layout-logit planes, stored as (B,T,Hd,Wd) pixels of 4 bytes [R, G, B, class id] (uint8, 16-byte aligned
+ * base for the staged frame warp).  Its UNPACKED form -- what every *_packed entry point computes with, bit for bit:
+ *   channel c < 3:  rgb_table[byte c], rgb_table = 256 fp32 values owned by the caller (read_rgb's (u8/255 - 0.5)/0.5);
+ *   channel 3 + n:  +5.0f where class id == n, -5.0f elsewhere (a class id >= Nl: -5 in every layout channel).
+ * Nl <= 32, the fused path's class limit.  The packed entry points produce what their fp32 twins produce on the
+ * unpacked clip (waldo_unpack_clip_fwd), bit for bit; the clip carries no gradient (no packed backward). */
+int waldo_unpack_clip_fwd(const uint8_t* clip, const float* rgb_table, float* out, int B, int T, int Nl, int Hd, int Wd,
+                          waldo_stream_t stream); /* out (B,T,3+Nl,Hd,Wd); 0 <= Nl <= 32 */
+
 /* ABI version: major*1000 + minor. */
 int waldo_version(void);
 const char* waldo_last_error_string(void);
@@ -268,6 +278,11 @@ int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* input, const fl
                              const float* occ, float* a01, float* alpha_out, unsigned* layer_bits, int B, int T,
                              int Tw, int L, int Nl, int C, int chan_off, int H, int W, int scale,
                              waldo_stream_t stream);
+/* The same on a packed clip (B,T,Hd,Wd) ("Packed clip" above) in place of `input`: the layout logits of a pixel are the
+ * +-5 of its class byte, fed to the same softmax.  1 <= Nl <= 32; `clip` is required. */
+int waldo_flow_ctx_alpha_packed_fwd(const float* alpha_lr, const uint8_t* clip, const float* dist, const float* occ,
+                                    float* a01, float* alpha_out, unsigned* layer_bits, int B, int T, int Tw, int L,
+                                    int Nl, int H, int W, int scale, waldo_stream_t stream);
 /* alpha_max (M,Hd,Wd), optional (NULL to skip): max over the layers of alpha_ctx -- what
  * Synthesizer.predict's disocclusion test takes from it (models/synthesizer.py:447, `alpha_ctx.max(dim=3)[0]`:
  * a pass over the largest tensor but one of the pipeline, here a by-product of writing it). */
@@ -335,6 +350,14 @@ int waldo_frame_warp_fuse_raw_fwd_dt(const float* input, const float* flow, cons
                                      const int64_t* ctx_ts, float* out, void* raw, int* status, int B, int T, int Tc,
                                      int Tp, int C, int L, int Hd, int Wd, int include_self, float eps, int raw_dtype,
                                      waldo_stream_t stream);
+/* The same on a packed clip (B,T,Hd,Wd) ("Packed clip" above) in place of `input`, C = 3 + Nl channels, 0 <= Nl <= 32;
+ * the self slot (include_self) is the unpacked frame.  Every form of the fp32 call (the staged boxes with Wd % 4 == 0,
+ * a 16-byte aligned clip and Tc <= 4 -- each box staged ONCE for all channels --, the per-context gathers, the plain
+ * kernel) with the bits of waldo_frame_warp_fuse_raw_fwd_dt on the unpacked clip. */
+int waldo_frame_warp_fuse_raw_packed_fwd(const uint8_t* clip, const float* rgb_table, const float* flow,
+                                         const float* score, const int64_t* ctx_ts, float* out, void* raw, int* status,
+                                         int B, int T, int Tc, int Tp, int Nl, int L, int Hd, int Wd, int include_self,
+                                         float eps, int raw_dtype, waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Backward of A9 / A10 (csrc/flow_ctx_bwd.hip): the reference's live backward path in LVD training
@@ -574,6 +597,10 @@ int waldo_time_gather_bwd(const float* grad_out, const int64_t* ctx_ts, const in
  * ------------------------------------------------------------------------------------- */
 int waldo_downscale_frames_fwd(const float* input, float* out, int B, int T, int Tw, int C, int c0, int H,
                                int W, int S, waldo_stream_t stream);
+/* The same for the layout channels of a packed clip (B,T,H*S,W*S) ("Packed clip" above): out (B,Tw,Nl,H,W), the bits of
+ * waldo_downscale_frames_fwd on the unpacked clip with c0 = 3.  1 <= Nl <= 32. */
+int waldo_downscale_frames_packed_fwd(const uint8_t* clip, float* out, int B, int T, int Tw, int Nl, int H, int W,
+                                      int S, waldo_stream_t stream);
 
 #ifdef __cplusplus
 }

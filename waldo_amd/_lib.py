@@ -57,6 +57,11 @@ SIGNATURES = {
     # the *_dt forms: the retyped buffers as void* plus WALDO_DTYPE_* codes (include/waldo_hip.h: enum waldo_dtype)
     "waldo_flow_ctx_warp_raw_fwd_dt": [_c_f] * 13 + [_int] * 12 + [_stream],
     "waldo_frame_warp_fuse_raw_fwd_dt": [_c_f] * 7 + [_int] * 9 + [_flt, _int, _stream],
+    # the packed clip (include/waldo_hip.h: "Packed clip"): uint8 (B, T, Hd, Wd, 4) in place of the fp32 input
+    "waldo_unpack_clip_fwd": [_c_f] * 3 + [_int] * 5 + [_stream],
+    "waldo_downscale_frames_packed_fwd": [_c_f, _c_f] + [_int] * 7 + [_stream],
+    "waldo_flow_ctx_alpha_packed_fwd": [_c_f] * 7 + [_int] * 8 + [_stream],
+    "waldo_frame_warp_fuse_raw_packed_fwd": [_c_f] * 8 + [_int] * 9 + [_flt, _int, _stream],
     "waldo_flow_ctx_alpha_bwd": [_c_f] * 10 + [_int] * 10 + [_stream],
     "waldo_flow_ctx_warp_bwd": [_c_f] * 13 + [_int] * 9 + [_stream],
     "waldo_frame_warp_fuse_bwd": [_c_f] * 8 + [_int] * 9 + [_flt, _stream],

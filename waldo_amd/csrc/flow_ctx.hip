@@ -24,12 +24,17 @@
 #include <type_traits>
 
 #include "flow_ctx_common.hip.h"
+#include "packed_clip.hip.h"
 
 namespace waldo {
 
-template <int LP, int NCP>
+static_assert(kMaxPackedCls == kMaxCls, "a packed clip's classes: the fused path's limit");
+
+// IN: the element type of `input` -- float, or uint32_t for a packed clip (packed_clip.hip.h: the layout logits are the
+// +-5 of the pixel's class byte, fed to the same softmax; C = 3 + Nl and chan_off = 3 of the unpacked form, not used)
+template <int LP, int NCP, typename IN = float>
 __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
-    const float* __restrict__ alpha_lr, const float* __restrict__ input,
+    const float* __restrict__ alpha_lr, const IN* __restrict__ input,
     const float* __restrict__ dist, const float* __restrict__ occ, float* __restrict__ a01,
     float* __restrict__ alpha_out, unsigned* __restrict__ layer_bits, int T, int Tw, int L, int Nl, int C, int chan_off,
     int H, int W, int scale, int units, int tiles, int nbands) {
@@ -71,13 +76,22 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
 
   if (dist != nullptr) {
     // softmax over the Nl layout logits of this pixel (held in registers)
-    const float* lg = input + (((int64_t)b * T + t) * C + chan_off) * HWd + p;
     float pr[NCP];
     float m = -INFINITY;
+    if constexpr (std::is_same<IN, uint32_t>::value) {
+      const uint32_t w = input[((int64_t)b * T + t) * HWd + p];
 #pragma unroll
-    for (int c = 0; c < NCP; ++c) {
-      pr[c] = (c < Nl) ? lg[(int64_t)min(c, Nl - 1) * HWd] : -INFINITY;
-      m = fmaxf(m, pr[c]);
+      for (int c = 0; c < NCP; ++c) {
+        pr[c] = (c < Nl) ? packed_lyt(w, c) : -INFINITY;
+        m = fmaxf(m, pr[c]);
+      }
+    } else {
+      const float* lg = input + (((int64_t)b * T + t) * C + chan_off) * HWd + p;
+#pragma unroll
+      for (int c = 0; c < NCP; ++c) {
+        pr[c] = (c < Nl) ? lg[(int64_t)min(c, Nl - 1) * HWd] : -INFINITY;
+        m = fmaxf(m, pr[c]);
+      }
     }
     float den = 0.0f;
 #pragma unroll
@@ -568,12 +582,16 @@ __device__ __forceinline__ void fwf_put(T* at, bool odd, float v) {
 // pulls a line of its own; the squarer wavefront keeps the footprint compact, and at 32 columns the stores
 // are still whole 128-byte lines.
 // RT: the element type of `raw` (16-bit: the raw path only -- `alpha` is then NULL -- one 2-byte store per pixel).
-template <int TCP, typename RT = float>
+// IN: the element type of `input` -- float, or uint32_t for a packed clip (the raw path only; packed_clip.hip.h): the four
+// tap words of a context are loaded ONCE and every channel is expanded from them (C = 3 + Nl channels, `rgb_table` the
+// RGB table; NULL for an fp32 input).  The taps, weights and the per-channel arithmetic (fwf_fuse) are the same code.
+template <int TCP, typename RT = float, typename IN = float>
 __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
-    const float* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
+    const IN* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
     const float* __restrict__ score, const int64_t* __restrict__ ctx_ts, float* __restrict__ out,
     RT* __restrict__ raw, int* __restrict__ status, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
-    float eps, int units, int tiles, int nbands) {
+    float eps, int units, int tiles, int nbands, const float* __restrict__ rgb_table) {
+  constexpr bool kPacked = std::is_same<IN, uint32_t>::value;
   const int64_t HWd = (int64_t)Hd * Wd;
   int n, x, y;  // n = (b, tp); the Tp predicted frames of a clip innermost in an XCD's tile walk
   if (!HdTile<WALDO_FWF_TILE_COLS>::pixel_grouped(units / Tp, Tp, Hd, Wd, tiles, nbands, n, x, y) || x >= Wd || y >= Hd) return;
@@ -594,7 +612,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
   uint32_t ob0[TCP], ob1[TCP];
   int shift[TCP];
   float w00[TCP], w01[TCP], w10[TCP], w11[TCP], sc[TCP];
-  const float* frame[TCP];
+  const IN* frame[TCP];
   float ssum = 0.0f;
   bool shifted = false;
 #pragma unroll
@@ -617,7 +635,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
     w10[tc] = t.w10;
     w11[tc] = t.w11;
     const int ts = __builtin_amdgcn_readfirstlane(checked_frame(ctx_ts, m, T, status, kStatusCtx));  // wave-uniform
-    frame[tc] = input + ((int64_t)b * T + ts) * C * HWd;
+    frame[tc] = input + ((int64_t)b * T + ts) * (kPacked ? 1 : C) * HWd;
     float s = 0.0f;
     if (score != nullptr) {
       // the alphas already sit in `raw` (waldo_flow_ctx_warp_raw_fwd wrote them there) and their sum came with
@@ -645,7 +663,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
   float wt[TCP];
 #pragma unroll
   for (int tc = 0; tc < TCP; ++tc) wt[tc] = (tc < Tc) ? (sc[tc] + eps) / den : 0.0f;
-  const float* self = input + ((int64_t)b * T + min(tp, T - 1)) * C * HWd + p;
+  const IN* self = input + ((int64_t)b * T + min(tp, T - 1)) * (kPacked ? 1 : C) * HWd + p;
   RT* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + p;  // context tc: + tc * (C+L) * HWd
   float* obase = out + ((int64_t)b * Tp + tp) * (C + 1) * HWd + p;
   // Channel loop, software-pipelined by hand: the sixteen tap loads of channel c + 1 are issued BEFORE the
@@ -653,15 +671,14 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
   // with the stores first every channel's taps would wait for the previous channel's stores to reach
   // memory -- gathers and stores then take turns instead of overlapping (timing ablations at the C5 size:
   // 4.5 ms as written that way, 3.3 without the raw stores, 3.3 without the gathers, 1.7 without both).
-  typedef float f32x2_fw __attribute__((ext_vector_type(2)));
   const bool any_shift = __ballot(shifted) != 0ull;  // wave-uniform
-  float tv[TCP][4];
-  auto load_taps = [&](int c, float (&v)[TCP][4]) {
+  typedef IN in2_fw __attribute__((ext_vector_type(2)));  // (two taps of a row: one 8-byte load)
+  auto load_taps = [&](int c, IN (&v)[TCP][4]) {
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
-      const float* plane = frame[tc] + (int64_t)c * HWd;
-      const f32x2_fw top = *reinterpret_cast<const f32x2_fw*>(reinterpret_cast<const char*>(plane) + ob0[tc]);
-      const f32x2_fw bot = *reinterpret_cast<const f32x2_fw*>(reinterpret_cast<const char*>(plane) + ob1[tc]);
+      const IN* plane = frame[tc] + (int64_t)c * HWd;
+      const in2_fw top = *reinterpret_cast<const in2_fw*>(reinterpret_cast<const char*>(plane) + ob0[tc]);
+      const in2_fw bot = *reinterpret_cast<const in2_fw*>(reinterpret_cast<const char*>(plane) + ob1[tc]);
       v[tc][0] = top[0];
       v[tc][1] = top[1];
       v[tc][2] = bot[0];
@@ -669,11 +686,11 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
     }
   };
   // corners of the footprint from the pair elements (see above); a no-op for interior wavefronts
-  auto assign = [&](float (&v)[TCP][4]) {
+  auto assign = [&](auto& v) {  // (float or uint32_t elements)
     if (any_shift) {
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc) {
-        const float a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
+        const auto a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
         v[tc][0] = shift[tc] > 0 ? a1 : a0;
         v[tc][1] = shift[tc] < 0 ? a0 : a1;
         v[tc][2] = shift[tc] > 0 ? b1 : b0;
@@ -681,12 +698,8 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
       }
     }
   };
-  load_taps(0, tv);
-  for (int c = 0; c < C; ++c) {
-    float nv[TCP][4];
-    load_taps(min(c + 1, C - 1), nv);  // the last trip re-reads its own channel: no branch around the loads
-    assign(tv);
-    const float vself = include_self ? self[(int64_t)c * HWd] : 0.0f;
+  // channel c of the output from the corner values of every context and the unwarped frame's (include_self)
+  auto fuse = [&](int c, const float (&tv)[TCP][4], float vself) {
     float acc = 0.0f;
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
@@ -699,10 +712,34 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
       acc += vself * wself;
     }
     fwf_store(obase + (int64_t)c * HWd, acc);
+  };
+  if constexpr (kPacked) {
+    // every channel of a tap is in its word: the taps of all contexts once, then C channels from registers
+    uint32_t tw[TCP][4];
+    load_taps(0, tw);
+    assign(tw);
+    const uint32_t pself = include_self ? self[0] : 0u;  // (the unwarped frame's word)
+    for (int c = 0; c < C; ++c) {
+      float tv[TCP][4];
 #pragma unroll
-    for (int tc = 0; tc < TCP; ++tc)
+      for (int tc = 0; tc < TCP; ++tc)
 #pragma unroll
-      for (int k = 0; k < 4; ++k) tv[tc][k] = nv[tc][k];
+        for (int k = 0; k < 4; ++k) tv[tc][k] = packed_channel(rgb_table, tw[tc][k], c);
+      fuse(c, tv, include_self ? packed_channel(rgb_table, pself, c) : 0.0f);
+    }
+  } else {
+    float tv[TCP][4];
+    load_taps(0, tv);
+    for (int c = 0; c < C; ++c) {
+      float nv[TCP][4];
+      load_taps(min(c + 1, C - 1), nv);  // the last trip re-reads its own channel: no branch around the loads
+      assign(tv);
+      fuse(c, tv, include_self ? self[(int64_t)c * HWd] : 0.0f);
+#pragma unroll
+      for (int tc = 0; tc < TCP; ++tc)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tv[tc][k] = nv[tc][k];
+    }
   }
   float acc = 0.0f;  // the score channel
 #pragma unroll
@@ -737,12 +774,16 @@ constexpr int kFwfCap = 1024;  // texels of one context's staged box = one float
 // (8 x 32 tiles with the same lane pairs write half lines: 8.66 against 7.33 ms per C5 step, profiles/r07_raw_dtype_*)
 template <typename RT>
 constexpr int fwf_kcols() { return std::is_same<RT, float>::value ? 32 : 64; }
-template <int TCP, bool FULL, typename RT = float>
+// IN = uint32_t: a packed clip (the raw path only, `rgb_table` its RGB table; packed_clip.hip.h).  A context's box holds
+// ONE word per pixel for all C = 3 + Nl channels: it is staged once, its taps are read from LDS once, and the channel
+// loop expands them with the same corner assignment and per-channel arithmetic (fuse_store) -- no loads, no barriers.
+template <int TCP, bool FULL, typename RT = float, typename IN = float>
 __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_lds_kernel(
-    const float* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
+    const IN* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
     const float* __restrict__ score, const int64_t* __restrict__ ctx_ts, float* __restrict__ out,
     RT* __restrict__ raw, int* __restrict__ status, int T, int Tc_, int Tp, int C, int L, int Hd, int Wd, int include_self_,
-    float eps, int units, int tiles, int nbands) {
+    float eps, int units, int tiles, int nbands, const float* __restrict__ rgb_table) {
+  constexpr bool kPacked = std::is_same<IN, uint32_t>::value;
   typedef float f32x2_fw __attribute__((ext_vector_type(2)));
   typedef short s16x2 __attribute__((ext_vector_type(2)));
   static_assert(kBlock * 4 == kFwfCap, "one float4 of the box per thread");
@@ -776,7 +817,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   int shift[TCP];
   float w00[TCP], w01[TCP], w10[TCP], w11[TCP], sc[TCP];
   int cyx0[TCP], cy1v[TCP];  // (clamped row y0, pair origin xb) packed; clamped row y1
-  const float* frame[TCP];
+  const IN* frame[TCP];
   float ssum = 0.0f;
   bool shifted = false;
 #pragma unroll
@@ -809,7 +850,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
       wbox[wave][tc][1] = __builtin_bit_cast(int, hi);
     }
     const int ts = __builtin_amdgcn_readfirstlane(checked_frame(ctx_ts, m, T, status, kStatusCtx));  // wave-uniform
-    frame[tc] = input + ((int64_t)b * T + ts) * C * HWd;
+    frame[tc] = input + ((int64_t)b * T + ts) * (kPacked ? 1 : C) * HWd;
     float sv = 0.0f;
     if (score != nullptr) {
       sv = score[m * HWd + p];
@@ -829,6 +870,12 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     RT* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + pr;
     for (int l = 0; l < L; ++l) fwf_put<true>(rw + (int64_t)l * HWd, odd, 1.0f);
     ssum += fabsf(1.0f + eps);
+  }
+  // (packed) the RGB table in LDS, one entry per thread (read after the barriers below)
+  __shared__ float stab[kPacked ? kRgbTable : 1];
+  if constexpr (kPacked) {
+    static_assert(kBlock == kRgbTable, "one table entry per thread");
+    stab[t] = rgb_table[t];
   }
   lds_barrier();
   // ---- per context (uniform): the tile's box, whether it fits, this thread's float4 of it
@@ -862,16 +909,16 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   float wt[TCP];
 #pragma unroll
   for (int tc = 0; tc < TCP; ++tc) wt[tc] = (tc < Tc) ? (sc[tc] + eps) / den : 0.0f;
-  const float* self = input + ((int64_t)b * T + min(tp, T - 1)) * C * HWd + p;
+  const IN* self = input + ((int64_t)b * T + min(tp, T - 1)) * (kPacked ? 1 : C) * HWd + p;
   RT* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + pr;  // context tc: + tc * (C+L) * HWd
   float* obase = out + ((int64_t)b * Tp + tp) * (C + 1) * HWd + p;
   const bool any_shift = __ballot(shifted) != 0ull;  // wave-uniform
   // corners of the footprint from the pair elements (see the kernel above); a no-op for interior wavefronts
-  auto assign = [&](float (&v)[TCP][4]) {
+  auto assign = [&](auto& v) {  // (float or uint32_t elements)
     if (any_shift) {
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc) {
-        const float a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
+        const auto a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
         v[tc][0] = shift[tc] > 0 ? a1 : a0;
         v[tc][1] = shift[tc] < 0 ? a0 : a1;
         v[tc][2] = shift[tc] > 0 ? b1 : b0;
@@ -879,8 +926,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
       }
     }
   };
-  auto fuse_store = [&](int c, const float (&v4)[TCP][4]) {
-    const float vself = include_self ? self[(int64_t)c * HWd] : 0.0f;
+  auto fuse_store = [&](int c, const float (&v4)[TCP][4], float vself) {
     float acc = 0.0f;
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
@@ -915,7 +961,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     auto issue = [&](int c) {  // channel c: this thread's float4 of every staged box, the pairs of the others
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc) {
-        const float* plane = frame[tc] + (int64_t)c * HWd;
+        const auto* plane = frame[tc] + (int64_t)c * HWd;
         if ((MASK >> tc) & 1u) {
           box4[tc] = *reinterpret_cast<const f32x4*>(plane + goff[tc]);
         } else {
@@ -962,7 +1008,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
         }
       }
       assign(tv);
-      fuse_store(c, tv);
+      fuse_store(c, tv, include_self ? self[(int64_t)c * HWd] : 0.0f);
       if (kAny) lds_barrier();  // every thread has read channel c's taps
       park();  // (waits for the boxes of channel c + 1, not for channel c's stores)
       take();
@@ -971,7 +1017,48 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   };
   // (uniform dispatch; a context beyond Tc repeats context Tc - 1: same box, same bit.  Tc = 4: a context whose box
   // does not fit gathers ALONE, where round 4 gathered for the whole tile)
-  if (FULL && TCP == 4) {
+  if constexpr (kPacked) {
+    // one word per pixel: every staged box once (one 16-byte load per thread), the pairs of the others once
+    typedef uint32_t u32x4_fw __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2_fw __attribute__((ext_vector_type(2)));
+    uint32_t tw[TCP][4];
+#pragma unroll
+    for (int tc = 0; tc < TCP; ++tc) {
+      if ((stage_mask >> tc) & 1u) {  // (uniform)
+        const u32x4_fw q = *reinterpret_cast<const u32x4_fw*>(frame[tc] + goff[tc]);
+        if ((mine >> tc) & 1u) *reinterpret_cast<u32x4_fw*>(&img[tc][4 * t]) = q;
+      } else {
+        const int cy0 = cyx0[tc] >> 16, xb = cyx0[tc] & 0xffff;
+        const char* fr = reinterpret_cast<const char*>(frame[tc]);
+        const u32x2_fw top = *reinterpret_cast<const u32x2_fw*>(fr + (uint32_t)(__mul24(cy0, Wd) + xb) * 4u);
+        const u32x2_fw bot = *reinterpret_cast<const u32x2_fw*>(fr + (uint32_t)(__mul24(cy1v[tc], Wd) + xb) * 4u);
+        tw[tc][0] = top[0];
+        tw[tc][1] = top[1];
+        tw[tc][2] = bot[0];
+        tw[tc][3] = bot[1];
+      }
+    }
+    lds_barrier();
+#pragma unroll
+    for (int tc = 0; tc < TCP; ++tc)
+      if ((stage_mask >> tc) & 1u) {
+        const char* im = reinterpret_cast<const char*>(&img[tc][0]);
+        tw[tc][0] = *reinterpret_cast<const uint32_t*>(im + ob0[tc]);
+        tw[tc][1] = *reinterpret_cast<const uint32_t*>(im + ob0[tc] + 4);
+        tw[tc][2] = *reinterpret_cast<const uint32_t*>(im + ob1[tc]);
+        tw[tc][3] = *reinterpret_cast<const uint32_t*>(im + ob1[tc] + 4);
+      }
+    assign(tw);
+    const uint32_t pself = include_self ? self[0] : 0u;  // (the unwarped frame's word)
+    for (int c = 0; c < C; ++c) {
+      float tv[TCP][4];
+#pragma unroll
+      for (int tc = 0; tc < TCP; ++tc)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tv[tc][k] = packed_channel(stab, tw[tc][k], c);
+      fuse_store(c, tv, include_self ? packed_channel(stab, pself, c) : 0.0f);
+    }
+  } else if (FULL && TCP == 4) {
     switch (stage_mask & 15u) {
 #define WALDO_FWF_CASE(M) case M: channel_loop(std::integral_constant<unsigned, M>{}); break;
       WALDO_FWF_CASE(0) WALDO_FWF_CASE(1) WALDO_FWF_CASE(2) WALDO_FWF_CASE(3) WALDO_FWF_CASE(4) WALDO_FWF_CASE(5)
@@ -1010,29 +1097,25 @@ static int check_flow_ctx(const char* fn, int64_t N, int L, int H, int W, int sc
 
 using namespace waldo;
 
-#ifndef WALDO_FC_RAW_HALF  // (the fp32 unit; flow_ctx_raw_bf16.hip / _f16.hip compile the 16-bit raw path: end of file)
-#define WALDO_FC_CASE(LPV, KERNEL, ...)                                                      \
-  case LPV:                                                                                  \
-    hipLaunchKernelGGL((KERNEL<LPV>), dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0, st, \
-                       __VA_ARGS__, (int)N, geom.tiles, geom.nbands);                        \
-    break;
-
-extern "C" int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* input, const float* dist,
-                                        const float* occ, float* a01, float* alpha_out, unsigned* layer_bits, int B,
-                                        int T, int Tw, int L, int Nl, int C, int chan_off, int H, int W,
-                                        int scale, waldo_stream_t stream) {
+// flow_ctx_alpha for an fp32 clip (IN = float: the layout logits in channels [chan_off, chan_off + Nl) of C) or a packed
+// one (IN = uint32_t: the class byte of the pixel's word; C = 3 + Nl, chan_off = 3 as in its unpacked form)
+template <typename IN>
+static int flow_ctx_alpha_launch(const char* fn, const float* alpha_lr, const IN* input, const float* dist,
+                                 const float* occ, float* a01, float* alpha_out, unsigned* layer_bits, int B, int T,
+                                 int Tw, int L, int Nl, int C, int chan_off, int H, int W, int scale,
+                                 waldo_stream_t stream) {
   const int64_t N = (int64_t)B * Tw;
-  int rc = check_flow_ctx("waldo_flow_ctx_alpha_fwd", N, L, H, W, scale);
+  int rc = check_flow_ctx(fn, N, L, H, W, scale);
   if (rc) return rc;
   if (B < 0 || T < 1 || Tw < 1 || Tw > T ||
       (dist != nullptr && (Nl < 1 || Nl > kMaxCls || chan_off < 0 || chan_off + Nl > C))) {
-    set_error("waldo_flow_ctx_alpha_fwd: bad frame window Tw=%d of T=%d or class channels [%d, %d) of %d "
-              "(at most %d classes)", Tw, T, chan_off, chan_off + Nl, C, kMaxCls);
+    set_error("%s: bad frame window Tw=%d of T=%d or class channels [%d, %d) of %d "
+              "(at most %d classes)", fn, Tw, T, chan_off, chan_off + Nl, C, kMaxCls);
     return WALDO_EINVAL;
   }
   if (N == 0) return WALDO_OK;
   if (!alpha_lr || !occ || !a01 || (dist != nullptr && !input)) {
-    set_error("waldo_flow_ctx_alpha_fwd: null pointer");
+    set_error("%s: null pointer", fn);
     return WALDO_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -1041,13 +1124,13 @@ extern "C" int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* inpu
 #define WALDO_FCA_CASE(LPV)                                                                                              \
   case LPV:                                                                                                              \
     if (dist == nullptr || Nl <= kFewCls)                                                                                \
-      hipLaunchKernelGGL((flow_ctx_alpha_kernel<LPV, kFewCls>), dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0, st,   \
-                         alpha_lr, input, dist, occ, a01, alpha_out, layer_bits, T, Tw, L, Nl, C, chan_off, H, W, scale, \
-                         (int)N, geom.tiles, geom.nbands);                                                               \
+      hipLaunchKernelGGL((flow_ctx_alpha_kernel<LPV, kFewCls, IN>), dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0,   \
+                         st, alpha_lr, input, dist, occ, a01, alpha_out, layer_bits, T, Tw, L, Nl, C, chan_off, H, W,    \
+                         scale, (int)N, geom.tiles, geom.nbands);                                                        \
     else                                                                                                                 \
-      hipLaunchKernelGGL((flow_ctx_alpha_kernel<LPV, kMaxCls>), dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0, st,   \
-                         alpha_lr, input, dist, occ, a01, alpha_out, layer_bits, T, Tw, L, Nl, C, chan_off, H, W, scale, \
-                         (int)N, geom.tiles, geom.nbands);                                                               \
+      hipLaunchKernelGGL((flow_ctx_alpha_kernel<LPV, kMaxCls, IN>), dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0,   \
+                         st, alpha_lr, input, dist, occ, a01, alpha_out, layer_bits, T, Tw, L, Nl, C, chan_off, H, W,    \
+                         scale, (int)N, geom.tiles, geom.nbands);                                                        \
     break;
   switch (flow_ctx_pad_l(L)) {
     WALDO_FCA_CASE(4)
@@ -1058,9 +1141,18 @@ extern "C" int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* inpu
     WALDO_FCA_CASE(32)
   }
 #undef WALDO_FCA_CASE
-  return launch_status("waldo_flow_ctx_alpha_fwd");
+  return launch_status(fn);
 }
-#endif  // !WALDO_FC_RAW_HALF
+
+#if !defined(WALDO_FC_RAW_HALF) && !defined(WALDO_FC_PACKED)  // (the fp32 unit; the 16-bit and packed units: end of file)
+extern "C" int waldo_flow_ctx_alpha_fwd(const float* alpha_lr, const float* input, const float* dist,
+                                        const float* occ, float* a01, float* alpha_out, unsigned* layer_bits, int B,
+                                        int T, int Tw, int L, int Nl, int C, int chan_off, int H, int W,
+                                        int scale, waldo_stream_t stream) {
+  return flow_ctx_alpha_launch("waldo_flow_ctx_alpha_fwd", alpha_lr, input, dist, occ, a01, alpha_out, layer_bits, B, T,
+                               Tw, L, Nl, C, chan_off, H, W, scale, stream);
+}
+#endif
 
 #define WALDO_FCW_LAUNCH(LPV, SC, RV)                                                                          \
   hipLaunchKernelGGL((flow_ctx_warp_kernel<LPV, SC, RV, AT>), dim3((unsigned)fcw_grid), dim3(kBlock), 0, st,  \
@@ -1148,11 +1240,12 @@ static int flow_ctx_warp_raw(const char* fn, const float* flow_lr, const float* 
                               score, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, stream);
 }
 
-template <typename RT>
-static int frame_warp_fuse_launch(const char* fn, const float* input, const float* flow, const float* alpha,
+// IN = uint32_t: a packed clip of C = 3 + Nl channels, rgb_table its RGB table (the raw path only); NULL for fp32
+template <typename RT, typename IN = float>
+static int frame_warp_fuse_launch(const char* fn, const IN* input, const float* flow, const float* alpha,
                                   const float* score, const int64_t* ctx_ts, float* out, RT* raw, int* status,
                                   int B, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
-                                  float eps, waldo_stream_t stream) {
+                                  float eps, waldo_stream_t stream, const float* rgb_table = nullptr) {
   if (B < 0 || T < 1 || Tc < 1 || Tc + (include_self ? 1 : 0) > kFwMaxCtx || Tp < 1 || C < 1 || L < 1 ||
       Hd < 1 || Wd < 1 || Hd > 32767 || Wd > 32767 || (include_self && Tp != T)) {
     set_error("%s: bad shape B=%d T=%d Tc=%d Tp=%d C=%d L=%d Hd=%d Wd=%d include_self=%d "
@@ -1194,9 +1287,9 @@ static int frame_warp_fuse_launch(const char* fn, const float* input, const floa
     // (the context count is a template parameter: a padding context repeats the last real one -- its taps, its box, its
     // loads -- so one context compiled for four did four contexts' work: the LVD recipe's "prev" mode, 114 us per call)
 #define WALDO_FWF_LAUNCH(TCPV, FULLV)                                                                                   \
-  hipLaunchKernelGGL((frame_warp_fuse_lds_kernel<TCPV, FULLV, RT>), lgrid, dim3(kBlock), 0, (hipStream_t)stream, input,   \
-                     flow, alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, \
-                     lgeom.tiles, lgeom.nbands)
+  hipLaunchKernelGGL((frame_warp_fuse_lds_kernel<TCPV, FULLV, RT, IN>), lgrid, dim3(kBlock), 0, (hipStream_t)stream,   \
+                     input, flow, alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps,      \
+                     (int)units, lgeom.tiles, lgeom.nbands, rgb_table)
     if (Tc == 4 && !include_self) WALDO_FWF_LAUNCH(4, true);
     else if (Tc == 1) WALDO_FWF_LAUNCH(1, false);
     else if (Tc == 2) WALDO_FWF_LAUNCH(2, false);
@@ -1206,27 +1299,31 @@ static int frame_warp_fuse_launch(const char* fn, const float* input, const floa
   }
 #endif
   if (Tc == 1)
-    hipLaunchKernelGGL((frame_warp_fuse_kernel<1, RT>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
-                       alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles, geom.nbands);
+    hipLaunchKernelGGL((frame_warp_fuse_kernel<1, RT, IN>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
+                       alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles,
+                       geom.nbands, rgb_table);
   else if (Tc <= 4)
-    hipLaunchKernelGGL((frame_warp_fuse_kernel<4, RT>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
-                       alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles, geom.nbands);
+    hipLaunchKernelGGL((frame_warp_fuse_kernel<4, RT, IN>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
+                       alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles,
+                       geom.nbands, rgb_table);
   else
-    hipLaunchKernelGGL((frame_warp_fuse_kernel<8, RT>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
-                       alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles, geom.nbands);
+    hipLaunchKernelGGL((frame_warp_fuse_kernel<8, RT, IN>), grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow,
+                       alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self, eps, (int)units, geom.tiles,
+                       geom.nbands, rgb_table);
   return launch_status(fn);
 }
 
-template <typename RT>
-static int frame_warp_fuse_raw(const char* fn, const float* input, const float* flow, const float* score,
+template <typename RT, typename IN = float>
+static int frame_warp_fuse_raw(const char* fn, const IN* input, const float* flow, const float* score,
                                const int64_t* ctx_ts, float* out, RT* raw, int* status, int B, int T, int Tc, int Tp,
-                               int C, int L, int Hd, int Wd, int include_self, float eps, waldo_stream_t stream) {
+                               int C, int L, int Hd, int Wd, int include_self, float eps, waldo_stream_t stream,
+                               const float* rgb_table = nullptr) {
   if (B > 0 && !score) {
     set_error("%s: null pointer", fn);
     return WALDO_EINVAL;
   }
   return frame_warp_fuse_launch(fn, input, flow, nullptr, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd, Wd,
-                                include_self, eps, stream);
+                                include_self, eps, stream, rgb_table);
 }
 
 // The 16-bit raw path, one compile unit per element type (flow_ctx_raw_bf16.hip, flow_ctx_raw_f16.hip: this file with
@@ -1243,8 +1340,56 @@ static int frame_warp_fuse_raw(const char* fn, const float* input, const float* 
                                                  const float* score, const int64_t* ctx_ts, float* out, void* raw,      \
                                                  int* status, int B, int T, int Tc, int Tp, int C, int L, int Hd,       \
                                                  int Wd, int include_self, float eps, waldo_stream_t stream);
+// The packed clip's frame warp, one compile unit per element type of `raw` (flow_ctx_packed.hip, _bf16, _f16: this file
+// with WALDO_FC_PACKED defined, and WALDO_FC_RAW_HALF for the 16-bit ones); the fp32 one also holds the packed
+// flow_ctx_alpha.  C = 3 + Nl.
+#define WALDO_FC_PACKED_PROTOS(SUFFIX)                                                                                \
+  int WALDO_FC_CAT(frame_warp_fuse_packed_, SUFFIX)(const char* fn, const uint32_t* clip, const float* rgb_table,      \
+                                                    const float* flow, const float* score, const int64_t* ctx_ts,     \
+                                                    float* out, void* raw, int* status, int B, int T, int Tc, int Tp, \
+                                                    int C, int L, int Hd, int Wd, int include_self, float eps,        \
+                                                    waldo_stream_t stream);
 
+#if defined(WALDO_FC_PACKED)
 #ifdef WALDO_FC_RAW_HALF
+#define WALDO_FC_RAW_T WALDO_FC_RAW_HALF
+#else
+#define WALDO_FC_RAW_T float
+#define WALDO_FC_RAW_SUFFIX f32
+#endif
+namespace waldo {
+WALDO_FC_PACKED_PROTOS(WALDO_FC_RAW_SUFFIX)
+
+int WALDO_FC_CAT(frame_warp_fuse_packed_, WALDO_FC_RAW_SUFFIX)(const char* fn, const uint32_t* clip,
+                                                               const float* rgb_table, const float* flow,
+                                                               const float* score, const int64_t* ctx_ts, float* out,
+                                                               void* raw, int* status, int B, int T, int Tc, int Tp,
+                                                               int C, int L, int Hd, int Wd, int include_self,
+                                                               float eps, waldo_stream_t stream) {
+  return frame_warp_fuse_raw(fn, clip, flow, score, ctx_ts, out, static_cast<WALDO_FC_RAW_T*>(raw), status, B, T, Tc, Tp,
+                             C, L, Hd, Wd, include_self, eps, stream, rgb_table);
+}
+}  // namespace waldo
+
+#ifndef WALDO_FC_RAW_HALF
+extern "C" int waldo_flow_ctx_alpha_packed_fwd(const float* alpha_lr, const uint8_t* clip, const float* dist,
+                                               const float* occ, float* a01, float* alpha_out, unsigned* layer_bits,
+                                               int B, int T, int Tw, int L, int Nl, int H, int W, int scale,
+                                               waldo_stream_t stream) {
+  const char* fn = "waldo_flow_ctx_alpha_packed_fwd";
+  if (Nl < 1 || Nl > kMaxCls) {
+    set_error("%s: %d classes (1 to %d)", fn, Nl, kMaxCls);
+    return WALDO_EINVAL;
+  }
+  if ((int64_t)B * Tw > 0 && !clip) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  return flow_ctx_alpha_launch(fn, alpha_lr, reinterpret_cast<const uint32_t*>(clip), dist, occ, a01, alpha_out,
+                               layer_bits, B, T, Tw, L, Nl, 3 + Nl, 3, H, W, scale, stream);
+}
+#endif
+#elif defined(WALDO_FC_RAW_HALF)
 namespace waldo {
 WALDO_FC_RAW_PROTOS(WALDO_FC_RAW_SUFFIX)
 
@@ -1270,6 +1415,9 @@ int WALDO_FC_CAT(frame_warp_fuse_raw_, WALDO_FC_RAW_SUFFIX)(const char* fn, cons
 namespace waldo {
 WALDO_FC_RAW_PROTOS(bf16)
 WALDO_FC_RAW_PROTOS(f16)
+WALDO_FC_PACKED_PROTOS(f32)
+WALDO_FC_PACKED_PROTOS(bf16)
+WALDO_FC_PACKED_PROTOS(f16)
 }  // namespace waldo
 
 extern "C" int waldo_flow_ctx_warp_fwd(const float* flow_lr, const float* isobj_lr, const float* a01,
@@ -1355,4 +1503,36 @@ extern "C" int waldo_frame_warp_fuse_raw_fwd_dt(const float* input, const float*
   set_error("%s: unknown raw dtype %d (WALDO_DTYPE_F32 / _F16 / _BF16)", fn, raw_dtype);
   return WALDO_EINVAL;
 }
-#endif  // WALDO_FC_RAW_HALF
+
+extern "C" int waldo_frame_warp_fuse_raw_packed_fwd(const uint8_t* clip, const float* rgb_table, const float* flow,
+                                                    const float* score, const int64_t* ctx_ts, float* out, void* raw,
+                                                    int* status, int B, int T, int Tc, int Tp, int Nl, int L, int Hd,
+                                                    int Wd, int include_self, float eps, int raw_dtype,
+                                                    waldo_stream_t stream) {
+  const char* fn = "waldo_frame_warp_fuse_raw_packed_fwd";
+  if (raw_dtype != WALDO_DTYPE_F32 && raw_dtype != WALDO_DTYPE_BF16 && raw_dtype != WALDO_DTYPE_F16) {
+    set_error("%s: unknown raw dtype %d (WALDO_DTYPE_F32 / _F16 / _BF16)", fn, raw_dtype);
+    return WALDO_EINVAL;
+  }
+  if (Nl < 0 || Nl > kMaxCls) {
+    set_error("%s: %d classes (0 to %d)", fn, Nl, kMaxCls);
+    return WALDO_EINVAL;
+  }
+  if (B > 0 && (!clip || !rgb_table)) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  const uint32_t* px = reinterpret_cast<const uint32_t*>(clip);
+  const int C = 3 + Nl;
+  switch (raw_dtype) {
+    case WALDO_DTYPE_BF16:
+      return frame_warp_fuse_packed_bf16(fn, px, rgb_table, flow, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd,
+                                         Wd, include_self, eps, stream);
+    case WALDO_DTYPE_F16:
+      return frame_warp_fuse_packed_f16(fn, px, rgb_table, flow, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd,
+                                        Wd, include_self, eps, stream);
+  }
+  return frame_warp_fuse_packed_f32(fn, px, rgb_table, flow, score, ctx_ts, out, raw, status, B, T, Tc, Tp, C, L, Hd, Wd,
+                                    include_self, eps, stream);
+}
+#endif  // WALDO_FC_PACKED / WALDO_FC_RAW_HALF

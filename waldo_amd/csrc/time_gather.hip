@@ -102,7 +102,7 @@ __global__ __launch_bounds__(kBlock) void downscale_frames_kernel(const float* _
   const float* src = input + (((b * T + t) * C + c0 + c) * Hd + ((int64_t)y * S + S / 2 - 1)) * Wd + (int64_t)x * S + S / 2 - 1;
   const f32x2_d r0 = *reinterpret_cast<const f32x2_d*>(src);
   const f32x2_d r1 = *reinterpret_cast<const f32x2_d*>(src + Wd);
-  out[(int64_t)pl * H * W + e] = 0.5f * (0.5f * r0[0] + 0.5f * r0[1]) + 0.5f * (0.5f * r1[0] + 0.5f * r1[1]);
+  out[(int64_t)pl * H * W + e] = down_mean4(r0[0], r0[1], r1[0], r1[1]);
 }
 
 static int check_time_gather(const char* fn, const void* x, const void* pred_ts, const void* out, int B, int T,

@@ -413,6 +413,13 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// F.interpolate(bilinear, align_corners=False) by 1 / S, S a power of two, from the 2 x 2 texels in the middle of a block
+// (a b / c d): 0.5 (0.5 a + 0.5 b) + 0.5 (0.5 c + 0.5 d) in F.interpolate's association (waldo_downscale_frames_fwd and
+// its packed twin)
+__device__ __forceinline__ float down_mean4(float a, float b, float c, float d) {
+  return 0.5f * (0.5f * a + 0.5f * b) + 0.5f * (0.5f * c + 0.5f * d);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);

@@ -799,9 +799,12 @@ def flow_ctx_alpha(alpha_lr, input, dist, occ, tw, chan_off, scale, want_alpha=T
     reconstruction drops it (synthesizer.py:445), and it is as large as ``a01``.
     ``want_bits`` (no autograd): a third result, ``layer_bits`` (B*Tw, Hd, ceil(Wd / 64)) int32 -- bit l of a word: layer
     l of ``a01`` is non-zero somewhere in that 64-pixel row segment -- for ``flow_ctx_warp(..., layer_bits=...)`` on the
-    path without a ghost mask (``Warper.grid_to_flow``)."""
-    _lib.check_cuda(alpha_lr, input, occ)
-    alpha_lr, input, occ = _c(alpha_lr), _c(input.detach()), _c(occ)
+    path without a ghost mask (``Warper.grid_to_flow``).
+    ``input`` may be a ``PackedClip`` (``chan_off`` 3), without autograd: the layout logits are read from its class
+    bytes (``waldo_flow_ctx_alpha_packed_fwd``), with the bits of the call on its unpacked form."""
+    packed = isinstance(input, PackedClip)
+    _lib.check_cuda(alpha_lr, occ, *(() if packed else (input,)))
+    alpha_lr, input, occ = _c(alpha_lr), (input if packed else _c(input.detach())), _c(occ)
     n, nl, h, w = alpha_lr.shape
     b, t, c, hd, wd = input.shape
     if n != b * tw or tuple(occ.shape) != (b, t, nl, nl) or hd != h * scale or wd != w * scale:
@@ -814,6 +817,20 @@ def flow_ctx_alpha(alpha_lr, input, dist, occ, tw, chan_off, scale, want_alpha=T
             raise _lib.WaldoHipError(f"flow_ctx_alpha: dist {tuple(dist.shape)} is not (B, L-1, Nl)")
     no_grad = not (torch.is_grad_enabled() and (alpha_lr.requires_grad or occ.requires_grad or
                                                 (dist is not None and dist.requires_grad)))
+    if packed:
+        if not no_grad:
+            raise _lib.WaldoHipError("flow_ctx_alpha: no gradient flows through a packed clip's pass; unpack() it")
+        if dist is not None and int(chan_off) != 3:
+            raise _lib.WaldoHipError(f"flow_ctx_alpha: a packed clip's layout channels start at 3, not {chan_off}")
+        data = _packed_data(input, "flow_ctx_alpha")
+        a01 = alpha_lr.new_empty(n, nl, hd, wd)
+        alpha = alpha_lr.new_empty(n, nl, hd, wd) if want_alpha else None
+        bits = torch.empty(n, hd, (wd + 63) // 64, dtype=torch.int32, device=alpha_lr.device) if want_bits else None
+        with _lib.on_device(alpha_lr.device):
+            _lib.call("waldo_flow_ctx_alpha_packed_fwd", _lib.ptr(alpha_lr), _lib.ptr(data), _lib.ptr(dist),
+                      _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl, input.num_lyt, h, w,
+                      scale, _lib.current_stream(alpha_lr.device))
+        return (a01, alpha, bits) if want_bits else (a01, alpha)
     if no_grad and (not want_alpha or want_bits):
         a01 = alpha_lr.new_empty(n, nl, hd, wd)
         alpha = alpha_lr.new_empty(n, nl, hd, wd) if want_alpha else None
@@ -1065,13 +1082,15 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
     plane per context instead of L alpha planes.  The same bits as ``frame_warp_fuse`` on the alpha view
     (tests/test_gpu_warper.py::test_alpha_ctx_written_into_raw_slots).  Returns (out, raw as (B, Tc', Tp, ...)).
     A 16-bit ``slots.raw`` (``flow_ctx_warp_into_raw(..., raw_dtype=...)``) gets the warped channels rounded to
-    nearest-even; ``out`` is fp32 either way."""
-    _lib.check_cuda(input, flow)
+    nearest-even; ``out`` is fp32 either way.  ``input`` may be a ``PackedClip``: the same bits as on its unpacked form
+    (``waldo_frame_warp_fuse_raw_packed_fwd``: one word per tap for all channels)."""
+    packed = isinstance(input, PackedClip)
+    _lib.check_cuda(flow, *(() if packed else (input,)))
     if not ctx_ts.is_cuda:
         raise _lib.WaldoHipError("frame_warp_fuse_raw: ctx_ts must be on the GPU")
     if torch.is_grad_enabled() and flow.requires_grad:
         raise _lib.WaldoHipError("frame_warp_fuse_raw: no gradient flows through the raw-slot path; use frame_warp_fuse")
-    input, flow = _c(input.detach()), _c(flow.detach())
+    input, flow = (input if packed else _c(input.detach())), _c(flow.detach())
     ctx_ts = _c(ctx_ts.long())
     b, t, c, hd, wd = input.shape
     raw, score = slots.raw, slots.score
@@ -1086,7 +1105,12 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
     st, strict = _status(status)
     out = input.new_empty(b, tp, c + 1, hd, wd)
     with torch.no_grad(), _lib.on_device(input.device):
-        if raw.dtype == torch.float32:
+        if packed:
+            _lib.call("waldo_frame_warp_fuse_raw_packed_fwd", _lib.ptr(_packed_data(input, "frame_warp_fuse_raw")),
+                      _lib.ptr(rgb_table(input.device)), _lib.ptr(flow), _lib.ptr(score), _lib.ptr(ctx_ts), _lib.ptr(out),
+                      _lib.ptr(raw), st.ptr, b, t, tc, tp, input.num_lyt, nl, hd, wd, 1 if slots.include_self else 0,
+                      float(eps), _DTYPE_CODE[raw.dtype], _lib.current_stream(input.device))
+        elif raw.dtype == torch.float32:
             _lib.call("waldo_frame_warp_fuse_raw_fwd", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
                       _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
                       1 if slots.include_self else 0, float(eps), _lib.current_stream(input.device))
@@ -1098,6 +1122,136 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
     if strict:
         st.check(sync=True)
     return out, raw.permute(0, 2, 1, 3, 4, 5)
+
+
+# --------------------------------------------------------------------------------------
+# The packed clip: (B, T, Hd, Wd) pixels of 4 bytes [R, G, B, class id] in place of the (B, T, 3 + Nl, Hd, Wd) fp32 clip
+# --------------------------------------------------------------------------------------
+MAX_PACKED_LYT = 32  # layout classes of a packed clip (the fused path's limit, include/waldo_hip.h "Packed clip")
+_RGB_TABLES = {}
+
+
+def rgb_table(device):
+    """The 256 fp32 values of read_rgb's normalisation (``tools.io.rgb_from_u8`` of every byte), built on the host as
+    ``read_rgb`` computes them and kept once per device."""
+    key = str(device)
+    if key not in _RGB_TABLES:
+        from .tools.io import rgb_from_u8
+        _RGB_TABLES[key] = rgb_from_u8(torch.arange(256, dtype=torch.uint8)).to(device)
+    return _RGB_TABLES[key]
+
+
+class PackedClip:
+    """A clip as ``data`` (B, T, Hd, Wd, 4) uint8, bytes [R, G, B, class id] per pixel: what a user loads from 8-bit PNG
+    frames and class maps, 4 bytes per pixel where the fp32 clip takes 4 (3 + ``num_lyt``).  It stands for its UNPACKED
+    form (B, T, 3 + num_lyt, Hd, Wd) fp32 (``unpack()``): channels 0-2 the ``rgb_table`` entries of the RGB bytes
+    (``tools.io.read_rgb``), channel 3 + n +5 where the class id is n and -5 elsewhere (``tools.io.read_layout``; a class
+    id >= num_lyt: -5 in every layout channel).
+
+    ``Warper`` / ``decode_output`` take it wherever they take the fp32 clip, with the same results bit for bit: on the
+    fused path without autograd the packed kernels read it (no fp32 copy is made), every other path unpacks it once.
+    It offers what that code reads of a clip -- ``shape`` / ``size()`` of the unpacked form, ``device``, slicing along
+    batch and time (views), ``new_empty`` (fp32, as the unpacked clip's) -- and carries no gradient."""
+
+    __slots__ = ("data", "num_lyt")
+    ndim = 5
+    dtype = torch.float32  # (of the unpacked form)
+    requires_grad = False
+
+    def __init__(self, data, num_lyt):
+        num_lyt = int(num_lyt)
+        if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.ndim != 5 or data.shape[-1] != 4:
+            raise ValueError(f"PackedClip: data must be a (B, T, Hd, Wd, 4) uint8 tensor, got "
+                             f"{getattr(data, 'dtype', type(data))} {tuple(getattr(data, 'shape', ()))}")
+        if not 0 <= num_lyt <= MAX_PACKED_LYT:
+            raise ValueError(f"PackedClip: num_lyt {num_lyt} outside [0, {MAX_PACKED_LYT}]")
+        self.data, self.num_lyt = data, num_lyt
+
+    @property
+    def shape(self):
+        b, t, hd, wd, _ = self.data.shape
+        return torch.Size((b, t, 3 + self.num_lyt, hd, wd))
+
+    def size(self, dim=None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self):
+        return 5
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def is_cuda(self):
+        return self.data.is_cuda
+
+    @property
+    def _version(self):  # (tools.demo.SharedContext keys on identity + version)
+        return self.data._version
+
+    def is_inference(self):
+        return self.data.is_inference()
+
+    def __getitem__(self, idx):
+        """Batch and time slices (views): ``clip[b0:b1]``, ``clip[:, t0:t1]``."""
+        idx = idx if isinstance(idx, tuple) else (idx,)
+        if len(idx) > 2 or not all(isinstance(i, slice) for i in idx):
+            raise IndexError("PackedClip: only slices along batch and time (clip[b0:b1, t0:t1]); unpack() for more")
+        return PackedClip(self.data[idx], self.num_lyt)
+
+    def to(self, device, non_blocking=False):
+        return PackedClip(self.data.to(device, non_blocking=non_blocking), self.num_lyt)
+
+    def new_empty(self, *size, dtype=torch.float32):
+        """An uninitialised tensor on the clip's device, fp32 like the unpacked clip's ``new_empty``."""
+        return torch.empty(*size, dtype=dtype, device=self.device)
+
+    def unpack(self):
+        """The unpacked fp32 clip (B, T, 3 + num_lyt, Hd, Wd): one ``waldo_unpack_clip_fwd`` launch."""
+        return unpack_clip(self)
+
+    def rgb(self):
+        """Channels 0-2 of the unpacked clip alone (B, T, 3, Hd, Wd): the same launch without the layout planes."""
+        return unpack_clip(PackedClip(self.data, 0))
+
+    def __repr__(self):
+        return f"PackedClip(shape={tuple(self.shape)}, num_lyt={self.num_lyt}, device={self.device})"
+
+
+def pack_clip(rgb_u8, class_ids, num_lyt):
+    """A ``PackedClip`` from tensors the caller holds: ``rgb_u8`` (B, T, 3, Hd, Wd) uint8 and ``class_ids`` (B, T, Hd, Wd)
+    integer class ids in [0, 255] (ids >= num_lyt stand for all-(-5) layout logits).  Data preparation (torch ops);
+    the result lives on ``rgb_u8``'s device."""
+    if not torch.is_tensor(rgb_u8) or rgb_u8.dtype != torch.uint8 or rgb_u8.ndim != 5 or rgb_u8.shape[2] != 3:
+        raise ValueError(f"pack_clip: rgb_u8 must be (B, T, 3, Hd, Wd) uint8, got {getattr(rgb_u8, 'dtype', None)} "
+                         f"{tuple(getattr(rgb_u8, 'shape', ()))}")
+    b, t, _, hd, wd = rgb_u8.shape
+    if tuple(class_ids.shape) != (b, t, hd, wd) or class_ids.is_floating_point() or class_ids.is_complex():
+        raise ValueError(f"pack_clip: class_ids must be integer (B, T, Hd, Wd) = {(b, t, hd, wd)}, got "
+                         f"{class_ids.dtype} {tuple(class_ids.shape)}")
+    if class_ids.dtype != torch.uint8 and class_ids.numel() and (int(class_ids.min()) < 0 or int(class_ids.max()) > 255):
+        raise ValueError("pack_clip: class ids outside [0, 255] do not fit a byte")
+    cls = class_ids.to(device=rgb_u8.device, dtype=torch.uint8)
+    return PackedClip(torch.cat([rgb_u8.permute(0, 1, 3, 4, 2), cls.unsqueeze(-1)], dim=-1).contiguous(), num_lyt)
+
+
+def _packed_data(clip, fn):
+    if not clip.is_cuda:
+        raise _lib.WaldoHipError(f"{fn}: the packed clip must be on the GPU (PackedClip.to(device)); there is no CPU "
+                                 "fallback")
+    return _c(clip.data)
+
+
+def unpack_clip(clip):
+    """``PackedClip`` -> its unpacked form (B, T, 3 + Nl, Hd, Wd) fp32 (``waldo_unpack_clip_fwd``)."""
+    data = _packed_data(clip, "unpack_clip")
+    b, t, hd, wd, _ = data.shape
+    out = torch.empty(clip.shape, dtype=torch.float32, device=data.device)
+    with _lib.on_device(data.device):
+        _lib.call("waldo_unpack_clip_fwd", _lib.ptr(data), _lib.ptr(rgb_table(data.device)), _lib.ptr(out), b, t,
+                  clip.num_lyt, hd, wd, _lib.current_stream(data.device))
+    return out
 
 
 # --------------------------------------------------------------------------------------
@@ -1179,12 +1333,24 @@ def downscale_frames(input, num_frames, first_channel, factor):
     """``scale(input[:, :num_frames, first_channel:], 1 / factor)`` of ``Warper.grid_to_flow[_ctx]``
     (models/nets/lvd.py:611 / 716): the low-resolution copy of the layout channels, the same bits as
     ``F.interpolate(..., scale_factor=1 / factor, mode="bilinear")`` on the device for a power-of-two ``factor``.
-    The frames are data: the result carries no gradient."""
-    _lib.check_cuda(input)
+    The frames are data: the result carries no gradient.  A ``PackedClip`` (``first_channel`` 3: its layout channels)
+    gives the bits of its unpacked form (``waldo_downscale_frames_packed_fwd``: one read of each pixel's word)."""
+    packed = isinstance(input, PackedClip)
+    if not packed:
+        _lib.check_cuda(input)
     b, t, c, hd, wd = input.shape
     s = int(factor)
     if s < 2 or s & (s - 1) or hd % s or wd % s:
         raise _lib.WaldoHipError(f"downscale_frames: factor {factor} on {hd} x {wd} frames (a power of two that divides both)")
+    if packed:
+        if int(first_channel) != 3:
+            raise _lib.WaldoHipError(f"downscale_frames: a packed clip's layout channels start at 3, not {first_channel}")
+        data = _packed_data(input, "downscale_frames")
+        out = torch.empty(b, int(num_frames), c - 3, hd // s, wd // s, device=data.device)
+        with _lib.on_device(data.device):
+            _lib.call("waldo_downscale_frames_packed_fwd", _lib.ptr(data), _lib.ptr(out), b, t, int(num_frames), c - 3,
+                      hd // s, wd // s, s, _lib.current_stream(data.device))
+        return out
     x = _c(input.detach().float())
     out = x.new_empty(b, int(num_frames), c - int(first_channel), hd // s, wd // s)
     with _lib.on_device(x.device):

@@ -440,6 +440,16 @@ class Warper(nn.Module):
                                 want_alpha=self.return_alpha, want_bits=want_bits)
         return res if want_bits else (*res, None)
 
+    def _packed_ok(self, input, grid, occ, obj_alpha, bg_alpha, cls):
+        """Where a ``WF.PackedClip`` is read by the packed kernels: the fused full-resolution passes (``_fused_ok``)
+        without autograd, at a power-of-two scale (``WF.downscale_frames``).  Everywhere else it is unpacked once
+        (``_clip``)."""
+        s = self.scale_hd
+        return (self.fuse_hd and float(s) == int(s) and int(s) >= 2 and int(s) & (int(s) - 1) == 0 and
+                self._fused_ok([input, occ, obj_alpha, bg_alpha, cls, *grid], grid[1].shape[2] + 1, input.size(2) - 3)
+                and not (torch.is_grad_enabled() and any(x is not None and x.requires_grad
+                                                         for x in (occ, obj_alpha, bg_alpha, cls, *grid))))
+
     def context_products(self, input, grid, occ, obj_alpha, bg_alpha, cls, num_ctx):
         """What ``grid_to_flow_ctx`` (``restrict_to_ctx``) computes from the CONTEXT frames alone: the composited
         full-resolution alphas of frames 0 .. num_ctx - 1.  ``input`` (B, >= num_ctx, C, Hd, Wd), ``grid`` / ``occ`` with
@@ -451,6 +461,7 @@ class Warper(nn.Module):
         if not (self.fuse_hd and self._fused_ok([input], grid[1].shape[2] + 1, input.size(2) - 3)):
             return None
         with torch.no_grad():
+            input = _clip(input, lambda: self._packed_ok(input, grid, occ, obj_alpha, bg_alpha, cls))
             g = [x[:, :num_ctx] if x is not None else None for x in grid]
             oc = occ.reshape(occ.shape[0], -1, *occ.shape[-2:])[:, :num_ctx]
             return self._composited_alphas(input[:, :num_ctx], g, oc, obj_alpha, bg_alpha, cls, num_ctx, True,
@@ -526,6 +537,7 @@ class Warper(nn.Module):
         # int64 + contiguous ONCE for every op below; what earlier launches reported about their indices surfaces here
         ctx_ts, pred_ts = WF.normalise_time_index(ctx_ts), WF.normalise_time_index(pred_ts)
         self.index_status.check()
+        input = _clip(input, lambda: self._packed_ok(input, grid, occ, obj_alpha, bg_alpha, cls))
         if self.fuse_hd and self._fused_ok([input, occ, obj_alpha, bg_alpha, cls, *grid],
                                            grid[1].shape[2] + 1, input.size(2) - 3):
             no_grad = not (torch.is_grad_enabled() and any(
@@ -603,6 +615,7 @@ class Warper(nn.Module):
 
     def input_to_output(self, input, alpha, flow, ctx_ts, eps=1e-6):
         """Reference lvd.py:830-853."""
+        input = _clip(input)
         b, tc, tp = flow.shape[:3]
         ctx_ts = WF.normalise_time_index(ctx_ts)
         self_slot = self.include_self and tp == input.size(1)
@@ -666,7 +679,8 @@ def decode_output(warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pr
     channel.  Returns ``(output, flow, alpha_unflt, alpha, raw_alpha, raw_output, alpha_ctx)``.
 
     ``input`` holds all T frames as in the reference -- or, with ``restrict_to_ctx`` and no ``include_self``, just the
-    context frames the path reads (``Warper._clip_length``).  Without autograd and without ``use_disocc``, ``alpha_ctx``
+    context frames the path reads (``Warper._clip_length``) -- as the fp32 clip or as a ``WF.PackedClip`` (the same
+    results bit for bit: read packed on the raw-slot path, unpacked once on every other).  Without autograd and without ``use_disocc``, ``alpha_ctx``
     is a strided VIEW into ``raw_output``'s storage (the reference returns two tensors; the values are the same): an
     in-place write to either shows in the other, and the view keeps the whole buffer alive -- clone it to detach.
     ``ctx_products``: ``Warper.context_products`` of the same context frames (``restrict_to_ctx``, no autograd), computed
@@ -678,6 +692,10 @@ def decode_output(warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pr
     ``output``, ``flow``, ``alpha``, ``alpha_unflt`` and ``raw_alpha`` stay fp32."""
     raw_dtype = _raw_dtype(raw_dtype)
     ctx_ts, pred_ts = WF.normalise_time_index(ctx_ts), WF.normalise_time_index(pred_ts)  # shared by both calls
+    # a packed clip stays packed on the raw-slot path alone (the fused passes and the frame warp without autograd);
+    # every other path unpacks it here, once
+    input = _clip(input, lambda: warper._packed_ok(input, grid, occ, obj_alpha, bg_alpha, cls) and warper.raw_slots and
+                  warper._frame_warp_fused(input, ctx_ts.size(1), pred_ts.size(0)))
     # (without autograd the context alphas are composited straight into raw_output's slots: `slots` receives what
     # the frame warp needs to know about them)
     slots = []
@@ -704,6 +722,14 @@ def decode_output(warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pr
         # (in raw_output's type: torch.cat would promote a 16-bit raw_output back to fp32)
         raw_output = torch.cat([raw_output, disocc.to(raw_output.dtype)], dim=3)
     return output, flow, alpha_unflt, alpha, raw_alpha, raw_output, alpha_ctx
+
+
+def _clip(input, packed_ok=None):
+    """The clip as the code below takes it: a ``WF.PackedClip`` stays packed where ``packed_ok()`` says the packed
+    kernels run, and is unpacked ONCE everywhere else -- today's fp32 code then runs unchanged.  A tensor passes."""
+    if isinstance(input, WF.PackedClip) and not (packed_ok is not None and packed_ok()):
+        return input.unpack()
+    return input
 
 
 def _raw_dtype(raw_dtype):

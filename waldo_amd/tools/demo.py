@@ -338,7 +338,9 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
 @torch.no_grad()
 def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None):
     """The hot-path part of Synthesizer.predict (models/synthesizer.py:434-480).  real_vid
-    (B, T, 3, H, W), real_lyt (B, T, Nl, H, W); ``net`` = synthetic_network_outputs(...).
+    (B, T, 3, H, W), real_lyt (B, T, Nl, H, W); ``net`` = synthetic_network_outputs(...).  Or real_vid a
+    ``WF.PackedClip`` of frames and class ids (``tools.io.load_clip(..., packed=True)``) and real_lyt None: the same
+    results bit for bit, without an fp32 copy of the clip on the fused path.
     ``raw_dtype``: the element type of the WIF input ``raw_output`` (None = fp32; torch.bfloat16 / torch.float16 for a
     UNet under autocast -- decode_output).  Returns a dict of the tensors predict produces."""
     b, t = real_vid.shape[:2]
@@ -350,7 +352,14 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None):
     # concatenated -- 29 % of the bytes, the same results bit for bit (tests/test_demo.py compares with the restatement
     # that is handed all T frames)
     n_in = t if getattr(opt, "include_self", False) else ctx_len
-    real_input = torch.cat([real_vid[:, :n_in], real_lyt[:, :n_in]], dim=2)
+    if isinstance(real_vid, WF.PackedClip):
+        if real_lyt is not None:
+            raise ValueError("predict: a packed clip holds the layout already; pass real_lyt=None")
+        real_input = real_vid[:, :n_in]
+        ctx_vid = real_vid[:, :ctx_len].rgb()  # (the context frames of pred_vid / inp_pred_vid)
+    else:
+        real_input = torch.cat([real_vid[:, :n_in], real_lyt[:, :n_in]], dim=2)
+        ctx_vid = real_vid[:, :ctx_len]
     if getattr(opt, "include_self", False) or not MERGE_DECODES or opt.no_future:
         # the reference's two calls, one after the other (include_self: every frame is a context of itself)
         shared = SharedContext() if not getattr(opt, "include_self", False) else None
@@ -379,8 +388,8 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None):
             out["pred_alpha"] = alpha[0]
         out["pred_disocc"] = dis
         out["pred_flow"] = flow
-        out["pred_vid"] = torch.cat([real_vid[:, :ctx_len], pred], dim=1)
-        out["inp_pred_vid"] = torch.cat([real_vid[:, :ctx_len], inp], dim=1)
+        out["pred_vid"] = torch.cat([ctx_vid, pred], dim=1)
+        out["inp_pred_vid"] = torch.cat([ctx_vid, inp], dim=1)
     return out
 
 
@@ -594,12 +603,17 @@ RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --
 
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
-        device="cuda:0", raw_dtype=None):
+        device="cuda:0", raw_dtype=None, packed=False):
+    """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
+    ``WF.PackedClip``) and predict() reads it as such -- the same results."""
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt)
     size = (dim, int(dim * aspect_ratio))
-    clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames)
+    clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames, packed=packed)
     dev = torch.device(device)
-    vid, lyt = clip["vid"].unsqueeze(0).to(dev), clip["lyt"].unsqueeze(0).to(dev)
+    if packed:
+        vid, lyt = clip["vid"].to(dev), None
+    else:
+        vid, lyt = clip["vid"].unsqueeze(0).to(dev), clip["lyt"].unsqueeze(0).to(dev)
     warper = Warper(opt).to(dev)
     wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     net = synthetic_network_outputs(opt, 1, vid.shape[1], ctx_len, seed=seed, device=dev)
@@ -628,9 +642,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--raw-dtype", choices=sorted(RAW_DTYPES), default="fp32",
                     help="element type of the WIF input raw_output (bf16 / fp16: what a UNet under autocast takes)")
+    ap.add_argument("--packed", action="store_true",
+                    help="hand the clip over packed: RGB bytes + class ids, 4 bytes per pixel (the same results)")
     args = ap.parse_args()
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
-              ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype])
+              ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "
               f"finite={bool(torch.isfinite(v).all())}")

@@ -71,11 +71,13 @@ def read_rgb(path, size=None):
     """RGB frame -> float32 (3, H, W) in [-1, 1].  ``size`` = (H, W): PIL bilinear resize first, as
     ``transforms.Resize(size, PIL.Image.BILINEAR)`` does on a PIL image; then ToTensor and
     Normalize(0.5, 0.5).  Reference: data/base_dataset.py:168-172, 344-345, 364-369."""
-    import PIL.Image
-    img = PIL.Image.open(path).convert("RGB")
-    if size is not None and (img.height, img.width) != tuple(size):
-        img = img.resize((int(size[1]), int(size[0])), PIL.Image.BILINEAR)
-    x = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).float().div_(255.0)
+    return rgb_from_u8(read_rgb_u8(path, size))
+
+
+def rgb_from_u8(u8):
+    """8-bit RGB -> fp32 in [-1, 1]: ToTensor and Normalize(0.5, 0.5) (read_rgb).  The packed clip's RGB table is this
+    expression on the 256 byte values (functional.PackedClip)."""
+    x = u8.float().div_(255.0)
     return (x - 0.5) / 0.5
 
 
@@ -98,12 +100,41 @@ def read_layout(path, num_lyt, size=None, remap_lyt=()):
     return 5 * (onehot * 2 - 1)
 
 
-def load_clip(frames_dir, size, num_lyt, max_frames=None, layout_dir=None, flow_dir=None, remap_lyt=()):
+def read_rgb_u8(path, size=None):
+    """The bytes ``read_rgb`` normalises: (3, H, W) uint8 after the same PIL bilinear resize."""
+    import PIL.Image
+    img = PIL.Image.open(path).convert("RGB")
+    if size is not None and (img.height, img.width) != tuple(size):
+        img = img.resize((int(size[1]), int(size[0])), PIL.Image.BILINEAR)
+    return torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1)
+
+
+def read_class_map(path, num_lyt, size=None, remap_lyt=()):
+    """The class ids ``read_layout`` one-hot encodes, (H, W) uint8, resized to ``size`` by nearest neighbour: the same
+    source pixel as the nearest resize of the one-hot planes picks (tests/test_packed_clip_abi.py proves the two equal).
+    Class ids >= ``num_lyt`` are refused, as ``read_layout`` refuses them."""
+    import PIL.Image
+    cm = torch.from_numpy(np.asarray(PIL.Image.open(path)).copy()).long()
+    if cm.ndim != 2:
+        raise ValueError(f"{path}: expected a single-channel class map, got shape {tuple(cm.shape)}")
+    for i in range(len(remap_lyt) // 2):
+        cm[cm == remap_lyt[2 * i]] = remap_lyt[2 * i + 1]
+    if cm.max() >= num_lyt:
+        raise ValueError(f"{path}: class id {int(cm.max())} >= num_lyt {num_lyt}")
+    if size is not None and tuple(cm.shape) != tuple(size):
+        cm = F.interpolate(cm[None, None].float(), size=tuple(int(v) for v in size), mode="nearest")[0, 0].long()
+    return cm.to(torch.uint8)
+
+
+def load_clip(frames_dir, size, num_lyt, max_frames=None, layout_dir=None, flow_dir=None, remap_lyt=(), packed=False):
     """A demo clip -> dict(vid (T, 3, H, W) in [-1, 1], lyt (T, num_lyt, H, W) logits,
     flow (T, 2, h, w) or None, names).  ``frames_dir`` holds the frame PNGs in order; the layout /
     flow siblings default to the reference's directory naming
     (.../leftImg8bit_sequence_512/... -> ..._deeplabv3_512 / ..._raft_128).  The first frame of a
-    clip has no flow file: it gets zeros (data/video_dataset.py pads the same way)."""
+    clip has no flow file: it gets zeros (data/video_dataset.py pads the same way).
+    ``packed``: ``vid`` is a ``functional.PackedClip`` of one clip (1, T, H, W, 4) uint8 -- the RGB bytes and class ids
+    the fp32 tensors are made of, whose unpacked form is ``cat([vid, lyt], dim=1)`` of the unpacked call, bit for bit
+    -- and ``lyt`` is None."""
     names = sorted(glob.glob(os.path.join(frames_dir, "*.png")))[:max_frames]
     if not names:
         raise ValueError(f"no frames under {frames_dir}")
@@ -120,9 +151,16 @@ def load_clip(frames_dir, size, num_lyt, max_frames=None, layout_dir=None, flow_
 
     layout_dir = layout_dir or sibling("_deeplabv3_512")
     flow_dir = flow_dir if flow_dir is not None else sibling("_raft_128")
-    vid = torch.stack([read_rgb(n, size) for n in names])
-    lyt = torch.stack([read_layout(os.path.join(layout_dir, os.path.basename(n)), num_lyt, size, remap_lyt)
-                       for n in names])
+    if packed:
+        from ..functional import pack_clip
+        rgb = torch.stack([read_rgb_u8(n, size) for n in names])
+        cls = torch.stack([read_class_map(os.path.join(layout_dir, os.path.basename(n)), num_lyt, size, remap_lyt)
+                           for n in names])
+        vid, lyt = pack_clip(rgb.unsqueeze(0), cls.unsqueeze(0), num_lyt), None
+    else:
+        vid = torch.stack([read_rgb(n, size) for n in names])
+        lyt = torch.stack([read_layout(os.path.join(layout_dir, os.path.basename(n)), num_lyt, size, remap_lyt)
+                           for n in names])
     flow = None
     if flow_dir and os.path.isdir(flow_dir):
         flows = []
