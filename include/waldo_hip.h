@@ -602,6 +602,38 @@ int waldo_downscale_frames_fwd(const float* input, float* out, int B, int T, int
 int waldo_downscale_frames_packed_fwd(const uint8_t* clip, float* out, int B, int T, int Tw, int Nl, int H, int W,
                                       int S, waldo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Frame metrics: PSNR, SSIM and MS-SSIM per frame of a predicted clip against the real one -- what the reference's
+ * scorer takes from TensorFlow (tools/eval/metrics.py:67-74: tf.image.psnr / ssim / ssim_multiscale, max_val = 1, on
+ * frames of bytes / 255).  Definitions: waldo_amd/metrics.py and DESIGN.md 4g.  Each operand is one of:
+ *   WALDO_METRICS_F32     (B,T,3,H,W) fp32 in [lo, hi]; element strides sb, st, sc, sh (W unit-stride); quantised
+ *                         by `quant` (below);
+ *   WALDO_METRICS_U8      (B,T,3,H,W) uint8 bytes taken as they are (byte / 255); byte strides, W unit-stride;
+ *   WALDO_METRICS_PACKED  a packed clip ("Packed clip" above) (B,T,H,W) of 4-byte pixels, read in place: its RGB
+ *                         bytes go through rgb_table and then through the quantisation of an fp32 operand (the bits
+ *                         of its unpacked form); strides sb, st, sh in PIXELS (sc unused), 4-byte aligned base.
+ * quant (fp32 and packed operands): u = clamp((x - lo) / range, 0, 1) in fp32, then
+ *   WALDO_METRICS_TRUNC  trunc(u * 255) / 255   (the reference's dump_video bytes, tools/utils.py:246-264),
+ *   WALDO_METRICS_ROUND  trunc(u * 255 + 0.5) / 255   (waldo_amd.tools.io.dump_video's bytes),
+ *   WALDO_METRICS_NONE   u.
+ * `range` is hi - lo, as the caller computes it (> 0).  mask: WALDO_METRIC_* bits; SSIM needs H, W >= 11, MS-SSIM
+ * five scales of at least 11 x 11 (each scale halves a side, rounding up: H, W >= 161).  partials / scratch: caller-
+ * owned workspaces of waldo_frame_metrics_partial_bytes / _scratch_bytes (scratch: 0 bytes without MS-SSIM, NULL
+ * allowed then).  Outputs (B*T) fp32 each, NULL where the mask does not ask for the metric; psnr = +inf for equal
+ * frames.  Deterministic: fixed-order sums, no atomics; metrics(a, b) and metrics(b, a) have the same bits. */
+enum waldo_metrics_enc { WALDO_METRICS_F32 = 0, WALDO_METRICS_U8 = 1, WALDO_METRICS_PACKED = 2 };
+enum waldo_metrics_quant { WALDO_METRICS_TRUNC = 0, WALDO_METRICS_ROUND = 1, WALDO_METRICS_NONE = 2 };
+#define WALDO_METRIC_PSNR 1
+#define WALDO_METRIC_SSIM 2
+#define WALDO_METRIC_MSSSIM 4
+int64_t waldo_frame_metrics_partial_bytes(int B, int T, int H, int W, int mask);
+int64_t waldo_frame_metrics_scratch_bytes(int B, int T, int H, int W, int mask);
+int waldo_frame_metrics_fwd(const void* a, int enc_a, int64_t sa_b, int64_t sa_t, int64_t sa_c, int64_t sa_h,
+                            const void* b, int enc_b, int64_t sb_b, int64_t sb_t, int64_t sb_c, int64_t sb_h,
+                            const float* rgb_table, int B, int T, int H, int W, float lo, float range, int quant,
+                            int mask, double* partials, float* scratch, float* psnr, float* ssim, float* msssim,
+                            waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

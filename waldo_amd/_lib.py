@@ -62,6 +62,9 @@ SIGNATURES = {
     "waldo_downscale_frames_packed_fwd": [_c_f, _c_f] + [_int] * 7 + [_stream],
     "waldo_flow_ctx_alpha_packed_fwd": [_c_f] * 7 + [_int] * 8 + [_stream],
     "waldo_frame_warp_fuse_raw_packed_fwd": [_c_f] * 8 + [_int] * 9 + [_flt, _int, _stream],
+    # frame metrics (include/waldo_hip.h "Frame metrics"): two operand descriptors, then the shared arguments
+    "waldo_frame_metrics_fwd": ([_c_f, _int] + [_i64] * 4) * 2 + [_c_f] + [_int] * 4 + [_flt, _flt, _int, _int]
+                               + [_c_f] * 5 + [_stream],
     "waldo_flow_ctx_alpha_bwd": [_c_f] * 10 + [_int] * 10 + [_stream],
     "waldo_flow_ctx_warp_bwd": [_c_f] * 13 + [_int] * 9 + [_stream],
     "waldo_frame_warp_fuse_bwd": [_c_f] * 8 + [_int] * 9 + [_flt, _stream],
@@ -91,6 +94,8 @@ SIGNATURES = {
 PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_warp_composite_bwd_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int]),
          "waldo_lyt_dist_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int, _int]),
+         "waldo_frame_metrics_partial_bytes": (_i64, [_int] * 5),
+         "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),
          "waldo_last_error_string": (ctypes.c_char_p, []),
          "waldo_set_debug_option": (_int, [_int, _int]),

@@ -603,9 +603,10 @@ RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --
 
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
-        device="cuda:0", raw_dtype=None, packed=False):
+        device="cuda:0", raw_dtype=None, packed=False, eval=False):
     """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
-    ``WF.PackedClip``) and predict() reads it as such -- the same results."""
+    ``WF.PackedClip``) and predict() reads it as such -- the same results.  ``eval``: also score ``rec_vid`` and
+    ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``."""
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt)
     size = (dim, int(dim * aspect_ratio))
     clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames, packed=packed)
@@ -627,7 +628,34 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
         if "pred_flow" in res:
             fl = res["pred_flow"][0, -1, 0]
             wio.write_flo(os.path.join(out_dir, "pred_flow_last.flo"), fl)
+    if eval:
+        res["metrics"] = evaluate_prediction(res, vid)
     return res
+
+
+EVAL_KEYS = ("rec_vid", "inp_pred_vid")
+
+
+def evaluate_prediction(res, real_vid):
+    """PSNR / SSIM / MS-SSIM of ``rec_vid`` and ``inp_pred_vid`` against the real frames at the same time indices, both
+    quantised to the bytes the reference dumps (its two save_vid calls: ``metrics.frame_metrics``'s "trunc").  ``real_vid``:
+    the fp32 clip (B, T, 3, H, W) or the ``WF.PackedClip``.  MS-SSIM is left out below its size limit (161 x 161).
+    Returns {key: {metric: (B, T) tensor}}."""
+    from .. import metrics as M
+    h, w = real_vid.shape[-2:]
+    names = tuple(m for m in M.METRICS if m != "msssim" or min(h, w) >= M.MIN_MSSSIM_SIDE)
+    real = real_vid if isinstance(real_vid, WF.PackedClip) else real_vid[:, :, :3]
+    return {key: M.frame_metrics(res[key], real, metrics=names) for key in EVAL_KEYS if key in res}
+
+
+def print_evaluation(scores, ctx_len, frame_size):
+    from .. import metrics as M
+    if min(frame_size) < M.MIN_MSSSIM_SIDE:
+        print(f"msssim: not applicable at {frame_size[0]}x{frame_size[1]} (needs {M.MIN_MSSSIM_SIDE}x{M.MIN_MSSSIM_SIDE})")
+    for key, sc in scores.items():
+        print(f"{key}:")
+        for line in M.format_lines(M.summarize(sc, ctx_len)):
+            print(line)
 
 
 def main():
@@ -644,12 +672,18 @@ def main():
                     help="element type of the WIF input raw_output (bf16 / fp16: what a UNet under autocast takes)")
     ap.add_argument("--packed", action="store_true",
                     help="hand the clip over packed: RGB bytes + class ids, 4 bytes per pixel (the same results)")
+    ap.add_argument("--eval", action="store_true",
+                    help="score rec_vid and inp_pred_vid against the real frames (PSNR, SSIM, MS-SSIM from 161x161)")
     args = ap.parse_args()
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
-              ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed)
+              ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
+              eval=args.eval)
+    scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "
               f"finite={bool(torch.isfinite(v).all())}")
+    if scores is not None:
+        print_evaluation(scores, args.ctx_len, tuple(res["rec_vid"].shape[-2:]))
 
 
 if __name__ == "__main__":

@@ -201,3 +201,24 @@ def dump_video(tensor, path, span=None, fps=4):
         raise ValueError("dump_video: no mp4 encoder in this image (torchvision.io / PyAV absent); "
                          "use .gif, .png (APNG), .webp or a directory")
     frames[0].save(path, save_all=True, append_images=frames[1:], duration=int(1000 / fps), loop=0)
+
+
+def load_video_u8(path):
+    """The frames ``dump_video`` wrote -> (T, 3, H, W) uint8: a directory of PNG frames (sorted by name), or an animated
+    PNG (APNG) / WebP / GIF.  PNG frames and APNG hold the bytes exactly; the WebP ``dump_video`` writes is lossy, and
+    GIF is palette-quantised (256 colours): neither is fit for scoring.  No mp4: there is no decoder in this image."""
+    import PIL.Image
+    import PIL.ImageSequence
+    if os.path.isdir(path):
+        names = sorted(glob.glob(os.path.join(path, "*.png")))
+        if not names:
+            raise ValueError(f"load_video_u8: no PNG frames under {path}")
+        frames = [np.asarray(PIL.Image.open(n).convert("RGB"), dtype=np.uint8) for n in names]
+    else:
+        if path.lower().endswith(".mp4"):
+            raise ValueError("load_video_u8: no mp4 decoder in this image; use PNG frames, APNG, WebP or GIF")
+        with PIL.Image.open(path) as im:
+            frames = [np.asarray(f.convert("RGB"), dtype=np.uint8) for f in PIL.ImageSequence.Iterator(im)]
+    if any(f.shape != frames[0].shape for f in frames):
+        raise ValueError(f"load_video_u8: frames of {path} differ in size")
+    return torch.from_numpy(np.stack(frames)).permute(0, 3, 1, 2).contiguous()
