@@ -9,7 +9,6 @@ snapshot to the GPU box.
 """
 import hashlib
 import os
-import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -37,16 +36,9 @@ def _deps():
     return sorted(hdrs)
 
 
-def _included_sources(src):
-    """The .hip files ``src`` includes (flow_ctx_raw_*.hip compile flow_ctx.hip once more): part of its stamp."""
-    with open(src) as fh:
-        names = re.findall(r'^\s*#\s*include\s+"([^"]+\.hip)"', fh.read(), flags=re.M)
-    return [os.path.join(os.path.dirname(src), n) for n in names]
-
-
 def _stamp(src):
     h = hashlib.sha1()
-    for p in [src] + _included_sources(src) + _deps():
+    for p in [src] + _deps():
         with open(p, "rb") as fh:
             h.update(fh.read())
     h.update(" ".join(CFLAGS).encode())

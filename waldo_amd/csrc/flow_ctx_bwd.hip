@@ -522,11 +522,6 @@ static int check_bwd_shape(const char* fn, int64_t N, int L, int H, int W, int s
   return WALDO_OK;
 }
 
-#define WALDO_FCB_CASE(LPV, KERNEL, ...)                                                         \
-  case LPV:                                                                                      \
-    hipLaunchKernelGGL((KERNEL<LPV>), dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, __VA_ARGS__); \
-    break;
-
 extern "C" int waldo_flow_ctx_alpha_bwd(const float* alpha_lr, const float* input, const float* dist,
                                         const float* occ, const float* grad_a01, const float* grad_alpha_out,
                                         float* grad_alpha_lr, float* grad_dist, float* grad_occ, float* workspace,
@@ -549,26 +544,16 @@ extern "C" int waldo_flow_ctx_alpha_bwd(const float* alpha_lr, const float* inpu
   const int tpb = acc_tiles(N, tiles), groups = (tiles + tpb - 1) / tpb;
   float* gup = scale > 1 ? workspace : grad_alpha_lr;
   // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
-#define WALDO_FCAB_CASE(LPV)                                                                                             \
-  case LPV:                                                                                                              \
-    if (dist == nullptr || Nl <= kFewCls)                                                                                \
-      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<LPV, kFewCls>), dim3((unsigned)(N * groups)), dim3(kBlock), 0, st,   \
-                         alpha_lr, input, dist, occ, grad_a01, grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, \
-                         chan_off, H, W, scale, tiles, tpb, groups);                                                     \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<LPV, kMaxCls>), dim3((unsigned)(N * groups)), dim3(kBlock), 0, st,   \
-                         alpha_lr, input, dist, occ, grad_a01, grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, \
-                         chan_off, H, W, scale, tiles, tpb, groups);                                                     \
-    break;
-  switch (flow_ctx_pad_l(L)) {
-    WALDO_FCAB_CASE(4)
-    WALDO_FCAB_CASE(8)
-    WALDO_FCAB_CASE(12)
-    WALDO_FCAB_CASE(17)
-    WALDO_FCAB_CASE(24)
-    WALDO_FCAB_CASE(32)
-  }
-#undef WALDO_FCAB_CASE
+  with_padded_layers(L, [&](auto lp) {
+    auto launch = [&](auto ncp) {
+      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<decltype(lp)::value, decltype(ncp)::value>),
+                         dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, alpha_lr, input, dist, occ, grad_a01,
+                         grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, chan_off, H, W, scale, tiles, tpb,
+                         groups);
+    };
+    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
+    else launch(std::integral_constant<int, kMaxCls>{});
+  });
   if (scale > 1) {
     const int64_t P = N * L;
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -598,14 +583,11 @@ extern "C" int waldo_flow_ctx_warp_bwd(const float* flow_lr, const float* isobj_
   const int tiles = (int)(((int64_t)H * scale * W * scale + kBlock - 1) / kBlock);
   const int tpb = acc_tiles(N, tiles), groups = (tiles + tpb - 1) / tpb;
   float* gup = scale > 1 ? workspace : grad_flow_lr;
-  switch (flow_ctx_pad_l(L)) {
-    WALDO_FCB_CASE(4, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
-    WALDO_FCB_CASE(8, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
-    WALDO_FCB_CASE(12, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
-    WALDO_FCB_CASE(17, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
-    WALDO_FCB_CASE(24, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
-    WALDO_FCB_CASE(32, flow_ctx_warp_bwd_kernel, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup, grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups)
-  }
+  with_padded_layers(L, [&](auto lp) {
+    hipLaunchKernelGGL((flow_ctx_warp_bwd_kernel<decltype(lp)::value>), dim3((unsigned)(N * groups)), dim3(kBlock), 0,
+                       st, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup,
+                       grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups);
+  });
   if (scale > 1) {
     const int64_t P = N * L * 2;
     hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
@@ -637,14 +619,14 @@ extern "C" int waldo_frame_warp_fuse_bwd(const float* input, const float* flow, 
   }
   const dim3 grid((unsigned)((int64_t)B * Tp * tiles));
   // (a padding context repeats the last real one's taps and its L alpha loads: the count is compiled in for 1, 2, 4)
-#define WALDO_FWFB_LAUNCH(TCPV)                                                                                         \
-  hipLaunchKernelGGL(frame_warp_fuse_bwd_kernel<TCPV>, grid, dim3(kBlock), 0, (hipStream_t)stream, input, flow, alpha, \
-                     ctx_ts, grad_out, grad_raw, grad_flow, grad_alpha, T, Tc, Tp, C, L, Hd, Wd, include_self, eps,      \
-                     (int)tiles)
-  if (Tc == 1) WALDO_FWFB_LAUNCH(1);
-  else if (Tc == 2) WALDO_FWFB_LAUNCH(2);
-  else if (Tc <= 4) WALDO_FWFB_LAUNCH(4);
-  else WALDO_FWFB_LAUNCH(8);
-#undef WALDO_FWFB_LAUNCH
+  auto launch = [&](auto tcp) {
+    hipLaunchKernelGGL(frame_warp_fuse_bwd_kernel<decltype(tcp)::value>, grid, dim3(kBlock), 0, (hipStream_t)stream,
+                       input, flow, alpha, ctx_ts, grad_out, grad_raw, grad_flow, grad_alpha, T, Tc, Tp, C, L, Hd, Wd,
+                       include_self, eps, (int)tiles);
+  };
+  if (Tc == 1) launch(std::integral_constant<int, 1>{});
+  else if (Tc == 2) launch(std::integral_constant<int, 2>{});
+  else if (Tc <= 4) launch(std::integral_constant<int, 4>{});
+  else launch(std::integral_constant<int, 8>{});
   return launch_status("waldo_frame_warp_fuse_bwd");
 }

@@ -1,4 +1,4 @@
-// Helpers shared by the fused full-resolution passes (flow_ctx.hip) and their backward
+// Helpers shared by the fused full-resolution passes (flow_ctx_kernels.hip.h) and their backward
 // (flow_ctx_bwd.hip): the taps of F.interpolate's bilinear upsampling and the identity grid of the
 // HD raster exactly as tools/utils.py:get_grid builds it.
 #pragma once
@@ -417,14 +417,5 @@ __device__ __forceinline__ void store_px16(T* at, float v) {
 }
 
 constexpr int kFwMaxCtx = 8;  // contexts (incl. self) of the fused frame warp
-
-inline int flow_ctx_pad_l(int L) {
-  if (L <= 4) return 4;
-  if (L <= 8) return 8;
-  if (L <= 12) return 12;
-  if (L <= 17) return 17;
-  if (L <= 24) return 24;
-  return 32;
-}
 
 }  // namespace waldo

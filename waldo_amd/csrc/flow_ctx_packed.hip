@@ -1,4 +1,8 @@
-// The packed clip's passes of flow_ctx.hip with an fp32 `raw` (frame warp) and its flow_ctx_alpha: a compile unit of
+// The packed clip's flow_ctx_alpha and its frame warp with an fp32 `raw` (flow_ctx_kernels.hip.h): a compile unit of
 // their own
-#define WALDO_FC_PACKED 1
-#include "flow_ctx.hip"
+#include "flow_ctx_kernels.hip.h"
+
+namespace waldo {
+template decltype(flow_ctx_alpha_launch<uint32_t>) flow_ctx_alpha_launch<uint32_t>;
+template decltype(frame_warp_fuse_raw<float, uint32_t>) frame_warp_fuse_raw<float, uint32_t>;
+}  // namespace waldo

@@ -1,5 +1,6 @@
-// The packed clip's frame warp of flow_ctx.hip with a bf16 `raw`: a compile unit of its own
-#define WALDO_FC_PACKED 1
-#define WALDO_FC_RAW_HALF __bf16
-#define WALDO_FC_RAW_SUFFIX bf16
-#include "flow_ctx.hip"
+// The packed clip's frame warp with a bf16 `raw` (flow_ctx_kernels.hip.h): a compile unit of its own
+#include "flow_ctx_kernels.hip.h"
+
+namespace waldo {
+template decltype(frame_warp_fuse_raw<__bf16, uint32_t>) frame_warp_fuse_raw<__bf16, uint32_t>;
+}  // namespace waldo

@@ -1,5 +1,6 @@
-// The packed clip's frame warp of flow_ctx.hip with an fp16 `raw`: a compile unit of its own
-#define WALDO_FC_PACKED 1
-#define WALDO_FC_RAW_HALF _Float16
-#define WALDO_FC_RAW_SUFFIX f16
-#include "flow_ctx.hip"
+// The packed clip's frame warp with an fp16 `raw` (flow_ctx_kernels.hip.h): a compile unit of its own
+#include "flow_ctx_kernels.hip.h"
+
+namespace waldo {
+template decltype(frame_warp_fuse_raw<_Float16, uint32_t>) frame_warp_fuse_raw<_Float16, uint32_t>;
+}  // namespace waldo

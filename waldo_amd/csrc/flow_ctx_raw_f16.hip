@@ -1,4 +1,7 @@
-// The f16 instances of the raw path of flow_ctx.hip (a 16-bit `raw`): a compile unit of their own
-#define WALDO_FC_RAW_HALF _Float16
-#define WALDO_FC_RAW_SUFFIX f16
-#include "flow_ctx.hip"
+// The raw path with an fp16 `raw` (flow_ctx_kernels.hip.h): a compile unit of its own
+#include "flow_ctx_kernels.hip.h"
+
+namespace waldo {
+template decltype(flow_ctx_warp_raw<_Float16>) flow_ctx_warp_raw<_Float16>;
+template decltype(frame_warp_fuse_raw<_Float16, float>) frame_warp_fuse_raw<_Float16, float>;
+}  // namespace waldo

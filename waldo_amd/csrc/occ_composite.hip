@@ -116,15 +116,6 @@ __global__ __launch_bounds__(kBlock) void occ_composite_bwd_kernel(
   }
 }
 
-static int pad_l(int L) {
-  if (L <= 4) return 4;
-  if (L <= 8) return 8;
-  if (L <= 12) return 12;
-  if (L <= 17) return 17;
-  if (L <= 24) return 24;
-  return 32;
-}
-
 static int check_occ(const char* fn, int64_t M, int L, int64_t HW, int64_t occ_div) {
   if (M < 0 || L < 1 || L > 32 || HW < 1 || occ_div < 1) {
     set_error("%s: bad shape M=%lld L=%d HW=%lld occ_div=%lld (need 1<=L<=32)", fn, (long long)M,
@@ -142,12 +133,6 @@ static int check_occ(const char* fn, int64_t M, int L, int64_t HW, int64_t occ_d
 
 using namespace waldo;
 
-#define WALDO_OCC_CASE(LPV, KERNEL, ...)                                                    \
-  case LPV:                                                                                 \
-    hipLaunchKernelGGL((KERNEL<LPV>), dim3((unsigned)(M * tiles)), dim3(kBlock), 0, st,     \
-                       __VA_ARGS__);                                                        \
-    break;
-
 extern "C" int waldo_occ_composite_fwd(const float* alpha, const float* occ, float* out,
                                        int64_t M, int L, int64_t HW, int64_t occ_div,
                                        waldo_stream_t stream) {
@@ -160,14 +145,10 @@ extern "C" int waldo_occ_composite_fwd(const float* alpha, const float* occ, flo
   }
   hipStream_t st = (hipStream_t)stream;
   const int tiles = (int)((HW + kBlock - 1) / kBlock);
-  switch (pad_l(L)) {
-    WALDO_OCC_CASE(4, occ_composite_fwd_kernel, alpha, occ, out, L, HW, tiles, occ_div)
-    WALDO_OCC_CASE(8, occ_composite_fwd_kernel, alpha, occ, out, L, HW, tiles, occ_div)
-    WALDO_OCC_CASE(12, occ_composite_fwd_kernel, alpha, occ, out, L, HW, tiles, occ_div)
-    WALDO_OCC_CASE(17, occ_composite_fwd_kernel, alpha, occ, out, L, HW, tiles, occ_div)
-    WALDO_OCC_CASE(24, occ_composite_fwd_kernel, alpha, occ, out, L, HW, tiles, occ_div)
-    WALDO_OCC_CASE(32, occ_composite_fwd_kernel, alpha, occ, out, L, HW, tiles, occ_div)
-  }
+  with_padded_layers(L, [&](auto lp) {
+    hipLaunchKernelGGL((occ_composite_fwd_kernel<decltype(lp)::value>), dim3((unsigned)(M * tiles)), dim3(kBlock), 0, st,
+                       alpha, occ, out, L, HW, tiles, occ_div);
+  });
   return launch_status("waldo_occ_composite_fwd");
 }
 
@@ -189,19 +170,9 @@ extern "C" int waldo_occ_composite_bwd(const float* alpha, const float* occ,
   int tpb = (int)min((int64_t)16, max((int64_t)1, (M * tiles) / 1024));
   if (grad_occ == nullptr) tpb = 1;
   const int groups = (tiles + tpb - 1) / tpb;
-#define WALDO_OCC_BWD(LPV)                                                                        \
-  case LPV:                                                                                       \
-    hipLaunchKernelGGL((occ_composite_bwd_kernel<LPV>), dim3((unsigned)(M * groups)), dim3(kBlock), 0, st, \
-                       alpha, occ, grad_out, grad_alpha, grad_occ, L, HW, tiles, tpb, groups, occ_div); \
-    break;
-  switch (pad_l(L)) {
-    WALDO_OCC_BWD(4)
-    WALDO_OCC_BWD(8)
-    WALDO_OCC_BWD(12)
-    WALDO_OCC_BWD(17)
-    WALDO_OCC_BWD(24)
-    WALDO_OCC_BWD(32)
-  }
-#undef WALDO_OCC_BWD
+  with_padded_layers(L, [&](auto lp) {
+    hipLaunchKernelGGL((occ_composite_bwd_kernel<decltype(lp)::value>), dim3((unsigned)(M * groups)), dim3(kBlock), 0,
+                       st, alpha, occ, grad_out, grad_alpha, grad_occ, L, HW, tiles, tpb, groups, occ_div);
+  });
   return launch_status("waldo_occ_composite_bwd");
 }

@@ -1,6 +1,6 @@
 // The packed clip (packed_clip.hip.h): its unpacked fp32 form, and the low-resolution copy of its layout channels that
 // Warper.grid_to_flow[_ctx] takes (waldo_downscale_frames_fwd's packed twin).  The frame warp and the first
-// full-resolution pass read the packed clip in flow_ctx.hip (flow_ctx_packed*.hip).
+// full-resolution pass read the packed clip in flow_ctx_kernels.hip.h (flow_ctx_packed*.hip).
 #include "packed_clip.hip.h"
 
 namespace waldo {

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/waldo_hip.h"
 #include "warp_composite_layout.hip.h"
@@ -436,6 +437,29 @@ __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
   return v;
+}
+
+// the layer counts the fused passes and the occlusion composite are compiled for: L padded up to 4, 8, 12, 17, 24, 32
+inline int flow_ctx_pad_l(int L) {
+  if (L <= 4) return 4;
+  if (L <= 8) return 8;
+  if (L <= 12) return 12;
+  if (L <= 17) return 17;
+  if (L <= 24) return 24;
+  return 32;
+}
+
+// f(std::integral_constant<int, LP>{}) for LP = flow_ctx_pad_l(L)
+template <typename F>
+void with_padded_layers(int L, F&& f) {
+  switch (flow_ctx_pad_l(L)) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 12: f(std::integral_constant<int, 12>{}); break;
+    case 17: f(std::integral_constant<int, 17>{}); break;
+    case 24: f(std::integral_constant<int, 24>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+  }
 }
 
 }  // namespace waldo

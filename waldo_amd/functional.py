@@ -630,6 +630,20 @@ def pose_affine(pose, mul6, bias6, base_pts, mul_delta=1.0, pts_mul=1.0):
 # --------------------------------------------------------------------------------------
 # A12: WIF fusion epilogue
 # --------------------------------------------------------------------------------------
+# element types of the *_dt entry points (include/waldo_hip.h: enum waldo_dtype)
+_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _call_dt(name, dtypes, *args):
+    """``name`` when every dtype is fp32, else ``name + "_dt"`` with the dtype codes inserted before the stream (the
+    last argument).  fp32 work keeps launching the fp32 entry point under its own name (KernelTimer keys on it)."""
+    codes = [_DTYPE_CODE[d] for d in dtypes]
+    if any(codes):
+        _lib.call(name + "_dt", *args[:-1], *codes, args[-1])
+    else:
+        _lib.call(name, *args)
+
+
 class _WifFuse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vid, net, ab):
@@ -641,13 +655,8 @@ class _WifFuse(torch.autograd.Function):
             raise _lib.WaldoHipError(f"wif_fuse: shapes {tuple(vid.shape)} vs {tuple(net.shape)}")
         out = vid.new_empty(b, t, 3, h, w, dtype=torch.float32)
         with _lib.on_device(vid.device):
-            if vid.dtype == torch.float32 and net.dtype == torch.float32:
-                _lib.call("waldo_wif_fuse_fwd", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out), b * t, tc,
-                          c, co, h * w, int(bool(ab)), _lib.current_stream(vid.device))
-            else:
-                _lib.call("waldo_wif_fuse_fwd_dt", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out), b * t, tc,
-                          c, co, h * w, int(bool(ab)), _DTYPE_CODE[vid.dtype], _DTYPE_CODE[net.dtype],
-                          _lib.current_stream(vid.device))
+            _call_dt("waldo_wif_fuse_fwd", (vid.dtype, net.dtype), _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
+                     b * t, tc, c, co, h * w, int(bool(ab)), _lib.current_stream(vid.device))
         ctx.save_for_backward(vid, net, out)
         ctx.ab = int(bool(ab))
         return out
@@ -661,14 +670,9 @@ class _WifFuse(torch.autograd.Function):
         gv = torch.empty_like(vid) if ctx.needs_input_grad[0] else None
         gn = torch.empty_like(net) if ctx.needs_input_grad[1] else None
         with _lib.on_device(vid.device):
-            if vid.dtype == torch.float32 and net.dtype == torch.float32:
-                _lib.call("waldo_wif_fuse_bwd", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
-                          _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w,
-                          ctx.ab, _lib.current_stream(vid.device))
-            else:
-                _lib.call("waldo_wif_fuse_bwd_dt", _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
-                          _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w,
-                          ctx.ab, _DTYPE_CODE[vid.dtype], _DTYPE_CODE[net.dtype], _lib.current_stream(vid.device))
+            _call_dt("waldo_wif_fuse_bwd", (vid.dtype, net.dtype), _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
+                     _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w, ctx.ab,
+                     _lib.current_stream(vid.device))
         return gv, gn, None
 
 
@@ -823,23 +827,20 @@ def flow_ctx_alpha(alpha_lr, input, dist, occ, tw, chan_off, scale, want_alpha=T
         if dist is not None and int(chan_off) != 3:
             raise _lib.WaldoHipError(f"flow_ctx_alpha: a packed clip's layout channels start at 3, not {chan_off}")
         data = _packed_data(input, "flow_ctx_alpha")
+    if packed or (no_grad and (not want_alpha or want_bits)):
         a01 = alpha_lr.new_empty(n, nl, hd, wd)
         alpha = alpha_lr.new_empty(n, nl, hd, wd) if want_alpha else None
         bits = torch.empty(n, hd, (wd + 63) // 64, dtype=torch.int32, device=alpha_lr.device) if want_bits else None
         with _lib.on_device(alpha_lr.device):
-            _lib.call("waldo_flow_ctx_alpha_packed_fwd", _lib.ptr(alpha_lr), _lib.ptr(data), _lib.ptr(dist),
-                      _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl, input.num_lyt, h, w,
-                      scale, _lib.current_stream(alpha_lr.device))
-        return (a01, alpha, bits) if want_bits else (a01, alpha)
-    if no_grad and (not want_alpha or want_bits):
-        a01 = alpha_lr.new_empty(n, nl, hd, wd)
-        alpha = alpha_lr.new_empty(n, nl, hd, wd) if want_alpha else None
-        bits = torch.empty(n, hd, (wd + 63) // 64, dtype=torch.int32, device=alpha_lr.device) if want_bits else None
-        with _lib.on_device(alpha_lr.device):
-            _lib.call("waldo_flow_ctx_alpha_fwd", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist), _lib.ptr(occ),
-                      _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl,
-                      dist.shape[2] if dist is not None else 0, c, chan_off, h, w, scale,
-                      _lib.current_stream(alpha_lr.device))
+            if packed:
+                _lib.call("waldo_flow_ctx_alpha_packed_fwd", _lib.ptr(alpha_lr), _lib.ptr(data), _lib.ptr(dist),
+                          _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl, input.num_lyt,
+                          h, w, scale, _lib.current_stream(alpha_lr.device))
+            else:
+                _lib.call("waldo_flow_ctx_alpha_fwd", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist),
+                          _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl,
+                          dist.shape[2] if dist is not None else 0, c, chan_off, h, w, scale,
+                          _lib.current_stream(alpha_lr.device))
         return (a01, alpha, bits) if want_bits else (a01, alpha)
     res = _FlowCtxAlpha.apply(alpha_lr, input, dist, occ, tw, chan_off, scale)
     return (*res, None) if want_bits else res
@@ -947,10 +948,6 @@ def flow_ctx_warp(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, scale, layer
     return (flow, alpha_ctx, disocc, amax) if layer_max else (flow, alpha_ctx, disocc)
 
 
-# element types of the *_dt entry points (include/waldo_hip.h: enum waldo_dtype)
-_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
-
-
 class RawSlots:
     """What ``flow_ctx_warp_into_raw`` leaves for ``frame_warp_fuse_raw``: the ``raw`` tensor of
     Warper.input_to_output, (B, Tp, Tc', C + L, Hd, Wd), with the alpha slots of its Tc contexts filled, and
@@ -991,18 +988,11 @@ def flow_ctx_warp_into_raw(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, sca
         disocc = flow_lr.new_empty(m, hd, wd)
         amax = flow_lr.new_empty(m, hd, wd) if layer_max else None
         with _lib.on_device(flow_lr.device):
-            if raw_dtype == torch.float32:
-                _lib.call("waldo_flow_ctx_warp_raw_fwd", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
-                          _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
-                          _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
-                          _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h,
-                          w, scale, int(channels), tcx, _lib.current_stream(flow_lr.device))
-            else:
-                _lib.call("waldo_flow_ctx_warp_raw_fwd_dt", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
-                          _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
-                          _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
-                          _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h,
-                          w, scale, int(channels), tcx, _DTYPE_CODE[raw_dtype], _lib.current_stream(flow_lr.device))
+            _call_dt("waldo_flow_ctx_warp_raw_fwd", (raw_dtype,), _lib.ptr(flow_lr), _lib.ptr(isobj_lr),
+                     _lib.ptr(a01), _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
+                     _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
+                     _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h, w,
+                     scale, int(channels), tcx, _lib.current_stream(flow_lr.device))
         alpha_ctx = raw[:, :, :tc, channels:].permute(0, 2, 1, 3, 4, 5)  # (B, Tc, Tp, L, Hd, Wd), strided
     if strict:
         st.check(sync=True)
@@ -1110,15 +1100,10 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
                       _lib.ptr(rgb_table(input.device)), _lib.ptr(flow), _lib.ptr(score), _lib.ptr(ctx_ts), _lib.ptr(out),
                       _lib.ptr(raw), st.ptr, b, t, tc, tp, input.num_lyt, nl, hd, wd, 1 if slots.include_self else 0,
                       float(eps), _DTYPE_CODE[raw.dtype], _lib.current_stream(input.device))
-        elif raw.dtype == torch.float32:
-            _lib.call("waldo_frame_warp_fuse_raw_fwd", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
-                      _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
-                      1 if slots.include_self else 0, float(eps), _lib.current_stream(input.device))
         else:
-            _lib.call("waldo_frame_warp_fuse_raw_fwd_dt", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
-                      _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
-                      1 if slots.include_self else 0, float(eps), _DTYPE_CODE[raw.dtype],
-                      _lib.current_stream(input.device))
+            _call_dt("waldo_frame_warp_fuse_raw_fwd", (raw.dtype,), _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
+                     _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
+                     1 if slots.include_self else 0, float(eps), _lib.current_stream(input.device))
     if strict:
         st.check(sync=True)
     return out, raw.permute(0, 2, 1, 3, 4, 5)

@@ -608,7 +608,7 @@ class Warper(nn.Module):
         return self._flow_common(input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts, True)
 
     def _frame_warp_fused(self, input, tc, tp):
-        """input_to_output runs as the fused kernel (csrc/flow_ctx.hip:frame_warp_fuse_kernel)."""
+        """input_to_output runs as the fused kernel (csrc/flow_ctx_kernels.hip.h:frame_warp_fuse_kernel)."""
         self_slot = self.include_self and tp == input.size(1)
         return self.fuse_hd and tc + int(self_slot) <= WF.MAX_FUSE_CTX and \
             not (torch.is_grad_enabled() and input.requires_grad)
