@@ -1,7 +1,8 @@
 """ctypes loader of the plain-C restatement (oracle/wif_oracle.c) -- TEST INFRASTRUCTURE ONLY.
 
 ``fused(...)`` runs TPS grid -> bilinear warp -> reduce_comp forward and backward in double precision
-and returns numpy arrays.  Built by ``make -C oracle`` (``__graft_entry__.build()`` does that)."""
+and returns numpy arrays; ``tps_chain(...)`` reproduces the fp32 sample coordinates of the fused HIP path
+bit for bit.  Built by ``make -C oracle`` (``__graft_entry__.build()`` does that)."""
 import ctypes
 import os
 import subprocess
@@ -23,6 +24,8 @@ def load():
         fp, dp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)
         _lib.waldo_oracle_fused.restype = ctypes.c_int
         _lib.waldo_oracle_fused.argtypes = [fp, fp, fp, fp] + [ctypes.c_int] * 5 + [fp, fp, ctypes.c_int, ctypes.c_double] + [dp] * 5
+        _lib.waldo_oracle_tps_chain.restype = ctypes.c_int
+        _lib.waldo_oracle_tps_chain.argtypes = [fp, fp, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_int] * 4 + [fp]
     return _lib
 
 
@@ -53,4 +56,20 @@ def fused(layers, pts, occ, ctrl, w_rgb=None, w_alpha=None, loss_sq=False, backw
         _ptr(out.get("grad_pts"), d), _ptr(out.get("grad_occ"), d))
     if rc != 0:
         raise RuntimeError(f"waldo_oracle_fused failed with code {rc}")
+    return out
+
+
+def tps_chain(basis_t, mapping, h, w, scaled):
+    """basis_t (K3, H*W), mapping (B, K3, 2), both fp32 -> (B, H*W, 2) float32: the sequential fmaf chain over k
+    of the fused path's tps_eval() (``scaled``: scaled_map() operands, coordinates in pixel units) or, without
+    ``scaled``, of tps_grid_fwd_kernel (the normalised grid of ``tps_grid``)."""
+    basis_t, mapping = _f32(basis_t), _f32(mapping)
+    k3, hw = basis_t.shape
+    b = mapping.shape[0]
+    assert mapping.shape == (b, k3, 2) and hw == h * w, (basis_t.shape, mapping.shape, h, w)
+    out = np.empty((b, hw, 2), dtype=np.float32)
+    rc = load().waldo_oracle_tps_chain(_ptr(basis_t, ctypes.c_float), _ptr(mapping, ctypes.c_float), b, hw, k3,
+                                       h, w, int(bool(scaled)), _ptr(out, ctypes.c_float))
+    if rc != 0:
+        raise RuntimeError(f"waldo_oracle_tps_chain failed with code {rc}")
     return out

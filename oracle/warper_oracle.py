@@ -236,21 +236,45 @@ def lyt_dist(alpha_obj, lyt, cls, weight_cls, min_cls):
     return mean.softmax(dim=2)                                          # B No Nl
 
 
-def _lyt_alpha(cfg, alpha_obj, lyt, hd_lyt, cls):
-    """Layout filter (lvd.py:624-639 / 731-751): per object, 1 - 0.5 * L1 distance between the
-    object's class distribution and the per-pixel class distribution at HD.
-    alpha_obj (B,Tw,No,1,H,W), lyt (B,Tw,Nl,H,W), hd_lyt (B,Tw,Nl,Hd,Wd) -> (B,Tw,No,1,Hd,Wd)."""
-    no = alpha_obj.shape[2]
+def _lyt_dist_prob(cfg, alpha_obj, lyt, hd_lyt, cls):
+    """The two distributions the layout filter compares: every object's (B,No,Nl) and every HD pixel's (B,Tw,Nl,Hd,Wd)."""
     hd_prob = hd_lyt.softmax(dim=2)                                     # B Tw Nl Hd Wd
     if cls is None or cfg.weight_cls:
         dist = lyt_dist(alpha_obj, lyt, cls, cfg.weight_cls, cfg.min_cls)
     else:
         dist = cls                                                      # B No Nl
+    return dist, hd_prob
+
+
+def _lyt_alpha(cfg, alpha_obj, lyt, hd_lyt, cls):
+    """Layout filter (lvd.py:624-639 / 731-751): per object, 1 - 0.5 * L1 distance between the
+    object's class distribution and the per-pixel class distribution at HD.
+    alpha_obj (B,Tw,No,1,H,W), lyt (B,Tw,Nl,H,W), hd_lyt (B,Tw,Nl,Hd,Wd) -> (B,Tw,No,1,Hd,Wd)."""
+    no = alpha_obj.shape[2]
+    dist, hd_prob = _lyt_dist_prob(cfg, alpha_obj, lyt, hd_lyt, cls)
     out = []
     for o in range(no):
         d = (dist[:, None, o, :, None, None] - hd_prob).abs().sum(dim=2, keepdim=True)  # B Tw 1 Hd Wd
         out.append(1 - d / 2)
     return torch.stack(out, dim=2)                                      # B Tw No 1 Hd Wd
+
+
+def lyt_margin(cfg, inp, grid, obj_alpha, bg_alpha, cls, ctx_ts, ctx_only):
+    """The layout filter's distance from its kinks, per object (B, No): the smallest |dist - prob| over the classes and
+    the HD pixels of the frames it filters (the L1 distance of _lyt_alpha is not differentiable where a term is 0, and
+    an fp32 evaluation within rounding of it may take the other side).  None when the chain has no layout filter.
+    Steps 1-2 of _grid_to_flow, in the dtype of the inputs."""
+    if cfg.no_filter and not ctx_only:
+        return None
+    t = inp.shape[1]
+    win = slice(0, ctx_ts.shape[1]) if ctx_only else slice(0, t)
+    oa = ((obj_alpha + 1) / 2).unsqueeze(1).expand(-1, t, -1, -1, -1, -1)
+    ba = ((bg_alpha + 1) / 2).unsqueeze(1).expand(-1, t, -1, -1, -1)
+    alpha = layer_to_output(cfg, oa, ba, grid, 0, 0)[:, win]
+    lo_inp = rescale(inp, 1 / cfg.scale_hd)
+    dist, hd_prob = _lyt_dist_prob(cfg, alpha[:, :, 1:], lo_inp[:, win, 3:], inp[:, win, 3:], cls)
+    d = (dist[:, None, :, :, None, None] - hd_prob[:, :, None]).abs()   # B Tw No Nl Hd Wd
+    return d.amin(dim=(1, 3, 4, 5))
 
 
 def grid_to_flow_ctx(cfg, inp, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts):

@@ -244,3 +244,40 @@ int waldo_oracle_fused(const float* layers, const float* pts, const float* occ, 
   free(ggrid);
   return 0;
 }
+
+/* The sample coordinates of the fused HIP path, reproduced bit for bit on the host (C99 fmaf is correctly
+ * rounded).  basis_t (K3, HW), mapping (B, K3, 2) -> out (B, HW, 2), for every map b and pixel p the
+ * sequential chain over k of  acc = fmaf(basis_t[k, p], m_k, acc)  from acc = 0, with
+ *   scaled == 0:  m_k = mapping[b, k, c]                   (tps_grid_fwd_kernel: the normalised grid)
+ *   scaled == 1:  m_k = scaled_map(mapping[b, k, c])       (tps_eval() of warp_composite_kernels.hip.h:
+ *                 m * size / 2, and fmaf(m, size / 2, (size - 1) / 2) for the constant term k == K3 - 3;
+ *                 the grid in PIXEL units, ((g + 1) * size - 1) / 2 of grid_sample, size = W for x, H for y) */
+int waldo_oracle_tps_chain(const float* basis_t, const float* mapping, long long B, long long HW, int K3,
+                           int H, int W, int scaled, float* out) {
+  if (B < 0 || HW <= 0 || K3 < 4 || !basis_t || !mapping || !out) return -1;
+  const float half[2] = {0.5f * (float)W, 0.5f * (float)H};
+  const float half_m1[2] = {0.5f * (float)(W - 1), 0.5f * (float)(H - 1)};
+  float* m = (float*)malloc((size_t)K3 * 2 * sizeof(float));
+  if (!m) return -2;
+  for (long long b = 0; b < B; ++b) {
+    const float* mb = mapping + b * K3 * 2;
+    for (int k = 0; k < K3; ++k)
+      for (int c = 0; c < 2; ++c) {
+        const float v = mb[2 * k + c];
+        m[2 * k + c] = !scaled ? v : (k == K3 - 3 ? fmaf(v, half[c], half_m1[c]) : v * half[c]);
+      }
+    float* ob = out + b * HW * 2;
+    for (long long p = 0; p < HW; ++p) {
+      float ax = 0.0f, ay = 0.0f;
+      for (int k = 0; k < K3; ++k) {
+        const float bv = basis_t[(long long)k * HW + p];
+        ax = fmaf(bv, m[2 * k], ax);
+        ay = fmaf(bv, m[2 * k + 1], ay);
+      }
+      ob[2 * p] = ax;
+      ob[2 * p + 1] = ay;
+    }
+  }
+  free(m);
+  return 0;
+}

@@ -113,9 +113,16 @@ def bilinear_sample(inp, grid):
     inp (N, C, Hi, Wi), grid (N, Ho, Wo, 2) -> (N, C, Ho, Wo).  Differentiable w.r.t. both.
     All F.grid_sample call sites on the path use the defaults, e.g. models/nets/lvd.py:518,548."""
     n, c, hi, wi = inp.shape
-    _, ho, wo, _ = grid.shape
     ix = ((grid[..., 0] + 1) * wi - 1) / 2
     iy = ((grid[..., 1] + 1) * hi - 1) / 2
+    return bilinear_sample_px(inp, ix, iy)
+
+
+def bilinear_sample_px(inp, ix, iy):
+    """bilinear_sample at coordinates already in PIXEL units: ix, iy (N, Ho, Wo), texel centres at integers.
+    Differentiable w.r.t. inp and the coordinates."""
+    n, c, hi, wi = inp.shape
+    _, ho, wo = ix.shape
     x0 = torch.floor(ix)
     y0 = torch.floor(iy)
     fx = ix - x0
@@ -213,6 +220,22 @@ def warp_composite(layers, src_pts, occ, inverse_kernel, tgt_grid_repr, explicit
     grid = tps_grid(inverse_kernel, tgt_grid_repr, src_pts, h, w)
     warped = grid_sample_delta(layers.reshape(f * nl, c, h, w), grid, delta, explicit).view(f, 1, nl, c, h, w)
     rgb, alpha, _ = reduce_comp(warped, occ.view(f, 1, nl, nl))
+    return rgb[:, 0], alpha[:, 0]
+
+
+def warp_composite_px(layers, src_pts, occ, inverse_kernel, tgt_grid_repr, pos, delta=0.0):
+    """warp_composite sampled at GIVEN coordinates: pos (F*L, H, W, 2) in pixel units, e.g. the fp32 coordinates
+    a kernel computed.  Every value -- and so every floor and in-range decision -- is taken at pos; the derivative
+    with respect to src_pts flows through this oracle's own TPS chain (straight through: pos + (p - p.detach()),
+    p = ((grid + 1) * size - 1) / 2 in the layers' dtype).  No round trip through normalised coordinates: that
+    would move an exact-integer position off its texel."""
+    f, nl, c, h, w = layers.shape
+    grid = tps_grid(inverse_kernel, tgt_grid_repr, src_pts, h, w)
+    size = torch.tensor([w, h], dtype=grid.dtype)
+    p = ((grid + 1) * size - 1) / 2
+    p = pos.to(p.dtype) + (p - p.detach())
+    warped = bilinear_sample_px(layers.reshape(f * nl, c, h, w) + delta, p[..., 0], p[..., 1]) - delta
+    rgb, alpha, _ = reduce_comp(warped.view(f, 1, nl, c, h, w), occ.view(f, 1, nl, nl))
     return rgb[:, 0], alpha[:, 0]
 
 

@@ -11,7 +11,7 @@ from oracle import wif_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-from parity import TOL, close  # noqa: E402  (tests/parity.py: 1e-4 + the measured fp32 noise of the reference)
+from parity import TOL, close, compare_warp_composite  # noqa: E402  (tests/parity.py: 1e-4 + the measured fp32 noise of the reference)
 
 
 def test_native_library_is_loaded(dev):
@@ -68,7 +68,7 @@ def test_tps_bg_sized(dev):
     out = mod(p2)
     close(out, ref, what="grid", exact=ref64)
     (out * wgt.to(dev)).sum().backward()
-    close(p2.grad, pts.grad, rel=True, what="grad_pts", exact=p64.grad)
+    close(p2.grad, pts.grad, rel=True, what="grad_pts", exact=p64.grad, noise_of="tensor")
 
 
 def test_tps_identity(dev):
@@ -337,13 +337,51 @@ def _hip_fused(dev, layers, pts, occ, ctrl, w1, w2, loss="weights", buffers=None
     return rgb, alpha, l2.grad, p2.grad, o2.grad
 
 
-def _compare_fused(hip, ref32, ref64, grad_tol=TOL, pts_outliers=0.0):
-    names = ["rgb", "alpha", "grad_layers", "grad_pts", "grad_occ"]
-    for i, name in enumerate(names):
-        if ref32[i] is None:
-            continue
-        close(hip[i], ref32[i], tol=TOL if i < 2 else grad_tol, rel=i >= 2, what=name,
-              exact=ref64[i], outliers=pts_outliers if i == 3 else 0.0)
+def _matched(dev, layers, pts, occ, ctrl, w1, w2, loss="weights", delta=0.0):
+    """The oracle at the fused path's OWN sample coordinates (oracle/wif_oracle.py:warp_composite_px), in fp32 and
+    fp64: every floor and in-range decision is the kernel's, so the control-point gradient -- discontinuous where a
+    sample crosses a texel boundary -- is compared at plain TOL * scale, and every other output per element.  The
+    coordinates are the fmaf chain of tps_eval() (warp_composite_kernels.hip.h) over the device's own mapping,
+    reproduced on the host (oracle/c_oracle.py); the same chain without the pixel scaling must give WF.tps_grid's
+    output bit for bit, on every call, and the coordinates must be within the fp32 error bound of the two chains
+    (mapping and grid: 2 (N + K3) 2^-24 sum|terms|, in fp64) of the oracle's own fp64 ones."""
+    from oracle import c_oracle
+    from waldo_amd import functional as WF
+    import waldo_amd
+    f, nl, _, h, w = layers.shape
+    tps = waldo_amd.TPSWarp(h, w, ctrl).to(dev)
+    with torch.no_grad():
+        pd = pts.detach().to(dev)
+        mapping = WF.tps_mapping(tps.inverse_kernel, pd).cpu()
+        grid = WF.tps_grid(tps.inverse_kernel, tps.basis_t, pd, h, w).cpu()
+    basis = tps.basis_t.cpu()
+    plain = torch.from_numpy(c_oracle.tps_chain(basis, mapping, h, w, scaled=False)).view(grid.shape)
+    assert torch.equal(plain.view(torch.int32), grid.view(torch.int32)), \
+        f"host fmaf chain != WF.tps_grid in {int((plain != grid).sum())} of {grid.numel()} coordinates"
+    pos = torch.from_numpy(c_oracle.tps_chain(basis, mapping, h, w, scaled=True)).view(f * nl, h, w, 2)
+    inv, rep = O.tps_init(h, w, ctrl)
+    size = torch.tensor([w, h], dtype=torch.float64)
+    pos64 = ((O.tps_grid(inv.double(), rep.double(), pts.double(), h, w) + 1) * size - 1) / 2
+    k3, n = basis.shape[0], pts.shape[1]
+    x = torch.cat([pts.double(), pts.new_zeros(pts.shape[0], 3, 2, dtype=torch.float64)], dim=1).abs()
+    m_abs = mapping.double().abs() + inv.double().abs() @ x                    # |m_k| + sum_n |inv_kn x_n|
+    terms = (basis.double().t().abs() @ (m_abs * size / 2)).view(f * nl, h, w, 2)
+    slack = (pos.double() - pos64).abs() - 2 * (n + k3) * 2.0 ** -24 * (terms + size)
+    assert slack.max() <= 0, f"coordinates off the fp64 TPS chain by up to {slack.max().item():.3e} px"
+    out = []
+    for dt in (torch.float32, torch.float64):
+        l, p, o = (x.detach().to(dt).requires_grad_() for x in (layers, pts, occ))
+        rgb, alpha = O.warp_composite_px(l, p, o, inv.to(dt), rep.to(dt), pos, delta=delta)
+        if loss == "weights":
+            ((rgb * w1.to(dt)).sum() + (alpha * w2.to(dt)).sum()).backward()
+        else:
+            rgb.square().mean().backward()
+        out.append((rgb.detach(), alpha.detach(), l.grad, p.grad, o.grad))
+    return out
+
+
+def _compare_fused(hip, m32, m64):
+    compare_warp_composite(hip, m32, m64)
 
 
 @pytest.mark.parametrize("tag", ["small", "l8", "big_warp"])
@@ -359,8 +397,14 @@ def test_warp_composite_golden(dev, golden, tag):
     O.compute_occ(score)[:, 0].backward(hip[4].cpu())
     s64 = g["score"].double().requires_grad_()
     O.compute_occ(s64)[:, 0].backward(ref64[4])
-    ref32 = (g["rgb"], g["alpha"], g["grad_layers"], g["grad_pts"], None)
-    _compare_fused(hip, ref32, ref64)
+    # against the reference's own outputs where they are continuous in the sample positions ...
+    for i, name in enumerate(("rgb", "alpha", "grad_layers")):
+        close(hip[i], g[name], rel=i >= 2, what=name + " vs the reference", exact=ref64[i])
+    # ... its control-point gradient, taken at ITS sample positions, at the bound it always had (the tensor's largest
+    # fp32 noise: a sample the reference rounds across a texel boundary moves every entry of that map) ...
+    close(hip[3], g["grad_pts"], rel=True, what="grad_pts vs the reference", exact=ref64[3], noise_of="tensor")
+    # ... and everything against the oracle at the kernel's coordinates
+    _compare_fused(hip, *_matched(dev, g["layers"], g["pts"], g["occ"], g["ctrl"], g["w1"], g["w2"]))
     close(score.grad, g["grad_score"], rel=True, what="grad_score", exact=s64.grad)
 
 
@@ -372,8 +416,10 @@ def test_warp_composite_delta_golden(dev, golden, tag):
     delta = float(g["delta"])
     ref64 = _oracle_fused(g["layers"], g["pts"], g["occ"], g["ctrl"], g["w1"], g["w2"], torch.float64, delta=delta)
     hip = _hip_fused(dev, g["layers"], g["pts"], g["occ"], g["ctrl"], g["w1"], g["w2"], delta=delta)
-    ref32 = (g["rgb"], g["alpha"], g["grad_layers"], g["grad_pts"], None)
-    _compare_fused(hip, ref32, ref64)
+    for i, name in enumerate(("rgb", "alpha", "grad_layers")):
+        close(hip[i], g[name], rel=i >= 2, what=name + " vs the reference", exact=ref64[i])
+    close(hip[3], g["grad_pts"], rel=True, what="grad_pts vs the reference", exact=ref64[3], noise_of="tensor")
+    _compare_fused(hip, *_matched(dev, g["layers"], g["pts"], g["occ"], g["ctrl"], g["w1"], g["w2"], delta=delta))
     # and the padding matters here: delta = 0 gives another picture
     plain = _hip_fused(dev, g["layers"], g["pts"], g["occ"], g["ctrl"], g["w1"], g["w2"])
     assert (plain[0].cpu() - g["rgb"]).abs().max() > 1e-2
@@ -392,10 +438,8 @@ def test_warp_composite_delta_random(dev, cfg):
     layers, pts, occ, _, _ = O.make_synthetic(f, nl, h, w, seed=nl + 50, sigma=cfg["sigma"])
     torch.manual_seed(f * 10 + nl)
     w1, w2 = torch.randn(f, 3, h, w), torch.randn(f, nl, h, w)
-    ref32 = _oracle_fused(layers, pts, occ, ctrl, w1, w2, torch.float32, delta=1.0)
-    ref64 = _oracle_fused(layers, pts, occ, ctrl, w1, w2, torch.float64, delta=1.0)
     hip = _hip_fused(dev, layers, pts, occ, ctrl, w1, w2, generic=cfg.get("generic", False), delta=1.0)
-    _compare_fused(hip, ref32, ref64)
+    _compare_fused(hip, *_matched(dev, layers, pts, occ, ctrl, w1, w2, delta=1.0))
 
 
 def test_warp_composite_golden_bench_loss(dev, golden):
@@ -412,7 +456,9 @@ def test_warp_composite_golden_bench_loss(dev, golden):
     close(rgb, g["rgb"], what="rgb", exact=ref64[0])
     rgb.square().mean().backward()
     close(l2.grad, g["grad_layers_sq"], rel=True, what="grad_layers", exact=ref64[2])
-    close(p2.grad, g["grad_pts_sq"], rel=True, what="grad_pts", exact=ref64[3])
+    close(p2.grad, g["grad_pts_sq"], rel=True, what="grad_pts vs the reference", exact=ref64[3], noise_of="tensor")
+    m32, m64 = _matched(dev, g["layers"], g["pts"], g["occ"], g["ctrl"], None, None, "sq")
+    _compare_fused((rgb, None, l2.grad, p2.grad, None), m32, m64)
 
 
 @pytest.mark.parametrize("cfg", [
@@ -445,17 +491,16 @@ def test_warp_composite_random(dev, cfg):
                                                   smooth=cfg.get("smooth", 0))
     torch.manual_seed(f * 100 + nl)
     w1, w2 = torch.randn(f, 3, h, w), torch.randn(f, nl, h, w)
-    ref32 = _oracle_fused(layers, pts, occ, ctrl, w1, w2, torch.float32)
-    ref64 = _oracle_fused(layers, pts, occ, ctrl, w1, w2, torch.float64)
     hip = _hip_fused(dev, layers, pts, occ, ctrl, w1, w2, generic=cfg.get("generic", False))
-    _compare_fused(hip, ref32, ref64)
+    _compare_fused(hip, *_matched(dev, layers, pts, occ, ctrl, w1, w2))
 
 
 def test_warp_composite_seeded_fuzz(dev):
     """Twenty-four shapes drawn from a seeded generator -- 1 ... 5 frames, 1 ... 32 layers, rasters of 4 ... 64 by
     4 ... 110 pixels (any remainder against the 16 x 16 / 4 x 64 / 32 x 64 tiles and the four-pixel vectors), 3 x 3 ...
     5 x 5 control points, mild to folding warps, the three `delta` paddings, both backward kernels -- forward and all
-    three gradients against the fp32 and fp64 oracle through the same `close` as every other case.  The fixed lists
+    three gradients against the fp32 and fp64 oracle at the kernel's own coordinates through the same
+    `_compare_fused` as every other case, the control-point gradient on every draw.  The fixed lists
     above hold the shapes somebody thought of; this holds the ones nobody did."""
     import random
     rng = random.Random(20260)
@@ -480,22 +525,11 @@ def test_warp_composite_seeded_fuzz(dev):
                                                       smooth=smooth)
         torch.manual_seed(case)
         w1, w2 = torch.randn(f, 3, h, w), torch.randn(f, nl, h, w)
-        ref32 = _oracle_fused(layers, pts, occ, ctrl, w1, w2, torch.float32, delta=delta)
-        ref64 = _oracle_fused(layers, pts, occ, ctrl, w1, w2, torch.float64, delta=delta)
         hip = _hip_fused(dev, layers, pts, occ, ctrl, w1, w2, generic=generic, delta=delta)
-        if smooth < 4 or nl == 1:
-            # white-noise layers: the control-point gradient is DISCONTINUOUS in the sample positions (the bilinear
-            # interpolant's derivative jumps by O(texel difference) across a texel boundary), one pixel whose position
-            # rounds to the other side of a boundary moves it by several per cent of its scale, and the two oracles'
-            # agreement there says nothing about a third summation order (seen: |hip - ref64| 49 where |ref32 - ref64|
-            # is 0.66 and another shape has the oracles themselves 31 apart, on a scale of 800-900).  Everything else is
-            # continuous and is compared; grad_pts is compared on the cases whose layers are upsampled x4 (x2 leaves a
-            # kink every other pixel: seen 27 x over the bound in one map's coordinates).
-            hip, ref32, ref64 = [[x if i != 3 else None for i, x in enumerate(t)] for t in (hip, ref32, ref64)]
         try:
-            # (upsampled layers are piecewise linear: the interpolant's derivative still jumps at the coarse knots, by
-            # less -- one map's 32 control-point gradients may sit up to 25 x over the bound: parity.close, `outliers`)
-            _compare_fused(hip, ref32, ref64, pts_outliers=0.05)
+            # grad_pts on every draw, white-noise layers included: the fp64 oracle takes each sample where the kernel
+            # does, so a texel boundary that one fp32 evaluation rounds to the other side is no longer a difference
+            _compare_fused(hip, *_matched(dev, layers, pts, occ, ctrl, w1, w2, delta=delta))
         except AssertionError as exc:
             raise AssertionError(f"case {case}: f={f} nl={nl} h={h} w={w} k={k} sigma={sigma} delta={delta} "
                                  f"generic={generic} smooth={smooth}: {exc}") from exc
@@ -548,10 +582,8 @@ def test_warp_composite_full_size(dev, h, w, nl, smooth):
     f = 2
     layers, pts, occ, inv, rep = O.make_synthetic(f, nl, h, w, seed=11, smooth=smooth)
     ctrl = O.get_grid(4, 4).view(-1, 2)
-    ref32 = _oracle_fused(layers, pts, occ, ctrl, None, None, torch.float32, "sq")
-    ref64 = _oracle_fused(layers, pts, occ, ctrl, None, None, torch.float64, "sq")
     hip = _hip_fused(dev, layers, pts, occ, ctrl, None, None, "sq")
-    _compare_fused(hip[:4] + (None,), ref32[:4] + (None,), ref64)
+    _compare_fused(hip[:4] + (None,), *_matched(dev, layers, pts, occ, ctrl, None, None, "sq"))
     # (ii) identity control points and (iii) transparent objects: against the oracle first ...
     tps = waldo_amd.TPSWarp(h, w, ctrl).to(dev)
     ld, od = layers.to(dev), occ.to(dev)
@@ -559,13 +591,13 @@ def test_warp_composite_full_size(dev, h, w, nl, smooth):
     rgb_i = WF.warp_composite(ld, ident.to(dev), od, tps.inverse_kernel, tps.basis_t)
     id64 = _oracle_fused(layers, ident, occ, ctrl, None, None, torch.float64, "sq")[0]
     id32 = _oracle_fused(layers, ident, occ, ctrl, None, None, torch.float32, "sq")[0]
-    close(rgb_i, id32, what="identity warp vs oracle", exact=id64)
+    close(rgb_i, id32, what="identity warp vs oracle", exact=id64, noise_of="tensor")
     l0 = layers.clone()
     l0[:, 1:, 3] = -1.0
     rgb_0 = WF.warp_composite(l0.to(dev), ident.to(dev), od, tps.inverse_kernel, tps.basis_t)
     bg64 = _oracle_fused(l0, ident, occ, ctrl, None, None, torch.float64, "sq")[0]
     bg32 = _oracle_fused(l0, ident, occ, ctrl, None, None, torch.float32, "sq")[0]
-    close(rgb_0, bg32, what="background only vs oracle", exact=bg64)
+    close(rgb_0, bg32, what="background only vs oracle", exact=bg64, noise_of="tensor")
     # ... then the size-independent properties themselves.  They hold only approximately, for the
     # reference as for the build: the TPS fixed point is reached to ~3e-6 in grid units (1e-3 px
     # at W=512), and at the image border that leaks a little zero padding into the sample.
@@ -582,10 +614,8 @@ def test_c3_eight_frames_with_grad_occ(dev):
     f, nl, h, w = 8, 8, 256, 512
     layers, pts, occ, _, _ = O.make_synthetic(f, nl, h, w, seed=13)
     ctrl = O.get_grid(4, 4).view(-1, 2)
-    ref32 = _oracle_fused(layers, pts, occ, ctrl, None, None, torch.float32, "sq")
-    ref64 = _oracle_fused(layers, pts, occ, ctrl, None, None, torch.float64, "sq")
     hip = _hip_fused(dev, layers, pts, occ, ctrl, None, None, "sq")
-    _compare_fused(hip, ref32, ref64)
+    _compare_fused(hip, *_matched(dev, layers, pts, occ, ctrl, None, None, "sq"))
 
 
 @pytest.mark.parametrize("name,f,nl,h,w,bwd", [
@@ -601,10 +631,8 @@ def test_baseline_configs_on_hip(dev, name, f, nl, h, w, bwd):
     assert _lib.load().waldo_warp_composite_bwd_workspace_bytes(f, nl, h, w, 19) > 0, name
     layers, pts, occ, _, _ = O.make_synthetic(f, nl, h, w, seed=nl + w)
     ctrl = O.get_grid(4, 4).view(-1, 2)
-    ref32 = _oracle_fused(layers, pts, occ, ctrl, None, None, torch.float32, "sq")
-    ref64 = _oracle_fused(layers, pts, occ, ctrl, None, None, torch.float64, "sq")
     hip = _hip_fused(dev, layers, pts, occ, ctrl, None, None, "sq")
-    _compare_fused(hip, ref32, ref64)
+    _compare_fused(hip, *_matched(dev, layers, pts, occ, ctrl, None, None, "sq"))
 
 
 @pytest.mark.parametrize("nl", [12, 17])

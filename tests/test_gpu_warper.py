@@ -438,9 +438,9 @@ def test_fused_hd_passes_seeded_fuzz(dev):
                 if y is None:
                     assert x is None, name
                     continue
-                close(x, y, what=name, exact=z)
-            close(out_h, out_o, what="out", exact=out64)
-            close(raw_h, raw_o, what="raw", exact=raw64)
+                close(x, y, what=name, exact=z, noise_of="tensor")
+            close(out_h, out_o, what="out", exact=out64, noise_of="tensor")
+            close(raw_h, raw_o, what="raw", exact=raw64, noise_of="tensor")
         except AssertionError as exc:
             raise AssertionError(f"{what}: {exc}") from exc
     assert fused == 30, fused
@@ -728,11 +728,11 @@ def test_fused_hd_backward(dev, over, ctx_only, include_self):
 def test_fused_hd_backward_seeded_fuzz(dev):
     """Ten more recipes from a seeded generator for the backward of the fused passes (1 ... 16 objects, x1 ... x3,
     2 ... 32 classes, 2 ... 4 frames, either context mode, the option sets): every differentiable input's gradient
-    against the oracle's autograd in fp32 and fp64, as ``test_fused_hd_backward`` -- with ``close``'s allowance for a
-    few elements downstream of a kink (an earlier draw of sixteen recipes had two -- one of 6.3 M
-    |dist - prob| terms of the layout filter with a margin of 2.4e-9, which the kernel's softmax rounds to the other side
-    and which moves the 32 class gradients of that object by 1.4e-3 of their scale, and a background-grid gradient 4 %
-    over its bound)."""
+    against the oracle's autograd in fp32 and fp64, as ``test_fused_hd_backward`` -- with ``close``'s allowance for the
+    elements the fp64 oracle finds downstream of a kink (_hd_kinks; DESIGN.md section 2: an earlier draw of sixteen
+    recipes had two -- one of 6.3 M |dist - prob| terms of the layout filter with a margin of 2.4e-9, which the
+    kernel's softmax rounds to the other side and which moves the 32 class gradients of that object by 1.4e-3 of their
+    scale, and a background-grid gradient 4 % over its bound)."""
     import random
     rng = random.Random(11)
     failures = []
@@ -749,7 +749,7 @@ def test_fused_hd_backward_seeded_fuzz(dev):
             (2, 3, rng.choice([2, 6, 20, 21, 32]))
         try:
             _hd_backward_case(dev, opt_ns(include_self=include_self, **over), ctx_only, include_self, b=b, t=t, nl=nl,
-                              seed=200 + case, per_op=False, outliers=0.05)
+                              seed=200 + case, per_op=False, kink_exempt=True)
         except AssertionError as exc:
             failures.append(f"case {case}: {over} include_self={include_self} ctx_only={ctx_only} b={b} t={t} "
                             f"nl={nl}: {exc}")
@@ -772,10 +772,10 @@ def test_fused_hd_backward_at_recipe_size(dev):
     _hd_backward_case(dev, opt, False, True, b=1, t=5, nl=20, seed=23, per_op=False)
 
 
-def _hd_backward_case(dev, opt, ctx_only, include_self, b, t, nl, seed, per_op=True, outliers=0.0):
-    from waldo_amd.nets import Warper
+def _hd_oracle(opt, ctx_only, include_self, b, t, nl, seed):
+    """The seeded inputs of one HD-backward recipe and the oracle's gradients of every differentiable input in fp32
+    (g_o) and fp64 (g_64); `run` evaluates the chain's loss with any implementation."""
     cfg = WO.WarperCfg.from_opt(opt)
-    wp = Warper(opt).to(dev)
     obj_pose, bg_pose, inp, occ, obj_alpha, bg_alpha, cls = _warper_inputs(cfg, b, t, nl, seed=seed)
     if include_self:  # ctx_mode "prev" of synthesizer.py:826-828
         ctx_ts = torch.roll(torch.arange(t), 1).view(1, 1, t).expand(b, -1, -1).contiguous()
@@ -786,7 +786,6 @@ def _hd_backward_case(dev, opt, ctx_only, include_self, b, t, nl, seed, per_op=T
         pred_ts = torch.tensor([2])
     with torch.no_grad():
         grid_o = WO.warper_grids(cfg, obj_pose, bg_pose)
-    names = ("tgo", "sgo", "tgb", "sgb", "obj_alpha", "occ", "cls")
 
     def run(fn_flow, fn_out, to, leaves, dtype=torch.float32):
         g4, oa, oc, cl = leaves[:4], leaves[4], leaves[5], leaves[6]
@@ -805,6 +804,18 @@ def _hd_backward_case(dev, opt, ctx_only, include_self, b, t, nl, seed, per_op=T
     g_o, _ = run(lambda *a: fo(cfg, *a), lambda *a: WO.input_to_output(cfg, *a), "cpu", lo)
     g_64, _ = run(lambda *a: fo(cfg, *dbl(a)), lambda *a: WO.input_to_output(cfg, *dbl(a)), "cpu",
                   [x.clone().double().requires_grad_() for x in base], dtype=torch.float64)
+    return types.SimpleNamespace(cfg=cfg, inp=inp, obj_alpha=obj_alpha, bg_alpha=bg_alpha, cls=cls, ctx_ts=ctx_ts,
+                                 grid_o=grid_o, base=base, run=run, g_o=g_o, g_64=g_64)
+
+
+HD_GRAD_NAMES = ("tgo", "sgo", "tgb", "sgb", "obj_alpha", "occ", "cls")
+
+
+def _hd_backward_case(dev, opt, ctx_only, include_self, b, t, nl, seed, per_op=True, kink_exempt=False):
+    from waldo_amd.nets import Warper
+    wp = Warper(opt).to(dev)
+    o = _hd_oracle(opt, ctx_only, include_self, b, t, nl, seed)
+    cfg, base, run, g_o, g_64, names = o.cfg, o.base, o.run, o.g_o, o.g_64, HD_GRAD_NAMES
     grads = {}
     for fused in ((True, False) if per_op else (True,)):
         wp.fuse_hd = fused
@@ -812,15 +823,48 @@ def _hd_backward_case(dev, opt, ctx_only, include_self, b, t, nl, seed, per_op=T
         fh = wp.grid_to_flow_ctx if ctx_only else wp.grid_to_flow
         grads[fused], _ = run(fh, wp.input_to_output, dev, lh)
     wp.fuse_hd = True
+    exempt = _hd_kinks(cfg, o.grid_o, o.inp, o.obj_alpha, o.bg_alpha, o.cls, o.ctx_ts, ctx_only) if kink_exempt else {}
     for i, name in enumerate(names):
         if g_o[i] is None:
             assert grads[True][i] is None or grads[True][i].abs().max() == 0, name
             continue
-        # 1e-4 of the largest gradient + 4 x the fp32 oracle's distance from its float64 self (gradients
-        # reach the loss through sample POSITIONS: a frame / alpha edge turns fp32 position noise into value noise)
-        close(grads[True][i], g_o[i], rel=True, what=f"fused vs oracle: grad {name}", exact=g_64[i], outliers=outliers)
+        # 1e-4 of the largest gradient (of the object's, for the per-object ones) + 4 x the fp32 oracle's distance
+        # from its float64 self at that element (gradients reach the loss through sample POSITIONS: a frame / alpha
+        # edge turns fp32 position noise into value noise)
+        sd = _HD_SLICES.get(name)
+        close(grads[True][i], g_o[i], rel=True, what=f"fused vs oracle: grad {name}", exact=g_64[i], slice_dims=sd,
+              exempt=exempt.get(name))
         if per_op:
-            close(grads[False][i], g_o[i], rel=True, what=f"per-op vs oracle: grad {name}", exact=g_64[i])
+            close(grads[False][i], g_o[i], rel=True, what=f"per-op vs oracle: grad {name}", exact=g_64[i],
+                  slice_dims=sd)
+
+
+# per-object gradients are judged against their object's own magnitude: (batch, [time,] object) slices
+_HD_SLICES = {"tgo": (0, 1, 2), "sgo": (0, 1, 2), "obj_alpha": (0, 1), "cls": (0, 1)}
+
+
+def _near_texel_boundary(grid, h, w, eps=1e-4):
+    """(..., H, W, 2) normalised sample positions -> (..., H, W, 1): True where either pixel coordinate of the sample
+    in an h x w raster is within eps of an integer (a texel boundary, or the edge of the zero padding), where the
+    derivative of the bilinear interpolant jumps."""
+    g = grid.double()
+    px = torch.stack([((g[..., 0] + 1) * w - 1) / 2, ((g[..., 1] + 1) * h - 1) / 2], dim=-1)
+    return ((px - px.round()).abs() < eps).any(dim=-1, keepdim=True)
+
+
+def _hd_kinks(cfg, grid_o, inp, obj_alpha, bg_alpha, cls, ctx_ts, ctx_only):
+    """The elements of the HD chain's gradients that the fp64 oracle finds downstream of a kink, as exempt= masks of
+    close(): the class and object-alpha gradients of an object whose layout-filter margin |dist - prob| is below
+    1e-6 somewhere, and the sample-position gradients (sgo, sgb) whose sample lies within 1e-4 px of a texel
+    boundary of the raster it samples."""
+    (ho, wo), (h, w) = cfg.tgt_shape, cfg.src_shape
+    out = {"sgo": _near_texel_boundary(grid_o[1], ho, wo), "sgb": _near_texel_boundary(grid_o[3], h, w)}
+    margin = WO.lyt_margin(cfg, *dbl((inp, grid_o, obj_alpha, bg_alpha, cls)), ctx_ts, ctx_only)
+    if margin is not None:
+        obj = margin < 1e-6                                              # B No
+        out["cls"] = obj[:, :, None]
+        out["obj_alpha"] = obj[:, :, None, None, None]
+    return out
 
 
 def _recipe_size_case(dev, ctx_only, recipe="cityscapes"):
@@ -883,9 +927,9 @@ def _recipe_size_case(dev, ctx_only, recipe="cityscapes"):
         # alpha_ctx / disocc sample the composited HD alpha at flow-displaced positions: at 1024 px a
         # position is good to ~1e-5 grid units in fp32 on either side, which a steep alpha edge turns
         # into ~1e-4 of value -- in the fp32 oracle too, which is what `exact` measures
-        close(x, y, what=f"{tag}, fused vs oracle: " + name, exact=z)
-    close(out_f, out_o, what=f"{tag}: output", exact=out64)
-    close(raw_f, raw_o, what=f"{tag}: raw_output", exact=raw64)
+        close(x, y, what=f"{tag}, fused vs oracle: " + name, exact=z, noise_of="tensor")
+    close(out_f, out_o, what=f"{tag}: output", exact=out64, noise_of="tensor")
+    close(raw_f, raw_o, what=f"{tag}: raw_output", exact=raw64, noise_of="tensor")
 
 
 def test_fused_hd_passes_at_recipe_size(dev):
@@ -1029,7 +1073,11 @@ def test_frame_warp_fuse_seeded_fuzz(dev):
             close(out, r32[0], what="out", exact=r64[0])
             close(raw, r32[1], what="raw", exact=r64[1])
             ((out * w_out.to(dev)).sum() + (raw * w_raw.to(dev)).sum()).backward()
-            close(f.grad, r32[2], rel=True, what="grad_flow", exact=r64[2], outliers=0.001)
+            # exempt: the flow of a pixel whose sample lies within 1e-4 px of a texel boundary (the interpolant's
+            # derivative jumps there, and an fp32 evaluation within rounding of it may take the other side)
+            samp = O.get_grid(hd, wd).double() + flow.double().permute(0, 1, 2, 4, 5, 3).reshape(-1, hd, wd, 2)
+            kink = _near_texel_boundary(samp, hd, wd).view(b, tc, tp, hd, wd, 1).permute(0, 1, 2, 5, 3, 4)
+            close(f.grad, r32[2], rel=True, what="grad_flow", exact=r64[2], exempt=kink)
             close(a.grad, r32[3], rel=True, what="grad_alpha", exact=r64[3])
             with torch.no_grad():  # the staged kernel of the no-grad path: the same values
                 out2, raw2 = WF.frame_warp_fuse(inp.to(dev), flow.to(dev), alpha.to(dev), ctx_ts.to(dev),
