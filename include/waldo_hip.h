@@ -486,6 +486,30 @@ int waldo_warp_composite_bwd(const float* layers, const float* basis_t, const fl
                              float* grad_layers, float* grad_mapping, float* grad_occ,
                              void* workspace, int64_t workspace_bytes, int64_t F, int L, int H,
                              int W, int K3, float delta, waldo_stream_t stream);
+/* The three calls above with `layers` (and, in the backward, `grad_layers`) of element type layers_dtype (enum
+ * waldo_dtype): a 16-bit layer stack from a decoder under autocast.  Every other buffer -- basis_t, mapping,
+ * inverse_kernel, src_pts, occ, rgb, alpha, grad_rgb, grad_alpha, grad_mapping, grad_occ, the workspace and its
+ * records -- stays fp32, and so does the arithmetic: each 16-bit texel is widened exactly on load.
+ *   forward:  rgb and alpha have the bits of the fp32 call on the widened stack (layers.float());
+ *   backward: grad_layers has the bits of the fp32 call's grad_layers rounded to nearest-even (NaN stays a NaN, its
+ *             payload is not kept); grad_mapping has the fp32 call's bits; grad_occ (float atomics) is the fp32
+ *             call's up to summation order.
+ * WALDO_DTYPE_F32: exactly the fp32 entry point.  An unknown code: WALDO_EINVAL ("unknown dtype") before any pointer
+ * is read.  A 16-bit code is served by the staged forward and the two-kernel backward only: WALDO_EINVAL with the
+ * reason, before any launch, where waldo_warp_composite_pts_supported(L, H, W, K3 - 3) == 0 (forward) or
+ * waldo_warp_composite_bwd_workspace_bytes(max(F, 1), L, H, W, K3) == 0 (backward; its workspace is then required).
+ * The workspace size query does not change. */
+int waldo_warp_composite_fwd_dt(const void* layers, const float* basis_t, const float* mapping, const float* occ,
+                                float* rgb, float* alpha, int64_t F, int L, int H, int W, int K3, float delta,
+                                int layers_dtype, waldo_stream_t stream);
+int waldo_warp_composite_pts_fwd_dt(const void* layers, const float* basis_t, const float* inverse_kernel,
+                                    const float* src_pts, const float* occ, float* rgb, float* alpha, int64_t F,
+                                    int L, int H, int W, int N, float delta, int layers_dtype, waldo_stream_t stream);
+int waldo_warp_composite_bwd_dt(const void* layers, const float* basis_t, const float* mapping, const float* occ,
+                                const float* grad_rgb, const float* grad_alpha, void* grad_layers,
+                                float* grad_mapping, float* grad_occ, void* workspace, int64_t workspace_bytes,
+                                int64_t F, int L, int H, int W, int K3, float delta, int layers_dtype,
+                                waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * A12. Fusion epilogue of WIF.forward with ii_score (models/nets/wif.py:49-54).

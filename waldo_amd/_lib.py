@@ -90,6 +90,10 @@ SIGNATURES = {
                                      _flt, _stream],
     "waldo_warp_composite_bwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64,
                                  _i64, _int, _int, _int, _int, _flt, _stream],
+    # the same with a 16-bit layer stack (and grad_layers): a WALDO_DTYPE_* code before the stream
+    "waldo_warp_composite_fwd_dt": [_c_f] * 6 + [_i64, _int, _int, _int, _int, _flt, _int, _stream],
+    "waldo_warp_composite_pts_fwd_dt": [_c_f] * 7 + [_i64, _int, _int, _int, _int, _flt, _int, _stream],
+    "waldo_warp_composite_bwd_dt": [_c_f] * 10 + [_i64, _i64, _int, _int, _int, _int, _flt, _int, _stream],
 }
 PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_warp_composite_bwd_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int]),
@@ -231,7 +235,8 @@ def ptr(t):
 
 
 def check_cuda(*tensors, half=False):
-    """GPU tensors of fp32 -- or, with ``half`` (the entry points with a dtype code), of fp32, fp16 or bf16."""
+    """GPU tensors of fp32 -- or, with ``half`` (the buffers an entry point with a dtype code retypes), of fp32, fp16
+    or bf16."""
     for t in tensors:
         if t is None:
             continue

@@ -343,8 +343,6 @@ __device__ __forceinline__ PairTaps pair_taps(float gx, float gy, int Hi, int Wi
   return t;
 }
 
-typedef float f32x2_p __attribute__((ext_vector_type(2)));
-
 // the two loads and the arithmetic apart, so that a kernel can put the loads of MANY samples in flight
 // before it consumes the first (a wavefront that waits for each sample in turn is bound by the memory
 // latency times the number of samples)
@@ -373,48 +371,8 @@ __device__ __forceinline__ float pair_sample(const float* __restrict__ plane, co
   return pair_value(a, b, t, interior);
 }
 
-// ---------------------------------------------------------------------------------------
-// 16-bit storage of the `raw` tensor (the *_dt entry points, WALDO_DTYPE_BF16 / _F16).  The arithmetic stays fp32; a
-// stored value is the fp32 value rounded to nearest-even (v_cvt_pk_bf16_f32 keeps NaN a NaN; v_cvt_pk_f16_f32 rounds
-// by the mode register, nearest-even), i.e. the bits of `fp32_result.to(dtype)`.  One lane owns one pixel; a 2-byte
-// store per lane is the slow store flavour of this part, so where two horizontally adjacent pixels sit in adjacent
-// lanes (x even in the even lane, Wd even: the pair is 4-byte aligned) each lane takes its neighbour's value across
-// the lane pair (DPP, no LDS) and BOTH lanes store the same packed 4-byte word -- unconditional, so no branch cuts
-// the store stream; a 64-lane row segment then writes 128 bytes, a whole line.
-// ---------------------------------------------------------------------------------------
-template <typename T>
-struct Half2;
-template <>
-struct Half2<__bf16> {
-  typedef __bf16 type __attribute__((ext_vector_type(2)));
-};
-template <>
-struct Half2<_Float16> {
-  typedef _Float16 type __attribute__((ext_vector_type(2)));
-};
-
-__device__ __forceinline__ float lane_pair_partner(float v) {  // the value of lane ^ 1 (quad_perm [1, 0, 3, 2])
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
-}
-
-// this lane's pixel (odd: the second of its pair) and its lane neighbour's as one 4-byte store at `pair`, the address
-// of the pair's first pixel; both lanes active
-template <bool NT, typename T>
-__device__ __forceinline__ void store_pair16(T* pair, bool odd, float v) {
-  typedef typename Half2<T>::type h2;
-  const float o = lane_pair_partner(v);
-  const f32x2_p pr = odd ? (f32x2_p){o, v} : (f32x2_p){v, o};
-  h2* q = reinterpret_cast<h2*>(pair);
-  const h2 w = __builtin_convertvector(pr, h2);
-  if (NT) __builtin_nontemporal_store(w, q);
-  else *q = w;
-}
-
-template <bool NT, typename T>
-__device__ __forceinline__ void store_px16(T* at, float v) {
-  if (NT) __builtin_nontemporal_store((T)v, at);
-  else *at = (T)v;
-}
+// 16-bit storage of the `raw` tensor (the *_dt entry points): Half2, store_pair16 and store_px16 live in
+// waldo_common.hip.h, shared with the 16-bit layer stack of the fused warp/composite.
 
 constexpr int kFwMaxCtx = 8;  // contexts (incl. self) of the fused frame warp
 

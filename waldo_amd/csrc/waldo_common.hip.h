@@ -218,16 +218,74 @@ __device__ __forceinline__ float ldb(const float* __restrict__ base, uint32_t by
   return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
+// A texel of a plane of element type T (float, __bf16, _Float16) at the byte offset its fp32 twin has (Taps offsets
+// count 4-byte texels): a 16-bit plane is read at half that offset and widened to fp32 exactly.
+template <typename T>
+__device__ __forceinline__ float ldt(const T* __restrict__ base, uint32_t off4) {
+  if constexpr (std::is_same_v<T, float>) {
+    return ldb(base, off4);
+  } else {
+    return (float)*reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (off4 >> 1));
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// 16-bit storage (the *_dt entry points, WALDO_DTYPE_BF16 / _F16: the `raw` tensor of the WIF path, the layer stack
+// and its gradient of the fused warp/composite).  The arithmetic stays fp32; a stored value is the fp32 value rounded
+// to nearest-even (v_cvt_pk_bf16_f32 keeps NaN a NaN; v_cvt_pk_f16_f32 rounds by the mode register, nearest-even),
+// i.e. the bits of `fp32_result.to(dtype)`.  In the raw path one lane owns one pixel; a 2-byte store per lane is the
+// slow store flavour of this part, so where two horizontally adjacent pixels sit in adjacent lanes (x even in the even
+// lane, Wd even: the pair is 4-byte aligned) each lane takes its neighbour's value across the lane pair (DPP, no LDS)
+// and BOTH lanes store the same packed 4-byte word -- unconditional, so no branch cuts the store stream; a 64-lane row
+// segment then writes 128 bytes, a whole line.
+// ---------------------------------------------------------------------------------------
+typedef float f32x2_p __attribute__((ext_vector_type(2)));
+
+template <typename T>
+struct Half2;
+template <>
+struct Half2<__bf16> {
+  typedef __bf16 type __attribute__((ext_vector_type(2)));
+};
+template <>
+struct Half2<_Float16> {
+  typedef _Float16 type __attribute__((ext_vector_type(2)));
+};
+
+__device__ __forceinline__ float lane_pair_partner(float v) {  // the value of lane ^ 1 (quad_perm [1, 0, 3, 2])
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+}
+
+// this lane's pixel (odd: the second of its pair) and its lane neighbour's as one 4-byte store at `pair`, the address
+// of the pair's first pixel; both lanes active
+template <bool NT, typename T>
+__device__ __forceinline__ void store_pair16(T* pair, bool odd, float v) {
+  typedef typename Half2<T>::type h2;
+  const float o = lane_pair_partner(v);
+  const f32x2_p pr = odd ? (f32x2_p){o, v} : (f32x2_p){v, o};
+  h2* q = reinterpret_cast<h2*>(pair);
+  const h2 w = __builtin_convertvector(pr, h2);
+  if (NT) __builtin_nontemporal_store(w, q);
+  else *q = w;
+}
+
+template <bool NT, typename T>
+__device__ __forceinline__ void store_px16(T* at, float v) {
+  if (NT) __builtin_nontemporal_store((T)v, at);
+  else *at = (T)v;
+}
+
 // Bilinear value in the "lerp" form, top + fy (bot - top) with top = v00 + fx (v01 - v00), on the
 // corner values times their validity: the same number as the four-weight sum of grid_sample up to
 // rounding, in 6 operations per channel instead of 8, and the ONE form every kernel of the fused
 // path uses (the LDS-staged kernels evaluate it on packed channel pairs: bit-identical).
 // delta: grid_sample(x + delta) - delta of Warper.obj_to_output / bg_to_output (lvd.py:548,559) --
 // the shift is applied to the corner values before their validity, exactly as the reference does;
-// with delta == 0 the result has the same bits as without.
-__device__ __forceinline__ float tap_sample(const float* __restrict__ plane, const Taps& t, float delta = 0.0f) {
-  const float p00 = ldb(plane, t.o00) + delta, p01 = ldb(plane, t.o01) + delta;
-  const float p10 = ldb(plane, t.o10) + delta, p11 = ldb(plane, t.o11) + delta;
+// with delta == 0 the result has the same bits as without.  A 16-bit plane (T) is widened exactly on load.
+template <typename T>
+__device__ __forceinline__ float tap_sample(const T* __restrict__ plane, const Taps& t, float delta = 0.0f) {
+  const float p00 = ldt(plane, t.o00) + delta, p01 = ldt(plane, t.o01) + delta;
+  const float p10 = ldt(plane, t.o10) + delta, p11 = ldt(plane, t.o11) + delta;
   const float v00 = p00 * (t.vx0 * t.vy0), v01 = p01 * (t.vx1 * t.vy0);
   const float v10 = p10 * (t.vx0 * t.vy1), v11 = p11 * (t.vx1 * t.vy1);
   const float top = fmaf(t.fx, v01 - v00, v00);
@@ -236,10 +294,11 @@ __device__ __forceinline__ float tap_sample(const float* __restrict__ plane, con
 }
 
 // sample + partial derivatives w.r.t. the UNNORMALISED coordinates (ix, iy)
-__device__ __forceinline__ float tap_sample_d(const float* __restrict__ plane, const Taps& t,
+template <typename T>
+__device__ __forceinline__ float tap_sample_d(const T* __restrict__ plane, const Taps& t,
                                               float& ddx, float& ddy, float delta = 0.0f) {
-  const float p00 = ldb(plane, t.o00) + delta, p01 = ldb(plane, t.o01) + delta;
-  const float p10 = ldb(plane, t.o10) + delta, p11 = ldb(plane, t.o11) + delta;
+  const float p00 = ldt(plane, t.o00) + delta, p01 = ldt(plane, t.o01) + delta;
+  const float p10 = ldt(plane, t.o10) + delta, p11 = ldt(plane, t.o11) + delta;
   float v00 = p00 * (t.vx0 * t.vy0), v01 = p01 * (t.vx1 * t.vy0);
   float v10 = p10 * (t.vx0 * t.vy1), v11 = p11 * (t.vx1 * t.vy1);
   float top = fmaf(t.fx, v01 - v00, v00);

@@ -1,6 +1,6 @@
 // Fused WIF hot path -- C-ABI entry points and dispatch over the compiled (LP, K3P) variants.
-// Kernels: warp_composite_kernels.hip.h; one translation unit per padded layer count
-// (warp_composite_lp*.hip) so that the variants compile in parallel.
+// Kernels: warp_composite_kernels.hip.h; one translation unit per padded layer count and layer element type
+// (warp_composite_lp*.hip, warp_composite_inst.hip.h) so that the variants compile in parallel.
 #include "waldo_common.hip.h"
 
 namespace waldo {
@@ -8,22 +8,15 @@ namespace waldo {
 constexpr int kMaxLayers = 32;
 constexpr int kMaxK3 = 32;
 
-#define WALDO_DECL_LP(LPV)                                                                      \
-  void wc_fwd_lp##LPV(bool k19, const float* layers, const float* basis_t, const float* mapping, \
-                      const float* inv_kernel, const float* src_pts, const float* occ,          \
-                      float* rgb, float* alpha, int F, int L, int H, int W, int K3, float delta, \
-                      hipStream_t st);                                                          \
-  void wc_bwd_lp##LPV(bool k19, const float* layers, const float* basis_t, const float* mapping, \
-                      const float* occ, const float* grad_rgb, const float* grad_alpha,         \
-                      float* grad_layers, float* grad_mapping, float* grad_occ,                 \
-                      void* workspace, int F, int L, int H, int W, int K3, float delta,         \
-                      hipStream_t st);
-WALDO_DECL_LP(4)
-WALDO_DECL_LP(8)
-WALDO_DECL_LP(12)
-WALDO_DECL_LP(17)
-WALDO_DECL_LP(24)
-WALDO_DECL_LP(32)
+// explicit instances in warp_composite_lp<LP>[_bf16 | _f16].hip (16-bit backward: LP <= kBwd2MaxLayers)
+template <int LP, typename T>
+void wc_fwd(bool k19, const T* layers, const float* basis_t, const float* mapping, const float* inv_kernel,
+            const float* src_pts, const float* occ, float* rgb, float* alpha, int F, int L, int H, int W, int K3,
+            float delta, hipStream_t st);
+template <int LP, typename T>
+void wc_bwd(bool k19, const T* layers, const float* basis_t, const float* mapping, const float* occ,
+            const float* grad_rgb, const float* grad_alpha, T* grad_layers, float* grad_mapping, float* grad_occ,
+            void* workspace, int F, int L, int H, int W, int K3, float delta, hipStream_t st);
 
 static int check_common(const char* fn, int64_t F, int L, int H, int W, int K3) {
   if (F < 0 || L < 1 || L > kMaxLayers || H < 1 || W < 1 || K3 < 3 || K3 > kMaxK3) {
@@ -40,19 +33,21 @@ static int check_common(const char* fn, int64_t F, int L, int H, int W, int K3) 
   return WALDO_OK;
 }
 
+// f(T{}) for the element type of a layer stack (enum waldo_dtype)
+template <typename F>
+static int layers_dispatch(const char* fn, int layers_dtype, F&& f) {
+  switch (layers_dtype) {
+    case WALDO_DTYPE_F32: return f(float{});
+    case WALDO_DTYPE_F16: return f(_Float16{});
+    case WALDO_DTYPE_BF16: return f(__bf16{});
+  }
+  set_error("%s: unknown dtype %d for layers (WALDO_DTYPE_F32 / _F16 / _BF16)", fn, layers_dtype);
+  return WALDO_EINVAL;
+}
+
 }  // namespace waldo
 
 using namespace waldo;
-
-#define WALDO_CALL_LP(FN, ...)                    \
-  do {                                            \
-    if (L <= 4) FN##4(__VA_ARGS__);               \
-    else if (L <= 8) FN##8(__VA_ARGS__);          \
-    else if (L <= 12) FN##12(__VA_ARGS__);        \
-    else if (L <= 17) FN##17(__VA_ARGS__);        \
-    else if (L <= 24) FN##24(__VA_ARGS__);        \
-    else FN##32(__VA_ARGS__);                     \
-  } while (0)
 
 extern "C" int waldo_max_layers(void) { return kMaxLayers; }
 
@@ -62,26 +57,133 @@ extern "C" int64_t waldo_warp_composite_bwd_workspace_bytes(int64_t F, int L, in
   return bwd_workspace_bytes(F, L, H, W, K3);
 }
 
+extern "C" int waldo_warp_composite_pts_supported(int L, int H, int W, int N) {
+  return N + 3 == kGmapK3 && L >= 1 && L <= kMaxLayers && H >= 1 && W >= 1 && staged_eligible(H, W) &&
+         (int64_t)H * W * kGmapK3 * 4 < 4294967296ll && !debug_option(WALDO_DEBUG_FWD_PLAIN);
+}
+
+namespace {
+
+// a 16-bit stack is served by the staged forward alone
+template <typename T>
+int check_fwd16(const char* fn, int L, int H, int W, int K3) {
+  if (!std::is_same_v<T, float> && !waldo_warp_composite_pts_supported(L, H, W, K3 - 3)) {
+    set_error("%s: a 16-bit layer stack needs the staged forward (K3 == 19, W %% 4 == 0, H, W >= 2, "
+              "WALDO_DEBUG_FWD_PLAIN off); not served: L=%d H=%d W=%d K3=%d -- pass fp32 layers",
+              fn, L, H, W, K3);
+    return WALDO_EINVAL;
+  }
+  return WALDO_OK;
+}
+
+template <typename T>
+int warp_composite_fwd(const char* fn, const T* layers, const float* basis_t, const float* mapping, const float* occ,
+                       float* rgb, float* alpha, int64_t F, int L, int H, int W, int K3, float delta,
+                       waldo_stream_t stream) {
+  int rc = check_common(fn, F, L, H, W, K3);
+  if (rc) return rc;
+  rc = check_fwd16<T>(fn, L, H, W, K3);
+  if (rc) return rc;
+  if (F == 0) return WALDO_OK;
+  if (!layers || !basis_t || !mapping || !occ || !rgb) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  with_padded_layers(L, [&](auto lp) {
+    wc_fwd<decltype(lp)::value>(K3 == 19, layers, basis_t, mapping, nullptr, nullptr, occ, rgb, alpha, (int)F, L, H,
+                                W, K3, delta, st);
+  });
+  return launch_status(fn);
+}
+
+template <typename T>
+int warp_composite_pts_fwd(const char* fn, const T* layers, const float* basis_t, const float* inverse_kernel,
+                           const float* src_pts, const float* occ, float* rgb, float* alpha, int64_t F, int L, int H,
+                           int W, int N, float delta, waldo_stream_t stream) {
+  int rc = check_common(fn, F, L, H, W, N + 3);
+  if (rc) return rc;
+  if (!waldo_warp_composite_pts_supported(L, H, W, N)) {
+    set_error("%s: shape not served (N=%d H=%d W=%d); use waldo_tps_mapping_fwd + "
+              "waldo_warp_composite_fwd%s", fn, N, H, W, std::is_same_v<T, float> ? "" : " with fp32 layers");
+    return WALDO_EINVAL;
+  }
+  if (F == 0) return WALDO_OK;
+  if (!layers || !basis_t || !inverse_kernel || !src_pts || !occ || !rgb) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int K3 = N + 3;
+  with_padded_layers(L, [&](auto lp) {
+    wc_fwd<decltype(lp)::value>(true, layers, basis_t, nullptr, inverse_kernel, src_pts, occ, rgb, alpha, (int)F, L,
+                                H, W, K3, delta, st);
+  });
+  return launch_status(fn);
+}
+
+template <typename T>
+int warp_composite_bwd(const char* fn, const T* layers, const float* basis_t, const float* mapping, const float* occ,
+                       const float* grad_rgb, const float* grad_alpha, T* grad_layers, float* grad_mapping,
+                       float* grad_occ, void* workspace, int64_t workspace_bytes, int64_t F, int L, int H, int W,
+                       int K3, float delta, waldo_stream_t stream) {
+  constexpr bool kF32 = std::is_same_v<T, float>;
+  int rc = check_common(fn, F, L, H, W, K3);
+  if (rc) return rc;
+  // a 16-bit stack is served by the two-kernel backward alone (whose size query does not depend on F being 0)
+  if (!kF32 && waldo_warp_composite_bwd_workspace_bytes(F > 0 ? F : 1, L, H, W, K3) == 0) {
+    set_error("%s: a 16-bit layer stack needs the two-kernel backward (K3 == 19, L <= %d, W %% 4 == 0, H, W >= 2, "
+              "WALDO_DEBUG_BWD_GENERIC off); not served: L=%d H=%d W=%d K3=%d -- pass fp32 layers",
+              fn, kBwd2MaxLayers, L, H, W, K3);
+    return WALDO_EINVAL;
+  }
+  if (F == 0) return WALDO_OK;
+  if (!layers || !basis_t || !mapping || !occ || !grad_rgb || !grad_layers) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t need = debug_option(WALDO_DEBUG_BWD_GENERIC) ? 0 : bwd_workspace_bytes(F, L, H, W, K3);
+  if (!kF32 && (workspace == nullptr || workspace_bytes < need)) {
+    set_error("%s: workspace of %lld bytes given, %lld needed (a 16-bit layer stack has no generic backward)", fn,
+              (long long)(workspace == nullptr ? 0 : workspace_bytes), (long long)need);
+    return WALDO_EINVAL;
+  }
+  if (workspace != nullptr && (need == 0 || workspace_bytes < need)) {
+    if (need != 0) {
+      set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)workspace_bytes, (long long)need);
+      return WALDO_EINVAL;
+    }
+    workspace = nullptr;  // shape served by the generic kernel, which needs none
+  }
+  with_padded_layers(L, [&](auto lp) {
+    constexpr int LP = decltype(lp)::value;
+    if constexpr (kF32 || LP <= kBwd2MaxLayers)
+      wc_bwd<LP>(K3 == 19, layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers, grad_mapping, grad_occ,
+                 workspace, (int)F, L, H, W, K3, delta, st);
+  });
+  return launch_status(fn);
+}
+
+}  // namespace
+
 extern "C" int waldo_warp_composite_fwd(const float* layers, const float* basis_t,
                                         const float* mapping, const float* occ, float* rgb,
                                         float* alpha, int64_t F, int L, int H, int W, int K3,
                                         float delta, waldo_stream_t stream) {
-  int rc = check_common("waldo_warp_composite_fwd", F, L, H, W, K3);
-  if (rc) return rc;
-  if (F == 0) return WALDO_OK;
-  if (!layers || !basis_t || !mapping || !occ || !rgb) {
-    set_error("waldo_warp_composite_fwd: null pointer");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  WALDO_CALL_LP(wc_fwd_lp, K3 == 19, layers, basis_t, mapping, nullptr, nullptr, occ, rgb, alpha, (int)F,
-                L, H, W, K3, delta, st);
-  return launch_status("waldo_warp_composite_fwd");
+  return warp_composite_fwd("waldo_warp_composite_fwd", layers, basis_t, mapping, occ, rgb, alpha, F, L, H, W, K3,
+                            delta, stream);
 }
 
-extern "C" int waldo_warp_composite_pts_supported(int L, int H, int W, int N) {
-  return N + 3 == kGmapK3 && L >= 1 && L <= kMaxLayers && H >= 1 && W >= 1 && staged_eligible(H, W) &&
-         (int64_t)H * W * kGmapK3 * 4 < 4294967296ll && !debug_option(WALDO_DEBUG_FWD_PLAIN);
+extern "C" int waldo_warp_composite_fwd_dt(const void* layers, const float* basis_t, const float* mapping,
+                                           const float* occ, float* rgb, float* alpha, int64_t F, int L, int H, int W,
+                                           int K3, float delta, int layers_dtype, waldo_stream_t stream) {
+  const char* fn = "waldo_warp_composite_fwd_dt";
+  return layers_dispatch(fn, layers_dtype, [&](auto lt) {
+    using T = decltype(lt);
+    return warp_composite_fwd(fn, static_cast<const T*>(layers), basis_t, mapping, occ, rgb, alpha, F, L, H, W, K3,
+                              delta, stream);
+  });
 }
 
 extern "C" int waldo_warp_composite_pts_fwd(const float* layers, const float* basis_t,
@@ -89,23 +191,20 @@ extern "C" int waldo_warp_composite_pts_fwd(const float* layers, const float* ba
                                             const float* occ, float* rgb, float* alpha, int64_t F,
                                             int L, int H, int W, int N, float delta,
                                             waldo_stream_t stream) {
-  int rc = check_common("waldo_warp_composite_pts_fwd", F, L, H, W, N + 3);
-  if (rc) return rc;
-  if (!waldo_warp_composite_pts_supported(L, H, W, N)) {
-    set_error("waldo_warp_composite_pts_fwd: shape not served (N=%d H=%d W=%d); use waldo_tps_mapping_fwd + "
-              "waldo_warp_composite_fwd", N, H, W);
-    return WALDO_EINVAL;
-  }
-  if (F == 0) return WALDO_OK;
-  if (!layers || !basis_t || !inverse_kernel || !src_pts || !occ || !rgb) {
-    set_error("waldo_warp_composite_pts_fwd: null pointer");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int K3 = N + 3;
-  WALDO_CALL_LP(wc_fwd_lp, true, layers, basis_t, nullptr, inverse_kernel, src_pts, occ, rgb, alpha, (int)F, L,
-                H, W, K3, delta, st);
-  return launch_status("waldo_warp_composite_pts_fwd");
+  return warp_composite_pts_fwd("waldo_warp_composite_pts_fwd", layers, basis_t, inverse_kernel, src_pts, occ, rgb,
+                                alpha, F, L, H, W, N, delta, stream);
+}
+
+extern "C" int waldo_warp_composite_pts_fwd_dt(const void* layers, const float* basis_t, const float* inverse_kernel,
+                                               const float* src_pts, const float* occ, float* rgb, float* alpha,
+                                               int64_t F, int L, int H, int W, int N, float delta, int layers_dtype,
+                                               waldo_stream_t stream) {
+  const char* fn = "waldo_warp_composite_pts_fwd_dt";
+  return layers_dispatch(fn, layers_dtype, [&](auto lt) {
+    using T = decltype(lt);
+    return warp_composite_pts_fwd(fn, static_cast<const T*>(layers), basis_t, inverse_kernel, src_pts, occ, rgb,
+                                  alpha, F, L, H, W, N, delta, stream);
+  });
 }
 
 extern "C" int waldo_warp_composite_bwd(const float* layers, const float* basis_t,
@@ -115,24 +214,21 @@ extern "C" int waldo_warp_composite_bwd(const float* layers, const float* basis_
                                         void* workspace, int64_t workspace_bytes, int64_t F,
                                         int L, int H, int W, int K3, float delta,
                                         waldo_stream_t stream) {
-  int rc = check_common("waldo_warp_composite_bwd", F, L, H, W, K3);
-  if (rc) return rc;
-  if (F == 0) return WALDO_OK;
-  if (!layers || !basis_t || !mapping || !occ || !grad_rgb || !grad_layers) {
-    set_error("waldo_warp_composite_bwd: null pointer");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t need = debug_option(WALDO_DEBUG_BWD_GENERIC) ? 0 : bwd_workspace_bytes(F, L, H, W, K3);
-  if (workspace != nullptr && (need == 0 || workspace_bytes < need)) {
-    if (need != 0) {
-      set_error("waldo_warp_composite_bwd: workspace of %lld bytes given, %lld needed",
-                (long long)workspace_bytes, (long long)need);
-      return WALDO_EINVAL;
-    }
-    workspace = nullptr;  // shape served by the generic kernel, which needs none
-  }
-  WALDO_CALL_LP(wc_bwd_lp, K3 == 19, layers, basis_t, mapping, occ, grad_rgb, grad_alpha,
-                grad_layers, grad_mapping, grad_occ, workspace, (int)F, L, H, W, K3, delta, st);
-  return launch_status("waldo_warp_composite_bwd");
+  return warp_composite_bwd("waldo_warp_composite_bwd", layers, basis_t, mapping, occ, grad_rgb, grad_alpha,
+                            grad_layers, grad_mapping, grad_occ, workspace, workspace_bytes, F, L, H, W, K3, delta,
+                            stream);
+}
+
+extern "C" int waldo_warp_composite_bwd_dt(const void* layers, const float* basis_t, const float* mapping,
+                                           const float* occ, const float* grad_rgb, const float* grad_alpha,
+                                           void* grad_layers, float* grad_mapping, float* grad_occ, void* workspace,
+                                           int64_t workspace_bytes, int64_t F, int L, int H, int W, int K3,
+                                           float delta, int layers_dtype, waldo_stream_t stream) {
+  const char* fn = "waldo_warp_composite_bwd_dt";
+  return layers_dispatch(fn, layers_dtype, [&](auto lt) {
+    using T = decltype(lt);
+    return warp_composite_bwd(fn, static_cast<const T*>(layers), basis_t, mapping, occ, grad_rgb, grad_alpha,
+                              static_cast<T*>(grad_layers), grad_mapping, grad_occ, workspace, workspace_bytes, F, L,
+                              H, W, K3, delta, stream);
+  });
 }

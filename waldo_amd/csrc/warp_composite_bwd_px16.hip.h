@@ -82,9 +82,10 @@ struct Px16Cfg {
   static constexpr int kWavesPerSimd = LP <= 8 ? 3 : 2;
 };
 
-template <int LP, bool EXL, bool GOCC>
+// TL: element type of the layer stack (float, or __bf16 / _Float16: staged as in warp_composite_fwd_lds_kernel)
+template <int LP, bool EXL, bool GOCC, typename TL = float>
 __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) void warp_composite_bwd_px16_kernel(
-    const float* __restrict__ layers, const float* __restrict__ basis_t,
+    const TL* __restrict__ layers, const float* __restrict__ basis_t,
     const float* __restrict__ mapping, const float* __restrict__ occ,
     const float* __restrict__ grad_rgb, const float* __restrict__ grad_alpha,
     float4* __restrict__ rec, int* __restrict__ cellbox,
@@ -297,10 +298,10 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
     constexpr int kAhead = LP < WALDO_K1_STAGE_AHEAD ? LP : WALDO_K1_STAGE_AHEAD;
     int item_l = threadIdx.x;
     asm volatile("" : "+v"(item_l));
-    StageRegs stg[LP];  // fully unrolled: a layer's registers live from its load to its LDS store
+    typename StageOf<TL>::type stg[LP];  // fully unrolled: a layer's registers live from its load to its LDS store
     auto issue = [&](int l) {
       const int lc = EXL ? l : min(l, L - 1);
-      const float* src = layers + ((int64_t)f * L + lc) * 4 * HW;
+      const TL* src = layers + ((int64_t)f * L + lc) * 4 * HW;
       // unconditional loads (items past the box re-read its last item; a box that does not fit
       // reads texel 0): no exec-mask branches, so the loads are issued back to back
       const int bw2 = bw[l] >> 1, n = fits[l] ? bh[l] * bw2 : 1;
@@ -310,11 +311,7 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
       const int item = min(item_l, n - 1);
       const int r = (int)(((float)item + 0.5f) * rcp);
       const int xh = item - __mul24(r, bw2);
-      const unsigned off = (unsigned)(ox + __mul24(r, W) + 2 * xh) * 4u;  // bytes; HW * 4 < 2^32 (launcher)
-      stg[l].c0 = ld8(src, off);
-      stg[l].c1 = ld8(src + HW, off);
-      stg[l].c2 = ld8(src + 2 * HW, off);
-      stg[l].c3 = ld8(src + 3 * HW, off);
+      stage_load(stg[l], src, HW, (unsigned)(ox + __mul24(r, W) + 2 * xh));
     };
 #pragma unroll
     for (int l = 0; l < kAhead; ++l) issue(l);
@@ -336,7 +333,7 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
         if (fits[l]) {
           const int n = bh[l] * (bw[l] >> 1);
           if (item_l < n)  // row-major with pitch bw: item = r * bw2 + xh, texel 2 * item
-            stage_store(img + (l & 1) * kImgBufFloats, item_l, stg[l]);
+            stage_put<TL>(img + (l & 1) * kImgBufFloats, item_l, stg[l]);
         }
         if (l + kAhead < LP) issue(l + kAhead);
         WALDO_PRIO_OFF(WALDO_K1_PRIO_MASK, 1);
@@ -351,7 +348,7 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
         float sv[4], sx[4], sy[4];
         if (!fits[l]) {  // box larger than the LDS image (violent warp): gather straight from memory
           const Taps tg = finish_taps(tc, H, W);
-          const float* base = layers + ((int64_t)f * L + l) * 4 * HW;
+          const TL* base = layers + ((int64_t)f * L + l) * 4 * HW;
 #pragma unroll
           for (int c = 0; c < 4; ++c) sv[c] = tap_sample_d(base + c * HW, tg, sx[c], sy[c], delta);
         } else {

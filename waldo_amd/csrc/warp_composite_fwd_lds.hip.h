@@ -135,6 +135,68 @@ __device__ __forceinline__ f32x2_t ld8(const float* __restrict__ base, uint32_t 
   return *reinterpret_cast<const f32x2_t*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 
+// ---- 16-bit layer stack (T = __bf16 / _Float16, the *_dt entry points): the same items of two texels, ONE 4-byte
+// load per plane, kept as loaded (two registers fewer per layer in flight) and widened exactly into the fp32
+// StageRegs when the item goes to LDS.  The staged image, and every operation after it, is the fp32 path's.
+struct StageRegs16 {
+  uint32_t c0, c1, c2, c3;  // texels (t, t + 1) of the four channel planes
+};
+template <typename T>
+struct StageOf {
+  typedef StageRegs16 type;
+};
+template <>
+struct StageOf<float> {
+  typedef StageRegs type;
+};
+
+template <typename T>
+__device__ __forceinline__ f32x2_t widen2(uint32_t w) {
+  if constexpr (std::is_same_v<T, __bf16>) {
+    return (f32x2_t){__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
+  } else {
+    typename Half2<T>::type h;
+    __builtin_memcpy(&h, &w, 4);
+    return __builtin_convertvector(h, f32x2_t);
+  }
+}
+
+// the item whose first texel is `tex` (row-major index inside the plane; even) of the four planes at src, src + HW, ..
+template <typename T>
+__device__ __forceinline__ void stage_load(typename StageOf<T>::type& r, const T* __restrict__ src, int64_t HW,
+                                           unsigned tex) {
+  if constexpr (std::is_same_v<T, float>) {
+    const unsigned off = tex * 4u;  // bytes; HW * 4 < 2^32 (launcher)
+    r.c0 = ld8(src, off);
+    r.c1 = ld8(src + HW, off);
+    r.c2 = ld8(src + 2 * HW, off);
+    r.c3 = ld8(src + 3 * HW, off);
+  } else {
+    auto ld4 = [](const T* base, unsigned byte_off) {
+      return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + byte_off);
+    };
+    const unsigned off = tex * 2u;
+    r.c0 = ld4(src, off);
+    r.c1 = ld4(src + HW, off);
+    r.c2 = ld4(src + 2 * HW, off);
+    r.c3 = ld4(src + 3 * HW, off);
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void stage_put(float* imgbuf, int item, const typename StageOf<T>::type& r) {
+  if constexpr (std::is_same_v<T, float>) {
+    stage_store(imgbuf, item, r);
+  } else {
+    StageRegs w;
+    w.c0 = widen2<T>(r.c0);
+    w.c1 = widen2<T>(r.c1);
+    w.c2 = widen2<T>(r.c2);
+    w.c3 = widen2<T>(r.c3);
+    stage_store(imgbuf, item, w);
+  }
+}
+
 // the four taps at texel index idx (row-major, pitch bw) of a layer image, as channel pairs
 struct PairBlock {
   f32x2_t p00[2], p01[2], p10[2], p11[2];  // [pair]: channels (0, 1) and (2, 3)
@@ -199,9 +261,10 @@ __device__ __forceinline__ f32x2_t lerp2(const f32x2_t p00, const f32x2_t p01, c
 // NW: wavefronts per workgroup.  4: a 16 x 16 tile (wave w = rows 4w .. 4w+3).  8: a 16 x 32 tile, waves 4 .. 7 on its
 // right half -- the footprint box of the wider tile has less halo per pixel (round 4's experiment: DESIGN.md
 // section 4); the staged image holds 128 NW texels, one two-texel item per lane as before.
-template <int LP, bool EXL, bool FOLD, int NW = 4>
+// TL: element type of the layer stack (float, or __bf16 / _Float16: widened exactly on load, StageRegs16).
+template <int LP, bool EXL, bool FOLD, int NW = 4, typename TL = float>
 __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FWD8_WAVES : (LP <= 12 ? (EXL ? WALDO_FWD12_WAVES : 3) : 2))) void warp_composite_fwd_lds_kernel(
-    const float* __restrict__ layers, const float* __restrict__ basis_t,
+    const TL* __restrict__ layers, const float* __restrict__ basis_t,
     const float* __restrict__ mapping, const float* __restrict__ inv_kernel,
     const float* __restrict__ src_pts, const float* __restrict__ occ, float* __restrict__ rgb,
     float* __restrict__ alpha_out, int F, int Lrt, int H, int W, int frames_per_block, int ntx,
@@ -434,10 +497,10 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
     int item_l = threadIdx.x;
     asm volatile("" : "+v"(item_l));
     float s[LP][4];
-    StageRegs stg[LP];  // fully unrolled: a layer's registers live from its load to its LDS store
+    typename StageOf<TL>::type stg[LP];  // fully unrolled: a layer's registers live from its load to its LDS store
     auto issue = [&](int l) {
       const int lc = EXL ? l : min(l, L - 1);
-      const float* src = layers + ((int64_t)f * L + lc) * 4 * HW;
+      const TL* src = layers + ((int64_t)f * L + lc) * 4 * HW;
       // unconditional loads (items past the box re-read its last item; a box that does not fit
       // reads texel 0): no exec-mask branches, so the loads are issued back to back
       const bool fits = bh[l] * bw[l] <= kCap;
@@ -448,11 +511,7 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
       const int item = min(item_l, n - 1);
       const int r = (int)(((float)item + 0.5f) * rcp);
       const int xh = item - __mul24(r, bw2);
-      const unsigned off = (unsigned)(ox + __mul24(r, W) + 2 * xh) * 4u;  // bytes; HW * 4 < 2^32 (launcher)
-      stg[l].c0 = ld8(src, off);
-      stg[l].c1 = ld8(src + HW, off);
-      stg[l].c2 = ld8(src + 2 * HW, off);
-      stg[l].c3 = ld8(src + 3 * HW, off);
+      stage_load(stg[l], src, HW, (unsigned)(ox + __mul24(r, W) + 2 * xh));
     };
     WALDO_PRIO_ON(WALDO_FWD_PRIO_MASK, 2);
 #pragma unroll
@@ -471,7 +530,7 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
         if (fits) {
           const int n = bh[l] * (bw[l] >> 1);
           if (item_l < n)  // row-major with pitch bw: item = r * bw2 + xh, texel 2 * item
-            stage_store(img + (l & 1) * kBuf, item_l, stg[l]);
+            stage_put<TL>(img + (l & 1) * kBuf, item_l, stg[l]);
         }
         if (l + kAhead < LP) issue(l + kAhead);
         WALDO_PRIO_OFF(WALDO_FWD_PRIO_MASK, 1);
@@ -504,7 +563,7 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
           s[l][3] = sv[1][1];
         } else {  // box larger than the LDS image (violent warp): gather straight from memory
           const Taps t = make_taps_px(gx[l], gy[l], H, W);
-          const float* base = layers + ((int64_t)f * L + l) * 4 * HW;
+          const TL* base = layers + ((int64_t)f * L + l) * 4 * HW;
 #pragma unroll
           for (int c = 0; c < 4; ++c) s[l][c] = tap_sample(base + c * HW, t, delta);
         }

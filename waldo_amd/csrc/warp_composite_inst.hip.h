@@ -1,43 +1,43 @@
-// Instantiation of the fused warp/composite kernels for padded layer count WALDO_LP.
+// Host wrappers of the fused warp/composite kernels for one padded layer count LP and layer element type T (float,
+// __bf16, _Float16).  Each compile unit warp_composite_lp<LP>[_bf16 | _f16].hip holds the explicit instances of one
+// (LP, T), so that the variants compile in parallel.  A 16-bit stack is served by the staged forward and the
+// two-kernel backward only (instances for LP <= kBwd2MaxLayers); the C-ABI entry points check its shape first.
+#pragma once
 #include "warp_composite_kernels.hip.h"
-
-#define WALDO_CAT_(a, b) a##b
-#define WALDO_CAT(a, b) WALDO_CAT_(a, b)
 
 namespace waldo {
 
-void WALDO_CAT(wc_fwd_lp, WALDO_LP)(bool k19, const float* layers, const float* basis_t,
-                                    const float* mapping, const float* inv_kernel,
-                                    const float* src_pts, const float* occ, float* rgb,
-                                    float* alpha, int F, int L, int H, int W, int K3, float delta,
-                                    hipStream_t st) {
+template <int LP, typename T>
+void wc_fwd(bool k19, const T* layers, const float* basis_t, const float* mapping, const float* inv_kernel,
+            const float* src_pts, const float* occ, float* rgb, float* alpha, int F, int L, int H, int W, int K3,
+            float delta, hipStream_t st) {
   if (k19)
-    launch_fwd<WALDO_LP, 19, true>(layers, basis_t, mapping, inv_kernel, src_pts, occ, rgb, alpha, F, L, H, W,
-                                   K3, delta, st);
-  else
-    launch_fwd<WALDO_LP, 32, false>(layers, basis_t, mapping, nullptr, nullptr, occ, rgb, alpha, F, L, H, W,
-                                    K3, delta, st);
+    launch_fwd<LP, 19, true>(layers, basis_t, mapping, inv_kernel, src_pts, occ, rgb, alpha, F, L, H, W, K3, delta,
+                             st);
+  else if constexpr (std::is_same_v<T, float>)
+    launch_fwd<LP, 32, false>(layers, basis_t, mapping, nullptr, nullptr, occ, rgb, alpha, F, L, H, W, K3, delta, st);
 }
 
 // `workspace` != nullptr selects the two-kernel backward (compiled for L <= kBwd2MaxLayers, K3 == 19)
-void WALDO_CAT(wc_bwd_lp, WALDO_LP)(bool k19, const float* layers, const float* basis_t,
-                                    const float* mapping, const float* occ, const float* grad_rgb,
-                                    const float* grad_alpha, float* grad_layers,
-                                    float* grad_mapping, float* grad_occ, void* workspace, int F,
-                                    int L, int H, int W, int K3, float delta, hipStream_t st) {
-#if WALDO_LP <= 17
-  if (k19 && workspace != nullptr) {
-    launch_bwd2<WALDO_LP>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, workspace,
-                          grad_layers, grad_mapping, grad_occ, F, L, H, W, delta, st);
-    return;
+template <int LP, typename T>
+void wc_bwd(bool k19, const T* layers, const float* basis_t, const float* mapping, const float* occ,
+            const float* grad_rgb, const float* grad_alpha, T* grad_layers, float* grad_mapping, float* grad_occ,
+            void* workspace, int F, int L, int H, int W, int K3, float delta, hipStream_t st) {
+  if constexpr (LP <= kBwd2MaxLayers) {
+    if (k19 && workspace != nullptr) {
+      launch_bwd2<LP>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, workspace, grad_layers, grad_mapping,
+                      grad_occ, F, L, H, W, delta, st);
+      return;
+    }
   }
-#endif
-  if (k19)
-    launch_bwd<WALDO_LP, 19>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers,
-                             grad_mapping, grad_occ, F, L, H, W, K3, delta, st);
-  else
-    launch_bwd<WALDO_LP, 32>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers,
-                             grad_mapping, grad_occ, F, L, H, W, K3, delta, st);
+  if constexpr (std::is_same_v<T, float>) {
+    if (k19)
+      launch_bwd<LP, 19>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers, grad_mapping, grad_occ, F,
+                         L, H, W, K3, delta, st);
+    else
+      launch_bwd<LP, 32>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers, grad_mapping, grad_occ, F,
+                         L, H, W, K3, delta, st);
+  }
 }
 
 }  // namespace waldo

@@ -360,9 +360,10 @@ static __global__ __launch_bounds__(kBlock) void warp_composite_gmap_reduce_kern
   }
 }
 
-// K2 (compiled once, warp_composite_splat.hip)
+// K2 (compiled once per gradient type T -- float, __bf16, _Float16 -- in warp_composite_splat.hip)
+template <typename T>
 void launch_splat(const float* rec, const float* grad_rgb, const int* cellbox,
-                  const unsigned* cellbound, float* grad_layers, int F, int L, int H, int W,
+                  const unsigned* cellbound, T* grad_layers, int F, int L, int H, int W,
                   hipStream_t st);
 
 }  // namespace waldo
@@ -403,11 +404,14 @@ static inline TileGeom tile_geom(int H, int W, int rows) {
 #ifndef WALDO_FWD_NW
 #define WALDO_FWD_NW 4
 #endif
-template <int LP, int K3P, bool EXK>
-static void launch_fwd(const float* layers, const float* basis_t, const float* mapping,
+// T: element type of the layer stack.  A 16-bit stack is served by the staged kernel alone (the C-ABI entry point
+// has checked that the shape is one it serves: waldo_warp_composite_pts_supported).
+template <int LP, int K3P, bool EXK, typename T>
+static void launch_fwd(const T* layers, const float* basis_t, const float* mapping,
                        const float* inv_kernel, const float* src_pts,
                        const float* occ, float* rgb, float* alpha, int F, int L, int H, int W,
                        int K3, float delta, hipStream_t st) {
+  constexpr bool kF32 = std::is_same_v<T, float>;
   const TileGeom g = tile_geom(H, W, 4);
   const int fpb = chunk_frames(F, g.ntiles);
   const int nchunks = (F + fpb - 1) / fpb;
@@ -417,7 +421,7 @@ static void launch_fwd(const float* layers, const float* basis_t, const float* m
   dim3 grid((unsigned)xcd_grid_banded(nchunks, nbands, g.ntiles, 1));
   if constexpr (EXK) {
     // LDS-staged sampling needs 16-byte-aligned rows and a 2x2 block inside the layer
-    if (!debug_option(WALDO_DEBUG_FWD_PLAIN) && staged_eligible(H, W)) {
+    if (!kF32 || (!debug_option(WALDO_DEBUG_FWD_PLAIN) && staged_eligible(H, W))) {
       // WALDO_FWD_NW: wavefronts per workgroup of the staged forward, 4 (16 x 16 tiles) or 8 (16 x 32; up to 12 layers)
       constexpr int NW = (WALDO_FWD_NW == 8 && LP <= 12) ? 8 : 4;
       constexpr int TW = kLdsTile * NW / 4;
@@ -425,28 +429,30 @@ static void launch_fwd(const float* layers, const float* basis_t, const float* m
       dim3 grid16((unsigned)xcd_grid_banded(nchunks, nbands, nt16, 1));
       auto go = [&](auto exl, auto fold) {
         constexpr bool EXL = decltype(exl)::value, FOLD = decltype(fold)::value;
-        hipLaunchKernelGGL((warp_composite_fwd_lds_kernel<LP, EXL, FOLD, NW>), grid16, dim3(NW * kWave), 0, st, layers,
+        hipLaunchKernelGGL((warp_composite_fwd_lds_kernel<LP, EXL, FOLD, NW, T>), grid16, dim3(NW * kWave), 0, st, layers,
                            basis_t, mapping, inv_kernel, src_pts, occ, rgb, alpha, F, L, H, W, fpb, ntx16, nt16,
                            nchunks, nbands, delta);
       };
-      using T = std::true_type;
+      using Y = std::true_type;
       using N = std::false_type;
       if (src_pts != nullptr) {
-        if (L == LP) go(T{}, T{}); else go(N{}, T{});
+        if (L == LP) go(Y{}, Y{}); else go(N{}, Y{});
       } else {
-        if (L == LP) go(T{}, N{}); else go(N{}, N{});
+        if (L == LP) go(Y{}, N{}); else go(N{}, N{});
       }
       return;
     }
   }
-  if (L == LP)
-    hipLaunchKernelGGL((warp_composite_fwd_kernel<LP, K3P, true, EXK>), grid, dim3(kBlock), 0, st,
-                       layers, basis_t, mapping, occ, rgb, alpha, F, L, H, W, K3, fpb, g.ntx, g.ntiles,
-                       nchunks, nbands, delta);
-  else
-    hipLaunchKernelGGL((warp_composite_fwd_kernel<LP, K3P, false, EXK>), grid, dim3(kBlock), 0, st,
-                       layers, basis_t, mapping, occ, rgb, alpha, F, L, H, W, K3, fpb, g.ntx, g.ntiles,
-                       nchunks, nbands, delta);
+  if constexpr (kF32) {
+    if (L == LP)
+      hipLaunchKernelGGL((warp_composite_fwd_kernel<LP, K3P, true, EXK>), grid, dim3(kBlock), 0, st,
+                         layers, basis_t, mapping, occ, rgb, alpha, F, L, H, W, K3, fpb, g.ntx, g.ntiles,
+                         nchunks, nbands, delta);
+    else
+      hipLaunchKernelGGL((warp_composite_fwd_kernel<LP, K3P, false, EXK>), grid, dim3(kBlock), 0, st,
+                         layers, basis_t, mapping, occ, rgb, alpha, F, L, H, W, K3, fpb, g.ntx, g.ntiles,
+                         nchunks, nbands, delta);
+  }
 }
 
 template <int LP, int K3P>
@@ -470,10 +476,11 @@ static void launch_bwd(const float* layers, const float* basis_t, const float* m
 // the records cost, and with K2 of pass c on a side stream beside K1 of pass c + 1 the two kernels
 // only slow each other down; a timing-only build whose records never leave the cache bounds the
 // prize at 9 % of the backward.  DESIGN.md section 4.)
-template <int LP>
-static void launch_bwd2(const float* layers, const float* basis_t, const float* mapping,
+// T: element type of the layer stack and of grad_layers (K2 rounds the fp32 sums to it)
+template <int LP, typename T>
+static void launch_bwd2(const T* layers, const float* basis_t, const float* mapping,
                         const float* occ, const float* grad_rgb, const float* grad_alpha,
-                        void* workspace, float* grad_layers, float* grad_mapping, float* grad_occ,
+                        void* workspace, T* grad_layers, float* grad_mapping, float* grad_occ,
                         int F, int L, int H, int W, float delta, hipStream_t st) {
   const Bwd2Layout lo = bwd2_layout(F, L, H, W);
   char* ws = reinterpret_cast<char*>(workspace);
@@ -483,7 +490,7 @@ static void launch_bwd2(const float* layers, const float* basis_t, const float* 
   float* part = grad_mapping == nullptr
                     ? nullptr
                     : reinterpret_cast<float*>(ws + lo.box_bytes + lo.bound_bytes + lo.rec_bytes);
-  using T = std::true_type;
+  using Y = std::true_type;
   using N = std::false_type;
   const int ntiles = lo.ntiles16;
   const int fpb = chunk_frames(F, ntiles);
@@ -493,22 +500,22 @@ static void launch_bwd2(const float* layers, const float* basis_t, const float* 
   dim3 grid((unsigned)xcd_grid_banded(nchunks, nbands, ntiles, 1));
   auto go = [&](auto exl, auto gocc) {
     constexpr bool EXL = decltype(exl)::value, GOCC = decltype(gocc)::value;
-    hipLaunchKernelGGL((warp_composite_bwd_px16_kernel<LP, EXL, GOCC>), grid, dim3(kBlock), 0, st, layers,
+    hipLaunchKernelGGL((warp_composite_bwd_px16_kernel<LP, EXL, GOCC, T>), grid, dim3(kBlock), 0, st, layers,
                        basis_t, mapping, occ, grad_rgb, grad_alpha, rec, boxes, bounds, part,
                        grad_occ, F, L, H, W, fpb, lo.ntx16, ntiles, nchunks, nbands, lo.ncx, lo.ncells,
                        delta);
   };
   if (L == LP) {
-    if (grad_occ != nullptr) go(T{}, T{}); else go(T{}, N{});
+    if (grad_occ != nullptr) go(Y{}, Y{}); else go(Y{}, N{});
   } else {
-    if (grad_occ != nullptr) go(N{}, T{}); else go(N{}, N{});
+    if (grad_occ != nullptr) go(N{}, Y{}); else go(N{}, N{});
   }
   if (part != nullptr) {
     const int groups = (int)((gmap_partial_floats(L) + kRedOut - 1) / kRedOut);
     hipLaunchKernelGGL(warp_composite_gmap_reduce_kernel, dim3((unsigned)((int64_t)F * groups)), dim3(kBlock),
                        0, st, part, grad_mapping, F, L, ntiles, groups);
   }
-  launch_splat(reinterpret_cast<const float*>(rec), grad_rgb, boxes, bounds, grad_layers, F, L, H, W, st);
+  launch_splat<T>(reinterpret_cast<const float*>(rec), grad_rgb, boxes, bounds, grad_layers, F, L, H, W, st);
 }
 
 }  // namespace waldo

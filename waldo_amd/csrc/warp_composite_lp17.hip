@@ -1,2 +1,7 @@
-#define WALDO_LP 17
+// The fused warp/composite for padded layer count 17, fp32 layer stack (warp_composite_inst.hip.h)
 #include "warp_composite_inst.hip.h"
+
+namespace waldo {
+template decltype(wc_fwd<17, float>) wc_fwd<17, float>;
+template decltype(wc_bwd<17, float>) wc_bwd<17, float>;
+}  // namespace waldo

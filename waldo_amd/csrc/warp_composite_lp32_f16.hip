@@ -1,0 +1,6 @@
+// The fused warp/composite for padded layer count 32, f16 layer stack (warp_composite_inst.hip.h)
+#include "warp_composite_inst.hip.h"
+
+namespace waldo {
+template decltype(wc_fwd<32, _Float16>) wc_fwd<32, _Float16>;
+}  // namespace waldo

@@ -167,10 +167,12 @@ __device__ __forceinline__ bool touches(const TapCore& t, int sx0, int sy0) {
   return lx0 >= -1 && lx0 < kSrcCols && ly0 >= -1 && ly0 < kSrcRows;
 }
 
+// T: element type of grad_layers (float, or __bf16 / _Float16: the decoded fp32 value rounded to nearest-even)
+template <typename T>
 __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
     const float4* __restrict__ rec, const float* __restrict__ grad_rgb,
     const int* __restrict__ cellbox, const unsigned* __restrict__ cellbound,
-    float* __restrict__ grad_layers, int F, int L, int H, int W, int nsx, int nstiles, int nbands,
+    T* __restrict__ grad_layers, int F, int L, int H, int W, int nsx, int nstiles, int nbands,
     int ncx, int ncells) {
   const int64_t HW = (int64_t)H * W;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
@@ -422,9 +424,9 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
   }
   __syncthreads();
   // ---- S is ours alone: plain row-coalesced stores (zeros included)
-  float* gbase = grad_layers + fl * 4 * HW;
+  T* gbase = grad_layers + fl * 4 * HW;
   if (poison) {  // block-uniform
-    const float qnan = __builtin_nanf("");
+    const T qnan = (T)__builtin_nanf("");
     for (int e = threadIdx.x; e < kSrcTex; e += kG2Threads) {
       const int y = sy0 + (e >> kColShift), x = sx0 + (e & (kSrcCols - 1));
       if (y < H && x < W) {
@@ -434,7 +436,44 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
     }
     return;
   }
-  if ((W & 3) == 0) {  // 16 bytes per lane: four texels of a row (rows are 16-byte aligned)
+  if constexpr (!std::is_same_v<T, float>) {
+    if ((W & 3) == 0) {
+      // 16-bit planes: NX texels of a row per lane, rounded in pairs (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32) and
+      // written with ONE store -- 16 bytes where W % 8 == 0 (half-line stores cost the 16-bit raw path time, DESIGN
+      // section 4e), else 8.  The NX texels lie in one sub-block; the decode is the fp32 branch's below.
+      auto store_rows = [&](auto nx_tag) {
+        constexpr int NX = decltype(nx_tag)::value, kPer = kSrcCols / NX;
+        typedef float f32xn __attribute__((ext_vector_type(NX)));
+        typedef T txn __attribute__((ext_vector_type(NX)));
+        for (int e = threadIdx.x; e < kSrcTex / NX; e += kG2Threads) {
+          const int y = sy0 + e / kPer, x = sx0 + NX * (e % kPer);
+          if (y < H && x < W) {
+            const unsigned doff = (unsigned)(__mul24(y, W) + x);
+            const int li = (e / kPer) * kPitch + NX * (e % kPer);
+            const f32x2_k2 sc = sbscale[((y - sy0) >> 3) * kSubX + ((x - sx0) >> 4)];
+            const float inv_rgb = __uint_as_float(0x7f000000u - __float_as_uint(sc[0]));
+            const float inv_a = __uint_as_float(0x7f000000u - __float_as_uint(sc[1]));
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const long long* w64 = reinterpret_cast<const long long*>(img) + (c >> 1) * kPlane + li;
+              const float inv = c < 3 ? inv_rgb : inv_a;
+              f32xn v;
+#pragma unroll
+              for (int i = 0; i < NX; ++i) {
+                const long long wd = w64[i];
+                const int lo = (int)(unsigned)(unsigned long long)wd, hi = (int)(wd >> 32);
+                v[i] = (float)((c & 1) ? hi - (lo >> 31) : lo) * inv;
+              }
+              *reinterpret_cast<txn*>(gbase + c * HW + doff) = __builtin_convertvector(v, txn);
+            }
+          }
+        }
+      };
+      if ((W & 7) == 0) store_rows(std::integral_constant<int, 8>{});
+      else store_rows(std::integral_constant<int, 4>{});
+      return;
+    }
+  } else if ((W & 3) == 0) {  // 16 bytes per lane: four texels of a row (rows are 16-byte aligned)
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     typedef int i32x4 __attribute__((ext_vector_type(4)));
     for (int e = threadIdx.x; e < kSrcTex / 4; e += kG2Threads) {
@@ -470,23 +509,31 @@ __global__ __launch_bounds__(kG2Threads, 2) void warp_composite_splat_kernel(
       for (int c = 0; c < 4; ++c) {
         const int lo = img[2 * ((c >> 1) * kPlane + li)], hi = img[2 * ((c >> 1) * kPlane + li) + 1];
         const int v = (c & 1) ? hi - (lo >> 31) : lo;
-        (gbase + c * HW)[doff] = (float)v * __uint_as_float(0x7f000000u - __float_as_uint(sc[c < 3 ? 0 : 1]));
+        (gbase + c * HW)[doff] = (T)((float)v * __uint_as_float(0x7f000000u - __float_as_uint(sc[c < 3 ? 0 : 1])));
       }
     }
   }
 }
 
+template <typename T>
 void launch_splat(const float* rec, const float* grad_rgb, const int* cellbox,
-                  const unsigned* cellbound, float* grad_layers, int F, int L, int H, int W,
+                  const unsigned* cellbound, T* grad_layers, int F, int L, int H, int W,
                   hipStream_t st) {
   const int nsx = (W + kSrcCols - 1) / kSrcCols, nsy = (H + kSrcRows - 1) / kSrcRows;
   const int ncx = (W + kCellCols - 1) / kCellCols, ncy = (H + kCellRows - 1) / kCellRows;
   const int nbands = xcd_bands(F);
   dim3 grid((unsigned)xcd_grid_banded(F, nbands, nsx * nsy, L));
-  hipLaunchKernelGGL(warp_composite_splat_kernel, grid, dim3(kG2Threads), 0, st,
+  hipLaunchKernelGGL(warp_composite_splat_kernel<T>, grid, dim3(kG2Threads), 0, st,
                      reinterpret_cast<const float4*>(rec),
                      grad_rgb, cellbox, cellbound, grad_layers, F, L, H, W, nsx, nsx * nsy, nbands, ncx,
                      ncx * ncy);
 }
+
+template void launch_splat<float>(const float*, const float*, const int*, const unsigned*, float*, int, int, int, int,
+                                  hipStream_t);
+template void launch_splat<__bf16>(const float*, const float*, const int*, const unsigned*, __bf16*, int, int, int,
+                                   int, hipStream_t);
+template void launch_splat<_Float16>(const float*, const float*, const int*, const unsigned*, _Float16*, int, int, int,
+                                     int, hipStream_t);
 
 }  // namespace waldo

@@ -1492,7 +1492,8 @@ def mask_expand(mask, num=1, dir=None, soft=False, alpha=0.97):
 class _WarpComposite(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layers, mapping, occ, basis_t, want_alpha, delta):
-        _lib.check_cuda(layers, mapping, occ, basis_t)
+        _lib.check_cuda(layers, half=True)  # (a 16-bit stack: warp_composite() sends only served shapes here)
+        _lib.check_cuda(mapping, occ, basis_t)
         layers, mapping, occ, basis_t = _c(layers), _c(mapping), _c(occ), _c(basis_t)
         f, nl, c, h, w = layers.shape
         if c != 4:
@@ -1503,12 +1504,12 @@ class _WarpComposite(torch.autograd.Function):
             raise _lib.WaldoHipError(
                 f"warp_composite: inconsistent shapes layers={tuple(layers.shape)} "
                 f"mapping={tuple(mapping.shape)} occ={tuple(occ.shape)} basis_t={tuple(basis_t.shape)}")
-        rgb = layers.new_empty(f, 3, h, w)
-        alpha = layers.new_empty(f, nl, h, w) if want_alpha else None
+        rgb = layers.new_empty(f, 3, h, w, dtype=torch.float32)
+        alpha = layers.new_empty(f, nl, h, w, dtype=torch.float32) if want_alpha else None
         with _lib.on_device(layers.device):
-            _lib.call("waldo_warp_composite_fwd", _lib.ptr(layers), _lib.ptr(basis_t),
-                      _lib.ptr(mapping), _lib.ptr(occ), _lib.ptr(rgb), _lib.ptr(alpha), f, nl, h,
-                      w, k3, float(delta), _lib.current_stream(layers.device))
+            _call_dt("waldo_warp_composite_fwd", (layers.dtype,), _lib.ptr(layers), _lib.ptr(basis_t),
+                     _lib.ptr(mapping), _lib.ptr(occ), _lib.ptr(rgb), _lib.ptr(alpha), f, nl, h,
+                     w, k3, float(delta), _lib.current_stream(layers.device))
         ctx.save_for_backward(layers, mapping, occ, basis_t)
         ctx.want_alpha = want_alpha
         ctx.delta = float(delta)
@@ -1527,13 +1528,14 @@ class _WarpComposite(torch.autograd.Function):
         ws_bytes = _lib.load().waldo_warp_composite_bwd_workspace_bytes(f, nl, h, w, k3)
         ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=layers.device) if ws_bytes else None
         # with a workspace the two-kernel path writes every texel of grad_layers exactly once;
-        # the generic kernel accumulates with atomics into a zero-filled buffer
+        # the generic kernel accumulates with atomics into a zero-filled buffer.  (A 16-bit stack: grad_layers in
+        # its type, from the two-kernel path only.)
         gl = torch.empty_like(layers) if ws_bytes else torch.zeros_like(layers)
         with _lib.on_device(layers.device):
-            _lib.call("waldo_warp_composite_bwd", _lib.ptr(layers), _lib.ptr(basis_t),
-                      _lib.ptr(mapping), _lib.ptr(occ), _lib.ptr(grad_rgb), _lib.ptr(grad_alpha),
-                      _lib.ptr(gl), _lib.ptr(gm), _lib.ptr(go), _lib.ptr(ws), ws_bytes, f, nl, h,
-                      w, k3, ctx.delta, _lib.current_stream(layers.device))
+            _call_dt("waldo_warp_composite_bwd", (layers.dtype,), _lib.ptr(layers), _lib.ptr(basis_t),
+                     _lib.ptr(mapping), _lib.ptr(occ), _lib.ptr(grad_rgb), _lib.ptr(grad_alpha),
+                     _lib.ptr(gl), _lib.ptr(gm), _lib.ptr(go), _lib.ptr(ws), ws_bytes, f, nl, h,
+                     w, k3, ctx.delta, _lib.current_stream(layers.device))
         return gl, gm, go, None, None, None
 
 
@@ -1549,10 +1551,18 @@ def warp_composite(layers, src_pts, occ, inverse_kernel, basis_t, return_alpha=F
     0 (default) is the BASELINE pipeline of SURVEY 8d: taps outside a layer contribute 0 (alpha 0.5 /
     grey after ``reduce_comp``'s ``(x + 1) / 2``); 1 is ``Warper.layer_to_output``'s default:
     out-of-range taps read -1, i.e. alpha 0 / black.  Precision / NaN contract of the backward:
-    include/waldo_hip.h."""
+    include/waldo_hip.h.
+
+    ``layers`` may be fp16 or bf16 (a decoder under autocast); every other operand stays fp32.  The kernels widen
+    each texel exactly: rgb and alpha (fp32) have the bits of the call on ``layers.float()``, and the gradient of
+    ``layers`` comes back in its type, the fp32 gradient rounded to nearest-even.  Shapes the 16-bit kernels do not
+    serve (``_layers16_served``) run the fp32 path on ``layers.float()`` inside the autograd graph, which keeps the
+    same contract."""
     f, nl = layers.shape[:2]
     needs_grad = torch.is_grad_enabled() and any(
         torch.is_tensor(t) and t.requires_grad for t in (layers, src_pts, occ, inverse_kernel, basis_t))
+    if layers.dtype in (torch.float16, torch.bfloat16) and not _layers16_served(layers, src_pts, needs_grad):
+        return warp_composite(layers.float(), src_pts, occ, inverse_kernel, basis_t, return_alpha, delta)
     # the one-launch forward pays for its launch saving with a mapping computation per (tile, frame):
     # worth it while the call is launch-bound (C2: 25 -> 19 us), 4 % slower at C4 size
     small = f * ((layers.shape[-2] + 15) // 16) * ((layers.shape[-1] + 15) // 16) <= FOLD_MAX_TILE_FRAMES
@@ -1573,11 +1583,25 @@ def warp_composite(layers, src_pts, occ, inverse_kernel, basis_t, return_alpha=F
     return (rgb, alpha) if return_alpha else rgb
 
 
+def _layers16_served(layers, src_pts, needs_grad):
+    """A 16-bit layer stack runs on its own kernels: the staged forward (waldo_warp_composite_pts_supported) and, with
+    a gradient, the two-kernel backward (a workspace size > 0).  Both queries honour the debug options."""
+    if layers.dim() != 5 or layers.shape[2] != 4 or src_pts.dim() != 3:
+        return False
+    f, nl, _, h, w = layers.shape
+    lib = _lib.load()
+    n = src_pts.shape[1]
+    if nl < 1 or not lib.waldo_warp_composite_pts_supported(nl, h, w, n):
+        return False
+    return not needs_grad or lib.waldo_warp_composite_bwd_workspace_bytes(max(f, 1), nl, h, w, n + 3) > 0
+
+
 def _warp_composite_pts(layers, src_pts, occ, inverse_kernel, basis_t, want_alpha, delta):
     """Forward without autograd, straight from the control points: ONE launch per call
     (waldo_warp_composite_pts_fwd; the TPS mapping is computed inside the kernel, same bits as
     tps_mapping + the two-step forward)."""
-    _lib.check_cuda(layers, src_pts, occ, inverse_kernel, basis_t)
+    _lib.check_cuda(layers, half=True)
+    _lib.check_cuda(src_pts, occ, inverse_kernel, basis_t)
     layers, src_pts, occ = _c(layers.detach()), _c(src_pts.detach().float()), _c(occ.detach())
     inverse_kernel, basis_t = _c(inverse_kernel.detach()), _c(basis_t.detach())
     f, nl, _, h, w = layers.shape
@@ -1587,16 +1611,16 @@ def _warp_composite_pts(layers, src_pts, occ, inverse_kernel, basis_t, want_alph
         raise _lib.WaldoHipError(
             f"warp_composite: inconsistent shapes layers={tuple(layers.shape)} src_pts={tuple(src_pts.shape)} "
             f"occ={tuple(occ.shape)} basis_t={tuple(basis_t.shape)} inverse_kernel={tuple(inverse_kernel.shape)}")
-    rgb = layers.new_empty(f, 3, h, w)
-    alpha = layers.new_empty(f, nl, h, w) if want_alpha else None
+    rgb = layers.new_empty(f, 3, h, w, dtype=torch.float32)
+    alpha = layers.new_empty(f, nl, h, w, dtype=torch.float32) if want_alpha else None
     per = max(1, MAX_FL_PER_LAUNCH // nl)
     with _lib.on_device(layers.device):
         for i in range(0, f, per):
             j = min(f, i + per)
-            _lib.call("waldo_warp_composite_pts_fwd", _lib.ptr(layers[i:j]), _lib.ptr(basis_t),
-                      _lib.ptr(inverse_kernel), _lib.ptr(src_pts[i * nl:j * nl]), _lib.ptr(occ[i:j]),
-                      _lib.ptr(rgb[i:j]), _lib.ptr(alpha[i:j]) if want_alpha else None, j - i, nl, h, w, n,
-                      delta, _lib.current_stream(layers.device))
+            _call_dt("waldo_warp_composite_pts_fwd", (layers.dtype,), _lib.ptr(layers[i:j]), _lib.ptr(basis_t),
+                     _lib.ptr(inverse_kernel), _lib.ptr(src_pts[i * nl:j * nl]), _lib.ptr(occ[i:j]),
+                     _lib.ptr(rgb[i:j]), _lib.ptr(alpha[i:j]) if want_alpha else None, j - i, nl, h, w, n,
+                     delta, _lib.current_stream(layers.device))
     return (rgb, alpha) if want_alpha else rgb
 
 
