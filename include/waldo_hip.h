@@ -174,7 +174,9 @@ int waldo_grid_sample2d_ex_fwd(const float* input, const float* grid, float* out
                                int64_t out_group, int64_t out_stride, int64_t out_offset, float pre_scale,
                                float pre_bias, waldo_stream_t stream);
 /* grad_input (Nin,C,Hi,Wi) must be ZERO-FILLED by the caller (accumulated with atomics; may be
- * NULL to skip); grad_grid (N,Ho,Wo,2) is overwritten (may be NULL to skip). */
+ * NULL to skip); grad_grid (N,Ho,Wo,2) is overwritten (may be NULL to skip).  The float atomics make the last bits of
+ * grad_input depend on the order of arrival; waldo_grid_sample2d_bwd_det ("Reproducible gradients" below) OVERWRITES
+ * it with a sum that does not. */
 int waldo_grid_sample2d_bwd(const float* input, const float* grid, const float* grad_output,
                             float* grad_input, float* grad_grid, int64_t N, int C, int Hi, int Wi,
                             int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
@@ -200,7 +202,8 @@ int waldo_grid_sample2d_ex_bwd(const float* input, const float* grid, const floa
 int waldo_occ_composite_fwd(const float* alpha, const float* occ, float* out, int64_t M, int L,
                             int64_t HW, int64_t occ_div, waldo_stream_t stream);
 /* grad_alpha (M,L,HW) overwritten; grad_occ (Mo,L,L) must be ZERO-FILLED by the caller
- * (accumulated with atomics; may be NULL to skip). */
+ * (accumulated with atomics; may be NULL to skip).  Order-independent and OVERWRITTEN instead:
+ * waldo_occ_composite_bwd_det ("Reproducible gradients" below). */
 int waldo_occ_composite_bwd(const float* alpha, const float* occ, const float* grad_out,
                             float* grad_alpha, float* grad_occ, int64_t M, int L, int64_t HW,
                             int64_t occ_div, waldo_stream_t stream);
@@ -657,6 +660,108 @@ int waldo_frame_metrics_fwd(const void* a, int enc_a, int64_t sa_b, int64_t sa_t
                             const float* rgb_table, int B, int T, int H, int W, float lo, float range, int quant,
                             int mask, double* partials, float* scratch, float* psnr, float* ssim, float* msssim,
                             waldo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Reproducible gradients (deterministic mode).  The backward entry points above that say "ZERO-FILLED ... atomics"
+ * sum with float atomics: the result depends on the order of arrival and differs in its last bits from run to run.
+ * Each has a twin, suffix _det, whose result is a function of its inputs alone -- the same bits from run to run,
+ * launched eagerly or replayed from a HIP graph.  Every other backward entry point already is (no atomics).  The
+ * library keeps no mode: the caller picks the entry point.
+ *
+ * Contract of every *_det entry point: the arguments of its twin, plus (where the twin has none) a workspace and
+ * its size in bytes from the *_det_workspace_bytes query next to it -- ONE workspace, which also holds what the
+ * twin keeps in its own (the HD gradients of scale > 1, the two-kernel backward's records).  The gradients are
+ * OVERWRITTEN: the caller zero-fills nothing (fills inside are kernels, never memset calls).  Caller-owned memory,
+ * the caller's stream, no allocation, no synchronisation, nothing returns to the host.  WALDO_EINVAL with a message
+ * before any launch for a bad argument, a workspace that is too small, or a shape that has no deterministic kernel.
+ * A query returns 0 for such a shape.
+ *
+ * Two forms (csrc/det_common.hip.h):
+ *
+ *   SLAB         small tables summed over all pixels: grad_occ, grad_dist, grad_mapping.  Every workgroup (every
+ *                wavefront of the fused backward's pixel kernel) stores its partial table to a row of a slab in the
+ *                workspace; a second kernel sums the rows of one destination in a fixed order.  The order depends on
+ *                the shapes and on nothing else.  fp32 throughout; values differ from the twin's by summation order.
+ *
+ *   FIXED POINT  bilinear splats onto texels chosen by the data: grad_input of grid_sample2d, grad_a01 of
+ *                flow_ctx_warp.  (1) the largest contribution magnitude of every destination PLANE (one (map,
+ *                channel) image) is taken with an integer atomic maximum on the bit patterns; (2) every contribution c
+ *                is added as the 64-bit integer rint(c * 2^k) with integer atomics; (3) the sums are converted to
+ *                fp32 with one rounding and scaled by 2^-k.  With the plane's maximum < 2^ex (frexp) and at most
+ *                2^clog contributions to one texel,
+ *
+ *                    k = 63 - ex - clog,     clog = ceil(log2(max contributions per texel)) <= 32
+ *
+ *                so that no sum can overflow for ANY input and one quantum 2^-k is at most 2^(clog - 62) <= 2^-30 of
+ *                the plane's largest contribution.  The contribution bound follows from the shapes:
+ *                    grid_sample2d:  min(N, ceil(outer_div / inner)) * Ho * Wo  (the output maps that read one input
+ *                                    map, one contribution per output pixel); the weights are in [0, 1], so the
+ *                                    maximum of |grad_output * pre_scale| over those maps bounds the contributions;
+ *                    flow_ctx_warp:  Tc * Tp * Hd * Wd; the value a pixel distributes (the gradient of its sample,
+ *                                    gs * ghost) comes out of the composite's backward and has no bound from the
+ *                                    inputs: the pixel kernel STORES it per (unit, layer, pixel) in the workspace, a
+ *                                    pass takes the maximum, and the splat kernel derives the taps again.
+ *                A shape beyond 2^32 contributions per texel is rejected.  k follows the maximum in powers of two:
+ *                doubling the incoming gradient doubles these gradients exactly.
+ *                NON-FINITE: a plane whose maximum is infinite or NaN comes back ALL NaN (a NaN has no integer);
+ *                other planes are unaffected.  Coarser than the twin, which poisons only the texels touched.
+ *
+ *   grad_input   of waldo_grid_sample2d_bwd_det / _ex_bwd_det: FIXED POINT; all Nin maps are written (the twin's
+ *                arguments do not say how many there are: Nin is an argument here).  grad_grid: per pixel, as the twin.
+ *                workspace: round256(Nin*C*Hi*Wi*8) + round256(Nin*C*4)   (round256: up to a multiple of 256)
+ *   grad_occ     of waldo_occ_composite_bwd_det: SLAB; the ceil(M / occ_div) matrices that maps read are written.
+ *                workspace: round256(M * groups * L*L*4); groups = workgroups per map = ceil(ceil(HW / 256) / 4)
+ *   grad_mapping of waldo_tps_grid_bwd_det: SLAB; K3 <= 136.
+ *                workspace: round256(B * gx * K3*2*4); gx = pixel groups per map = ceil(ceil(HW / 1024) / 4)
+ *   grad_dist, grad_occ of waldo_flow_ctx_alpha_bwd_det: SLAB; all of (B,L-1,Nl) and (B,T,L,L) written.
+ *                workspace: [scale > 1: round256(B*Tw*L*Hd*Wd*4)] + round256(B*Tw*groups*L*L*4)
+ *                           + round256(B*Tw*groups*(L-1)*Nl*4)    (Nl: 0 without a filter);
+ *                           groups = workgroups per (b, t) = ceil(ceil(Hd*Wd / 256) / 4)
+ *   grad_a01     of waldo_flow_ctx_warp_bwd_det: FIXED POINT; grad_occ: SLAB, summed per predicted frame; all written.
+ *                workspace: [scale > 1: round256(M*L*2*Hd*Wd*4)] + round256(M*L*Hd*Wd*4) + round256(B*Tw*L*Hd*Wd*8)
+ *                           + round256(B*Tw*L*4) + round256(M*groups*L*L*4),  M = B*Tc*Tp (groups as above)
+ *   grad_occ     of waldo_warp_composite_bwd_det (layers of any waldo_dtype): SLAB, one row per (frame, 16x16 tile,
+ *                wavefront).  The two-kernel backward only (K3 == 19, L <= 17, W % 4 == 0, H, W >= 2), where
+ *                grad_layers and grad_mapping already are order-independent; the generic backward (per-tap float
+ *                atomics for everything) has no twin: such a shape is rejected.  grad_mapping is zero-filled inside.
+ *                workspace: waldo_warp_composite_bwd_workspace_bytes + round256(F * tiles16 * 4 * L*L*4),
+ *                           tiles16 = ceil(H / 16) * ceil(W / 16)
+ * ------------------------------------------------------------------------------------- */
+int64_t waldo_grid_sample2d_bwd_det_workspace_bytes(int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho, int Wo);
+int waldo_grid_sample2d_bwd_det(const float* input, const float* grid, const float* grad_output, float* grad_input,
+                                float* grad_grid, int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho, int Wo,
+                                float delta, int64_t outer_div, int64_t inner, void* workspace,
+                                int64_t workspace_bytes, waldo_stream_t stream);
+int waldo_grid_sample2d_ex_bwd_det(const float* input, const float* grid, const float* grad_output, float* grad_input,
+                                   float* grad_grid, int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho, int Wo,
+                                   float delta, int64_t outer_div, int64_t inner, int64_t gout_group,
+                                   int64_t gout_stride, int64_t gout_offset, float pre_scale, float pre_bias,
+                                   void* workspace, int64_t workspace_bytes, waldo_stream_t stream);
+int64_t waldo_occ_composite_bwd_det_workspace_bytes(int64_t M, int L, int64_t HW);
+int waldo_occ_composite_bwd_det(const float* alpha, const float* occ, const float* grad_out, float* grad_alpha,
+                                float* grad_occ, int64_t M, int L, int64_t HW, int64_t occ_div, void* workspace,
+                                int64_t workspace_bytes, waldo_stream_t stream);
+int64_t waldo_tps_grid_bwd_det_workspace_bytes(int64_t B, int64_t HW, int K3);
+int waldo_tps_grid_bwd_det(const float* basis_t, const float* grad_grid, float* grad_mapping, int64_t B, int64_t HW,
+                           int K3, void* workspace, int64_t workspace_bytes, waldo_stream_t stream);
+int64_t waldo_flow_ctx_alpha_bwd_det_workspace_bytes(int B, int Tw, int L, int Nl, int H, int W, int scale);
+int waldo_flow_ctx_alpha_bwd_det(const float* alpha_lr, const float* input, const float* dist, const float* occ,
+                                 const float* grad_a01, const float* grad_alpha_out, float* grad_alpha_lr,
+                                 float* grad_dist, float* grad_occ, void* workspace, int64_t workspace_bytes, int B,
+                                 int T, int Tw, int L, int Nl, int C, int chan_off, int H, int W, int scale,
+                                 waldo_stream_t stream);
+int64_t waldo_flow_ctx_warp_bwd_det_workspace_bytes(int B, int Tw, int Tc, int Tp, int L, int H, int W, int scale);
+int waldo_flow_ctx_warp_bwd_det(const float* flow_lr, const float* isobj_lr, const float* a01, const int64_t* ctx_ts,
+                                const int64_t* pred_ts, const float* occ, const float* grad_flow,
+                                const float* grad_alpha_ctx, const float* grad_disocc, float* grad_flow_lr,
+                                float* grad_a01, float* grad_occ, void* workspace, int64_t workspace_bytes, int B,
+                                int T, int Tw, int Tc, int Tp, int L, int H, int W, int scale, waldo_stream_t stream);
+int64_t waldo_warp_composite_bwd_det_workspace_bytes(int64_t F, int L, int H, int W, int K3);
+int waldo_warp_composite_bwd_det(const void* layers, const float* basis_t, const float* mapping, const float* occ,
+                                 const float* grad_rgb, const float* grad_alpha, void* grad_layers,
+                                 float* grad_mapping, float* grad_occ, void* workspace, int64_t workspace_bytes,
+                                 int64_t F, int L, int H, int W, int K3, float delta, int layers_dtype,
+                                 waldo_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,26 @@ SIGNATURES = {
     "waldo_warp_composite_fwd_dt": [_c_f] * 6 + [_i64, _int, _int, _int, _int, _flt, _int, _stream],
     "waldo_warp_composite_pts_fwd_dt": [_c_f] * 7 + [_i64, _int, _int, _int, _int, _flt, _int, _stream],
     "waldo_warp_composite_bwd_dt": [_c_f] * 10 + [_i64, _i64, _int, _int, _int, _int, _flt, _int, _stream],
+    # deterministic mode (include/waldo_hip.h "Reproducible gradients"): the backward entry points whose sums do not
+    # depend on the order of arrival; outputs overwritten, one workspace each (DET_QUERIES)
+    "waldo_grid_sample2d_bwd_det": [_c_f] * 5 + [_i64, _i64, _int, _int, _int, _int, _int, _flt, _i64, _i64, _c_f, _i64,
+                                                 _stream],
+    "waldo_grid_sample2d_ex_bwd_det": [_c_f] * 5 + [_i64, _i64, _int, _int, _int, _int, _int, _flt, _i64, _i64, _i64,
+                                                    _i64, _i64, _flt, _flt, _c_f, _i64, _stream],
+    "waldo_occ_composite_bwd_det": [_c_f] * 5 + [_i64, _int, _i64, _i64, _c_f, _i64, _stream],
+    "waldo_tps_grid_bwd_det": [_c_f, _c_f, _c_f, _i64, _i64, _int, _c_f, _i64, _stream],
+    "waldo_flow_ctx_alpha_bwd_det": [_c_f] * 10 + [_i64] + [_int] * 10 + [_stream],
+    "waldo_flow_ctx_warp_bwd_det": [_c_f] * 13 + [_i64] + [_int] * 9 + [_stream],
+    "waldo_warp_composite_bwd_det": [_c_f] * 10 + [_i64, _i64, _int, _int, _int, _int, _flt, _int, _stream],
+}
+# workspace size of each *_det entry point (0: no deterministic kernel for the shape)
+DET_QUERIES = {
+    "waldo_grid_sample2d_bwd_det_workspace_bytes": [_i64, _i64, _int, _int, _int, _int, _int],
+    "waldo_occ_composite_bwd_det_workspace_bytes": [_i64, _int, _i64],
+    "waldo_tps_grid_bwd_det_workspace_bytes": [_i64, _i64, _int],
+    "waldo_flow_ctx_alpha_bwd_det_workspace_bytes": [_int] * 7,
+    "waldo_flow_ctx_warp_bwd_det_workspace_bytes": [_int] * 8,
+    "waldo_warp_composite_bwd_det_workspace_bytes": [_i64, _int, _int, _int, _int],
 }
 PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_warp_composite_bwd_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int]),
@@ -104,6 +124,7 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_last_error_string": (ctypes.c_char_p, []),
          "waldo_set_debug_option": (_int, [_int, _int]),
          "waldo_host_device_pointer": (_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)])}
+PLAIN.update({name: (_i64, argtypes) for name, argtypes in DET_QUERIES.items()})
 
 # include/waldo_hip.h: test-only switches between kernel variants (waldo_set_debug_option: the library's one piece of
 # process-global state)
@@ -321,3 +342,8 @@ def call(name, *args):
     if rc != 0:
         msg = lib.waldo_last_error_string()
         raise WaldoHipError(f"{name} failed ({rc}): {msg.decode() if msg else '?'}")
+
+
+def query(name, *args):
+    """A size query of the library (``*_workspace_bytes``): launches nothing."""
+    return getattr(load(), name)(*args)

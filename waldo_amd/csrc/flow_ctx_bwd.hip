@@ -19,6 +19,7 @@
 // wave transpose-reduce into the wave's own row of an LDS table, one float atomic per workgroup and
 // entry at the end.
 #include "flow_ctx_common.hip.h"
+#include "det_common.hip.h"
 
 namespace waldo {
 
@@ -111,7 +112,9 @@ struct GradOfA01 {
   }
 };
 
-template <int LP, int NCP>
+// DET (deterministic mode, det_common.hip.h): g_occ and g_dist are slabs of one row per workgroup -- L x L and
+// (L - 1) x Nl floats -- stored, not added.
+template <int LP, int NCP, bool DET = false>
 __global__ __launch_bounds__(kBlock, WALDO_FCB_ALPHA_WAVES) void flow_ctx_alpha_bwd_kernel(
     const float* __restrict__ alpha_lr, const float* __restrict__ input,
     const float* __restrict__ dist, const float* __restrict__ occ, const float* __restrict__ g_a01,
@@ -211,22 +214,33 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_ALPHA_WAVES) void flow_ctx_alpha_
   if (g_occ != nullptr)
     for (int e = threadIdx.x; e < LP * LP; e += kBlock) {
       const int i = e / LP, j = e % LP;
-      if (i < L && j < L)
-        atomicAdd(g_occ + ((int64_t)b * T + t) * L * L + i * L + j,
-                  (acc_o[0][e] + acc_o[1][e]) + (acc_o[2][e] + acc_o[3][e]));
+      if (i < L && j < L) {
+        if constexpr (DET)
+          g_occ[(int64_t)blockIdx.x * L * L + i * L + j] = (acc_o[0][e] + acc_o[1][e]) + (acc_o[2][e] + acc_o[3][e]);
+        else
+          atomicAdd(g_occ + ((int64_t)b * T + t) * L * L + i * L + j,
+                    (acc_o[0][e] + acc_o[1][e]) + (acc_o[2][e] + acc_o[3][e]));
+      }
     }
   if (filt && g_dist != nullptr)
     for (int e = threadIdx.x; e < (LP - 1) * kMaxCls; e += kBlock) {
       const int o = e / kMaxCls, c = e % kMaxCls;
-      if (o < No && c < Nl)
-        atomicAdd(g_dist + ((int64_t)b * No + o) * Nl + c, (acc_d[0][e] + acc_d[1][e]) + (acc_d[2][e] + acc_d[3][e]));
+      if (o < No && c < Nl) {
+        if constexpr (DET)
+          g_dist[((int64_t)blockIdx.x * No + o) * Nl + c] = (acc_d[0][e] + acc_d[1][e]) + (acc_d[2][e] + acc_d[3][e]);
+        else
+          atomicAdd(g_dist + ((int64_t)b * No + o) * Nl + c, (acc_d[0][e] + acc_d[1][e]) + (acc_d[2][e] + acc_d[3][e]));
+      }
     }
 }
 
 #ifndef WALDO_FCB_WARP_WAVES
 #define WALDO_FCB_WARP_WAVES 3
 #endif
-template <int LP>
+// DET (deterministic mode, det_common.hip.h): g_occ is a slab of one L x L row per workgroup; g_a01 holds, per (unit,
+// layer, pixel), the value the splat distributes (gs * ghost, a plain store) -- flow_ctx_warp_det_splat_kernel
+// derives the taps again and adds it in fixed point.
+template <int LP, bool DET = false>
 __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bwd_kernel(
     const float* __restrict__ flow_lr, const float* __restrict__ isobj_lr,
     const float* __restrict__ a01, const int64_t* __restrict__ ctx_ts,
@@ -331,7 +345,9 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bw
             g_fup[(((int64_t)m * L + l) * 2 + 1) * HWd + p] = gfyl;
           }
           // d / d a01: bilinear splat of gs * ghost
-          if (g_a01 != nullptr) {
+          if constexpr (DET) {
+            if (g_a01 != nullptr && live) g_a01[((int64_t)m * L + l) * HWd + p] = gs * ghost;
+          } else if (g_a01 != nullptr) {
             const float gsg = live ? gs * ghost : 0.0f;
             if (gsg != 0.0f) {
               float* gp = g_a01 + (((int64_t)b * Tw + ts) * L + l) * HWd;
@@ -354,10 +370,74 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bw
   if (g_occ != nullptr)
     for (int e = threadIdx.x; e < LP * LP; e += kBlock) {
       const int i = e / LP, j = e % LP;
-      if (i < L && j < L)
-        atomicAdd(g_occ + ((int64_t)b * T + tpred) * L * L + i * L + j,
-                  (acc_o[0][e] + acc_o[1][e]) + (acc_o[2][e] + acc_o[3][e]));
+      if (i < L && j < L) {
+        if constexpr (DET)
+          g_occ[(int64_t)blockIdx.x * L * L + i * L + j] = (acc_o[0][e] + acc_o[1][e]) + (acc_o[2][e] + acc_o[3][e]);
+        else
+          atomicAdd(g_occ + ((int64_t)b * T + tpred) * L * L + i * L + j,
+                    (acc_o[0][e] + acc_o[1][e]) + (acc_o[2][e] + acc_o[3][e]));
+      }
     }
+}
+
+// ---- deterministic grad_a01 (det_common.hip.h: the 64-bit fixed-point splat).  `vals` (M, L, Hd, Wd): what the DET
+// instance of the kernel above stored.  The weights are products of factors in [0, 1], so the largest |vals| among the
+// units that sample plane (b, ts, l) bounds every contribution to it; a texel of the plane receives at most one
+// contribution per (unit of the batch element, pixel): Tc * Tp * Hd * Wd.
+constexpr int kFcwMaxChunk = 4096;
+
+__global__ __launch_bounds__(kBlock) void flow_ctx_warp_det_max_kernel(const float* __restrict__ vals,
+                                                                       const int64_t* __restrict__ ctx_ts,
+                                                                       unsigned* __restrict__ plane_max, int Tw, int Tc,
+                                                                       int Tp, int L, int64_t HWd, int chunks) {
+  const int64_t plane = blockIdx.x / chunks, m = plane / L;
+  const int l = (int)(plane % L);
+  const int64_t b = m / ((int64_t)Tc * Tp);
+  const int ts = (int)min(max(ctx_ts[m], (int64_t)0), (int64_t)(Tw - 1));
+  const int64_t i0 = (int64_t)(blockIdx.x % chunks) * kFcwMaxChunk, i1 = min(HWd, i0 + kFcwMaxChunk);
+  const float* v = vals + plane * HWd;
+  unsigned bits = 0u;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += kBlock) bits = max(bits, abs_bits(v[i]));
+  plane_max_update(plane_max + (b * Tw + ts) * L + l, bits);
+}
+
+__global__ __launch_bounds__(kBlock) void flow_ctx_warp_det_splat_kernel(
+    const float* __restrict__ flow_lr, const float* __restrict__ vals, const int64_t* __restrict__ ctx_ts,
+    unsigned long long* __restrict__ acc, const unsigned* __restrict__ plane_max, int Tw, int Tc, int Tp, int L, int H,
+    int W, int scale, int tiles, int clog) {
+  const int Hd = H * scale, Wd = W * scale;
+  const int64_t HWd = (int64_t)Hd * Wd, HW = (int64_t)H * W;
+  const int64_t m = blockIdx.x / tiles;
+  const int64_t p = (int64_t)(blockIdx.x % tiles) * kBlock + threadIdx.x;
+  if (p >= HWd) return;
+  const int64_t b = m / ((int64_t)Tc * Tp);
+  const int ts = (int)min(max(ctx_ts[m], (int64_t)0), (int64_t)(Tw - 1));
+  const int y = (int)(p / Wd), x = (int)(p - (int64_t)y * Wd);
+  const UpTaps ut = up_taps(y, x, 1.0f / (float)scale, H, W);
+  float gx0, gy0;
+  identity_grid(x, y, Wd, Hd, gx0, gy0);
+  for (int l = 0; l < L; ++l) {
+    const int64_t plane = (b * Tw + ts) * L + l;
+    const unsigned mb = plane_max[plane];        // (uniform)
+    if (mb == 0u || mb >= kInfBits) continue;    // nothing to add / the plane comes back NaN
+    const float gsg = vals[(m * L + l) * HWd + p];
+    if (gsg == 0.0f) continue;
+    const int k = splat_shift(mb, clog);
+    // the sample position and the weights as flow_ctx_warp_bwd_kernel takes them
+    const float* fl = flow_lr + ((m * L + l) * 2) * HW;
+    const float fxl = up_sample(fl, ut), fyl = up_sample(fl + HW, ut);
+    const Taps t = make_taps(gx0 + fxl, gy0 + fyl, Hd, Wd);
+    const float wx0 = 1.0f - t.fx, wy0 = 1.0f - t.fy;
+    const float wq[4] = {wx0 * wy0 * (t.vx0 * t.vy0), t.fx * wy0 * (t.vx1 * t.vy0), wx0 * t.fy * (t.vx0 * t.vy1),
+                         t.fx * t.fy * (t.vx1 * t.vy1)};
+    const uint32_t key[4] = {t.o00, t.o01, t.o10, t.o11};
+    unsigned long long* ap = acc + plane * HWd;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned long long term = splat_term(gsg * wq[q], k);
+      if (term != 0ull) atomicAdd(ap + (key[q] >> 2), term);
+    }
+  }
 }
 
 // transpose of F.interpolate(scale_factor=S, "bilinear", align_corners=False) on P planes:
@@ -629,4 +709,197 @@ extern "C" int waldo_frame_warp_fuse_bwd(const float* input, const float* flow, 
   else if (Tc <= 4) launch(std::integral_constant<int, 4>{});
   else launch(std::integral_constant<int, 8>{});
   return launch_status("waldo_frame_warp_fuse_bwd");
+}
+
+// ---- deterministic mode (det_common.hip.h).  The same arguments as the entry points above, with ONE workspace that
+// also holds what they keep there; grad_dist / grad_occ / grad_a01 are OVERWRITTEN.
+namespace {
+
+struct AlphaDetLayout {
+  int64_t up_bytes, occ_bytes, dist_bytes, total;
+  int tiles, tpb, groups;
+};
+
+AlphaDetLayout alpha_det_layout(int64_t N, int L, int Nl, int H, int W, int scale) {
+  AlphaDetLayout o;
+  const int64_t HWd = (int64_t)H * scale * W * scale;
+  o.tiles = (int)((HWd + kBlock - 1) / kBlock);
+  o.tpb = kDetTilesPerBlock;
+  o.groups = (o.tiles + o.tpb - 1) / o.tpb;
+  o.up_bytes = scale > 1 ? round256(N * L * HWd * 4) : 0;
+  o.occ_bytes = round256(N * o.groups * L * L * 4);
+  o.dist_bytes = round256(N * o.groups * (int64_t)(L - 1) * Nl * 4);
+  o.total = o.up_bytes + o.occ_bytes + o.dist_bytes;
+  return o;
+}
+
+struct WarpDetLayout {
+  int64_t up_bytes, vals_bytes, acc_bytes, max_bytes, occ_bytes, total;
+  int tiles, tpb, groups, clog;  // clog -1: a texel could receive more than 2^32 contributions
+};
+
+WarpDetLayout warp_det_layout(int64_t B, int Tw, int Tc, int Tp, int L, int H, int W, int scale) {
+  WarpDetLayout o;
+  const int64_t N = B * Tc * Tp, HWd = (int64_t)H * scale * W * scale;
+  o.tiles = (int)((HWd + kBlock - 1) / kBlock);
+  o.tpb = kDetTilesPerBlock;
+  o.groups = (o.tiles + o.tpb - 1) / o.tpb;
+  o.up_bytes = scale > 1 ? round256(N * L * 2 * HWd * 4) : 0;
+  o.vals_bytes = round256(N * L * HWd * 4);
+  o.acc_bytes = round256(B * Tw * L * HWd * 8);
+  o.max_bytes = round256(B * Tw * L * 4);
+  o.occ_bytes = round256(N * o.groups * L * L * 4);
+  o.total = o.up_bytes + o.vals_bytes + o.acc_bytes + o.max_bytes + o.occ_bytes;
+  const int64_t count = (int64_t)Tc * Tp * HWd;
+  const int clog = splat_count_log(count > 1 ? count : 1);
+  o.clog = clog <= kSplatMaxLog ? clog : -1;
+  return o;
+}
+
+}  // namespace
+
+extern "C" int64_t waldo_flow_ctx_alpha_bwd_det_workspace_bytes(int B, int Tw, int L, int Nl, int H, int W, int scale) {
+  if (B < 0 || Tw < 1 || Nl < 0 || Nl > kMaxCls || check_bwd_shape("", (int64_t)B * Tw, L, H, W, scale)) return 0;
+  return alpha_det_layout((int64_t)B * Tw, L, Nl, H, W, scale).total;
+}
+
+extern "C" int waldo_flow_ctx_alpha_bwd_det(const float* alpha_lr, const float* input, const float* dist,
+                                            const float* occ, const float* grad_a01, const float* grad_alpha_out,
+                                            float* grad_alpha_lr, float* grad_dist, float* grad_occ, void* workspace,
+                                            int64_t workspace_bytes, int B, int T, int Tw, int L, int Nl, int C,
+                                            int chan_off, int H, int W, int scale, waldo_stream_t stream) {
+  const char* fn = "waldo_flow_ctx_alpha_bwd_det";
+  const int64_t N = (int64_t)B * Tw;
+  if (int rc = check_bwd_shape(fn, N, L, H, W, scale)) return rc;
+  if (B < 0 || T < 1 || Tw < 1 || Tw > T ||
+      (dist != nullptr && (Nl < 1 || Nl > kMaxCls || chan_off < 0 || chan_off + Nl > C))) {
+    set_error("%s: bad frame window Tw=%d of T=%d or class channels", fn, Tw, T);
+    return WALDO_EINVAL;
+  }
+  if (N == 0) return WALDO_OK;
+  const AlphaDetLayout lo = alpha_det_layout(N, L, dist != nullptr ? Nl : 0, H, W, scale);
+  if (workspace == nullptr || workspace_bytes < lo.total) {
+    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
+              (long long)lo.total);
+    return WALDO_EINVAL;
+  }
+  if (!alpha_lr || !occ || (!grad_a01 && !grad_alpha_out) || !grad_alpha_lr || (dist != nullptr && !input)) {
+    set_error("%s: null pointer (one of grad_a01 / grad_alpha_out)", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = reinterpret_cast<char*>(workspace);
+  float* up = reinterpret_cast<float*>(ws);
+  float* slab_o = reinterpret_cast<float*>(ws + lo.up_bytes);
+  float* slab_d = reinterpret_cast<float*>(ws + lo.up_bytes + lo.occ_bytes);
+  float* gup = scale > 1 ? up : grad_alpha_lr;
+  const bool want_d = dist != nullptr && grad_dist != nullptr;
+  with_padded_layers(L, [&](auto lp) {
+    auto launch = [&](auto ncp) {
+      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<decltype(lp)::value, decltype(ncp)::value, true>),
+                         dim3((unsigned)(N * lo.groups)), dim3(kBlock), 0, st, alpha_lr, input, dist, occ, grad_a01,
+                         grad_alpha_out, gup, want_d ? slab_d : nullptr, grad_occ != nullptr ? slab_o : nullptr, T, Tw,
+                         L, Nl, C, chan_off, H, W, scale, lo.tiles, lo.tpb, lo.groups);
+    };
+    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
+    else launch(std::integral_constant<int, kMaxCls>{});
+  });
+  if (grad_occ != nullptr) {
+    // frames Tw .. T - 1 of a batch element receive nothing
+    if (Tw < T) fill_words(grad_occ, 0u, sizeof(float) * (size_t)B * T * L * L, st);
+    slab_reduce(slab_o, grad_occ, N, lo.groups, L * L, SlabPlain{N * lo.groups, Tw, T}, st);
+  }
+  if (want_d)  // a batch element's Tw * groups workgroups: consecutive rows
+    slab_reduce(slab_d, grad_dist, B, Tw * lo.groups, (L - 1) * Nl, SlabPlain{N * lo.groups, B, B}, st);
+  if (scale > 1) {
+    const int64_t P = N * L;
+    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       st, up, grad_alpha_lr, P, H, W, scale);
+  }
+  return launch_status(fn);
+}
+
+extern "C" int64_t waldo_flow_ctx_warp_bwd_det_workspace_bytes(int B, int Tw, int Tc, int Tp, int L, int H, int W,
+                                                               int scale) {
+  if (B < 0 || Tw < 1 || Tc < 0 || Tp < 0 || check_bwd_shape("", (int64_t)B * Tc * Tp, L, H, W, scale)) return 0;
+  return warp_det_layout(B, Tw, Tc, Tp, L, H, W, scale).total;
+}
+
+extern "C" int waldo_flow_ctx_warp_bwd_det(const float* flow_lr, const float* isobj_lr, const float* a01,
+                                           const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ,
+                                           const float* grad_flow, const float* grad_alpha_ctx,
+                                           const float* grad_disocc, float* grad_flow_lr, float* grad_a01,
+                                           float* grad_occ, void* workspace, int64_t workspace_bytes, int B, int T,
+                                           int Tw, int Tc, int Tp, int L, int H, int W, int scale,
+                                           waldo_stream_t stream) {
+  const char* fn = "waldo_flow_ctx_warp_bwd_det";
+  const int64_t N = (int64_t)B * Tc * Tp;
+  if (int rc = check_bwd_shape(fn, N, L, H, W, scale)) return rc;
+  if (B < 0 || T < 1 || Tw < 1 || Tw > T || Tc < 0 || Tp < 0) {
+    set_error("%s: bad frame counts T=%d Tw=%d Tc=%d Tp=%d", fn, T, Tw, Tc, Tp);
+    return WALDO_EINVAL;
+  }
+  const WarpDetLayout lo = warp_det_layout(B, Tw, Tc, Tp, L, H, W, scale);
+  const int64_t HWd = (int64_t)H * scale * W * scale;
+  if (grad_a01 != nullptr && lo.clog < 0) {
+    set_error("%s: a texel of grad_a01 may receive more than 2^%d contributions (Tc=%d Tp=%d Hd*Wd=%lld): no "
+              "deterministic sum for this shape", fn, kSplatMaxLog, Tc, Tp, (long long)HWd);
+    return WALDO_EINVAL;
+  }
+  const int chunks = (int)((HWd + kFcwMaxChunk - 1) / kFcwMaxChunk);
+  if (N * L * chunks > 2147483647 || ((int64_t)B * Tw * L * HWd + kBlock - 1) / kBlock > 2147483647) {
+    set_error("%s: problem too large for one launch", fn);
+    return WALDO_EINVAL;
+  }
+  if (B == 0) return WALDO_OK;
+  if (workspace == nullptr || workspace_bytes < lo.total) {
+    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
+              (long long)lo.total);
+    return WALDO_EINVAL;
+  }
+  if (!a01 || !occ || (N > 0 && (!flow_lr || !ctx_ts || !pred_ts || !grad_flow_lr))) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = reinterpret_cast<char*>(workspace);
+  float* up = reinterpret_cast<float*>(ws);
+  float* vals = reinterpret_cast<float*>(ws + lo.up_bytes);
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + lo.up_bytes + lo.vals_bytes);
+  unsigned* plane_max = reinterpret_cast<unsigned*>(ws + lo.up_bytes + lo.vals_bytes + lo.acc_bytes);
+  float* slab_o = reinterpret_cast<float*>(ws + lo.up_bytes + lo.vals_bytes + lo.acc_bytes + lo.max_bytes);
+  float* gup = scale > 1 ? up : grad_flow_lr;
+  if (grad_a01 != nullptr) fill_words(acc, 0u, (size_t)(lo.acc_bytes + lo.max_bytes), st);
+  if (N > 0) {
+    with_padded_layers(L, [&](auto lp) {
+      hipLaunchKernelGGL((flow_ctx_warp_bwd_kernel<decltype(lp)::value, true>), dim3((unsigned)(N * lo.groups)),
+                         dim3(kBlock), 0, st, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx,
+                         grad_disocc, gup, grad_a01 != nullptr ? vals : nullptr, grad_occ != nullptr ? slab_o : nullptr, T,
+                         Tw, Tc, Tp, L, H, W, scale, lo.tiles, lo.tpb, lo.groups);
+    });
+    if (grad_a01 != nullptr) {
+      hipLaunchKernelGGL(flow_ctx_warp_det_max_kernel, dim3((unsigned)(N * L * chunks)), dim3(kBlock), 0, st, vals,
+                         ctx_ts, plane_max, Tw, Tc, Tp, L, HWd, chunks);
+      hipLaunchKernelGGL(flow_ctx_warp_det_splat_kernel, dim3((unsigned)(N * lo.tiles)), dim3(kBlock), 0, st, flow_lr,
+                         vals, ctx_ts, acc, plane_max, Tw, Tc, Tp, L, H, W, scale, lo.tiles, lo.clog);
+    }
+    if (scale > 1) {
+      const int64_t P = N * L * 2;
+      hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                         st, up, grad_flow_lr, P, H, W, scale);
+    }
+  }
+  if (grad_a01 != nullptr) {
+    const int64_t total = (int64_t)B * Tw * L * HWd;
+    hipLaunchKernelGGL(splat_convert_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, acc,
+                       plane_max, grad_a01, HWd, total, lo.clog);
+  }
+  if (grad_occ != nullptr) {
+    if (N > 0)  // matrix (b, t) sums the workgroups of the units (b, tc, tp) whose predicted frame is t
+      slab_reduce(slab_o, grad_occ, (int64_t)B * T, Tc * Tp * lo.groups, L * L,
+                  SlabByPredFrame{pred_ts, T, Tc, Tp, lo.groups}, st);
+    else
+      fill_words(grad_occ, 0u, sizeof(float) * (size_t)B * T * L * L, st);
+  }
+  return launch_status(fn);
 }

@@ -4,7 +4,7 @@
 // (models/nets/lvd.py:502-559) and the HD gathers of grid_to_flow_ctx / input_to_output
 // (lvd.py:801,837).  One thread per output pixel, looping over the C channel planes so the tap
 // weights are computed once; a wavefront covers 64 consecutive output pixels.
-#include "waldo_common.hip.h"
+#include "det_common.hip.h"
 
 namespace waldo {
 
@@ -285,6 +285,70 @@ static int check_gs(const char* fn, int64_t N, int C, int Hi, int Wi, int Ho, in
   return WALDO_OK;
 }
 
+// ---- deterministic mode (det_common.hip.h: the 64-bit fixed-point splat) --------------------------------------
+// The contributions to plane (nin, c) are grad_output * pre_scale * weight with weights in [0, 1]: the maximum of
+// |grad_output * pre_scale| over the output maps that read input map nin bounds them.
+constexpr int kGsMaxChunk = 4096;  // outputs per workgroup of the maximum pass
+
+__global__ __launch_bounds__(kBlock) void grid_sample2d_det_max_kernel(
+    const float* __restrict__ grad_output, unsigned* __restrict__ plane_max, int C, int64_t HWo, int chunks,
+    int64_t outer_div, int64_t inner, OutSlots gos, float pre_scale) {
+  const int64_t plane = blockIdx.x / chunks, n = plane / C;
+  const int c = (int)(plane % C);
+  const int64_t i0 = (int64_t)(blockIdx.x % chunks) * kGsMaxChunk, i1 = min(HWo, i0 + kGsMaxChunk);
+  const float* go = grad_output + (gos.slot(n) * C + c) * HWo;
+  unsigned bits = 0u;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += kBlock) bits = max(bits, abs_bits(go[i] * pre_scale));
+  plane_max_update(plane_max + in_index(n, outer_div, inner) * C + c, bits);
+}
+
+__global__ __launch_bounds__(kBlock) void grid_sample2d_det_splat_kernel(
+    const float* __restrict__ grid, const float* __restrict__ grad_output, unsigned long long* __restrict__ acc,
+    const unsigned* __restrict__ plane_max, int C, int Hi, int Wi, int64_t HWo, int tiles, int64_t outer_div,
+    int64_t inner, OutSlots gos, float pre_scale, int clog) {
+  const int64_t n = blockIdx.x / tiles;
+  const int64_t p = (int64_t)(blockIdx.x % tiles) * kBlock + threadIdx.x;
+  if (p >= HWo) return;
+  const float2 g = *reinterpret_cast<const float2*>(grid + (n * HWo + p) * 2);
+  const Taps t = make_taps(g.x, g.y, Hi, Wi);
+  const int64_t HWi = (int64_t)Hi * Wi;
+  const int64_t nin = in_index(n, outer_div, inner);
+  const float* go = grad_output + gos.slot(n) * C * HWo + p;
+  const uint32_t key[4] = {t.o00, t.o01, t.o10, t.o11};
+  const float wq[4] = {t.w00, t.w01, t.w10, t.w11};
+  for (int c = 0; c < C; ++c) {
+    const unsigned mb = plane_max[nin * C + c];  // (uniform)
+    if (mb == 0u || mb >= kInfBits) continue;    // nothing to add / the plane comes back NaN
+    const int k = splat_shift(mb, clog);
+    const float gvs = go[(int64_t)c * HWo] * pre_scale;
+    unsigned long long* ap = acc + (nin * C + c) * HWi;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned long long term = splat_term(gvs * wq[q], k);
+      if (term != 0ull) atomicAdd(ap + (key[q] >> 2), term);
+    }
+  }
+}
+
+struct GsDetLayout {
+  int64_t acc_bytes, max_bytes, total;
+  int clog;  // -1: a texel could receive more than 2^32 contributions
+};
+
+static GsDetLayout gs_det_layout(int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho, int Wo, int64_t outer_div,
+                                 int64_t inner) {
+  GsDetLayout o;
+  o.acc_bytes = round256(Nin * C * (int64_t)Hi * Wi * 8);
+  o.max_bytes = round256(Nin * C * 4);
+  o.total = o.acc_bytes + o.max_bytes;
+  // output maps that read one input map: n / outer_div fixed, n % inner fixed
+  const int64_t per_map = (outer_div + inner - 1) / inner;
+  const int64_t copies = N < 1 ? 1 : (N < per_map ? N : per_map);
+  const int clog = splat_count_log(copies * (int64_t)Ho * Wo);
+  o.clog = clog <= kSplatMaxLog ? clog : -1;
+  return o;
+}
+
 }  // namespace waldo
 
 using namespace waldo;
@@ -387,4 +451,97 @@ extern "C" int waldo_grid_sample2d_ex_bwd(const float* input, const float* grid,
   return grid_sample2d_bwd_launch("waldo_grid_sample2d_ex_bwd", input, grid, grad_output, grad_input, grad_grid, N, C,
                                   Hi, Wi, Ho, Wo, delta, outer_div, inner,
                                   OutSlots{gout_group, gout_stride, gout_offset}, PreAffine{pre_scale, pre_bias}, stream);
+}
+
+// ---- deterministic mode: grad_input OVERWRITTEN (all Nin maps), the same bits whatever the order of arrival
+extern "C" int64_t waldo_grid_sample2d_bwd_det_workspace_bytes(int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho,
+                                                               int Wo) {
+  if (N < 0 || Nin < 0 || C < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return 0;
+  return gs_det_layout(N, Nin, C, Hi, Wi, Ho, Wo, 1, 1).total;
+}
+
+static int grid_sample2d_bwd_det_launch(const char* fn, const float* input, const float* grid, const float* grad_output,
+                                        float* grad_input, float* grad_grid, int64_t N, int64_t Nin, int C, int Hi,
+                                        int Wi, int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
+                                        OutSlots gos, PreAffine pre, void* workspace, int64_t workspace_bytes,
+                                        waldo_stream_t stream) {
+  if (gos.group < 1 || gos.stride < gos.group || gos.offset < 0 || gos.offset + gos.group > gos.stride) {
+    set_error("%s: bad gradient slots (group %lld, stride %lld, offset %lld)", fn, (long long)gos.group,
+              (long long)gos.stride, (long long)gos.offset);
+    return WALDO_EINVAL;
+  }
+  int rc = check_gs(fn, N, C, Hi, Wi, Ho, Wo, outer_div, inner);
+  if (rc) return rc;
+  if (Nin < 0 || (N > 0 && ((N - 1) / outer_div) * inner + (inner < N ? inner : N) > Nin)) {
+    set_error("%s: Nin=%lld input maps, the broadcast (%lld, %lld) of N=%lld outputs reads more", fn, (long long)Nin,
+              (long long)outer_div, (long long)inner, (long long)N);
+    return WALDO_EINVAL;
+  }
+  const int64_t HWo = (int64_t)Ho * Wo, HWi = (int64_t)Hi * Wi;
+  const int chunks = (int)((HWo + kGsMaxChunk - 1) / kGsMaxChunk);
+  const GsDetLayout lo = gs_det_layout(N, Nin, C, Hi, Wi, Ho, Wo, outer_div, inner);
+  if (grad_input != nullptr) {
+    if (lo.clog < 0) {
+      set_error("%s: a texel of grad_input may receive more than 2^%d contributions (N=%lld Ho=%d Wo=%d): no "
+                "deterministic sum for this shape", fn, kSplatMaxLog, (long long)N, Ho, Wo);
+      return WALDO_EINVAL;
+    }
+    if (N * C * chunks > 2147483647 || (Nin * C * HWi + kBlock - 1) / kBlock > 2147483647) {
+      set_error("%s: problem too large for one launch", fn);
+      return WALDO_EINVAL;
+    }
+    if (Nin > 0 && (workspace == nullptr || workspace_bytes < lo.total)) {
+      set_error("%s: workspace of %lld bytes given, %lld needed", fn,
+                (long long)(workspace == nullptr ? 0 : workspace_bytes), (long long)lo.total);
+      return WALDO_EINVAL;
+    }
+  }
+  if (N > 0 && (!input || !grid || !grad_output)) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  if (!grad_input && !grad_grid) return WALDO_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = (int)((HWo + kBlock - 1) / kBlock);
+  if (grad_grid != nullptr && N > 0)
+    hipLaunchKernelGGL(grid_sample2d_bwd_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st, input, grid,
+                       grad_output, (float*)nullptr, grad_grid, N, C, Hi, Wi, HWo, tiles, delta, outer_div, inner, gos,
+                       pre);
+  if (grad_input != nullptr && Nin > 0) {
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(workspace);
+    unsigned* plane_max = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + lo.acc_bytes);
+    fill_words(workspace, 0u, (size_t)lo.total, st);
+    if (N > 0) {
+      hipLaunchKernelGGL(grid_sample2d_det_max_kernel, dim3((unsigned)(N * C * chunks)), dim3(kBlock), 0, st,
+                         grad_output, plane_max, C, HWo, chunks, outer_div, inner, gos, pre.scale);
+      hipLaunchKernelGGL(grid_sample2d_det_splat_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st, grid,
+                         grad_output, acc, plane_max, C, Hi, Wi, HWo, tiles, outer_div, inner, gos, pre.scale, lo.clog);
+    }
+    const int64_t total = Nin * C * HWi;
+    hipLaunchKernelGGL(splat_convert_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, acc,
+                       plane_max, grad_input, HWi, total, lo.clog);
+  }
+  return launch_status(fn);
+}
+
+extern "C" int waldo_grid_sample2d_bwd_det(const float* input, const float* grid, const float* grad_output,
+                                           float* grad_input, float* grad_grid, int64_t N, int64_t Nin, int C, int Hi,
+                                           int Wi, int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
+                                           void* workspace, int64_t workspace_bytes, waldo_stream_t stream) {
+  return grid_sample2d_bwd_det_launch("waldo_grid_sample2d_bwd_det", input, grid, grad_output, grad_input, grad_grid,
+                                      N, Nin, C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
+                                      OutSlots{N > 0 ? N : 1, N > 0 ? N : 1, 0}, PreAffine{1.0f, 0.0f}, workspace,
+                                      workspace_bytes, stream);
+}
+
+extern "C" int waldo_grid_sample2d_ex_bwd_det(const float* input, const float* grid, const float* grad_output,
+                                              float* grad_input, float* grad_grid, int64_t N, int64_t Nin, int C,
+                                              int Hi, int Wi, int Ho, int Wo, float delta, int64_t outer_div,
+                                              int64_t inner, int64_t gout_group, int64_t gout_stride,
+                                              int64_t gout_offset, float pre_scale, float pre_bias, void* workspace,
+                                              int64_t workspace_bytes, waldo_stream_t stream) {
+  return grid_sample2d_bwd_det_launch("waldo_grid_sample2d_ex_bwd_det", input, grid, grad_output, grad_input,
+                                      grad_grid, N, Nin, C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
+                                      OutSlots{gout_group, gout_stride, gout_offset}, PreAffine{pre_scale, pre_bias},
+                                      workspace, workspace_bytes, stream);
 }

@@ -3,7 +3,7 @@
 // 764-765, 809 (spec: LVD.reduce_comp, lvd.py:109-111).  The reference materialises an
 // (L, L, h, w) tensor per map; here every thread keeps its L alphas in registers, occ is
 // wave-uniform (scalar cache), and nothing of size L*L*h*w exists.
-#include "waldo_common.hip.h"
+#include "det_common.hip.h"
 
 namespace waldo {
 
@@ -38,7 +38,8 @@ __global__ __launch_bounds__(kBlock) void occ_composite_fwd_kernel(
 // are summed in a fixed order and leave the workgroup as ONE float atomic per matrix entry (the
 // first version issued one per wave, tile and entry: thousands of waves on a few hundred addresses,
 // 0.37 ms for 22 MB at the LVD recipe -- the pattern measured 14x below the streaming atomic rate).
-template <int LP>
+// DET (deterministic mode): grad_occ is a slab of one L x L row per workgroup, stored, not added (det_common.hip.h).
+template <int LP, bool DET = false>
 __global__ __launch_bounds__(kBlock) void occ_composite_bwd_kernel(
     const float* __restrict__ alpha, const float* __restrict__ occ,
     const float* __restrict__ grad_out, float* __restrict__ grad_alpha,
@@ -110,8 +111,12 @@ __global__ __launch_bounds__(kBlock) void occ_composite_bwd_kernel(
     __syncthreads();
     for (int e = threadIdx.x; e < LP * LP; e += kBlock) {
       const int i = e / LP, j = e % LP;
-      if (i < L && j < L)
-        atomicAdd(grad_occ + (m / occ_div) * L * L + i * L + j, (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]));
+      if (i < L && j < L) {
+        if constexpr (DET)
+          grad_occ[(int64_t)blockIdx.x * L * L + i * L + j] = (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]);
+        else
+          atomicAdd(grad_occ + (m / occ_div) * L * L + i * L + j, (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]));
+      }
     }
   }
 }
@@ -152,6 +157,14 @@ extern "C" int waldo_occ_composite_fwd(const float* alpha, const float* occ, flo
   return launch_status("waldo_occ_composite_fwd");
 }
 
+static int occ_bwd_tiles_per_block(int64_t M, int tiles, bool want_occ) {
+  // several pixel tiles per workgroup (fewer atomics per matrix entry) while keeping >= ~1024
+  // workgroups in flight
+  int tpb = (int)min((int64_t)16, max((int64_t)1, (M * tiles) / 1024));
+  if (!want_occ) tpb = 1;
+  return tpb;
+}
+
 extern "C" int waldo_occ_composite_bwd(const float* alpha, const float* occ,
                                        const float* grad_out, float* grad_alpha, float* grad_occ,
                                        int64_t M, int L, int64_t HW, int64_t occ_div,
@@ -165,14 +178,59 @@ extern "C" int waldo_occ_composite_bwd(const float* alpha, const float* occ,
   }
   hipStream_t st = (hipStream_t)stream;
   const int tiles = (int)((HW + kBlock - 1) / kBlock);
-  // several pixel tiles per workgroup (fewer atomics per matrix entry) while keeping >= ~1024
-  // workgroups in flight
-  int tpb = (int)min((int64_t)16, max((int64_t)1, (M * tiles) / 1024));
-  if (grad_occ == nullptr) tpb = 1;
+  const int tpb = occ_bwd_tiles_per_block(M, tiles, grad_occ != nullptr);
   const int groups = (tiles + tpb - 1) / tpb;
   with_padded_layers(L, [&](auto lp) {
     hipLaunchKernelGGL((occ_composite_bwd_kernel<decltype(lp)::value>), dim3((unsigned)(M * groups)), dim3(kBlock), 0,
                        st, alpha, occ, grad_out, grad_alpha, grad_occ, L, HW, tiles, tpb, groups, occ_div);
   });
   return launch_status("waldo_occ_composite_bwd");
+}
+
+// ---- deterministic mode: grad_occ (ceil(M / occ_div) matrices) OVERWRITTEN; slab form
+extern "C" int64_t waldo_occ_composite_bwd_det_workspace_bytes(int64_t M, int L, int64_t HW) {
+  if (M < 0 || L < 1 || L > 32 || HW < 1) return 0;
+  const int tiles = (int)((HW + kBlock - 1) / kBlock);
+  return round256(M * ((tiles + kDetTilesPerBlock - 1) / kDetTilesPerBlock) * L * L * 4);
+}
+
+extern "C" int waldo_occ_composite_bwd_det(const float* alpha, const float* occ, const float* grad_out,
+                                           float* grad_alpha, float* grad_occ, int64_t M, int L, int64_t HW,
+                                           int64_t occ_div, void* workspace, int64_t workspace_bytes,
+                                           waldo_stream_t stream) {
+  const char* fn = "waldo_occ_composite_bwd_det";
+  int rc = check_occ(fn, M, L, HW, occ_div);
+  if (rc) return rc;
+  const int64_t need = grad_occ != nullptr ? waldo_occ_composite_bwd_det_workspace_bytes(M, L, HW) : 0;
+  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) {
+    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
+              (long long)need);
+    return WALDO_EINVAL;
+  }
+  if (M == 0) return WALDO_OK;
+  if (!alpha || !occ || !grad_out || !grad_alpha) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = (int)((HW + kBlock - 1) / kBlock);
+  const int tpb = grad_occ != nullptr ? kDetTilesPerBlock : 1;
+  const int groups = (tiles + tpb - 1) / tpb;
+  float* slab = reinterpret_cast<float*>(workspace);
+  with_padded_layers(L, [&](auto lp) {
+    constexpr int LP = decltype(lp)::value;
+    if (grad_occ != nullptr)
+      hipLaunchKernelGGL((occ_composite_bwd_kernel<LP, true>), dim3((unsigned)(M * groups)), dim3(kBlock), 0, st, alpha,
+                         occ, grad_out, grad_alpha, slab, L, HW, tiles, tpb, groups, occ_div);
+    else
+      hipLaunchKernelGGL((occ_composite_bwd_kernel<LP>), dim3((unsigned)(M * groups)), dim3(kBlock), 0, st, alpha, occ,
+                         grad_out, grad_alpha, grad_occ, L, HW, tiles, tpb, groups, occ_div);
+  });
+  if (grad_occ != nullptr) {
+    // matrix d sums the workgroups of maps d * occ_div .. (d + 1) * occ_div - 1: consecutive rows of the slab
+    const int64_t D = (M + occ_div - 1) / occ_div;
+    const int nparts = (int)((occ_div < M ? occ_div : M) * groups);
+    slab_reduce(slab, grad_occ, D, nparts, L * L, SlabPlain{M * groups, D, D}, st);
+  }
+  return launch_status(fn);
 }

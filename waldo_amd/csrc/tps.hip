@@ -3,7 +3,7 @@
 //   grid    = basis @ mapping       (output-bound: 8 B written per pixel per map)
 // The basis is stored transposed (K3, HW): lane i of a wavefront reads pixel p0+i of basis
 // function k, one coalesced 256-B request per k.
-#include "waldo_common.hip.h"
+#include "det_common.hip.h"
 
 namespace waldo {
 
@@ -144,6 +144,9 @@ constexpr int kGradMaxK = 136;  // K3 values whose partial sums fit the workgrou
 // four rows are summed in a fixed order and leave the workgroup as ONE float atomic per (map, k,
 // component) -- the first version issued one per wave and chunk on a few hundred addresses, the
 // pattern measured 14x below the streaming atomic rate.  K3 > kGradMaxK: per-wave atomics as before.
+// DET (deterministic mode, K3 <= kGradMaxK only): gmap is a slab of one (K3, 2) row per (map, blockIdx.x), stored, not
+// added (det_common.hip.h).
+template <bool DET = false>
 __global__ __launch_bounds__(kBlock) void tps_grid_bwd_kernel(const float* __restrict__ basis_t,
                                                               const float* __restrict__ ggrid,
                                                               float* __restrict__ gmap, int64_t B,
@@ -214,9 +217,14 @@ __global__ __launch_bounds__(kBlock) void tps_grid_bwd_kernel(const float* __res
     __syncthreads();
     for (int e = kbeg * kGradNB * 2 + threadIdx.x; e < kend * kGradNB * 2; e += kBlock) {
       const int k = e / (kGradNB * 2), idx = e % (kGradNB * 2);
-      if (idx < nb * 2)
-        atomicAdd(gmap + ((b0 + (idx >> 1)) * K3 + k) * 2 + (idx & 1),
-                  (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]));
+      if (idx < nb * 2) {
+        if constexpr (DET)
+          gmap[(((b0 + (idx >> 1)) * gridDim.x + blockIdx.x) * K3 + k) * 2 + (idx & 1)] =
+              (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]);
+        else
+          atomicAdd(gmap + ((b0 + (idx >> 1)) * K3 + k) * 2 + (idx & 1),
+                    (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]));
+      }
     }
   }
 }
@@ -285,6 +293,27 @@ extern "C" int waldo_tps_grid_fwd(const float* basis_t, const float* mapping, fl
   return launch_status("waldo_tps_grid_fwd");
 }
 
+struct TpsGradGeom {
+  int chunks, kper;
+  dim3 grid;
+};
+
+static TpsGradGeom tps_grad_geom(int64_t B, int64_t HW, int K3, bool det = false) {
+  TpsGradGeom o;
+  const int64_t per_chunk = (int64_t)kBlock * kGradPPT;
+  const int64_t nchunks = (HW + per_chunk - 1) / per_chunk, groups_b = (B + kGradNB - 1) / kGradNB;
+  // several chunks per workgroup (fewer atomics per output) while keeping >= ~512 workgroups
+  o.chunks = (int)min((int64_t)16, max((int64_t)1, nchunks * groups_b / 512));
+  if (det) o.chunks = kDetTilesPerBlock;  // (a constant: the slab grows with every size)
+  // few workgroups (few, large maps): the basis functions are dealt over blockIdx.z, in multiples of kGradKB
+  const int64_t wgs = ((nchunks + o.chunks - 1) / o.chunks) * groups_b;
+  const int rounds = (K3 + kGradKB - 1) / kGradKB;
+  const int ksplit = (int)min((int64_t)rounds, max((int64_t)1, 512 / wgs));
+  o.kper = ((rounds + ksplit - 1) / ksplit) * kGradKB;
+  o.grid = dim3((unsigned)((nchunks + o.chunks - 1) / o.chunks), (unsigned)groups_b, (unsigned)((K3 + o.kper - 1) / o.kper));
+  return o;
+}
+
 extern "C" int waldo_tps_grid_bwd(const float* basis_t, const float* grad_grid,
                                   float* grad_mapping, int64_t B, int64_t HW, int K3,
                                   waldo_stream_t stream) {
@@ -300,17 +329,46 @@ extern "C" int waldo_tps_grid_bwd(const float* basis_t, const float* grad_grid,
   }
   hipStream_t st = (hipStream_t)stream;
   fill_words(grad_mapping, 0u, sizeof(float) * B * K3 * 2, st);
-  const int64_t per_chunk = (int64_t)kBlock * kGradPPT;
-  const int64_t nchunks = (HW + per_chunk - 1) / per_chunk, groups_b = (B + kGradNB - 1) / kGradNB;
-  // several chunks per workgroup (fewer atomics per output) while keeping >= ~512 workgroups
-  const int chunks = (int)min((int64_t)16, max((int64_t)1, nchunks * groups_b / 512));
-  // few workgroups (few, large maps): the basis functions are dealt over blockIdx.z, in multiples of kGradKB
-  const int64_t wgs = ((nchunks + chunks - 1) / chunks) * groups_b;
-  const int rounds = (K3 + kGradKB - 1) / kGradKB;
-  const int ksplit = (int)min((int64_t)rounds, max((int64_t)1, 512 / wgs));
-  const int kper = ((rounds + ksplit - 1) / ksplit) * kGradKB;
-  dim3 g((unsigned)((nchunks + chunks - 1) / chunks), (unsigned)groups_b, (unsigned)((K3 + kper - 1) / kper));
-  hipLaunchKernelGGL(tps_grid_bwd_kernel, g, dim3(kBlock), 0, st, basis_t, grad_grid,
-                     grad_mapping, B, HW, K3, chunks, kper);
+  const TpsGradGeom g = tps_grad_geom(B, HW, K3);
+  hipLaunchKernelGGL(tps_grid_bwd_kernel<false>, g.grid, dim3(kBlock), 0, st, basis_t, grad_grid,
+                     grad_mapping, B, HW, K3, g.chunks, g.kper);
   return launch_status("waldo_tps_grid_bwd");
+}
+
+// ---- deterministic mode: grad_mapping OVERWRITTEN; slab form.  K3 <= 136 (the LDS table of the workgroup's partials)
+extern "C" int64_t waldo_tps_grid_bwd_det_workspace_bytes(int64_t B, int64_t HW, int K3) {
+  if (B < 0 || HW < 1 || K3 < 3 || K3 > kGradMaxK || (B + kGradNB - 1) / kGradNB > 65535) return 0;
+  return round256(B * (int64_t)tps_grad_geom(B, HW, K3, true).grid.x * K3 * 2 * 4);
+}
+
+extern "C" int waldo_tps_grid_bwd_det(const float* basis_t, const float* grad_grid, float* grad_mapping, int64_t B,
+                                      int64_t HW, int K3, void* workspace, int64_t workspace_bytes,
+                                      waldo_stream_t stream) {
+  const char* fn = "waldo_tps_grid_bwd_det";
+  if (B < 0 || HW < 1 || K3 < 3 || (B + kGradNB - 1) / kGradNB > 65535) {
+    set_error("%s: bad shape B=%lld HW=%lld K3=%d", fn, (long long)B, (long long)HW, K3);
+    return WALDO_EINVAL;
+  }
+  if (K3 > kGradMaxK) {
+    set_error("%s: K3=%d: the deterministic sum needs the workgroup's table of partials (K3 <= %d)", fn, K3, kGradMaxK);
+    return WALDO_EINVAL;
+  }
+  const int64_t need = waldo_tps_grid_bwd_det_workspace_bytes(B, HW, K3);
+  if (B > 0 && (workspace == nullptr || workspace_bytes < need)) {
+    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
+              (long long)need);
+    return WALDO_EINVAL;
+  }
+  if (B == 0) return WALDO_OK;
+  if (!basis_t || !grad_grid || !grad_mapping) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const TpsGradGeom g = tps_grad_geom(B, HW, K3, true);
+  float* slab = reinterpret_cast<float*>(workspace);
+  hipLaunchKernelGGL(tps_grid_bwd_kernel<true>, g.grid, dim3(kBlock), 0, st, basis_t, grad_grid, slab, B, HW, K3,
+                     g.chunks, g.kper);
+  slab_reduce(slab, grad_mapping, B, (int)g.grid.x, K3 * 2, SlabPlain{B * (int64_t)g.grid.x, B, B}, st);
+  return launch_status(fn);
 }

@@ -16,7 +16,7 @@ void wc_fwd(bool k19, const T* layers, const float* basis_t, const float* mappin
 template <int LP, typename T>
 void wc_bwd(bool k19, const T* layers, const float* basis_t, const float* mapping, const float* occ,
             const float* grad_rgb, const float* grad_alpha, T* grad_layers, float* grad_mapping, float* grad_occ,
-            void* workspace, int F, int L, int H, int W, int K3, float delta, hipStream_t st);
+            void* workspace, int F, int L, int H, int W, int K3, float delta, hipStream_t st, float* occ_slab);
 
 static int check_common(const char* fn, int64_t F, int L, int H, int W, int K3) {
   if (F < 0 || L < 1 || L > kMaxLayers || H < 1 || W < 1 || K3 < 3 || K3 > kMaxK3) {
@@ -122,14 +122,50 @@ int warp_composite_pts_fwd(const char* fn, const T* layers, const float* basis_t
   return launch_status(fn);
 }
 
+// slab of the deterministic grad_occ: one L x L row per (frame, 16 x 16 tile, wave) of K1
+int64_t occ_slab_bytes(int64_t F, int L, int H, int W) { return round256(F * bwd2_layout(F, L, H, W).ntiles16 * 4 * L * L * 4); }
+
+// det: the *_det entry points -- two-kernel backward only, its workspace followed by the grad_occ slab; grad_mapping
+// and grad_occ are overwritten
 template <typename T>
 int warp_composite_bwd(const char* fn, const T* layers, const float* basis_t, const float* mapping, const float* occ,
                        const float* grad_rgb, const float* grad_alpha, T* grad_layers, float* grad_mapping,
                        float* grad_occ, void* workspace, int64_t workspace_bytes, int64_t F, int L, int H, int W,
-                       int K3, float delta, waldo_stream_t stream) {
+                       int K3, float delta, waldo_stream_t stream, bool det = false) {
   constexpr bool kF32 = std::is_same_v<T, float>;
   int rc = check_common(fn, F, L, H, W, K3);
   if (rc) return rc;
+  if (det) {
+    const int64_t need2 = bwd_workspace_bytes(F > 0 ? F : 1, L, H, W, K3);
+    if (need2 == 0) {
+      set_error("%s: no deterministic kernel for this shape: it needs the two-kernel backward (K3 == 19, L <= %d, "
+                "W %% 4 == 0, H, W >= 2); the generic backward sums with float atomics: L=%d H=%d W=%d K3=%d", fn,
+                kBwd2MaxLayers, L, H, W, K3);
+      return WALDO_EINVAL;
+    }
+    if (F == 0) return WALDO_OK;
+    const int64_t need = bwd_workspace_bytes(F, L, H, W, K3), total = need + occ_slab_bytes(F, L, H, W);
+    if (workspace == nullptr || workspace_bytes < total) {
+      set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
+                (long long)total);
+      return WALDO_EINVAL;
+    }
+    if (!layers || !basis_t || !mapping || !occ || !grad_rgb || !grad_layers) {
+      set_error("%s: null pointer", fn);
+      return WALDO_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // (the reduction of the control-point partials adds to grad_mapping)
+    if (grad_mapping != nullptr) fill_words(grad_mapping, 0u, sizeof(float) * (size_t)F * L * K3 * 2, st);
+    float* slab = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + need);
+    with_padded_layers(L, [&](auto lp) {
+      constexpr int LP = decltype(lp)::value;
+      if constexpr (LP <= kBwd2MaxLayers)
+        wc_bwd<LP>(true, layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers, grad_mapping, grad_occ,
+                   workspace, (int)F, L, H, W, K3, delta, st, slab);
+    });
+    return launch_status(fn);
+  }
   // a 16-bit stack is served by the two-kernel backward alone (whose size query does not depend on F being 0)
   if (!kF32 && waldo_warp_composite_bwd_workspace_bytes(F > 0 ? F : 1, L, H, W, K3) == 0) {
     set_error("%s: a 16-bit layer stack needs the two-kernel backward (K3 == 19, L <= %d, W %% 4 == 0, H, W >= 2, "
@@ -160,7 +196,7 @@ int warp_composite_bwd(const char* fn, const T* layers, const float* basis_t, co
     constexpr int LP = decltype(lp)::value;
     if constexpr (kF32 || LP <= kBwd2MaxLayers)
       wc_bwd<LP>(K3 == 19, layers, basis_t, mapping, occ, grad_rgb, grad_alpha, grad_layers, grad_mapping, grad_occ,
-                 workspace, (int)F, L, H, W, K3, delta, st);
+                 workspace, (int)F, L, H, W, K3, delta, st, nullptr);
   });
   return launch_status(fn);
 }
@@ -230,5 +266,27 @@ extern "C" int waldo_warp_composite_bwd_dt(const void* layers, const float* basi
     return warp_composite_bwd(fn, static_cast<const T*>(layers), basis_t, mapping, occ, grad_rgb, grad_alpha,
                               static_cast<T*>(grad_layers), grad_mapping, grad_occ, workspace, workspace_bytes, F, L,
                               H, W, K3, delta, stream);
+  });
+}
+
+// ---- deterministic mode: the two-kernel backward with grad_occ in slab form; grad_layers, grad_mapping and grad_occ
+// are OVERWRITTEN.  0: no deterministic kernel for the shape (the generic backward would serve it)
+extern "C" int64_t waldo_warp_composite_bwd_det_workspace_bytes(int64_t F, int L, int H, int W, int K3) {
+  if (F < 0 || L < 1 || H < 1 || W < 1) return 0;
+  const int64_t need = bwd_workspace_bytes(F, L, H, W, K3);
+  return need == 0 ? 0 : need + occ_slab_bytes(F, L, H, W);
+}
+
+extern "C" int waldo_warp_composite_bwd_det(const void* layers, const float* basis_t, const float* mapping,
+                                            const float* occ, const float* grad_rgb, const float* grad_alpha,
+                                            void* grad_layers, float* grad_mapping, float* grad_occ, void* workspace,
+                                            int64_t workspace_bytes, int64_t F, int L, int H, int W, int K3,
+                                            float delta, int layers_dtype, waldo_stream_t stream) {
+  const char* fn = "waldo_warp_composite_bwd_det";
+  return layers_dispatch(fn, layers_dtype, [&](auto lt) {
+    using T = decltype(lt);
+    return warp_composite_bwd(fn, static_cast<const T*>(layers), basis_t, mapping, occ, grad_rgb, grad_alpha,
+                              static_cast<T*>(grad_layers), grad_mapping, grad_occ, workspace, workspace_bytes, F, L,
+                              H, W, K3, delta, stream, true);
   });
 }

@@ -83,7 +83,9 @@ struct Px16Cfg {
 };
 
 // TL: element type of the layer stack (float, or __bf16 / _Float16: staged as in warp_composite_fwd_lds_kernel)
-template <int LP, bool EXL, bool GOCC, typename TL = float>
+// DET (deterministic mode, with GOCC): grad_occ is a slab of one L x L row per (frame, tile, wave), stored, not added
+// (det_common.hip.h; every row is written exactly once)
+template <int LP, bool EXL, bool GOCC, typename TL = float, bool DET = false>
 __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) void warp_composite_bwd_px16_kernel(
     const TL* __restrict__ layers, const float* __restrict__ basis_t,
     const float* __restrict__ mapping, const float* __restrict__ occ,
@@ -468,13 +470,21 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
         }
         if (GOCC) {  // compile-time: the reduction costs ~60 registers
           const int m = bitrev6(lane);
+          [[maybe_unused]] float* go_row = nullptr;
+          if constexpr (DET) go_row = grad_occ + ((((int64_t)f * ntiles + tile) * 4 + wave) * L) * L;
           if (EXL || j < L) {
             const float redv = wave_transpose_reduce<LP>(gocc0, lane);
-            if (m < L) atomicAdd(grad_occ + (int64_t)f * L * L + m * L + j, redv);
+            if (m < L) {
+              if constexpr (DET) go_row[m * L + j] = redv;
+              else atomicAdd(grad_occ + (int64_t)f * L * L + m * L + j, redv);
+            }
           }
           if (has1 && (EXL || j + 1 < L)) {
             const float redv = wave_transpose_reduce<LP>(gocc1, lane);
-            if (m < L) atomicAdd(grad_occ + (int64_t)f * L * L + m * L + j + 1, redv);
+            if (m < L) {
+              if constexpr (DET) go_row[m * L + j + 1] = redv;
+              else atomicAdd(grad_occ + (int64_t)f * L * L + m * L + j + 1, redv);
+            }
           }
         }
       }

@@ -18,15 +18,16 @@ void wc_fwd(bool k19, const T* layers, const float* basis_t, const float* mappin
     launch_fwd<LP, 32, false>(layers, basis_t, mapping, nullptr, nullptr, occ, rgb, alpha, F, L, H, W, K3, delta, st);
 }
 
-// `workspace` != nullptr selects the two-kernel backward (compiled for L <= kBwd2MaxLayers, K3 == 19)
+// `workspace` != nullptr selects the two-kernel backward (compiled for L <= kBwd2MaxLayers, K3 == 19); with
+// `occ_slab` its deterministic grad_occ (launch_bwd2)
 template <int LP, typename T>
 void wc_bwd(bool k19, const T* layers, const float* basis_t, const float* mapping, const float* occ,
             const float* grad_rgb, const float* grad_alpha, T* grad_layers, float* grad_mapping, float* grad_occ,
-            void* workspace, int F, int L, int H, int W, int K3, float delta, hipStream_t st) {
+            void* workspace, int F, int L, int H, int W, int K3, float delta, hipStream_t st, float* occ_slab) {
   if constexpr (LP <= kBwd2MaxLayers) {
     if (k19 && workspace != nullptr) {
       launch_bwd2<LP>(layers, basis_t, mapping, occ, grad_rgb, grad_alpha, workspace, grad_layers, grad_mapping,
-                      grad_occ, F, L, H, W, delta, st);
+                      grad_occ, F, L, H, W, delta, st, occ_slab);
       return;
     }
   }

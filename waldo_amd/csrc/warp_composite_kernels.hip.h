@@ -368,6 +368,7 @@ void launch_splat(const float* rec, const float* grad_rgb, const int* cellbox,
 
 }  // namespace waldo
 
+#include "det_common.hip.h"
 #include "warp_composite_fwd_lds.hip.h"
 #include "warp_composite_bwd_px16.hip.h"
 
@@ -477,11 +478,13 @@ static void launch_bwd(const float* layers, const float* basis_t, const float* m
 // only slow each other down; a timing-only build whose records never leave the cache bounds the
 // prize at 9 % of the backward.  DESIGN.md section 4.)
 // T: element type of the layer stack and of grad_layers (K2 rounds the fp32 sums to it)
+// occ_slab != nullptr (deterministic mode): K1 stores its per-wave grad_occ sums there and a fixed-order reduction
+// overwrites grad_occ (det_common.hip.h)
 template <int LP, typename T>
 static void launch_bwd2(const T* layers, const float* basis_t, const float* mapping,
                         const float* occ, const float* grad_rgb, const float* grad_alpha,
                         void* workspace, T* grad_layers, float* grad_mapping, float* grad_occ,
-                        int F, int L, int H, int W, float delta, hipStream_t st) {
+                        int F, int L, int H, int W, float delta, hipStream_t st, float* occ_slab = nullptr) {
   const Bwd2Layout lo = bwd2_layout(F, L, H, W);
   char* ws = reinterpret_cast<char*>(workspace);
   int* boxes = reinterpret_cast<int*>(ws);
@@ -505,7 +508,15 @@ static void launch_bwd2(const T* layers, const float* basis_t, const float* mapp
                        grad_occ, F, L, H, W, fpb, lo.ntx16, ntiles, nchunks, nbands, lo.ncx, lo.ncells,
                        delta);
   };
-  if (L == LP) {
+  if (grad_occ != nullptr && occ_slab != nullptr) {
+    auto go_det = [&](auto exl) {
+      hipLaunchKernelGGL((warp_composite_bwd_px16_kernel<LP, decltype(exl)::value, true, T, true>), grid, dim3(kBlock), 0,
+                         st, layers, basis_t, mapping, occ, grad_rgb, grad_alpha, rec, boxes, bounds, part, occ_slab, F,
+                         L, H, W, fpb, lo.ntx16, ntiles, nchunks, nbands, lo.ncx, lo.ncells, delta);
+    };
+    if (L == LP) go_det(Y{}); else go_det(N{});
+    slab_reduce(occ_slab, grad_occ, F, ntiles * 4, L * L, SlabPlain{(int64_t)F * ntiles * 4, F, F}, st);
+  } else if (L == LP) {
     if (grad_occ != nullptr) go(Y{}, Y{}); else go(Y{}, N{});
   } else {
     if (grad_occ != nullptr) go(N{}, Y{}); else go(N{}, N{});

@@ -15,6 +15,70 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# --------------------------------------------------------------------------------------
+# deterministic mode (include/waldo_hip.h "Reproducible gradients")
+# --------------------------------------------------------------------------------------
+_deterministic = None  # None: follow torch.are_deterministic_algorithms_enabled(); True / False: override it
+
+
+def set_deterministic(mode):
+    """Deterministic mode: every gradient of the library is a function of the inputs alone (the same bits from run to
+    run, eagerly or replayed from a HIP graph) -- the ``*_det`` entry points replace the backward kernels that sum
+    with float atomics.  ``True`` / ``False`` switch it on / off; ``None`` (the default) follows
+    ``torch.are_deterministic_algorithms_enabled()``.  The mode is read when an op's FORWARD runs and travels with the
+    autograd node: a graph built in one mode runs its backward in that mode.  A shape without a deterministic kernel
+    raises ``WaldoHipError`` from the forward when a gradient is required."""
+    global _deterministic
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError(f"set_deterministic: mode must be True, False or None, got {mode!r}")
+    _deterministic = mode
+
+
+def is_deterministic():
+    """Whether an op whose forward runs now will run its backward on the deterministic kernels."""
+    if _deterministic is None:
+        return bool(torch.are_deterministic_algorithms_enabled())
+    return _deterministic
+
+
+class deterministic:
+    """``with deterministic(mode=True):`` -- ``set_deterministic(mode)`` for the block; the earlier setting comes back
+    on exit, also after an exception.  Nests."""
+
+    def __init__(self, mode=True):
+        if mode is not None and not isinstance(mode, bool):
+            raise TypeError(f"deterministic: mode must be True, False or None, got {mode!r}")
+        self.mode = mode
+        self.prev = []
+
+    def __enter__(self):
+        self.prev.append(_deterministic)
+        set_deterministic(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev.pop())
+        return False
+
+
+def _det_unserved(op, reason):
+    return _lib.WaldoHipError(f"{op}: no deterministic kernel ({reason}); deterministic mode is on "
+                              "(waldo_amd.set_deterministic / torch.use_deterministic_algorithms) and a gradient is "
+                              "required")
+
+
+def _det_workspace(op, query, args, device):
+    """(buffer, bytes) for a ``*_det`` entry point: its ``*_det_workspace_bytes`` query, at least one word."""
+    nbytes = int(_lib.query(query, *args))
+    if nbytes <= 0:
+        raise _det_unserved(op, f"{query}{tuple(args)} = {nbytes}")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device), nbytes
+
+
+_SPLAT_MAX_CONTRIBUTIONS = 1 << 32  # per texel (include/waldo_hip.h)
+_TPS_DET_MAX_K3 = 136
+
+
 _MERGE_FILL_BYTES = 1 << 20
 
 
@@ -136,6 +200,9 @@ class _TpsGrid(torch.autograd.Function):
                       b, hw, k3, _lib.current_stream(mapping.device))
         ctx.save_for_backward(basis_t)
         ctx.k3 = k3
+        ctx.det = is_deterministic()
+        if ctx.det and ctx.needs_input_grad[1] and k3 > _TPS_DET_MAX_K3:
+            raise _det_unserved("tps_grid", f"K3 = {k3} > {_TPS_DET_MAX_K3}")
         return grid
 
     @staticmethod
@@ -144,6 +211,13 @@ class _TpsGrid(torch.autograd.Function):
         grad_grid = _c(grad_grid)
         b, hw, _ = grad_grid.shape
         grad_mapping = grad_grid.new_empty(b, ctx.k3, 2)  # zero-filled by the launcher
+        if ctx.det:
+            with _lib.on_device(grad_grid.device):
+                ws, nb = _det_workspace("tps_grid", "waldo_tps_grid_bwd_det_workspace_bytes", (b, hw, ctx.k3),
+                                        grad_grid.device)
+                _lib.call("waldo_tps_grid_bwd_det", _lib.ptr(basis_t), _lib.ptr(grad_grid), _lib.ptr(grad_mapping), b,
+                          hw, ctx.k3, _lib.ptr(ws), nb, _lib.current_stream(grad_grid.device))
+            return None, grad_mapping
         with _lib.on_device(grad_grid.device):
             _lib.call("waldo_tps_grid_bwd", _lib.ptr(basis_t), _lib.ptr(grad_grid),
                       _lib.ptr(grad_mapping), b, hw, ctx.k3,
@@ -253,6 +327,20 @@ def inverse_warp(src_grid, src_id, tgt_id, gauss, niter=5, erode=True, perm=None
 # --------------------------------------------------------------------------------------
 # A4/A5: bilinear warp
 # --------------------------------------------------------------------------------------
+def _gs_det_check(op, n, hwo, outer_div, inner):
+    """The deterministic splat's limit: a texel of grad_input receives at most copies * Ho * Wo contributions."""
+    copies = max(1, min(n, -(-outer_div // inner)))
+    if copies * hwo > _SPLAT_MAX_CONTRIBUTIONS:
+        raise _det_unserved(op, f"a texel of grad_input may receive {copies * hwo} > 2^32 contributions")
+
+
+def _gs_det_workspace(gi, n, nin, c, hi, wi, ho, wo, device):
+    if gi is None:  # (the grid's gradient alone: written per pixel, nothing to sum)
+        return None, 0
+    return _det_workspace("grid_sample", "waldo_grid_sample2d_bwd_det_workspace_bytes", (n, nin, c, hi, wi, ho, wo),
+                          device)
+
+
 class _GridSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, grid, delta, outer_div, inner, want_mask=False):
@@ -279,6 +367,9 @@ class _GridSample(torch.autograd.Function):
                           _lib.current_stream(inp.device))
         ctx.save_for_backward(inp, grid)
         ctx.cfg = (float(delta), outer_div, inner)
+        ctx.det = is_deterministic()
+        if ctx.det and ctx.needs_input_grad[0]:
+            _gs_det_check("grid_sample", n, ho * wo, outer_div, inner)
         if want_mask:
             ctx.mark_non_differentiable(mask)
             return out, mask
@@ -291,6 +382,15 @@ class _GridSample(torch.autograd.Function):
         grad_out = _c(grad_out)
         nin, c, hi, wi = inp.shape
         n, ho, wo, _ = grid.shape
+        if ctx.det:
+            gi = torch.empty_like(inp) if ctx.needs_input_grad[0] else None
+            gg = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
+            with _lib.on_device(inp.device):
+                ws, nb = _gs_det_workspace(gi, n, nin, c, hi, wi, ho, wo, inp.device)
+                _lib.call("waldo_grid_sample2d_bwd_det", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(grad_out), _lib.ptr(gi),
+                          _lib.ptr(gg), n, nin, c, hi, wi, ho, wo, delta, outer_div, inner, _lib.ptr(ws), nb,
+                          _lib.current_stream(inp.device))
+            return gi, gg, None, None, None, None
         gi = torch.zeros_like(inp) if ctx.needs_input_grad[0] else None
         gg = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
         with _lib.on_device(inp.device):
@@ -380,6 +480,11 @@ class _LayersToOutput(torch.autograd.Function):
                           *slots, float(pre[0]), float(pre[1]), _lib.current_stream(obj.device))
         ctx.save_for_backward(obj, bg, grid_obj, grid_bg)
         ctx.cfg = (float(delta_obj), float(delta_bg), obj_bc, bg_bc, (float(pre[0]), float(pre[1])), no)
+        ctx.det = is_deterministic()
+        if ctx.det:
+            for need, n, bc in ((ctx.needs_input_grad[0], nf * no, obj_bc), (ctx.needs_input_grad[1], nf, bg_bc)):
+                if need and n > 0:
+                    _gs_det_check("layers_to_output", n, h * w, *(bc if bc is not None else (n, n)))
         if want_mask:
             ctx.mark_non_differentiable(mask)
             return out, mask
@@ -395,14 +500,23 @@ class _LayersToOutput(torch.autograd.Function):
         grad_out = _c(grad_out)
         need = ctx.needs_input_grad
         res = []
-        gis = _zeros_like_each(obj if need[0] else None, bg if need[1] else None)
+        if ctx.det:  # (overwritten by the kernels)
+            gis = [torch.empty_like(obj) if need[0] else None, torch.empty_like(bg) if need[1] else None]
+        else:
+            gis = _zeros_like_each(obj if need[0] else None, bg if need[1] else None)
         calls = ((obj, grid_obj, nf * no, delta_obj, obj_bc, (no, nl, 1), gis[0], need[2]),
                  (bg, grid_bg, nf, delta_bg, bg_bc, (1, nl, 0), gis[1], need[3]))
         with _lib.on_device(obj.device):
             for inp, grid, n, delta, bc, slots, gi, want_g in calls:
                 want_i = gi is not None
                 gg = torch.empty_like(grid) if want_g else None
-                if n > 0 and (want_i or want_g):
+                if ctx.det and (want_i or want_g):
+                    od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
+                    ws, nb = _gs_det_workspace(gi, n, inp.shape[0], c, inp.shape[2], inp.shape[3], h, w, obj.device)
+                    _lib.call("waldo_grid_sample2d_ex_bwd_det", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(grad_out),
+                              _lib.ptr(gi), _lib.ptr(gg), n, inp.shape[0], c, inp.shape[2], inp.shape[3], h, w, delta,
+                              od, inn, *slots, pre[0], pre[1], _lib.ptr(ws), nb, _lib.current_stream(obj.device))
+                elif n > 0 and (want_i or want_g):
                     od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
                     _lib.call("waldo_grid_sample2d_ex_bwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(grad_out),
                               _lib.ptr(gi), _lib.ptr(gg), n, c, inp.shape[2], inp.shape[3], h, w, delta, od, inn,
@@ -465,6 +579,7 @@ class _OccComposite(torch.autograd.Function):
                       nl, hw, occ_div, _lib.current_stream(alpha.device))
         ctx.save_for_backward(alpha, occ)
         ctx.occ_div = occ_div
+        ctx.det = is_deterministic()
         return out
 
     @staticmethod
@@ -473,6 +588,16 @@ class _OccComposite(torch.autograd.Function):
         grad_out = _c(grad_out)
         m, nl, hw = alpha.shape
         ga = torch.empty_like(alpha)
+        if ctx.det and ctx.needs_input_grad[1]:
+            go = torch.empty_like(occ)
+            with _lib.on_device(alpha.device):
+                ws, nb = _det_workspace("occ_composite", "waldo_occ_composite_bwd_det_workspace_bytes", (m, nl, hw),
+                                        alpha.device)
+                if occ.shape[0] * ctx.occ_div != m:  # (matrices no map reads: the kernel overwrites those it sums)
+                    go.zero_()
+                _lib.call("waldo_occ_composite_bwd_det", _lib.ptr(alpha), _lib.ptr(occ), _lib.ptr(grad_out), _lib.ptr(ga),
+                          _lib.ptr(go), m, nl, hw, ctx.occ_div, _lib.ptr(ws), nb, _lib.current_stream(alpha.device))
+            return ga, go, None
         go = torch.zeros_like(occ) if ctx.needs_input_grad[1] else None
         with _lib.on_device(alpha.device):
             _lib.call("waldo_occ_composite_bwd", _lib.ptr(alpha), _lib.ptr(occ),
@@ -765,6 +890,7 @@ class _FlowCtxAlpha(torch.autograd.Function):
                       scale, _lib.current_stream(alpha_lr.device))
         ctx.save_for_backward(alpha_lr, input, dist, occ)
         ctx.cfg = (tw, chan_off, scale)
+        ctx.det = is_deterministic()
         ctx.set_materialize_grads(False)  # backward below handles a missing gradient of either output
         return a01, out
 
@@ -782,6 +908,17 @@ class _FlowCtxAlpha(torch.autograd.Function):
         g_a01 = _c(g_a01) if g_a01 is not None else None
         g_out = _c(g_out) if g_out is not None else None
         g_lr = torch.empty_like(alpha_lr)
+        if ctx.det:
+            g_dist = torch.empty_like(dist) if (dist is not None and ctx.needs_input_grad[2]) else None
+            g_occ = torch.empty_like(occ) if ctx.needs_input_grad[3] else None
+            with _lib.on_device(alpha_lr.device):
+                ws, nb = _det_workspace("flow_ctx_alpha", "waldo_flow_ctx_alpha_bwd_det_workspace_bytes",
+                                        (b, tw, nl, ncls, h, w, scale), alpha_lr.device)
+                _lib.call("waldo_flow_ctx_alpha_bwd_det", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist),
+                          _lib.ptr(occ), _lib.ptr(g_a01), _lib.ptr(g_out), _lib.ptr(g_lr), _lib.ptr(g_dist),
+                          _lib.ptr(g_occ), _lib.ptr(ws), nb, b, t, tw, nl, ncls, c, chan_off, h, w, scale,
+                          _lib.current_stream(alpha_lr.device))
+            return g_lr, None, g_dist, g_occ, None, None, None
         g_dist, g_occ = _zeros_like_each(dist if (dist is not None and ctx.needs_input_grad[2]) else None,
                                          occ if ctx.needs_input_grad[3] else None)
         ws = alpha_lr.new_empty(n, nl, hd, wd) if scale > 1 else None
@@ -864,6 +1001,9 @@ class _FlowCtxWarp(torch.autograd.Function):
                       h, w, scale, _lib.current_stream(flow_lr.device))
         ctx.save_for_backward(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ)
         ctx.cfg = (tw, scale)
+        ctx.det = is_deterministic()
+        if ctx.det and ctx.needs_input_grad[2] and tc * tp * hd * wd > _SPLAT_MAX_CONTRIBUTIONS:
+            raise _det_unserved("flow_ctx_warp", f"a texel of grad_a01 may receive {tc * tp * hd * wd} > 2^32 contributions")
         ctx.mark_non_differentiable(amax)
         ctx.set_materialize_grads(False)  # unused outputs: None, not zero-filled tensors (the kernel takes NULL)
         return flow, alpha_ctx, disocc, amax
@@ -880,6 +1020,17 @@ class _FlowCtxWarp(torch.autograd.Function):
         g_actx = _c(g_actx) if g_actx is not None else None
         g_dis = _c(g_dis) if g_dis is not None else None
         g_lr = torch.empty_like(flow_lr)
+        if ctx.det:
+            g_a01 = torch.empty_like(a01) if ctx.needs_input_grad[2] else None
+            g_occ = torch.empty_like(occ) if ctx.needs_input_grad[5] else None
+            with _lib.on_device(flow_lr.device):
+                ws, nb = _det_workspace("flow_ctx_warp", "waldo_flow_ctx_warp_bwd_det_workspace_bytes",
+                                        (b, tw, tc, tp, nl, h, w, scale), flow_lr.device)
+                _lib.call("waldo_flow_ctx_warp_bwd_det", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
+                          _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(g_flow), _lib.ptr(g_actx),
+                          _lib.ptr(g_dis), _lib.ptr(g_lr), _lib.ptr(g_a01), _lib.ptr(g_occ), _lib.ptr(ws), nb, b, t, tw,
+                          tc, tp, nl, h, w, scale, _lib.current_stream(flow_lr.device))
+            return g_lr, None, g_a01, None, None, g_occ, None, None, None, None, None
         g_a01, g_occ = _zeros_like_each(a01 if ctx.needs_input_grad[2] else None, occ if ctx.needs_input_grad[5] else None)
         ws = flow_lr.new_empty(m, nl, 2, hd, wd) if scale > 1 else None
         with _lib.on_device(flow_lr.device):
@@ -1513,6 +1664,11 @@ class _WarpComposite(torch.autograd.Function):
         ctx.save_for_backward(layers, mapping, occ, basis_t)
         ctx.want_alpha = want_alpha
         ctx.delta = float(delta)
+        ctx.det = is_deterministic()
+        if ctx.det and any(ctx.needs_input_grad[:3]) and f > 0 and \
+                _lib.query("waldo_warp_composite_bwd_det_workspace_bytes", f, nl, h, w, k3) <= 0:
+            raise _det_unserved("warp_composite", f"L = {nl}, K3 = {k3}, W = {w}: the generic backward sums with float "
+                                "atomics; the two-kernel backward needs L <= 17, K3 == 19 and 4 | W")
         return rgb, alpha
 
     @staticmethod
@@ -1523,6 +1679,19 @@ class _WarpComposite(torch.autograd.Function):
         grad_rgb = _c(grad_rgb)
         if grad_alpha is not None:
             grad_alpha = _c(grad_alpha)
+        if ctx.det:
+            gm = torch.empty_like(mapping) if ctx.needs_input_grad[1] else None
+            go = torch.empty_like(occ) if ctx.needs_input_grad[2] else None
+            gl = torch.empty_like(layers)
+            if f > 0:
+                with _lib.on_device(layers.device):
+                    ws, nb = _det_workspace("warp_composite", "waldo_warp_composite_bwd_det_workspace_bytes",
+                                            (f, nl, h, w, k3), layers.device)
+                    _lib.call("waldo_warp_composite_bwd_det", _lib.ptr(layers), _lib.ptr(basis_t), _lib.ptr(mapping),
+                              _lib.ptr(occ), _lib.ptr(grad_rgb), _lib.ptr(grad_alpha), _lib.ptr(gl), _lib.ptr(gm),
+                              _lib.ptr(go), _lib.ptr(ws), nb, f, nl, h, w, k3, ctx.delta, _DTYPE_CODE[layers.dtype],
+                              _lib.current_stream(layers.device))
+            return gl, gm, go, None, None, None
         gm, go = _zeros_like_each(mapping if ctx.needs_input_grad[1] else None, occ if ctx.needs_input_grad[2] else None)
         # 0: the shape is served by the generic kernel (or a test asked for it: WALDO_DEBUG_BWD_GENERIC)
         ws_bytes = _lib.load().waldo_warp_composite_bwd_workspace_bytes(f, nl, h, w, k3)
