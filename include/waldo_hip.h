@@ -563,6 +563,53 @@ int waldo_mask_expand_fwd(const float* mask, float* out, float* scratch, int64_t
  * ------------------------------------------------------------------------------------- */
 int waldo_points_in_polygon_fwd(const float* pts, const double* corners_host, int K, float* out, int64_t N,
                                 waldo_stream_t stream);
+/* The same test, operation by operation, for P polygons whose corners are in DEVICE memory (what
+ * waldo_border_objects_fwd leaves there: nothing is read on the host, nothing stops the stream):
+ *   pts (N,2) f32, shared by the polygons;  corners f64: polygon p's K corners (x, y) at corners + p * corner_stride
+ *   (corner_stride in doubles, >= 0; (P,K,2) contiguous: 2 K);  valid: polygon p is tested where
+ *   valid[p * valid_stride] != 0 (int32; NULL: every polygon);  out (P,N) f32 -- an invalid polygon, or K < 3: zeros.
+ *   0 <= K <= 16. */
+int waldo_points_in_polygon_dev_fwd(const float* pts, const double* corners, int64_t corner_stride, const int* valid,
+                                    int64_t valid_stride, int K, float* out, int64_t P, int64_t N,
+                                    waldo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * f3. The border objects of WIF.inpaint (models/nets/wif.py:134-157) for a BATCH of clips, chosen on the device: per
+ * clip b and side s (0 = left, 1 = right image border) the object that enters the last predicted frame through that
+ * border and the four corners of the region it enters from.  With ident (H,W,2) the identity grid and
+ * to_px(g) = ((g.x W + W - 1) / 2, (g.y H + H - 1) / 2), every operation in the framework's order:
+ *   pred_px = to_px(pred_flow[b] + ident),  orig_px = to_px(ident)
+ *   at      = pred_px.x < 3 (left),  pred_px.x >= W - 3 (right)
+ *   obj[o]  = max over tc of (alpha_ctx[b, tc, Tp - 1, 1 + o] + 1) / 2  >  0.9        (a NaN wins the maximum)
+ *   count[o] = number of pixels with at & obj[o];  valid = any count > 0;  obj_id = the first o of the largest count
+ *   over the pixels with at & obj[obj_id]: by0, by1 = min, max of pred_px.y; ox0, ox1, oy0, oy1 of orig_px.x / .y
+ *   (a NaN among them gives NaN, as torch.min / torch.max do)
+ *   corners: left (0, by0) (0, by1) (ox1, oy1) (ox1, oy0);  right (ox0, oy0) (ox0, oy1) (W - 1, by1) (W - 1, by0)
+ * Counts are integers and the extrema are min / max (integer atomics on order-preserving keys): the result does not
+ * depend on the order of arrival.
+ *   pred_flow: the (2,H,W) flow planes of the last context and last predicted frame of clip b at
+ *   pred_flow + b * flow_stride_b + c * flow_stride_c (element strides; the planes contiguous);
+ *   alpha_ctx (B,Tc,Tp,L,H,W) f32 by its element strides over (b, tc, tp, l), the (H,W) planes contiguous, as
+ *   waldo_inpaint_holes_fwd takes it (the raw-slot view of decode_output is read in place);  2 <= L <= 32;
+ *   out: valid (B,2) int32 (1 / 0), obj_id (B,2) int64 (0 where invalid), corners (B,2,4,2) f64 -- the exact widening
+ *   of the fp32 extrema; zeros where invalid;
+ *   workspace: waldo_border_objects_workspace_bytes(B) bytes, 4-byte aligned, any contents (a kernel initialises it).
+ * How waldo_amd.nets.WIF uses it (two attributes of the module):
+ *   border_on_device = None (default): a one-clip call takes the reference's branch, unchanged (host reads of the hit
+ *     test, the object id and the corners; waldo_points_in_polygon_fwd); a batch takes this entry point, then
+ *     waldo_points_in_polygon_dev_fwd per side and one object id per clip for the flow.  True: one clip too.  False: never.
+ *   always_inpaint_borders = False (default): ONE device -> host read per call, of `valid`, to skip the external
+ *     inpainter for a side nothing enters through; True: no read, both sides' inpainter calls always made -- the call
+ *     is stream-ordered from start to end (HIP-graph capture).
+ *   A clip with valid == 0 at a side gets a zero region and a zero appearance in that slot, whatever the inpainter
+ *   returned for it.  The inpainter is called on the whole batch and must treat its clips independently; clips with an
+ *   empty mask are passed along and their result is ignored.
+ * ------------------------------------------------------------------------------------- */
+int64_t waldo_border_objects_workspace_bytes(int64_t B);
+int waldo_border_objects_fwd(const float* pred_flow, int64_t flow_stride_b, int64_t flow_stride_c, const float* ident,
+                             const float* alpha_ctx, int64_t stride_b, int64_t stride_tc, int64_t stride_tp,
+                             int64_t stride_l, int* valid, int64_t* obj_id, double* corners, void* workspace, int64_t B,
+                             int Tc, int Tp, int L, int H, int W, waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * f3. The per-frame propagation step of WIF.inpaint (models/nets/wif.py:179-214) as one launch: the inpainted reference

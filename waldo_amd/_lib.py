@@ -81,6 +81,9 @@ SIGNATURES = {
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],
     "waldo_mask_expand_fwd": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _int, _int, _flt, _stream],
     "waldo_points_in_polygon_fwd": [_c_f, _c_f, _int, _c_f, _i64, _stream],
+    "waldo_points_in_polygon_dev_fwd": [_c_f, _c_f, _i64, _c_f, _i64, _int, _c_f, _i64, _i64, _stream],
+    "waldo_border_objects_fwd": [_c_f, _i64, _i64, _c_f, _c_f, _i64, _i64, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _i64, _int,
+                                 _int, _int, _int, _int, _stream],
     "waldo_inpaint_propagate_fwd": [_c_f] * 8 + [_int] + [_c_f] * 7 + [_i64, _int, _int, _int, _int, _stream],
     "waldo_inpaint_blend_fwd": [_c_f] * 4 + [_i64, _i64, _stream],
     "waldo_inpaint_holes_fwd": [_c_f, _i64, _i64, _i64, _i64, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _flt, _stream],
@@ -118,6 +121,7 @@ DET_QUERIES = {
 PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_warp_composite_bwd_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int]),
          "waldo_lyt_dist_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int, _int]),
+         "waldo_border_objects_workspace_bytes": (_i64, [_i64]),
          "waldo_frame_metrics_partial_bytes": (_i64, [_int] * 5),
          "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),

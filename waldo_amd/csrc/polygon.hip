@@ -16,7 +16,8 @@
 // x86-64 wheel has none either) -- so that a pixel ON an edge falls on the side matplotlib puts it
 // (tests/test_inpaint.py::test_points_in_polygon_is_matplotlibs: random, concave and degenerate polygons, points on
 // vertices and edges, against matplotlib itself).  The corners are read on the HOST (they come from host scalars,
-// wif.py:146-157) and travel as kernel arguments: no copy is queued.
+// wif.py:146-157) and travel as kernel arguments: no copy is queued.  waldo_points_in_polygon_dev_fwd is the same walk
+// for corners that are in DEVICE memory (border_objects.hip leaves one polygon per clip and side there).
 #include "waldo_common.hip.h"
 
 namespace waldo {
@@ -28,15 +29,9 @@ struct PolygonArg {
   double y[kMaxCorners];
 };
 
-__global__ __launch_bounds__(kBlock) void points_in_polygon_kernel(const float* __restrict__ pts, PolygonArg poly, int K,
-                                                                   float* __restrict__ out, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const double tx = (double)pts[2 * i], ty = (double)pts[2 * i + 1];
-  if (!(fabs(tx) <= 1.7976931348623157e308) || !(fabs(ty) <= 1.7976931348623157e308)) {  // not finite: outside
-    out[i] = 0.0f;
-    return;
-  }
+// the walk over the closed path for one finite point; `Poly` holds x[] / y[] (the kernel argument, or its copy in LDS)
+template <typename Poly>
+__device__ __forceinline__ bool crossings_inside(const Poly& poly, int K, double tx, double ty) {
   bool inside = false;
   double ax = poly.x[0], ay = poly.y[0];        // the edge's first vertex (vtx0, vty0)
   double bx = ax, by = ay;                      // its second (vtx1, vty1): the walk starts with the edge (v0, v0)
@@ -55,7 +50,50 @@ __global__ __launch_bounds__(kBlock) void points_in_polygon_kernel(const float* 
     bx = poly.x[nxt];
     by = poly.y[nxt];
   }
-  out[i] = inside ? 1.0f : 0.0f;
+  return inside;
+}
+
+__device__ __forceinline__ bool finite_point(double tx, double ty) {
+  return fabs(tx) <= 1.7976931348623157e308 && fabs(ty) <= 1.7976931348623157e308;
+}
+
+__global__ __launch_bounds__(kBlock) void points_in_polygon_kernel(const float* __restrict__ pts, PolygonArg poly, int K,
+                                                                   float* __restrict__ out, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double tx = (double)pts[2 * i], ty = (double)pts[2 * i + 1];
+  if (!finite_point(tx, ty)) {  // not finite: outside
+    out[i] = 0.0f;
+    return;
+  }
+  out[i] = crossings_inside(poly, K, tx, ty) ? 1.0f : 0.0f;
+}
+
+// P polygons whose corners are in device memory (waldo_border_objects_fwd's, one per clip): blockIdx.y = the polygon,
+// its corners staged in LDS; the same walk.  An invalid polygon writes zeros.
+__global__ __launch_bounds__(kBlock) void points_in_polygon_dev_kernel(const float* __restrict__ pts,
+                                                                       const double* __restrict__ corners,
+                                                                       int64_t corner_stride, const int* __restrict__ valid,
+                                                                       int64_t valid_stride, int K, float* __restrict__ out,
+                                                                       int64_t n) {
+  __shared__ PolygonArg poly;
+  const int64_t pg = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = K >= 3 && (valid == nullptr || valid[pg * valid_stride] != 0);  // (uniform over the workgroup)
+  if (live) {
+    if (threadIdx.x < K) {
+      poly.x[threadIdx.x] = corners[pg * corner_stride + 2 * threadIdx.x];
+      poly.y[threadIdx.x] = corners[pg * corner_stride + 2 * threadIdx.x + 1];
+    }
+    __syncthreads();
+  }
+  if (i >= n) return;
+  float r = 0.0f;
+  if (live) {
+    const double tx = (double)pts[2 * i], ty = (double)pts[2 * i + 1];
+    if (finite_point(tx, ty)) r = crossings_inside(poly, K, tx, ty) ? 1.0f : 0.0f;
+  }
+  out[pg * n + i] = r;
 }
 
 }  // namespace waldo
@@ -89,4 +127,27 @@ extern "C" int waldo_points_in_polygon_fwd(const float* pts, const double* corne
   }
   points_in_polygon_kernel<<<dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream>>>(pts, poly, K, out, N);
   return launch_status("waldo_points_in_polygon_fwd");
+}
+
+extern "C" int waldo_points_in_polygon_dev_fwd(const float* pts, const double* corners, int64_t corner_stride,
+                                               const int* valid, int64_t valid_stride, int K, float* out, int64_t P,
+                                               int64_t N, waldo_stream_t stream) {
+  if (N < 0 || P < 0 || K < 0 || K > kMaxCorners || corner_stride < 0 || valid_stride < 0) {
+    set_error("waldo_points_in_polygon_dev_fwd: bad arguments P=%lld N=%lld K=%d (at most %d corners, strides >= 0)",
+              (long long)P, (long long)N, K, kMaxCorners);
+    return WALDO_EINVAL;
+  }
+  if (N == 0 || P == 0) return WALDO_OK;
+  if (!pts || !out || (K > 0 && !corners)) {
+    set_error("waldo_points_in_polygon_dev_fwd: null pointer");
+    return WALDO_EINVAL;
+  }
+  const int64_t blocks = (N + kBlock - 1) / kBlock;
+  if (blocks > 2147483647 || P > 65535) {
+    set_error("waldo_points_in_polygon_dev_fwd: too many points or polygons for one launch (P <= 65535)");
+    return WALDO_EINVAL;
+  }
+  points_in_polygon_dev_kernel<<<dim3((unsigned)blocks, (unsigned)P), dim3(kBlock), 0, (hipStream_t)stream>>>(
+      pts, corners, corner_stride, valid, valid_stride, K, out, N);
+  return launch_status("waldo_points_in_polygon_dev_fwd");
 }

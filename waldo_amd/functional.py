@@ -1495,15 +1495,23 @@ def downscale_frames(input, num_frames, first_channel, factor):
     return out
 
 
-def points_in_polygon(pts, corners):
+def points_in_polygon(pts, corners, valid=None):
     """``matplotlib.path.Path(corners).contains_points(pts)`` (radius 0, no transform) on the device, as ``WIF.inpaint``
     uses it (models/nets/wif.py:228-235): ``pts`` (..., 2) float32 (x, y) on the GPU, ``corners`` a sequence of 3 ... 16
     (x, y) pairs of host numbers -> a bool tensor of ``pts.shape[:-1]``.  matplotlib's crossings test in double precision,
-    operation by operation: points on an edge get matplotlib's answer."""
+    operation by operation: points on an edge get matplotlib's answer.
+
+    ``corners`` may also be a tensor ON THE DEVICE (nothing is read on the host): (K, 2) -> ``pts.shape[:-1]``, or
+    (P, K, 2), P polygons tested against the same points -> (P, *pts.shape[:-1]); float64 (float32 is widened
+    exactly).  ``valid`` (P,) on the device, any integer or bool type: a polygon whose entry is zero contains nothing."""
     import ctypes
     _lib.check_cuda(pts)
     if pts.shape[-1] != 2:
         raise _lib.WaldoHipError(f"points_in_polygon: points of shape {tuple(pts.shape)} (..., 2)")
+    if torch.is_tensor(corners):
+        return _points_in_polygon_dev(pts, corners, valid)
+    if valid is not None:
+        raise _lib.WaldoHipError("points_in_polygon: `valid` goes with corners on the device")
     flat = [float(v) for c in corners for v in c]
     k = len(flat) // 2
     if len(flat) != 2 * k or any(len(c) != 2 for c in corners) or k > 16:
@@ -1516,6 +1524,75 @@ def points_in_polygon(pts, corners):
         _lib.call("waldo_points_in_polygon_fwd", _lib.ptr(x), ctypes.addressof(host), k, _lib.ptr(out), n,
                   _lib.current_stream(x.device))
     return out > 0
+
+
+def _polygon_regions(pts, corners, valid):
+    """The device form of the polygon test as 0 / 1 floats: ``corners`` (P, K, 2) float64 and ``valid`` (P,) int32 or
+    None, both on the device and taken by their strides (a side of ``border_objects``' tables is read in place) ->
+    (P, *pts.shape[:-1]) float32."""
+    if not corners.is_cuda or corners.dim() != 3 or corners.shape[2] != 2 or corners.shape[1] > 16:
+        raise _lib.WaldoHipError(f"points_in_polygon: device corners of shape {tuple(corners.shape)} ((P, K, 2) on the "
+                                 "GPU, at most 16 corners)")
+    p, k = corners.shape[:2]
+    cn = corners.detach().to(torch.float64)
+    if k and (cn.stride(2) != 1 or cn.stride(1) != 2 or cn.stride(0) < 0):
+        cn = cn.contiguous()
+    if valid is not None:
+        if not valid.is_cuda or tuple(valid.shape) != (p,):
+            raise _lib.WaldoHipError(f"points_in_polygon: `valid` of shape {tuple(valid.shape)} for {p} polygons on the GPU")
+        valid = valid.detach()
+        if valid.dtype != torch.int32 or valid.stride(0) < 0:
+            valid = (valid != 0).to(torch.int32)
+    x = _c(pts.detach())
+    n = x.numel() // 2
+    out = x.new_empty((p,) + tuple(x.shape[:-1]))
+    with _lib.on_device(x.device):
+        _lib.call("waldo_points_in_polygon_dev_fwd", _lib.ptr(x), _lib.ptr(cn), cn.stride(0) if p and k else 0,
+                  _lib.ptr(valid), valid.stride(0) if valid is not None else 0, k, _lib.ptr(out), p, n,
+                  _lib.current_stream(x.device))
+    return out
+
+
+def _points_in_polygon_dev(pts, corners, valid):
+    if corners.dim() == 2:
+        if valid is not None:
+            valid = valid.reshape(1)
+        return _polygon_regions(pts, corners.unsqueeze(0), valid)[0] > 0
+    return _polygon_regions(pts, corners, valid) > 0
+
+
+def border_objects(pred_flow, ident, alpha_ctx):
+    """The border objects of ``WIF.inpaint`` (models/nets/wif.py:134-157) for every clip of a batch, chosen on the
+    device (csrc/border_objects.hip): ``pred_flow`` (B, 2, H, W), the flow of the last context to the last predicted
+    frame in grid units (any strides over B and the channel: ``pred_flow[:, -1, -1]`` is read in place), ``ident``
+    (H, W, 2) the identity grid, ``alpha_ctx`` (B, Tc, Tp, L, H, W) in [-1, 1] (any strides over the first four
+    dimensions) -> ``(valid (B, 2) int32, obj_id (B, 2) int64, corners (B, 2, 4, 2) float64)``, side 0 = left, 1 = right.
+    No host read; the values have the bits of the torch expressions evaluated per clip."""
+    _lib.check_cuda(pred_flow, ident, alpha_ctx)
+    if alpha_ctx.dim() != 6 or pred_flow.dim() != 4:
+        raise _lib.WaldoHipError(f"border_objects: alpha_ctx of shape {tuple(alpha_ctx.shape)} (B, Tc, Tp, L, H, W), "
+                                 f"pred_flow of shape {tuple(pred_flow.shape)} (B, 2, H, W)")
+    b, tc, tp, nl, h, w = alpha_ctx.shape
+    if tuple(pred_flow.shape) != (b, 2, h, w) or ident.numel() != h * w * 2 or ident.shape[-1] != 2:
+        raise _lib.WaldoHipError(f"border_objects: pred_flow {tuple(pred_flow.shape)}, identity grid {tuple(ident.shape)} "
+                                 f"for {b} clips of {h} x {w}")
+    if not 2 <= nl <= 32 or tc < 1 or tp < 1:
+        raise _lib.WaldoHipError(f"border_objects: {nl} layers, {tc} contexts, {tp} predicted frames (2 ... 32 layers)")
+    x, f, ident = alpha_ctx.detach(), pred_flow.detach(), _c(ident.detach())
+    if x.stride(5) != 1 or x.stride(4) != w or min(x.stride()[:4]) < 0:
+        x = x.contiguous()
+    if f.stride(3) != 1 or f.stride(2) != w or min(f.stride()[:2]) < 0:
+        f = f.contiguous()
+    dev = x.device
+    valid = torch.empty(b, 2, dtype=torch.int32, device=dev)
+    obj_id = torch.empty(b, 2, dtype=torch.int64, device=dev)
+    corners = torch.empty(b, 2, 4, 2, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(_lib.query("waldo_border_objects_workspace_bytes", b) // 4, 1), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("waldo_border_objects_fwd", _lib.ptr(f), f.stride(0), f.stride(1), _lib.ptr(ident), _lib.ptr(x),
+                  x.stride(0), x.stride(1), x.stride(2), x.stride(3), _lib.ptr(valid), _lib.ptr(obj_id), _lib.ptr(corners),
+                  _lib.ptr(ws), b, tc, tp, nl, h, w, _lib.current_stream(dev))
+    return valid, obj_id, corners
 
 
 def inpaint_propagate(flow, ident, ref_img, ref_mask, shadow, entering, img, todo, obj, soft_shadow=False,

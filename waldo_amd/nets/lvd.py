@@ -304,8 +304,18 @@ class Warper(nn.Module):
         return scale(bg_flow, self.scale_hd).permute(0, 1, 3, 4, 2)
 
     def grid_to_obj_flow_from_ref_to_pred(self, grid, ctx_len, ref, obj_id):
+        """``obj_id``: an int (the reference: one object, one clip), or a (B,) long tensor on the device -- one object
+        per clip, gathered there with no host read (``WIF.inpaint`` on a batch)."""
         tgt_grid_obj, src_grid_obj, _, _ = grid
-        if tgt_grid_obj.shape[0] == 1:  # (WIF.inpaint: one clip; the list indices of lvd.py:586-588 as slices)
+        if torch.is_tensor(obj_id):
+            if tuple(obj_id.shape) != (tgt_grid_obj.shape[0],) or obj_id.dtype != torch.long:
+                raise ValueError(f"obj_id: a long tensor of shape ({tgt_grid_obj.shape[0]},), one object per clip, "
+                                 f"got {tuple(obj_id.shape)} {obj_id.dtype}")
+            pick = obj_id.remainder(tgt_grid_obj.shape[2]).view(-1, 1, 1, 1, 1, 1)
+            one = tgt_grid_obj.gather(2, pick.expand(-1, tgt_grid_obj.shape[1], 1, *tgt_grid_obj.shape[3:]))
+            obj_flow = self._frame(one, ref) - one[:, ctx_len:]
+            src_one = src_grid_obj.gather(2, pick.expand(-1, src_grid_obj.shape[1], 1, *src_grid_obj.shape[3:]))
+        elif tgt_grid_obj.shape[0] == 1:  # (WIF.inpaint: one clip; the list indices of lvd.py:586-588 as slices)
             one = tgt_grid_obj.narrow(2, obj_id % tgt_grid_obj.shape[2], 1)
             obj_flow = self._frame(one, ref) - one[:, ctx_len:]
             src_one = src_grid_obj.narrow(2, obj_id % src_grid_obj.shape[2], 1)

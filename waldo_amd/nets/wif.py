@@ -40,6 +40,14 @@ class WIF(nn.Module):
         self.opt = opt
         self.unet = unet
         self.fuse_propagate = True  # WIF.inpaint's per-frame propagation as one launch (False: the spelled-out loop)
+        # WIF.inpaint's border objects: None = one clip as the reference handles it (host reads of the hit test, the
+        # object id and the polygon corners), a batch on the device (per-clip ids and corners never leave it); True =
+        # the device path for one clip too; False = the reference's one-clip branch whatever the batch
+        self.border_on_device = None
+        # the device path's ONE host read -- the (B, 2) table of which clip has an object at which border, read to skip
+        # the external inpainter for a side nothing enters through -- traded for two inpainter calls per call of
+        # `inpaint`, always: the call is then stream-ordered from start to end (HIP-graph capture)
+        self.always_inpaint_borders = False
         if hasattr(opt, "dim"):  # the HD identity grid `inpaint` warps against (wif.py:29-31)
             shape = [opt.dim, int(opt.dim * opt.aspect_ratio)]
             if getattr(opt, "load_dim", 0) > 0:
@@ -125,7 +133,11 @@ class WIF(nn.Module):
     def _border_objects(self, inpainter, raw_output, alpha_ctx, pred_flow, ctx_len, warper, grid, ref):
         """Objects cut by the left / right image border in the last prediction: polygon mask of the
         region they enter from, inpainted appearance, and their flow to every predicted frame
-        (wif.py:130-172).  Returns a list of (mask, appearance, flow (B, Tp, Hd, Wd, 2))."""
+        (wif.py:130-172).  Returns a list of (mask, appearance, flow (B, Tp, Hd, Wd, 2)).
+        One clip (``border_on_device``: a batch too, if set to False) takes the reference's branch below; a batch goes
+        to ``_border_objects_device``."""
+        if self.border_on_device or (self.border_on_device is None and alpha_ctx.shape[0] > 1):
+            return self._border_objects_device(inpainter, raw_output, alpha_ctx, pred_flow, ctx_len, warper, grid, ref)
         border = 3  # pixels
         h, w = self.src_grid_hd.shape[1:3]
 
@@ -155,12 +167,44 @@ class WIF(nn.Module):
             out.append((region, look, warper.grid_to_obj_flow_from_ref_to_pred(grid, ctx_len, ref, obj_id)))
         return out
 
+    def _border_objects_device(self, inpainter, raw_output, alpha_ctx, pred_flow, ctx_len, warper, grid, ref):
+        """``_border_objects`` for a batch, every clip with an object and a polygon of its own: one selection pass
+        (csrc/border_objects.hip) leaves ``valid (B, 2)``, ``obj_id (B, 2)`` and ``corners (B, 2, 4, 2)`` on the device,
+        the polygon test and the object flow read them there.  Slot 0 is the left border, slot 1 the right one.  A
+        clip with no object at a side has an all-zero region and an all-zero appearance in that slot, whatever the
+        inpainter returned for it: the propagation step leaves it alone.  Clip b gets what the one-clip branch gives
+        on clip b alone, provided the ``inpainter`` treats the clips of a batch independently (it is called on the whole
+        batch; a clip whose mask is empty is passed along and its result dropped)."""
+        h, w = self.src_grid_hd.shape[1:3]
+        valid, obj_id, corners = WF.border_objects(pred_flow[:, -1, -1].float(), self.src_grid_hd, alpha_ctx)
+        if self.always_inpaint_borders:
+            sides = [0, 1]
+        else:  # (the one device -> host read of the call: the reference skips the inpainter where nothing enters)
+            table = valid.tolist()
+            sides = [s for s in (0, 1) if any(row[s] for row in table)]
+        if not sides:
+            return []
+        g = self.src_grid_hd[0]
+        orig_px = torch.stack([(g[..., 0] * w + w - 1) / 2, (g[..., 1] * h + h - 1) / 2], dim=-1)
+        last = raw_output[:, -1, -1, :3].float()  # (fp32: a 16-bit raw_output too)
+        out = []
+        for s in sides:
+            region = WF._polygon_regions(orig_px, corners[:, s], valid[:, s]).unsqueeze(1)
+            look = inpainter((1 - region) * last, region)
+            look = torch.where(valid[:, s].view(-1, 1, 1, 1) != 0, look, look.new_zeros(()))
+            out.append((region, look, warper.grid_to_obj_flow_from_ref_to_pred(grid, ctx_len, ref, obj_id[:, s])))
+        return out
+
     def inpaint(self, inpainter, raw_output, alpha, alpha_ctx, real_vid, pred_flow, ctx_len, warper, grid):
         """``WIF.inpaint`` (wif.py:58-226): fuse the warped context frames, inpaint the disoccluded
         background ONCE in a reference frame (the last prediction) and propagate it to the other
         predicted frames along the background flow.  `inpainter(img, mask, ...)` is the external
         MAT network (out of scope: any callable with the reference's signature).
         Returns (B, ctx_len + Tp, 3, H, W).
+        Any batch size: the objects that enter through the left / right border (``propagate_obj``) are chosen per clip
+        on the device (``border_on_device``, ``always_inpaint_borders``: the constructor's comments), and clip b of a
+        batched call gets what a one-clip call gives on clip b alone -- given an ``inpainter`` that treats the clips
+        of a batch independently.
         A 16-bit ``raw_output`` / ``alpha_ctx`` (``decode_output(..., raw_dtype=...)``): ``forward`` fuses the 16-bit
         tensor itself; the mask and propagation passes (``inpaint_holes``, the border objects) are fp32-only and get
         an fp32 copy of ``alpha_ctx`` and of the 3-channel slice of ``raw_output`` the border objects read -- the same
