@@ -709,6 +709,46 @@ int waldo_frame_metrics_fwd(const void* a, int enc_a, int64_t sa_b, int64_t sa_t
                             waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Byte output: predicted frames as uint8, quantised on the device -- what the reference's save_vid -> dump_video makes
+ * of every clip predict() returns (models/synthesizer.py:403-411, tools/utils.py:246-264) and its scorer reads.
+ * THE quantisation of the library (csrc/quantize.hip.h; waldo_frame_metrics_fwd applies the same text before its / 255):
+ * for a value x and a span (lo, hi), hi > lo, range = hi - lo as the caller computes it in fp32,
+ *     u = clamp((x - lo) / range, 0, 1)
+ *     WALDO_METRICS_TRUNC   byte = (uint8) truncf(u * 255)         (the reference's dump_video)
+ *     WALDO_METRICS_ROUND   byte = (uint8) truncf(u * 255 + 0.5)   (waldo_amd.tools.io.dump_video / dump_image)
+ * in fp32 with IEEE division; a 16-bit value is widened exactly first.  NaN RULE: the clamp is fminf(fmaxf(u, 0), 1), so a
+ * NaN gives byte 0; -inf gives 0 and +inf 255.  WALDO_METRICS_NONE is not a byte quantisation: WALDO_EINVAL.
+ *
+ * waldo_frames_to_bytes_fwd: N frames of C planes of H x W values -> uint8.
+ *   src       src_code WALDO_DTYPE_F32 / _F16 / _BF16: planar frames, element strides ss_n, ss_c, ss_h (W unit-stride:
+ *             a channel or time slice of a larger tensor needs no copy), aligned to its elements;
+ *             src_code WALDO_BYTES_SRC_PACKED: a packed clip ("Packed clip" above), N frames of H x W 4-byte pixels,
+ *             strides ss_n, ss_h in PIXELS (ss_c unused), 4-byte aligned, C = 3: the bytes are
+ *             quantise(rgb_table[byte]) -- NOT the clip's own bytes, which "trunc" does not give back for 63 of the 256
+ *             values; rgb_table (256 fp32) is read for a packed source only (else NULL allowed);
+ *   dst       WALDO_BYTES_NCHW: (N, C, H, W), or WALDO_BYTES_NHWC: (N, H, W, 3) with C = 3 (what a video writer takes);
+ *             each frame dense, frame stride ds_n in bytes, ANY alignment of the base (a view into a larger buffer).
+ * Caller-owned buffers, the caller's stream, no allocation, no synchronisation; N == 0: WALDO_OK without a launch.
+ * WALDO_EINVAL with a message before any launch: an unknown source, layout or quantisation code; range <= 0 or a
+ * non-finite span; a negative stride; C != 3 with WALDO_BYTES_NHWC or a packed source; H or W outside [1, 32768], C
+ * outside [1, 4096]; a null pointer; a source that is not aligned to its elements; more than 2^31 - 1 workgroups.
+ *
+ * waldo_wif_fuse_bytes_fwd / _dt: waldo_wif_fuse_fwd / _dt (A12 above) with out as bytes, (N, 3, HW) or (N, HW, 3):
+ * the bytes of waldo_frames_to_bytes_fwd on A12's fp32 result, bit for bit (the same arithmetic in the same order, then
+ * the quantisation above), without the 12 bytes per pixel in between.  Forward only.
+ * ------------------------------------------------------------------------------------- */
+enum waldo_bytes_layout { WALDO_BYTES_NCHW = 0, WALDO_BYTES_NHWC = 1 };
+#define WALDO_BYTES_SRC_PACKED 3 /* a source code next to enum waldo_dtype's */
+int waldo_frames_to_bytes_fwd(const void* src, int src_code, int64_t ss_n, int64_t ss_c, int64_t ss_h,
+                              const float* rgb_table, uint8_t* dst, int64_t ds_n, int layout, int64_t N, int C, int H,
+                              int W, float lo, float range, int quant, waldo_stream_t stream);
+int waldo_wif_fuse_bytes_fwd(const float* vid, const float* net, uint8_t* out, int64_t N, int Tc, int C, int Co,
+                             int64_t HW, int ab, float lo, float range, int quant, int layout, waldo_stream_t stream);
+int waldo_wif_fuse_bytes_fwd_dt(const void* vid, const void* net, uint8_t* out, int64_t N, int Tc, int C, int Co,
+                                int64_t HW, int ab, float lo, float range, int quant, int layout, int vid_dtype,
+                                int net_dtype, waldo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Reproducible gradients (deterministic mode).  The backward entry points above that say "ZERO-FILLED ... atomics"
  * sum with float atomics: the result depends on the order of arrival and differs in its last bits from run to run.
  * Each has a twin, suffix _det, whose result is a function of its inputs alone -- the same bits from run to run,

@@ -76,6 +76,12 @@ SIGNATURES = {
     "waldo_wif_fuse_fwd_dt": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _int, _int, _stream],
     "waldo_wif_fuse_bwd_dt": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _int, _int,
                               _stream],
+    # byte output (include/waldo_hip.h "Byte output"): source descriptor, table, destination, shape, span, codes
+    "waldo_frames_to_bytes_fwd": [_c_f, _int, _i64, _i64, _i64, _c_f, _c_f, _i64, _int, _i64, _int, _int, _int, _flt,
+                                  _flt, _int, _stream],
+    "waldo_wif_fuse_bytes_fwd": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _flt, _flt, _int, _int, _stream],
+    "waldo_wif_fuse_bytes_fwd_dt": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _flt, _flt, _int, _int, _int,
+                                    _int, _stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],

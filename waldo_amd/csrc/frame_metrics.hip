@@ -9,6 +9,7 @@
 // scale, symmetric padding at an odd end) into the caller's scratch: each scale's source is read from HBM once.
 // The combine kernel sums the partials of a frame in a fixed order in fp64: no atomics, the same bits on every call.
 #include "packed_clip.hip.h"
+#include "quantize.hip.h"
 
 namespace waldo {
 
@@ -46,10 +47,9 @@ struct PassArgs {
 };
 
 __device__ __forceinline__ float quantize(float x, float lo, float range, int quant) {
-  float u = (x - lo) / range;
-  u = fminf(fmaxf(u, 0.0f), 1.0f);
-  if (quant == WALDO_METRICS_TRUNC) return truncf(u * 255.0f) / 255.0f;
-  if (quant == WALDO_METRICS_ROUND) return truncf(u * 255.0f + 0.5f) / 255.0f;
+  const float u = quant_unit(x, lo, range);  // (quantize.hip.h: the formula of every byte the library writes)
+  if (quant == WALDO_METRICS_TRUNC) return quant_level_trunc(u) / 255.0f;
+  if (quant == WALDO_METRICS_ROUND) return quant_level_round(u) / 255.0f;
   return u;
 }
 

@@ -11,6 +11,7 @@
 // the fp32 one rounded to nearest-even.
 #include <type_traits>
 
+#include "quantize.hip.h"
 #include "waldo_common.hip.h"
 
 namespace waldo {
@@ -105,6 +106,96 @@ __global__ __launch_bounds__(kBlock) void wif_fuse_bwd_kernel(
   }
 }
 
+// ---- the epilogue with BYTES out (include/waldo_hip.h "Byte output"): the forward above, quantised (quantize.hip.h) and
+// stored as uint8, planar (N, 3, HW) or interleaved (N, HW, 3): 3 bytes per pixel written in place of 12.  A lane owns
+// 4 consecutive pixels, so that a plane's four bytes are one dword store (sub-dword stores: ~12 x the cost per byte).
+// vec (HW % 4 == 0, 16-byte aligned fp32 / 8-byte aligned 16-bit bases): every plane is read with one 16- / 8-byte load
+// per lane; otherwise element loads (an odd HW misaligns every second plane) and, where a group is cut by the end of
+// the plane or its bytes do not start a dword, single-byte stores.
+template <typename T>
+__device__ __forceinline__ void load_px4(const T* __restrict__ p, bool vec, int valid, float (&v)[4]) {
+  if (vec) {
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    const t4 q = *reinterpret_cast<const t4*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (float)q[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = j < valid ? (float)p[j] : 0.0f;
+  }
+}
+
+template <typename VT, typename NT>
+__global__ __launch_bounds__(kBlock) void wif_fuse_bytes_kernel(const VT* __restrict__ vid, const NT* __restrict__ net,
+                                                                uint8_t* __restrict__ out, int Tc, int C, int Co,
+                                                                int64_t HW, int tiles, int ab, int vec, int nhwc,
+                                                                float lo, float range, int quant) {
+  const int64_t n = blockIdx.x / tiles;
+  const int64_t p = ((int64_t)(blockIdx.x % tiles) * kBlock + threadIdx.x) * 4;
+  if (p >= HW) return;
+  const int valid = (int)min((int64_t)4, HW - p);
+  const VT* v = vid + n * Tc * C * HW + p;
+  const NT* o = net + n * Tc * Co * HW + p;
+  // (per pixel j: the text of wif_fuse_fwd_kernel, same order, same fmafs)
+  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  for (int t = 0; t < Tc; ++t) {
+    float s[4];
+    load_px4(o + ((int64_t)t * Co + 3) * HW, vec, valid, s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], s[j]);
+  }
+  float den[4] = {0.0f, 0.0f, 0.0f, 0.0f}, acc[3][4] = {};
+  for (int t = 0; t < Tc; ++t) {
+    float s[4], g[4] = {0.0f, 0.0f, 0.0f, 0.0f}, e[4], a[4];
+    load_px4(o + ((int64_t)t * Co + 3) * HW, vec, valid, s);
+    if (ab) load_px4(v + ((int64_t)t * C + 4) * HW, vec, valid, g);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      e[j] = expf(s[j] - m[j]);
+      a[j] = ab ? sigmoidf(g[j] + 5.0f) : 0.0f;
+      den[j] += e[j];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float x[4], b[4];
+      load_px4(v + ((int64_t)t * C + c) * HW, vec, valid, x);
+      load_px4(o + ((int64_t)t * Co + c) * HW, vec, valid, b);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[c][j] = fmaf(fmaf(a[j], x[j], b[j]), e[j], acc[c][j]);
+    }
+  }
+  uint32_t q[3][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float r = 1.0f / den[j];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c][j] = quant_byte(acc[c][j] * r, lo, range, quant);
+  }
+  if (nhwc) {
+    uint8_t* d = out + (n * HW + p) * 3;
+    if (valid == 4 && ((uintptr_t)d & 3u) == 0) {
+      uint32_t* w = reinterpret_cast<uint32_t*>(d);
+      w[0] = q[0][0] | (q[1][0] << 8) | (q[2][0] << 16) | (q[0][1] << 24);
+      w[1] = q[1][1] | (q[2][1] << 8) | (q[0][2] << 16) | (q[1][2] << 24);
+      w[2] = q[2][2] | (q[0][3] << 8) | (q[1][3] << 16) | (q[2][3] << 24);
+    } else {
+      for (int j = 0; j < valid; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[3 * j + c] = (uint8_t)q[c][j];
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      uint8_t* d = out + (n * 3 + c) * HW + p;
+      if (valid == 4 && ((uintptr_t)d & 3u) == 0) {
+        *reinterpret_cast<uint32_t*>(d) = q[c][0] | (q[c][1] << 8) | (q[c][2] << 16) | (q[c][3] << 24);
+      } else {
+        for (int j = 0; j < valid; ++j) d[j] = (uint8_t)q[c][j];
+      }
+    }
+  }
+}
+
 static int check_wif(const char* fn, int64_t N, int Tc, int C, int Co, int64_t HW) {
   if (N < 0 || Tc < 1 || C < 5 || Co < 4 || HW < 1 || N * ((HW + kBlock - 1) / kBlock) > 2147483647) {
     set_error("%s: bad shape N=%lld Tc=%d C=%d Co=%d HW=%lld (need C >= 5, Co >= 4)", fn,
@@ -152,6 +243,40 @@ static int wif_bwd_launch(const char* fn, const void* vid, const void* net, cons
   hipLaunchKernelGGL((wif_fuse_bwd_kernel<VT, NT>), dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st,
                      static_cast<const VT*>(vid), static_cast<const NT*>(net), out, grad_out,
                      static_cast<VT*>(grad_vid), static_cast<NT*>(grad_net), Tc, C, Co, HW, tiles, ab);
+  return launch_status(fn);
+}
+
+template <typename VT, typename NT>
+static int wif_bytes_launch(const char* fn, const void* vid, const void* net, uint8_t* out, int64_t N, int Tc, int C,
+                            int Co, int64_t HW, int ab, float lo, float range, int quant, int layout,
+                            waldo_stream_t stream) {
+  int rc = check_wif(fn, N, Tc, C, Co, HW);
+  if (rc) return rc;
+  if ((quant != WALDO_METRICS_TRUNC && quant != WALDO_METRICS_ROUND) ||
+      (layout != WALDO_BYTES_NCHW && layout != WALDO_BYTES_NHWC)) {
+    set_error("%s: unknown quantisation %d (WALDO_METRICS_TRUNC / _ROUND) or layout %d (WALDO_BYTES_NCHW / _NHWC)", fn,
+              quant, layout);
+    return WALDO_EINVAL;
+  }
+  if (!(range > 0.0f) || !(range <= 3.4028234664e38f) || !(lo >= -3.4028234664e38f && lo <= 3.4028234664e38f)) {
+    set_error("%s: bad span lo=%g range=%g (range = hi - lo must be positive and finite)", fn, (double)lo,
+              (double)range);
+    return WALDO_EINVAL;
+  }
+  if (N == 0) return WALDO_OK;
+  if (!vid || !net || !out) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  if ((uintptr_t)vid % sizeof(VT) || (uintptr_t)net % sizeof(NT)) {
+    set_error("%s: vid / net not aligned to their elements", fn);
+    return WALDO_EINVAL;
+  }
+  const int vec = HW % 4 == 0 && (uintptr_t)vid % (4 * sizeof(VT)) == 0 && (uintptr_t)net % (4 * sizeof(NT)) == 0;
+  const int tiles = (int)(((HW + 3) / 4 + kBlock - 1) / kBlock);  // (<= check_wif's one-pixel tiles)
+  hipLaunchKernelGGL((wif_fuse_bytes_kernel<VT, NT>), dim3((unsigned)(N * tiles)), dim3(kBlock), 0,
+                     (hipStream_t)stream, static_cast<const VT*>(vid), static_cast<const NT*>(net), out, Tc, C, Co,
+                     HW, tiles, ab, vec, (int)(layout == WALDO_BYTES_NHWC), lo, range, quant);
   return launch_status(fn);
 }
 
@@ -211,5 +336,22 @@ extern "C" int waldo_wif_fuse_bwd_dt(const void* vid, const void* net, const flo
   return wif_dispatch(fn, vid_dtype, net_dtype, [&](auto vt, auto nt) {
     return wif_bwd_launch<decltype(vt), decltype(nt)>(fn, vid, net, out, grad_out, grad_vid, grad_net, N, Tc, C, Co,
                                                       HW, ab, stream);
+  });
+}
+
+extern "C" int waldo_wif_fuse_bytes_fwd(const float* vid, const float* net, uint8_t* out, int64_t N, int Tc, int C,
+                                        int Co, int64_t HW, int ab, float lo, float range, int quant, int layout,
+                                        waldo_stream_t stream) {
+  return wif_bytes_launch<float, float>("waldo_wif_fuse_bytes_fwd", vid, net, out, N, Tc, C, Co, HW, ab, lo, range,
+                                        quant, layout, stream);
+}
+
+extern "C" int waldo_wif_fuse_bytes_fwd_dt(const void* vid, const void* net, uint8_t* out, int64_t N, int Tc, int C,
+                                           int Co, int64_t HW, int ab, float lo, float range, int quant, int layout,
+                                           int vid_dtype, int net_dtype, waldo_stream_t stream) {
+  const char* fn = "waldo_wif_fuse_bytes_fwd_dt";
+  return wif_dispatch(fn, vid_dtype, net_dtype, [&](auto vt, auto nt) {
+    return wif_bytes_launch<decltype(vt), decltype(nt)>(fn, vid, net, out, N, Tc, C, Co, HW, ab, lo, range, quant,
+                                                        layout, stream);
   });
 }

@@ -104,7 +104,8 @@ def all_gather_frames_async(local, frames, group=None):
     """``all_gather_frames`` without waiting: the collective runs on the communicator's own stream (RCCL) while the
     caller launches the next frames' kernels; ``.wait()`` on the returned ``PendingGather`` before the result is read.
     The frames of step i travel over xGMI while step i + 1 computes -- at the Cityscapes recipe 352 MB per rank
-    against a 28 ms step."""
+    against a 19 ms step (uint8 frames -- ``predict_sharded(out_bytes=...)`` -- are a quarter of that).
+    Dtype-agnostic: the block travels in the dtype it has."""
     if not dist.is_initialized() or dist.get_world_size(group) == 1:
         assert local.shape[0] == frames
         return PendingGather(None, local, local, frames)

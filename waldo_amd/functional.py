@@ -4,6 +4,7 @@ Every function here launches hand-written gfx950 kernels on the caller's current
 function has a CPU or eager-PyTorch fallback (``_lib.check_cuda`` raises on CPU tensors).
 PyTorch is used for memory (output allocation), streams and autograd bookkeeping only.
 """
+import ctypes
 import math
 
 import torch
@@ -1387,6 +1388,131 @@ def unpack_clip(clip):
     with _lib.on_device(data.device):
         _lib.call("waldo_unpack_clip_fwd", _lib.ptr(data), _lib.ptr(rgb_table(data.device)), _lib.ptr(out), b, t,
                   clip.num_lyt, hd, wd, _lib.current_stream(data.device))
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# Byte output (include/waldo_hip.h "Byte output"): predicted frames as uint8, quantised on the device
+# --------------------------------------------------------------------------------------
+BYTE_QUANTIZE = {"trunc": 0, "round": 1}  # WALDO_METRICS_TRUNC / _ROUND
+BYTE_LAYOUT = {"nchw": 0, "nhwc": 1}  # WALDO_BYTES_NCHW / _NHWC
+_SRC_PACKED = 3  # WALDO_BYTES_SRC_PACKED
+
+
+def _f32(v):
+    return ctypes.c_float(v).value
+
+
+def _byte_args(fn, span, quantize, layout):
+    """(lo, range, quantisation code, layout code); range = hi - lo in fp32, as the header defines it."""
+    if quantize not in BYTE_QUANTIZE:
+        raise ValueError(f"{fn}: quantize must be one of {tuple(BYTE_QUANTIZE)}, got {quantize!r}")
+    if layout not in BYTE_LAYOUT:
+        raise ValueError(f"{fn}: layout must be one of {tuple(BYTE_LAYOUT)}, got {layout!r}")
+    lo, hi = (_f32(float(v)) for v in span)
+    if not hi > lo:
+        raise ValueError(f"{fn}: span {tuple(span)} must have lo < hi")
+    return lo, _f32(hi - lo), BYTE_QUANTIZE[quantize], BYTE_LAYOUT[layout]
+
+
+def _dense_tail(t, k):
+    """Whether the last ``k`` dimensions of ``t`` are laid out densely (a dimension of size 1 may have any stride)."""
+    expect = 1
+    for d in range(t.ndim - 1, t.ndim - 1 - k, -1):
+        if t.shape[d] != 1 and t.stride(d) != expect:
+            return False
+        expect *= t.shape[d]
+    return True
+
+
+def frames_to_bytes(x, span=(-1.0, 1.0), quantize="trunc", layout="nchw", out=None):
+    """Frames as bytes (``waldo_frames_to_bytes_fwd``): with ``u = clamp((x - lo) / (hi - lo), 0, 1)`` in fp32,
+    ``"trunc"``: ``uint8(trunc(u * 255))``, what the reference's ``dump_video`` writes (tools/utils.py:246-264);
+    ``"round"``: ``uint8(trunc(u * 255 + 0.5))``, what ``tools.io.dump_video`` / ``dump_image`` write.  NaN gives 0.
+    These are the bytes ``metrics.frame_metrics`` scores under the same ``quantize``.
+
+    ``x``: a tensor (..., C, H, W) in fp32, bf16 or fp16 (W unit-stride; the leading dimensions are flattened by stride
+    where that is possible -- ``output[:, :, :3]`` is read in place -- and copied once otherwise), or a ``PackedClip``
+    (its three RGB channels: the quantised ``rgb_table`` values of its bytes, which under ``"trunc"`` are NOT its bytes
+    for 63 of the 256 values).  ``layout``: ``"nchw"`` -> uint8 (..., C, H, W); ``"nhwc"`` -> uint8 (..., H, W, 3), what a
+    video writer takes (C must be 3).  ``out``: a uint8 tensor of the result's shape to write into -- each frame dense,
+    the leading dimensions flattenable by stride, any alignment (a view into a larger buffer).
+    Detached: no gradient flows, nothing is registered with autograd.  No CPU fallback."""
+    fn = "frames_to_bytes"
+    lo, rng, quant, lay = _byte_args(fn, span, quantize, layout)
+    if isinstance(x, PackedClip):
+        d = _packed_data_view(x, fn)
+        lead, (h, w), c = tuple(d.shape[:2]), d.shape[2:4], 3
+        d = d.flatten(0, 1)  # (a view where the strides allow it)
+        code, strides, table = _SRC_PACKED, (d.stride(0) // 4, 0, d.stride(1) // 4), rgb_table(d.device)
+    else:
+        if not torch.is_tensor(x) or x.ndim < 3 or x.dtype not in _DTYPE_CODE:
+            raise ValueError(f"{fn}: x must be a (..., C, H, W) float32 / bfloat16 / float16 tensor or a PackedClip, got "
+                             f"{getattr(x, 'dtype', type(x).__name__)} {tuple(getattr(x, 'shape', ()))}")
+        if not x.is_cuda:
+            raise _lib.WaldoHipError(f"{fn}: x must be on the GPU (cuda device); there is no CPU fallback")
+        d = x.detach()
+        lead, (c, h, w) = tuple(d.shape[:-3]), d.shape[-3:]
+        if min(c, h, w) < 1:
+            raise ValueError(f"{fn}: empty frames {tuple(x.shape)}")
+        if d.stride(-1) != 1 and w > 1:
+            d = d.contiguous()
+        d = d.reshape(-1, c, h, w)  # (a view where the strides allow it)
+        code, strides, table = _DTYPE_CODE[d.dtype], (d.stride(0), d.stride(1), d.stride(2)), None
+    if lay and c != 3:
+        raise ValueError(f"{fn}: layout 'nhwc' takes 3 channels, got {c}")
+    n = d.shape[0]
+    frame = (h, w, 3) if lay else (c, h, w)
+    if out is None:
+        o = torch.empty((n, *frame), dtype=torch.uint8, device=d.device)
+    else:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (*lead, *frame):
+            raise ValueError(f"{fn}: out must be a uint8 tensor of shape {(*lead, *frame)}, got "
+                             f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
+        if out.device != d.device:
+            raise ValueError(f"{fn}: x on {d.device}, out on {out.device}")
+        try:
+            o = out.view(n, *frame)
+        except RuntimeError:
+            o = None
+        if o is None or not _dense_tail(o, 3):
+            raise ValueError(f"{fn}: out must hold dense frames whose leading dimensions flatten by stride "
+                             f"(strides {tuple(out.stride())})")
+    with _lib.on_device(d.device):
+        _lib.call("waldo_frames_to_bytes_fwd", _lib.ptr(d), code, *strides, _lib.ptr(table), _lib.ptr(o),
+                  o.stride(0) if n > 1 else c * h * w, lay, n, c, h, w, lo, rng, quant, _lib.current_stream(d.device))
+    return out if out is not None else o.view(*lead, *frame)
+
+
+def _packed_data_view(clip, fn):
+    """A packed clip's bytes as the kernels address them: 4-byte pixels at 4-byte aligned, pixel-multiple strides."""
+    if not clip.is_cuda:
+        raise _lib.WaldoHipError(f"{fn}: the packed clip must be on the GPU (PackedClip.to(device)); there is no CPU "
+                                 "fallback")
+    d = clip.data
+    if d.stride(-1) != 1 or d.stride(-2) != 4 or d.data_ptr() % 4 or any(d.stride(i) % 4 for i in range(3)):
+        d = d.contiguous()
+    return d
+
+
+def wif_fuse_bytes(vid, net_out, ab=True, span=(-1.0, 1.0), quantize="trunc", layout="nchw"):
+    """``frames_to_bytes(wif_fuse(vid, net_out, ab), span, quantize, layout)`` in ONE launch
+    (``waldo_wif_fuse_bytes_fwd``): the same bytes, without the fp32 frames in between.  uint8 (B, T, 3, H, W) or, with
+    ``layout="nhwc"``, (B, T, H, W, 3).  Forward only: raises when grad mode is on and an input requires a gradient."""
+    fn = "wif_fuse_bytes"
+    lo, rng, quant, lay = _byte_args(fn, span, quantize, layout)
+    _lib.check_cuda(vid, net_out, half=True)
+    if torch.is_grad_enabled() and (vid.requires_grad or net_out.requires_grad):
+        raise _lib.WaldoHipError(f"{fn}: no gradient flows through the byte output; use wif_fuse")
+    vid, net = _c(vid.detach()), _c(net_out.detach())
+    b, t, tc, c, h, w = vid.shape
+    co = net.shape[3]
+    if tuple(net.shape) != (b, t, tc, co, h, w):
+        raise _lib.WaldoHipError(f"{fn}: shapes {tuple(vid.shape)} vs {tuple(net.shape)}")
+    out = torch.empty((b, t, h, w, 3) if lay else (b, t, 3, h, w), dtype=torch.uint8, device=vid.device)
+    with _lib.on_device(vid.device):
+        _call_dt("waldo_wif_fuse_bytes_fwd", (vid.dtype, net.dtype), _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
+                 b * t, tc, c, co, h * w, int(bool(ab)), lo, rng, quant, lay, _lib.current_stream(vid.device))
     return out
 
 

@@ -57,18 +57,26 @@ class WIF(nn.Module):
     def get_last_layer(self):
         return self.unet.from_emb.weight
 
-    def fuse(self, vid_t, net_out):
-        """vid_t (B, T, Tc, C, H, W) (already permuted), net_out (B, T, Tc, Co, H, W)."""
+    def fuse(self, vid_t, net_out, out_bytes=None):
+        """vid_t (B, T, Tc, C, H, W) (already permuted), net_out (B, T, Tc, Co, H, W).  ``out_bytes`` ("trunc" /
+        "round"): the fused frames as uint8 (B, T, 3, H, W), quantised inside the fusion kernel
+        (``WF.wif_fuse_bytes``: the bytes of ``WF.frames_to_bytes`` on the fp32 result); forward only."""
+        if out_bytes is not None:
+            return WF.wif_fuse_bytes(vid_t, net_out, ab=self.ab, quantize=out_bytes)
         return WF.wif_fuse(vid_t, net_out, ab=self.ab)
 
-    def forward(self, vid):
+    def forward(self, vid, out_bytes=None):
+        """``out_bytes``: None (fp32 frames, as ever), or "trunc" / "round": uint8 frames (``fuse``; without
+        ``ii_score`` the network's output quantised by ``WF.frames_to_bytes``)."""
+        if out_bytes is not None and out_bytes not in WF.BYTE_QUANTIZE:
+            raise ValueError(f"WIF.forward: out_bytes must be None or one of {tuple(WF.BYTE_QUANTIZE)}, got {out_bytes!r}")
         b, tc, t, c, h, w = vid.shape
         vid = vid.permute(0, 2, 1, 3, 4, 5).contiguous()
         if not self.score:
-            out = self.unet(vid.reshape(b * t, tc * c, h, w))
-            return out.reshape(b, t, -1, h, w)
+            out = self.unet(vid.reshape(b * t, tc * c, h, w)).reshape(b, t, -1, h, w)
+            return out if out_bytes is None else WF.frames_to_bytes(out, quantize=out_bytes)
         out = self.unet(vid.reshape(b * t * tc, c, h, w))
-        return self.fuse(vid, out.reshape(b, t, tc, -1, h, w))
+        return self.fuse(vid, out.reshape(b, t, tc, -1, h, w), out_bytes=out_bytes)
 
     # ------------------------------------------------------------------ inpaint (wif.py:58-226)
     def _warp(self, x, flow):

@@ -221,7 +221,7 @@ def _points_grids_occ(opt, warper, net, nb, nt):
 
 
 def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, shared=None, shared_key=None,
-                  out_alpha=None, raw_dtype=None):
+                  out_alpha=None, raw_dtype=None, out_bytes=None):
     """One decode of predict() (estimate_alpha_grid_occ -> decode_output -> disocclusion test -> WIF fusion,
     synthesizer.py:434-460 / 464-484) for ``nb`` clips on the compact time axis ``sel`` (frame numbers: the context
     frames 0 .. ctx_len - 1, then the other frames whose poses the decode needs -- a frame may stand there twice, with
@@ -233,7 +233,9 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
     (nb, n, 1, Hd, Wd), inpainted (nb, n, 3, Hd, Wd), flow (nb, Tc, n, 2, Hd, Wd)).  Every kernel of the chain works
     per (b, t) unit (the layout filter's class distribution per clip, over its context frames), so the bits of a frame
     do not depend on which other frames or clips are decoded beside it (tests/test_gpu_pipeline.py).  ``raw_dtype``:
-    decode_output's (None = fp32; bf16 / fp16: the WIF input in 16 bits, fused by the 16-bit wif_fuse)."""
+    decode_output's (None = fp32; bf16 / fp16: the WIF input in 16 bits, fused by the 16-bit wif_fuse).  ``out_bytes``
+    ("trunc" / "round"): output, disocc and inpainted come back as uint8 (``WF.frames_to_bytes``; the inpainted frames
+    quantised inside the fusion kernel) -- the bytes the reference's save_vid writes of them; flow stays fp32."""
     no = opt.num_obj
     dev = real_input.device
     nt, n = len(sel), len(where)
@@ -332,17 +334,31 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
     dmax = WF.disocc_test(mx)
     if out_alpha is not None:
         out_alpha.append(alpha)
+    if out_bytes is not None:  # (the 3-channel slice and the map are read in place)
+        return (WF.frames_to_bytes(output[:, :, :3], quantize=out_bytes),
+                WF.frames_to_bytes(dmax.unsqueeze(2), quantize=out_bytes), wif(raw_output, out_bytes=out_bytes), flow)
     return output[:, :, :3], dmax.unsqueeze(2), wif(raw_output), flow  # (wif: synthesizer.py:460)
 
 
+def _check_out_bytes(fn, out_bytes):
+    if out_bytes is not None and out_bytes not in WF.BYTE_QUANTIZE:
+        raise ValueError(f"{fn}: out_bytes must be None or one of {tuple(WF.BYTE_QUANTIZE)}, got {out_bytes!r}")
+
+
 @torch.no_grad()
-def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None):
+def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, out_bytes=None):
     """The hot-path part of Synthesizer.predict (models/synthesizer.py:434-480).  real_vid
     (B, T, 3, H, W), real_lyt (B, T, Nl, H, W); ``net`` = synthetic_network_outputs(...).  Or real_vid a
     ``WF.PackedClip`` of frames and class ids (``tools.io.load_clip(..., packed=True)``) and real_lyt None: the same
     results bit for bit, without an fp32 copy of the clip on the fused path.
     ``raw_dtype``: the element type of the WIF input ``raw_output`` (None = fp32; torch.bfloat16 / torch.float16 for a
-    UNet under autocast -- decode_output).  Returns a dict of the tensors predict produces."""
+    UNet under autocast -- decode_output).  Returns a dict of the tensors predict produces.
+    ``out_bytes`` (None, "trunc" or "round"): the ``*_vid`` keys come back as uint8 with 3 channels and the two
+    ``*_disocc`` keys as uint8 with 1 channel -- ``WF.frames_to_bytes`` of what they are without it ("trunc": the bytes
+    the reference's save_vid -> dump_video writes of them, synthesizer.py:403-411), quantised on the device; ``pred_flow``
+    and ``pred_alpha`` stay as they are.  The context frames in front of ``pred_vid`` / ``inp_pred_vid`` are quantised
+    from the clip (a packed clip's bytes are not copied: "trunc" does not give them back)."""
+    _check_out_bytes("predict", out_bytes)
     b, t = real_vid.shape[:2]
     every = list(range(t))
     out = {}
@@ -356,28 +372,31 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None):
         if real_lyt is not None:
             raise ValueError("predict: a packed clip holds the layout already; pass real_lyt=None")
         real_input = real_vid[:, :n_in]
-        ctx_vid = real_vid[:, :ctx_len].rgb()  # (the context frames of pred_vid / inp_pred_vid)
+        ctx_vid = real_vid[:, :ctx_len]  # (the context frames of pred_vid / inp_pred_vid)
+        ctx_vid = ctx_vid.rgb() if out_bytes is None else WF.frames_to_bytes(ctx_vid, quantize=out_bytes)
     else:
         real_input = torch.cat([real_vid[:, :n_in], real_lyt[:, :n_in]], dim=2)
         ctx_vid = real_vid[:, :ctx_len]
+        if out_bytes is not None:
+            ctx_vid = WF.frames_to_bytes(ctx_vid, quantize=out_bytes)
     if getattr(opt, "include_self", False) or not MERGE_DECODES or opt.no_future:
         # the reference's two calls, one after the other (include_self: every frame is a context of itself)
         shared = SharedContext() if not getattr(opt, "include_self", False) else None
         rec, dis, inp, _ = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every, every, shared=shared,
-                                         raw_dtype=raw_dtype)
+                                         raw_dtype=raw_dtype, out_bytes=out_bytes)
         out["rec_vid"], out["rec_disocc"], out["inp_rec_vid"] = rec, dis, inp
         if not opt.no_future:
             alpha = []
             pred, dis, inp, flow = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every,
                                                  list(range(ctx_len, t)), shared=shared, out_alpha=alpha,
-                                                 raw_dtype=raw_dtype)
+                                                 raw_dtype=raw_dtype, out_bytes=out_bytes)
     else:
         # ONE decode for the reconstruction's and the prediction's units (see decode_units): the context's products once,
         # every full-resolution pass launched once with T + Tp units per clip
         alpha = []
         (rec, dis, inp, _), (pred, dis_p, inp_p, flow) = decode_units(
             opt, warper, wif, real_input, net, ctx_len, b, t, 0, b, every, list(range(ctx_len, t)), out_alpha=alpha,
-            raw_dtype=raw_dtype)
+            raw_dtype=raw_dtype, out_bytes=out_bytes)
         out["rec_vid"], out["rec_disocc"], out["inp_rec_vid"] = rec, dis, inp
         dis, inp = dis_p, inp_p
     if not opt.no_future:
@@ -404,10 +423,10 @@ MERGE_DECODES = True
 
 
 def decode_units(opt, warper, wif, real_input, net, ctx_len, b, t, b0, b1, rec_frames, pred_frames, out_alpha=None,
-                 raw_dtype=None):
+                 raw_dtype=None, out_bytes=None):
     """The reconstruction's frames ``rec_frames`` and the prediction's frames ``pred_frames`` (clip-relative frame numbers,
     ascending) of clips b0:b1 in ONE decode.  Returns the two 4-tuples of ``_decode_block`` (either may be None when its
-    list is empty).  ``raw_dtype``: see ``_decode_block``."""
+    list is empty).  ``raw_dtype``, ``out_bytes``: see ``_decode_block``."""
     dev = real_input.device
     rec_new = [f for f in rec_frames if f >= ctx_len]
     sel = list(range(ctx_len)) + rec_new + list(pred_frames)
@@ -415,7 +434,7 @@ def decode_units(opt, warper, wif, real_input, net, ctx_len, b, t, b0, b1, rec_f
             [ctx_len + len(rec_new) + i for i in range(len(pred_frames))]
     blk = _block_net(opt, net, b, t, b0, b1, sel, dev)
     vid, dis, inp, flow = _decode_block(opt, warper, wif, real_input, blk, ctx_len, b1 - b0, sel, where, out_alpha=out_alpha,
-                                        raw_dtype=raw_dtype)
+                                        raw_dtype=raw_dtype, out_bytes=out_bytes)
     nr = len(rec_frames)
 
     def part(lo, hi):
@@ -487,7 +506,7 @@ UNIT_KEYS = {"rec": ("rec_vid", "rec_disocc", "inp_rec_vid"), "pred": ("pred_vid
 
 @torch.no_grad()
 def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, world, phases=("rec", "pred"),
-                    raw_dtype=None):
+                    raw_dtype=None, out_bytes=None):
     """This rank's share of predict() when ONE job (B clips) is split over ``world`` ranks: the
     (b, t) output units of each decode -- B * T reconstructed frames, B * (T - Tc) predicted ones -- are dealt in
     contiguous blocks of the phase's dealing order (dist.shard_range over ``phase_order``: the reconstruction's spreads
@@ -499,8 +518,10 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
     Returns {key: (units, C, Hd, Wd)} with the rank's units in the order of ``local_unit_ids``, for the keys of UNIT_KEYS
     (``pred_vid`` / ``inp_pred_vid``: the predicted frames only; ``pred_flow``: Tc * 2 channels); ``gather_predict`` puts
     the ranks' blocks together into predict()'s dict.  Reference: the data-parallel split of tools/engine.py:63-64, here
-    over frames instead of clips so that one clip can use every GPU.  ``raw_dtype``: see ``predict``."""
+    over frames instead of clips so that one clip can use every GPU.  ``raw_dtype``, ``out_bytes``: see ``predict`` (with
+    ``out_bytes`` the image blocks are uint8 -- a quarter of the bytes the all-gather moves; ``pred_flow`` stays fp32)."""
     from ..dist import shard_range
+    _check_out_bytes("predict_sharded", out_bytes)
     if opt.include_self:
         raise ValueError("predict_sharded: include_self appends the predicted frame itself as a context "
                          "(lvd.py:842-845): every rank would need every frame")
@@ -541,7 +562,7 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
         # this rank's reconstruction and prediction units belong to the same clips: ONE decode for both (decode_units)
         b0, b1, rec_frames = segs["rec"][0]
         rec, pred = decode_units(opt, warper, wif, clip_input(b0, b1), net, ctx_len, b, t, b0, b1, rec_frames,
-                                 segs["pred"][0][2], raw_dtype=raw_dtype)
+                                 segs["pred"][0][2], raw_dtype=raw_dtype, out_bytes=out_bytes)
         keep("rec", b1 - b0, rec)
         keep("pred", b1 - b0, pred)
     else:
@@ -551,22 +572,25 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
                 blk = _block_net(opt, net, b, t, b0, b1, sel, dev)
                 res = _decode_block(opt, warper, wif, clip_input(b0, b1), blk, ctx_len, b1 - b0, sel,
                                     [sel.index(f) for f in frames], shared=shared[(b0, b1)],
-                                    shared_key=job + (inputs[(b0, b1)],), raw_dtype=raw_dtype)
+                                    shared_key=job + (inputs[(b0, b1)],), raw_dtype=raw_dtype, out_bytes=out_bytes)
                 keep(phase, b1 - b0, res)
     for k, v in parts.items():
         if v:
             out[k] = v[0] if len(v) == 1 else torch.cat(v, dim=0)
         else:  # a rank past the end of a short job holds no unit
             ch = {"disocc": 1, "flow": 2 * (opt.last_n_ctx or ctx_len)}.get(k.split("_")[-1], 3)
-            out[k] = real_vid.new_empty(0, ch, hd, wd)
+            as_bytes = out_bytes is not None and k != "pred_flow"
+            out[k] = real_vid.new_empty(0, ch, hd, wd, dtype=torch.uint8 if as_bytes else torch.float32)
     return out
 
 
-def units_to_clips(key, units, b, t, ctx_len, world, real_vid=None):
+def units_to_clips(key, units, b, t, ctx_len, world, real_vid=None, out_bytes=None):
     """The ranks' unit blocks of one key, concatenated in rank order (what the all-gather returns), shaped as predict()
     returns that key: the reconstruction's units go back from dealing order to frame order (one index copy; the
     prediction's are in frame order already), ``pred_flow`` to (B, Tc, Tp, 2, Hd, Wd), the context frames in front of
-    ``pred_vid`` / ``inp_pred_vid`` (``real_vid``)."""
+    ``pred_vid`` / ``inp_pred_vid`` (``real_vid``; with ``out_bytes``, for uint8 units of ``predict_sharded(out_bytes=...)``:
+    quantised the same way -- ``real_vid`` the fp32 clip or a ``WF.PackedClip``)."""
+    _check_out_bytes("units_to_clips", out_bytes)
     phase = "rec" if key in UNIT_KEYS["rec"] else "pred"
     per_clip = t if phase == "rec" else t - ctx_len
     if phase == "rec" and world > 1:
@@ -580,13 +604,18 @@ def units_to_clips(key, units, b, t, ctx_len, world, real_vid=None):
         hd, wd = full.shape[-2:]
         return full.view(b, per_clip, -1, 2, hd, wd).permute(0, 2, 1, 3, 4, 5).contiguous()
     if key in ("pred_vid", "inp_pred_vid") and real_vid is not None:
-        return torch.cat([real_vid[:, :ctx_len], full], dim=1)
+        ctx_vid = real_vid[:, :ctx_len]
+        if out_bytes is not None:
+            ctx_vid = WF.frames_to_bytes(ctx_vid if isinstance(ctx_vid, WF.PackedClip) else ctx_vid[:, :, :3],
+                                         quantize=out_bytes)
+        return torch.cat([ctx_vid, full], dim=1)
     return full
 
 
-def gather_predict(local, real_vid, ctx_len, keys=None, group=None):
+def gather_predict(local, real_vid, ctx_len, keys=None, group=None, out_bytes=None):
     """All-gather the ranks' blocks of ``predict_sharded`` (one collective per key, ALL issued before the first is waited
-    for -- dist.all_gather_frames_async: RCCL over xGMI, or gloo in the tests) and shape them as predict() returns them."""
+    for -- dist.all_gather_frames_async: RCCL over xGMI, or gloo in the tests) and shape them as predict() returns them.
+    ``out_bytes``: what ``predict_sharded`` was given (the collectives then move uint8 blocks)."""
     import torch.distributed as dist
     from ..dist import all_gather_frames_async
     b, t = real_vid.shape[:2]
@@ -596,17 +625,18 @@ def gather_predict(local, real_vid, ctx_len, keys=None, group=None):
     for k in keys:
         per_clip = t if k in UNIT_KEYS["rec"] else t - ctx_len
         pending[k] = all_gather_frames_async(local[k], b * per_clip, group=group)
-    return {k: units_to_clips(k, pending[k].wait(), b, t, ctx_len, world, real_vid) for k in keys}
+    return {k: units_to_clips(k, pending[k].wait(), b, t, ctx_len, world, real_vid, out_bytes=out_bytes) for k in keys}
 
 
 RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --raw-dtype
 
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
-        device="cuda:0", raw_dtype=None, packed=False, eval=False):
+        device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None):
     """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
     ``WF.PackedClip``) and predict() reads it as such -- the same results.  ``eval``: also score ``rec_vid`` and
-    ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``."""
+    ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``.  ``out_bytes``
+    ("trunc" / "round"): predict() returns its clips as uint8, and those bytes are what is written and scored."""
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt)
     size = (dim, int(dim * aspect_ratio))
     clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames, packed=packed)
@@ -618,7 +648,7 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
     warper = Warper(opt).to(dev)
     wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     net = synthetic_network_outputs(opt, 1, vid.shape[1], ctx_len, seed=seed, device=dev)
-    res = predict(opt, warper, wif, vid, lyt, net, ctx_len, raw_dtype=raw_dtype)
+    res = predict(opt, warper, wif, vid, lyt, net, ctx_len, raw_dtype=raw_dtype, out_bytes=out_bytes)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         for key in ("rec_vid", "inp_rec_vid", "pred_vid", "inp_pred_vid"):
@@ -672,12 +702,15 @@ def main():
                     help="element type of the WIF input raw_output (bf16 / fp16: what a UNet under autocast takes)")
     ap.add_argument("--packed", action="store_true",
                     help="hand the clip over packed: RGB bytes + class ids, 4 bytes per pixel (the same results)")
+    ap.add_argument("--bytes", choices=sorted(WF.BYTE_QUANTIZE), default=None, dest="out_bytes",
+                    help="return and write the clips as bytes quantised on the device (trunc: the reference's "
+                         "dump_video; round: this package's)")
     ap.add_argument("--eval", action="store_true",
                     help="score rec_vid and inp_pred_vid against the real frames (PSNR, SSIM, MS-SSIM from 161x161)")
     args = ap.parse_args()
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
-              eval=args.eval)
+              eval=args.eval, out_bytes=args.out_bytes)
     scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "

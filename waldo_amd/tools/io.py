@@ -179,19 +179,38 @@ def _to_uint8(tensor, span):
     return (x * 255.0 + 0.5).to(torch.uint8)
 
 
+def _frames_hwc(tensor, span, fn):
+    """(T, 3 | 1, H, W) in ``span``, or uint8 (T, 3 | 1, H, W) / (T, H, W, 3) taken as it is (``functional.frames_to_bytes``,
+    ``predict(out_bytes=...)``: already quantised, ``span`` is not applied) -> uint8 (T, H, W, 3) on the host.  A
+    1-channel clip (a disocclusion map) is repeated to 3, as the reference's save_vid expands it (synthesizer.py:410)."""
+    if tensor.dtype == torch.uint8:
+        x = tensor.detach().cpu()
+        if x.ndim != 4 or not (x.shape[1] in (1, 3) or x.shape[-1] == 3):
+            raise ValueError(f"{fn}: a uint8 clip must be (T, 3 | 1, H, W) or (T, H, W, 3), got {tuple(x.shape)}")
+        if x.shape[1] not in (1, 3):  # (T, H, W, 3) already; a (T, 3, H, 3) clip reads as planar
+            return x.contiguous()
+    else:
+        x = _to_uint8(tensor, span)
+    if x.shape[1] == 1:
+        x = x.expand(-1, 3, -1, -1)
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
 def dump_image(tensor, path, span=None):
-    """(3, H, W) in ``span`` (default [-1, 1]) -> PNG.  Reference: tools/utils.py:250-255."""
+    """(3, H, W) in ``span`` (default [-1, 1]) -> PNG.  Reference: tools/utils.py:250-255.  A uint8 image -- (3 | 1, H, W)
+    or (H, W, 3) -- is written as it is."""
     import PIL.Image
-    PIL.Image.fromarray(_to_uint8(tensor, span).permute(1, 2, 0).numpy()).save(path)
+    PIL.Image.fromarray(_frames_hwc(tensor.unsqueeze(0), span, "dump_image")[0].numpy()).save(path)
 
 
 def dump_video(tensor, path, span=None, fps=4):
-    """(T, 3, H, W) in ``span`` -> an animation.  The reference writes mp4 through
+    """(T, 3, H, W) in ``span`` -> an animation; a uint8 clip, (T, 3 | 1, H, W) or (T, H, W, 3), is written as it is (no
+    rescaling: the bytes of ``functional.frames_to_bytes``).  The reference writes mp4 through
     torchvision.io.write_video (tools/utils.py:258-264), which needs PyAV / ffmpeg; neither is in
     this image, so the container format follows the extension PIL can write: ``.gif`` / ``.png``
     (APNG) / ``.webp``; a directory path gets one PNG per frame."""
     import PIL.Image
-    frames = [PIL.Image.fromarray(f.permute(1, 2, 0).numpy()) for f in _to_uint8(tensor, span)]
+    frames = [PIL.Image.fromarray(f.numpy()) for f in _frames_hwc(tensor, span, "dump_video")]
     if os.path.isdir(path) or not os.path.splitext(path)[1]:
         os.makedirs(path, exist_ok=True)
         for i, f in enumerate(frames):
