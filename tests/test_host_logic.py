@@ -75,3 +75,20 @@ def test_device_guard_is_free_without_a_device_index():
         pass
     t = torch.zeros(3)
     assert _lib.ptr(None) is None and _lib.ptr(t) == t.data_ptr()
+
+
+def test_launch_arguments_tensors_become_pointers():
+    """`_lib.pointers`, the argument conversion of `_lib.launch`: tensors (subclasses too) travel as their device
+    address, everything else as it is."""
+    from waldo_amd import _lib
+    from waldo_amd.functional import arange_index
+    t = torch.zeros(3)
+    par = torch.nn.Parameter(torch.zeros(2, 2))
+    idx = arange_index(4)
+    n, big, x = 7, 1 << 40, 0.25
+    out = _lib.pointers((t, par, idx, None, n, big, x))
+    assert out[:3] == [t.data_ptr(), par.data_ptr(), idx.data_ptr()] and all(type(v) is int for v in out[:3])
+    assert out[3] is None
+    assert out[4] is n and out[5] is big and out[6] is x
+    view = torch.zeros(4, 6)[:, 2:]                      # a strided view: its own first element
+    assert _lib.pointers([view]) == [view.data_ptr()]

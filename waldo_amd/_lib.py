@@ -357,3 +357,27 @@ def call(name, *args):
 def query(name, *args):
     """A size query of the library (``*_workspace_bytes``): launches nothing."""
     return getattr(load(), name)(*args)
+
+
+_Tensor = torch.Tensor
+_AS_IS = frozenset((int, float, type(None)))
+
+
+def pointers(args):
+    """``args`` as an entry point takes them: every tensor (subclasses too) as its ``data_ptr()``; None (NULL), ints and
+    floats as they are -- addresses that already travel as integers (status words, host arrays) among them.  (Most
+    arguments are plain ints: their exact type is looked up first, ``isinstance`` of a tensor class goes through its
+    metaclass.)"""
+    return [a if type(a) in _AS_IS else a.data_ptr() if isinstance(a, _Tensor) else a for a in args]
+
+
+def launch(name, device, *args):
+    """THE way an op launches: entry point ``name`` on ``device`` (entered only when it is not the current one), tensors
+    passed as themselves (``pointers``), on the stream PyTorch launches on for that very device, appended as the last
+    argument -- where every prototype of SIGNATURES has it.  No checks of the arguments: strided views are passed on
+    purpose, and this is the host's hot path (see ``current_stream``)."""
+    if device.index is None or device.index == torch.cuda.current_device():
+        call(name, *pointers(args), current_stream(device))
+    else:
+        with torch.cuda.device(device):
+            call(name, *pointers(args), current_stream(device))

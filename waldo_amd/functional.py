@@ -110,6 +110,11 @@ def _zeros_like_each(*tensors):
     return out
 
 
+def _empty_like_each(*tensors):
+    """Uninitialised tensors shaped like each argument (None -> None): the gradients a ``*_det`` kernel overwrites."""
+    return [torch.empty_like(t) if t is not None else None for t in tensors]
+
+
 class ArangeIndex(torch.Tensor):
     """A frame index KNOWN on the host to be 0, 1, ..., n - 1 (``arange_index``): ``time_gather`` may then hand out
     the clip itself instead of a gathered copy.  Plain tensors never take that short cut -- telling would need a
@@ -168,9 +173,7 @@ class _TpsMapping(torch.autograd.Function):
         inverse_kernel = _c(inverse_kernel)
         b, n, _ = src_pts.shape
         mapping = src_pts.new_empty(b, n + 3, 2)
-        with _lib.on_device(src_pts.device):
-            _lib.call("waldo_tps_mapping_fwd", _lib.ptr(inverse_kernel), _lib.ptr(src_pts),
-                      _lib.ptr(mapping), b, n, _lib.current_stream(src_pts.device))
+        _lib.launch("waldo_tps_mapping_fwd", src_pts.device, inverse_kernel, src_pts, mapping, b, n)
         ctx.save_for_backward(inverse_kernel)
         ctx.n = n
         return mapping
@@ -181,9 +184,7 @@ class _TpsMapping(torch.autograd.Function):
         grad_mapping = _c(grad_mapping)
         b = grad_mapping.shape[0]
         grad_pts = grad_mapping.new_empty(b, ctx.n, 2)
-        with _lib.on_device(grad_mapping.device):
-            _lib.call("waldo_tps_mapping_bwd", _lib.ptr(inverse_kernel), _lib.ptr(grad_mapping),
-                      _lib.ptr(grad_pts), b, ctx.n, _lib.current_stream(grad_mapping.device))
+        _lib.launch("waldo_tps_mapping_bwd", grad_mapping.device, inverse_kernel, grad_mapping, grad_pts, b, ctx.n)
         return None, grad_pts
 
 
@@ -196,9 +197,7 @@ class _TpsGrid(torch.autograd.Function):
         b, k3, _ = mapping.shape
         hw = basis_t.shape[1]
         grid = mapping.new_empty(b, hw, 2)
-        with _lib.on_device(mapping.device):
-            _lib.call("waldo_tps_grid_fwd", _lib.ptr(basis_t), _lib.ptr(mapping), _lib.ptr(grid),
-                      b, hw, k3, _lib.current_stream(mapping.device))
+        _lib.launch("waldo_tps_grid_fwd", mapping.device, basis_t, mapping, grid, b, hw, k3)
         ctx.save_for_backward(basis_t)
         ctx.k3 = k3
         ctx.det = is_deterministic()
@@ -212,17 +211,13 @@ class _TpsGrid(torch.autograd.Function):
         grad_grid = _c(grad_grid)
         b, hw, _ = grad_grid.shape
         grad_mapping = grad_grid.new_empty(b, ctx.k3, 2)  # zero-filled by the launcher
+        args = (basis_t, grad_grid, grad_mapping, b, hw, ctx.k3)
         if ctx.det:
-            with _lib.on_device(grad_grid.device):
-                ws, nb = _det_workspace("tps_grid", "waldo_tps_grid_bwd_det_workspace_bytes", (b, hw, ctx.k3),
-                                        grad_grid.device)
-                _lib.call("waldo_tps_grid_bwd_det", _lib.ptr(basis_t), _lib.ptr(grad_grid), _lib.ptr(grad_mapping), b,
-                          hw, ctx.k3, _lib.ptr(ws), nb, _lib.current_stream(grad_grid.device))
-            return None, grad_mapping
-        with _lib.on_device(grad_grid.device):
-            _lib.call("waldo_tps_grid_bwd", _lib.ptr(basis_t), _lib.ptr(grad_grid),
-                      _lib.ptr(grad_mapping), b, hw, ctx.k3,
-                      _lib.current_stream(grad_grid.device))
+            ws, nb = _det_workspace("tps_grid", "waldo_tps_grid_bwd_det_workspace_bytes", (b, hw, ctx.k3),
+                                    grad_grid.device)
+            _lib.launch("waldo_tps_grid_bwd_det", grad_grid.device, *args, ws, nb)
+        else:
+            _lib.launch("waldo_tps_grid_bwd", grad_grid.device, *args)
         return None, grad_mapping
 
 
@@ -263,23 +258,18 @@ class _InverseWarp(torch.autograd.Function):
         denom = src_grid.new_empty(b, hwp)
         mask_a = torch.empty(b, hwp, dtype=torch.uint8, device=dev)
         mask_b = torch.empty(b, hwp, dtype=torch.uint8, device=dev)
-        work = (_lib.ptr(out), _lib.ptr(dxy), _lib.ptr(cell), _lib.ptr(winner), _lib.ptr(field_a),
-                _lib.ptr(field_b), _lib.ptr(fill_iter), _lib.ptr(denom), _lib.ptr(mask_a),
-                _lib.ptr(mask_b), b, hs, ws, h, w, niter, int(bool(erode)), ksize)
-        with _lib.on_device(dev):
-            if order is None:
-                _lib.call("waldo_inverse_warp_fwd", _lib.ptr(src_grid), _lib.ptr(src_id),
-                          _lib.ptr(tgt_id), _lib.ptr(gauss), *work, _lib.current_stream(dev))
-            else:
-                if not (rank.is_cuda and order.is_cuda):
-                    raise _lib.WaldoHipError("inverse_warp: rank / order must be on the GPU")
-                if (rank.dtype != torch.int32 or order.dtype != torch.int32
-                        or rank.numel() != h * w or order.numel() != h * w):
-                    raise _lib.WaldoHipError("inverse_warp: rank / order must be int32 of H*W elements")
-                rank, order = rank.contiguous(), order.contiguous()
-                _lib.call("waldo_inverse_warp_order_fwd", _lib.ptr(src_grid), _lib.ptr(src_id),
-                          _lib.ptr(tgt_id), _lib.ptr(gauss), _lib.ptr(rank), _lib.ptr(order), *work,
-                          _lib.current_stream(dev))
+        work = (out, dxy, cell, winner, field_a, field_b, fill_iter, denom, mask_a, mask_b, b, hs, ws, h, w, niter,
+                int(bool(erode)), ksize)
+        if order is None:
+            _lib.launch("waldo_inverse_warp_fwd", dev, src_grid, src_id, tgt_id, gauss, *work)
+        else:
+            if not (rank.is_cuda and order.is_cuda):
+                raise _lib.WaldoHipError("inverse_warp: rank / order must be on the GPU")
+            if (rank.dtype != torch.int32 or order.dtype != torch.int32
+                    or rank.numel() != h * w or order.numel() != h * w):
+                raise _lib.WaldoHipError("inverse_warp: rank / order must be int32 of H*W elements")
+            rank, order = rank.contiguous(), order.contiguous()
+            _lib.launch("waldo_inverse_warp_order_fwd", dev, src_grid, src_id, tgt_id, gauss, rank, order, *work)
         ctx.save_for_backward(gauss, cell, winner, fill_iter, denom, mask_a)
         ctx.cfg = (b, hs, ws, h, w, niter, ksize)
         return out
@@ -291,11 +281,8 @@ class _InverseWarp(torch.autograd.Function):
         grad_out = _c(grad_out)
         gfield = grad_out.new_empty(b, 2, fill_iter.shape[1])
         gsrc = grad_out.new_empty(b, hs, ws, 2)
-        with _lib.on_device(grad_out.device):
-            _lib.call("waldo_inverse_warp_bwd", _lib.ptr(grad_out), _lib.ptr(gauss), _lib.ptr(cell),
-                      _lib.ptr(winner), _lib.ptr(fill_iter), _lib.ptr(denom), _lib.ptr(mask),
-                      _lib.ptr(gfield), _lib.ptr(gsrc), b, hs, ws, h, w, niter, ksize,
-                      _lib.current_stream(grad_out.device))
+        _lib.launch("waldo_inverse_warp_bwd", grad_out.device, grad_out, gauss, cell, winner, fill_iter, denom, mask,
+                    gfield, gsrc, b, hs, ws, h, w, niter, ksize)
         return gsrc, None, None, None, None, None, None, None
 
 
@@ -357,15 +344,12 @@ class _GridSample(torch.autograd.Function):
             outer_div = inner = max(n, 1)
         out = inp.new_empty(n, c, ho, wo)
         mask = inp.new_empty(n, 1, ho, wo) if want_mask else None
-        with _lib.on_device(inp.device):
-            if want_mask:
-                _lib.call("waldo_grid_sample2d_ex_fwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(out), _lib.ptr(mask),
-                          n, c, hi, wi, ho, wo, float(delta), outer_div, inner, max(n, 1), max(n, 1),
-                          max(n, 1), max(n, 1), 0, 1.0, 0.0, _lib.current_stream(inp.device))
-            else:
-                _lib.call("waldo_grid_sample2d_fwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(out), n,
-                          c, hi, wi, ho, wo, float(delta), outer_div, inner, max(n, 1), max(n, 1),
-                          _lib.current_stream(inp.device))
+        if want_mask:
+            _lib.launch("waldo_grid_sample2d_ex_fwd", inp.device, inp, grid, out, mask, n, c, hi, wi, ho, wo,
+                        float(delta), outer_div, inner, max(n, 1), max(n, 1), max(n, 1), max(n, 1), 0, 1.0, 0.0)
+        else:
+            _lib.launch("waldo_grid_sample2d_fwd", inp.device, inp, grid, out, n, c, hi, wi, ho, wo, float(delta),
+                        outer_div, inner, max(n, 1), max(n, 1))
         ctx.save_for_backward(inp, grid)
         ctx.cfg = (float(delta), outer_div, inner)
         ctx.det = is_deterministic()
@@ -383,21 +367,15 @@ class _GridSample(torch.autograd.Function):
         grad_out = _c(grad_out)
         nin, c, hi, wi = inp.shape
         n, ho, wo, _ = grid.shape
-        if ctx.det:
-            gi = torch.empty_like(inp) if ctx.needs_input_grad[0] else None
-            gg = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
-            with _lib.on_device(inp.device):
-                ws, nb = _gs_det_workspace(gi, n, nin, c, hi, wi, ho, wo, inp.device)
-                _lib.call("waldo_grid_sample2d_bwd_det", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(grad_out), _lib.ptr(gi),
-                          _lib.ptr(gg), n, nin, c, hi, wi, ho, wo, delta, outer_div, inner, _lib.ptr(ws), nb,
-                          _lib.current_stream(inp.device))
-            return gi, gg, None, None, None, None
-        gi = torch.zeros_like(inp) if ctx.needs_input_grad[0] else None
+        # grad_input: overwritten by the deterministic kernel, accumulated into with atomics by the other
+        gi = (torch.empty_like if ctx.det else torch.zeros_like)(inp) if ctx.needs_input_grad[0] else None
         gg = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
-        with _lib.on_device(inp.device):
-            _lib.call("waldo_grid_sample2d_bwd", _lib.ptr(inp), _lib.ptr(grid),
-                      _lib.ptr(grad_out), _lib.ptr(gi), _lib.ptr(gg), n, c, hi, wi, ho, wo,
-                      delta, outer_div, inner, _lib.current_stream(inp.device))
+        head, tail = (inp, grid, grad_out, gi, gg, n), (c, hi, wi, ho, wo, delta, outer_div, inner)
+        if ctx.det:
+            ws, nb = _gs_det_workspace(gi, n, nin, c, hi, wi, ho, wo, inp.device)
+            _lib.launch("waldo_grid_sample2d_bwd_det", inp.device, *head, nin, *tail, ws, nb)
+        else:
+            _lib.launch("waldo_grid_sample2d_bwd", inp.device, *head, *tail)
         return gi, gg, None, None, None, None
 
 
@@ -447,14 +425,12 @@ def grid_sample(inp, grid, delta=0.0, broadcast=None, grid_repeat=None, return_m
             grp, stride, off = max(n_out, 1), max(n_out, 1), 0
             res = inp.new_empty(n_out, c, ho, wo)
         mask = inp.new_empty(n_out, 1, ho, wo) if return_mask else None
-        with _lib.on_device(inp.device):
-            if return_mask or out is not None:
-                _lib.call("waldo_grid_sample2d_ex_fwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(res), _lib.ptr(mask),
-                          n_out, c, hi, wi, ho, wo, float(delta), od, inn, god, gin, grp, stride, off, 1.0, 0.0,
-                          _lib.current_stream(inp.device))
-            else:
-                _lib.call("waldo_grid_sample2d_fwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(res), n_out, c, hi, wi,
-                          ho, wo, float(delta), od, inn, god, gin, _lib.current_stream(inp.device))
+        if return_mask or out is not None:
+            _lib.launch("waldo_grid_sample2d_ex_fwd", inp.device, inp, grid, res, mask, n_out, c, hi, wi, ho, wo,
+                        float(delta), od, inn, god, gin, grp, stride, off, 1.0, 0.0)
+        else:
+            _lib.launch("waldo_grid_sample2d_fwd", inp.device, inp, grid, res, n_out, c, hi, wi, ho, wo, float(delta),
+                        od, inn, god, gin)
         return (res, mask) if return_mask else res
     od, inn = broadcast if broadcast is not None else (None, None)
     return _GridSample.apply(inp, grid, delta, od, inn, bool(return_mask))
@@ -471,14 +447,12 @@ class _LayersToOutput(torch.autograd.Function):
         mask = obj.new_empty(nf * no, 1, h, w) if want_mask else None
         calls = ((obj, grid_obj, mask, nf * no, delta_obj, obj_bc, (no, nl, 1)),
                  (bg, grid_bg, None, nf, delta_bg, bg_bc, (1, nl, 0)))
-        with _lib.on_device(obj.device):
-            for inp, grid, msk, n, delta, bc, slots in calls:
-                if n == 0:  # (no frames, or no objects: the background alone)
-                    continue
-                od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
-                _lib.call("waldo_grid_sample2d_ex_fwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(out), _lib.ptr(msk),
-                          n, c, inp.shape[2], inp.shape[3], h, w, float(delta), od, inn, max(n, 1), max(n, 1),
-                          *slots, float(pre[0]), float(pre[1]), _lib.current_stream(obj.device))
+        for inp, grid, msk, n, delta, bc, slots in calls:
+            if n == 0:  # (no frames, or no objects: the background alone)
+                continue
+            od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
+            _lib.launch("waldo_grid_sample2d_ex_fwd", obj.device, inp, grid, out, msk, n, c, inp.shape[2], inp.shape[3],
+                        h, w, float(delta), od, inn, max(n, 1), max(n, 1), *slots, float(pre[0]), float(pre[1]))
         ctx.save_for_backward(obj, bg, grid_obj, grid_bg)
         ctx.cfg = (float(delta_obj), float(delta_bg), obj_bc, bg_bc, (float(pre[0]), float(pre[1])), no)
         ctx.det = is_deterministic()
@@ -501,28 +475,22 @@ class _LayersToOutput(torch.autograd.Function):
         grad_out = _c(grad_out)
         need = ctx.needs_input_grad
         res = []
-        if ctx.det:  # (overwritten by the kernels)
-            gis = [torch.empty_like(obj) if need[0] else None, torch.empty_like(bg) if need[1] else None]
-        else:
-            gis = _zeros_like_each(obj if need[0] else None, bg if need[1] else None)
+        # (overwritten by the deterministic kernels, accumulated into by the others)
+        gis = (_empty_like_each if ctx.det else _zeros_like_each)(obj if need[0] else None, bg if need[1] else None)
         calls = ((obj, grid_obj, nf * no, delta_obj, obj_bc, (no, nl, 1), gis[0], need[2]),
                  (bg, grid_bg, nf, delta_bg, bg_bc, (1, nl, 0), gis[1], need[3]))
-        with _lib.on_device(obj.device):
-            for inp, grid, n, delta, bc, slots, gi, want_g in calls:
-                want_i = gi is not None
-                gg = torch.empty_like(grid) if want_g else None
-                if ctx.det and (want_i or want_g):
-                    od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
-                    ws, nb = _gs_det_workspace(gi, n, inp.shape[0], c, inp.shape[2], inp.shape[3], h, w, obj.device)
-                    _lib.call("waldo_grid_sample2d_ex_bwd_det", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(grad_out),
-                              _lib.ptr(gi), _lib.ptr(gg), n, inp.shape[0], c, inp.shape[2], inp.shape[3], h, w, delta,
-                              od, inn, *slots, pre[0], pre[1], _lib.ptr(ws), nb, _lib.current_stream(obj.device))
-                elif n > 0 and (want_i or want_g):
-                    od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
-                    _lib.call("waldo_grid_sample2d_ex_bwd", _lib.ptr(inp), _lib.ptr(grid), _lib.ptr(grad_out),
-                              _lib.ptr(gi), _lib.ptr(gg), n, c, inp.shape[2], inp.shape[3], h, w, delta, od, inn,
-                              *slots, pre[0], pre[1], _lib.current_stream(obj.device))
-                res.append((gi, gg))
+        for inp, grid, n, delta, bc, slots, gi, want_g in calls:
+            gg = torch.empty_like(grid) if want_g else None
+            if (ctx.det or n > 0) and (gi is not None or want_g):
+                nin, _, hi, wi = inp.shape
+                od, inn = bc if bc is not None else (max(n, 1), max(n, 1))
+                head, tail = (inp, grid, grad_out, gi, gg, n), (c, hi, wi, h, w, delta, od, inn, *slots, pre[0], pre[1])
+                if ctx.det:
+                    ws, nb = _gs_det_workspace(gi, n, nin, c, hi, wi, h, w, obj.device)
+                    _lib.launch("waldo_grid_sample2d_ex_bwd_det", obj.device, *head, nin, *tail, ws, nb)
+                else:
+                    _lib.launch("waldo_grid_sample2d_ex_bwd", obj.device, *head, *tail)
+            res.append((gi, gg))
         return res[0][0], res[1][0], res[0][1], res[1][1], None, None, None, None, None, None
 
 
@@ -575,9 +543,7 @@ class _OccComposite(torch.autograd.Function):
         occ = _c(occ)
         m, nl, hw = alpha.shape
         out = torch.empty_like(alpha)
-        with _lib.on_device(alpha.device):
-            _lib.call("waldo_occ_composite_fwd", _lib.ptr(alpha), _lib.ptr(occ), _lib.ptr(out), m,
-                      nl, hw, occ_div, _lib.current_stream(alpha.device))
+        _lib.launch("waldo_occ_composite_fwd", alpha.device, alpha, occ, out, m, nl, hw, occ_div)
         ctx.save_for_backward(alpha, occ)
         ctx.occ_div = occ_div
         ctx.det = is_deterministic()
@@ -589,21 +555,17 @@ class _OccComposite(torch.autograd.Function):
         grad_out = _c(grad_out)
         m, nl, hw = alpha.shape
         ga = torch.empty_like(alpha)
-        if ctx.det and ctx.needs_input_grad[1]:
-            go = torch.empty_like(occ)
-            with _lib.on_device(alpha.device):
-                ws, nb = _det_workspace("occ_composite", "waldo_occ_composite_bwd_det_workspace_bytes", (m, nl, hw),
-                                        alpha.device)
-                if occ.shape[0] * ctx.occ_div != m:  # (matrices no map reads: the kernel overwrites those it sums)
-                    go.zero_()
-                _lib.call("waldo_occ_composite_bwd_det", _lib.ptr(alpha), _lib.ptr(occ), _lib.ptr(grad_out), _lib.ptr(ga),
-                          _lib.ptr(go), m, nl, hw, ctx.occ_div, _lib.ptr(ws), nb, _lib.current_stream(alpha.device))
-            return ga, go, None
-        go = torch.zeros_like(occ) if ctx.needs_input_grad[1] else None
-        with _lib.on_device(alpha.device):
-            _lib.call("waldo_occ_composite_bwd", _lib.ptr(alpha), _lib.ptr(occ),
-                      _lib.ptr(grad_out), _lib.ptr(ga), _lib.ptr(go), m, nl, hw, ctx.occ_div,
-                      _lib.current_stream(alpha.device))
+        det = ctx.det and ctx.needs_input_grad[1]  # (grad_alpha is written per pixel: only grad_occ is a sum)
+        go = (torch.empty_like if det else torch.zeros_like)(occ) if ctx.needs_input_grad[1] else None
+        args = (alpha, occ, grad_out, ga, go, m, nl, hw, ctx.occ_div)
+        if det:
+            ws, nb = _det_workspace("occ_composite", "waldo_occ_composite_bwd_det_workspace_bytes", (m, nl, hw),
+                                    alpha.device)
+            if occ.shape[0] * ctx.occ_div != m:  # (matrices no map reads: the kernel overwrites those it sums)
+                go.zero_()
+            _lib.launch("waldo_occ_composite_bwd_det", alpha.device, *args, ws, nb)
+        else:
+            _lib.launch("waldo_occ_composite_bwd", alpha.device, *args)
         return ga, go, None
 
 
@@ -626,9 +588,7 @@ class _ComputeOcc(torch.autograd.Function):
         score = _c(score)
         m, no = score.shape
         occ = score.new_empty(m, no + 1, no + 1)
-        with _lib.on_device(score.device):
-            _lib.call("waldo_compute_occ_fwd", _lib.ptr(score), _lib.ptr(occ), m, no, float(eps),
-                      _lib.current_stream(score.device))
+        _lib.launch("waldo_compute_occ_fwd", score.device, score, occ, m, no, float(eps))
         ctx.save_for_backward(score)
         ctx.eps = float(eps)
         return occ
@@ -639,9 +599,7 @@ class _ComputeOcc(torch.autograd.Function):
         grad_occ = _c(grad_occ)
         m, no = score.shape
         gs = torch.empty_like(score)
-        with _lib.on_device(score.device):
-            _lib.call("waldo_compute_occ_bwd", _lib.ptr(score), _lib.ptr(grad_occ), _lib.ptr(gs), m, no,
-                      ctx.eps, _lib.current_stream(score.device))
+        _lib.launch("waldo_compute_occ_bwd", score.device, score, grad_occ, gs, m, no, ctx.eps)
         return gs, None
 
 
@@ -667,9 +625,8 @@ class _AlphaHead(torch.autograd.Function):
             raise _lib.WaldoHipError(f"alpha_head: mask has {mask.numel()} elements, expected "
                                      f"{h * scale}x{w * scale}")
         out = x.new_empty(n, c, h * scale, w * scale)
-        with _lib.on_device(x.device):
-            _lib.call("waldo_alpha_head_fwd", _lib.ptr(x), _lib.ptr(prior), _lib.ptr(mask), _lib.ptr(out), n, c,
-                      h, w, scale, float(bias), int(has_alpha), mode, _lib.current_stream(x.device))
+        _lib.launch("waldo_alpha_head_fwd", x.device, x, prior, mask, out, n, c, h, w, scale, float(bias),
+                    int(has_alpha), mode)
         ctx.save_for_backward(x, prior, mask)
         ctx.cfg = (scale, float(bias), int(has_alpha), mode)
         return out
@@ -681,9 +638,8 @@ class _AlphaHead(torch.autograd.Function):
         grad_out = _c(grad_out)
         n, c, h, w = x.shape
         gx = torch.empty_like(x)
-        with _lib.on_device(x.device):
-            _lib.call("waldo_alpha_head_bwd", _lib.ptr(x), _lib.ptr(prior), _lib.ptr(mask), _lib.ptr(grad_out),
-                      _lib.ptr(gx), n, c, h, w, scale, bias, has_alpha, mode, _lib.current_stream(x.device))
+        _lib.launch("waldo_alpha_head_bwd", x.device, x, prior, mask, grad_out, gx, n, c, h, w, scale, bias, has_alpha,
+                    mode)
         return gx, None, None, None, None, None, None
 
 
@@ -697,9 +653,7 @@ def disocc_test(layer_max):
     layer_max = _c(layer_max.detach())
     b, tc, tp, h, w = layer_max.shape
     out = layer_max.new_empty(b, tp, h, w)
-    with _lib.on_device(layer_max.device):
-        _lib.call("waldo_disocc_test_fwd", _lib.ptr(layer_max), _lib.ptr(out), b, tc, tp, h * w,
-                  _lib.current_stream(layer_max.device))
+    _lib.launch("waldo_disocc_test_fwd", layer_max.device, layer_max, out, b, tc, tp, h * w)
     return out
 
 
@@ -723,9 +677,8 @@ class _PoseAffine(torch.autograd.Function):
             raise _lib.WaldoHipError(f"pose_affine: inconsistent shapes pose={tuple(pose.shape)} "
                                      f"base={tuple(base.shape)}")
         out = pose.new_empty(r, p, 2)
-        with _lib.on_device(pose.device):
-            _lib.call("waldo_pose_affine_fwd", _lib.ptr(pose), _lib.ptr(mul6), _lib.ptr(bias6), _lib.ptr(base),
-                      _lib.ptr(out), r, p, float(mul_delta), float(pts_mul), _lib.current_stream(pose.device))
+        _lib.launch("waldo_pose_affine_fwd", pose.device, pose, mul6, bias6, base, out, r, p, float(mul_delta),
+                    float(pts_mul))
         ctx.save_for_backward(pose, mul6, bias6, base)
         ctx.cfg = (float(mul_delta), float(pts_mul))
         return out
@@ -736,10 +689,8 @@ class _PoseAffine(torch.autograd.Function):
         grad_out = _c(grad_out)
         r, d = pose.shape
         gp = torch.empty_like(pose)
-        with _lib.on_device(pose.device):
-            _lib.call("waldo_pose_affine_bwd", _lib.ptr(pose), _lib.ptr(mul6), _lib.ptr(bias6), _lib.ptr(base),
-                      _lib.ptr(grad_out), _lib.ptr(gp), r, (d - 6) // 2, ctx.cfg[0], ctx.cfg[1],
-                      _lib.current_stream(pose.device))
+        _lib.launch("waldo_pose_affine_bwd", pose.device, pose, mul6, bias6, base, grad_out, gp, r, (d - 6) // 2,
+                    ctx.cfg[0], ctx.cfg[1])
         return gp, None, None, None, None, None
 
 
@@ -760,14 +711,12 @@ def pose_affine(pose, mul6, bias6, base_pts, mul_delta=1.0, pts_mul=1.0):
 _DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def _call_dt(name, dtypes, *args):
-    """``name`` when every dtype is fp32, else ``name + "_dt"`` with the dtype codes inserted before the stream (the
-    last argument).  fp32 work keeps launching the fp32 entry point under its own name (KernelTimer keys on it)."""
-    codes = [_DTYPE_CODE[d] for d in dtypes]
-    if any(codes):
-        _lib.call(name + "_dt", *args[:-1], *codes, args[-1])
-    else:
-        _lib.call(name, *args)
+def _dt_entry(name, *dtypes):
+    """(entry point, its trailing arguments) for buffers of ``dtypes``: ``name`` and nothing when every one is fp32,
+    else ``name + "_dt"`` and the dtype codes.  fp32 work keeps launching the fp32 entry point under its own name
+    (KernelTimer keys on it)."""
+    codes = tuple(_DTYPE_CODE[d] for d in dtypes)
+    return (name + "_dt", codes) if any(codes) else (name, ())
 
 
 class _WifFuse(torch.autograd.Function):
@@ -780,9 +729,8 @@ class _WifFuse(torch.autograd.Function):
         if tuple(net.shape) != (b, t, tc, co, h, w):
             raise _lib.WaldoHipError(f"wif_fuse: shapes {tuple(vid.shape)} vs {tuple(net.shape)}")
         out = vid.new_empty(b, t, 3, h, w, dtype=torch.float32)
-        with _lib.on_device(vid.device):
-            _call_dt("waldo_wif_fuse_fwd", (vid.dtype, net.dtype), _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
-                     b * t, tc, c, co, h * w, int(bool(ab)), _lib.current_stream(vid.device))
+        name, codes = _dt_entry("waldo_wif_fuse_fwd", vid.dtype, net.dtype)
+        _lib.launch(name, vid.device, vid, net, out, b * t, tc, c, co, h * w, int(bool(ab)), *codes)
         ctx.save_for_backward(vid, net, out)
         ctx.ab = int(bool(ab))
         return out
@@ -795,10 +743,8 @@ class _WifFuse(torch.autograd.Function):
         grad_out = _c(grad_out)
         gv = torch.empty_like(vid) if ctx.needs_input_grad[0] else None
         gn = torch.empty_like(net) if ctx.needs_input_grad[1] else None
-        with _lib.on_device(vid.device):
-            _call_dt("waldo_wif_fuse_bwd", (vid.dtype, net.dtype), _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
-                     _lib.ptr(grad_out), _lib.ptr(gv), _lib.ptr(gn), b * t, tc, c, co, h * w, ctx.ab,
-                     _lib.current_stream(vid.device))
+        name, codes = _dt_entry("waldo_wif_fuse_bwd", vid.dtype, net.dtype)
+        _lib.launch(name, vid.device, vid, net, out, grad_out, gv, gn, b * t, tc, c, co, h * w, ctx.ab, *codes)
         return gv, gn, None
 
 
@@ -823,12 +769,10 @@ class _LytDist(torch.autograd.Function):
         dist = alpha.new_empty(b, no, nl)
         mean = alpha.new_empty(b, no, nl)
         total = alpha.new_empty(b, no)
-        wsb = _lib.load().waldo_lyt_dist_workspace_bytes(b, tw, no, nl, h, w)
+        wsb = _lib.query("waldo_lyt_dist_workspace_bytes", b, tw, no, nl, h, w)
         ws = alpha.new_empty(max(wsb, 4) // 4)
-        with _lib.on_device(dev):
-            _lib.call("waldo_lyt_dist_fwd", _lib.ptr(alpha), _lib.ptr(lyt), lyt.stride(0), lyt.stride(1),
-                      _lib.ptr(cls), float(min_cls), _lib.ptr(dist), _lib.ptr(mean), _lib.ptr(total),
-                      _lib.ptr(ws), b, tw, la, first_obj, no, nl, h, w, _lib.current_stream(dev))
+        _lib.launch("waldo_lyt_dist_fwd", dev, alpha, lyt, lyt.stride(0), lyt.stride(1), cls, float(min_cls), dist, mean,
+                    total, ws, b, tw, la, first_obj, no, nl, h, w)
         ctx.save_for_backward(alpha, lyt, cls, dist, mean, total)
         ctx.cfg = (float(min_cls), first_obj)
         ctx.mark_non_differentiable(mean, total)
@@ -845,13 +789,10 @@ class _LytDist(torch.autograd.Function):
         g_dist = _c(g_dist)
         g_alpha = torch.empty_like(alpha)
         g_cls = torch.empty_like(cls) if cls is not None else None
-        wsb = _lib.load().waldo_lyt_dist_workspace_bytes(b, tw, no, nl, h, w)
+        wsb = _lib.query("waldo_lyt_dist_workspace_bytes", b, tw, no, nl, h, w)
         ws = alpha.new_empty(max(wsb, 4) // 4)
-        with _lib.on_device(dev):
-            _lib.call("waldo_lyt_dist_bwd", _lib.ptr(g_dist), _lib.ptr(alpha), _lib.ptr(lyt), lyt.stride(0),
-                      lyt.stride(1), _lib.ptr(cls), min_cls, _lib.ptr(dist), _lib.ptr(mean),
-                      _lib.ptr(total), _lib.ptr(g_alpha), _lib.ptr(g_cls), _lib.ptr(ws), b, tw, la,
-                      first_obj, no, nl, h, w, _lib.current_stream(dev))
+        _lib.launch("waldo_lyt_dist_bwd", dev, g_dist, alpha, lyt, lyt.stride(0), lyt.stride(1), cls, min_cls, dist, mean,
+                    total, g_alpha, g_cls, ws, b, tw, la, first_obj, no, nl, h, w)
         return g_alpha, None, g_cls, None, None
 
 
@@ -877,18 +818,28 @@ def lyt_dist(alpha, lyt, cls=None, min_cls=0.0, first_obj=1):
     return _LytDist.apply(alpha, lyt, cls, float(min_cls), int(first_obj))[0]
 
 
+def _flow_ctx_alpha_fwd(alpha_lr, input, dist, occ, tw, chan_off, scale, want_alpha=True, want_bits=False):
+    """The forward launch of ``flow_ctx_alpha`` on checked, contiguous arguments (``input``: the fp32 clip or a
+    ``PackedClip``) -> (a01, alpha or None, layer_bits or None)."""
+    n, nl, h, w = alpha_lr.shape
+    b, t, c, hd, wd = input.shape
+    dev = alpha_lr.device
+    a01 = alpha_lr.new_empty(n, nl, hd, wd)
+    alpha = alpha_lr.new_empty(n, nl, hd, wd) if want_alpha else None
+    bits = torch.empty(n, hd, (wd + 63) // 64, dtype=torch.int32, device=dev) if want_bits else None
+    if isinstance(input, PackedClip):
+        _lib.launch("waldo_flow_ctx_alpha_packed_fwd", dev, alpha_lr, _packed_data(input, "flow_ctx_alpha"), dist, occ,
+                    a01, alpha, bits, b, t, tw, nl, input.num_lyt, h, w, scale)
+    else:
+        _lib.launch("waldo_flow_ctx_alpha_fwd", dev, alpha_lr, input, dist, occ, a01, alpha, bits, b, t, tw, nl,
+                    dist.shape[2] if dist is not None else 0, c, chan_off, h, w, scale)
+    return a01, alpha, bits
+
+
 class _FlowCtxAlpha(torch.autograd.Function):
     @staticmethod
     def forward(ctx, alpha_lr, input, dist, occ, tw, chan_off, scale):
-        n, nl, h, w = alpha_lr.shape
-        b, t, c, hd, wd = input.shape
-        ncls = dist.shape[2] if dist is not None else 0
-        a01 = alpha_lr.new_empty(n, nl, hd, wd)
-        out = alpha_lr.new_empty(n, nl, hd, wd)
-        with _lib.on_device(alpha_lr.device):
-            _lib.call("waldo_flow_ctx_alpha_fwd", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist),
-                      _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(out), None, b, t, tw, nl, ncls, c, chan_off, h, w,
-                      scale, _lib.current_stream(alpha_lr.device))
+        a01, out, _ = _flow_ctx_alpha_fwd(alpha_lr, input, dist, occ, tw, chan_off, scale)
         ctx.save_for_backward(alpha_lr, input, dist, occ)
         ctx.cfg = (tw, chan_off, scale)
         ctx.det = is_deterministic()
@@ -909,25 +860,18 @@ class _FlowCtxAlpha(torch.autograd.Function):
         g_a01 = _c(g_a01) if g_a01 is not None else None
         g_out = _c(g_out) if g_out is not None else None
         g_lr = torch.empty_like(alpha_lr)
-        if ctx.det:
-            g_dist = torch.empty_like(dist) if (dist is not None and ctx.needs_input_grad[2]) else None
-            g_occ = torch.empty_like(occ) if ctx.needs_input_grad[3] else None
-            with _lib.on_device(alpha_lr.device):
-                ws, nb = _det_workspace("flow_ctx_alpha", "waldo_flow_ctx_alpha_bwd_det_workspace_bytes",
-                                        (b, tw, nl, ncls, h, w, scale), alpha_lr.device)
-                _lib.call("waldo_flow_ctx_alpha_bwd_det", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist),
-                          _lib.ptr(occ), _lib.ptr(g_a01), _lib.ptr(g_out), _lib.ptr(g_lr), _lib.ptr(g_dist),
-                          _lib.ptr(g_occ), _lib.ptr(ws), nb, b, t, tw, nl, ncls, c, chan_off, h, w, scale,
-                          _lib.current_stream(alpha_lr.device))
-            return g_lr, None, g_dist, g_occ, None, None, None
-        g_dist, g_occ = _zeros_like_each(dist if (dist is not None and ctx.needs_input_grad[2]) else None,
-                                         occ if ctx.needs_input_grad[3] else None)
-        ws = alpha_lr.new_empty(n, nl, hd, wd) if scale > 1 else None
-        with _lib.on_device(alpha_lr.device):
-            _lib.call("waldo_flow_ctx_alpha_bwd", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist),
-                      _lib.ptr(occ), _lib.ptr(g_a01), _lib.ptr(g_out), _lib.ptr(g_lr), _lib.ptr(g_dist), _lib.ptr(g_occ),
-                      _lib.ptr(ws), b, t, tw, nl, ncls, c, chan_off, h, w, scale,
-                      _lib.current_stream(alpha_lr.device))
+        summed = (dist if (dist is not None and ctx.needs_input_grad[2]) else None, occ if ctx.needs_input_grad[3] else None)
+        if ctx.det:  # (the sums are overwritten; the workspace travels with its size)
+            name = "waldo_flow_ctx_alpha_bwd_det"
+            g_dist, g_occ = _empty_like_each(*summed)
+            ws = _det_workspace("flow_ctx_alpha", "waldo_flow_ctx_alpha_bwd_det_workspace_bytes",
+                                (b, tw, nl, ncls, h, w, scale), alpha_lr.device)
+        else:
+            name = "waldo_flow_ctx_alpha_bwd"
+            g_dist, g_occ = _zeros_like_each(*summed)
+            ws = (alpha_lr.new_empty(n, nl, hd, wd) if scale > 1 else None,)
+        _lib.launch(name, alpha_lr.device, alpha_lr, input, dist, occ, g_a01, g_out, g_lr, g_dist, g_occ, *ws, b, t, tw,
+                    nl, ncls, c, chan_off, h, w, scale)
         return g_lr, None, g_dist, g_occ, None, None, None
 
 
@@ -964,42 +908,41 @@ def flow_ctx_alpha(alpha_lr, input, dist, occ, tw, chan_off, scale, want_alpha=T
             raise _lib.WaldoHipError("flow_ctx_alpha: no gradient flows through a packed clip's pass; unpack() it")
         if dist is not None and int(chan_off) != 3:
             raise _lib.WaldoHipError(f"flow_ctx_alpha: a packed clip's layout channels start at 3, not {chan_off}")
-        data = _packed_data(input, "flow_ctx_alpha")
     if packed or (no_grad and (not want_alpha or want_bits)):
-        a01 = alpha_lr.new_empty(n, nl, hd, wd)
-        alpha = alpha_lr.new_empty(n, nl, hd, wd) if want_alpha else None
-        bits = torch.empty(n, hd, (wd + 63) // 64, dtype=torch.int32, device=alpha_lr.device) if want_bits else None
-        with _lib.on_device(alpha_lr.device):
-            if packed:
-                _lib.call("waldo_flow_ctx_alpha_packed_fwd", _lib.ptr(alpha_lr), _lib.ptr(data), _lib.ptr(dist),
-                          _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl, input.num_lyt,
-                          h, w, scale, _lib.current_stream(alpha_lr.device))
-            else:
-                _lib.call("waldo_flow_ctx_alpha_fwd", _lib.ptr(alpha_lr), _lib.ptr(input), _lib.ptr(dist),
-                          _lib.ptr(occ), _lib.ptr(a01), _lib.ptr(alpha), _lib.ptr(bits), b, t, tw, nl,
-                          dist.shape[2] if dist is not None else 0, c, chan_off, h, w, scale,
-                          _lib.current_stream(alpha_lr.device))
+        a01, alpha, bits = _flow_ctx_alpha_fwd(alpha_lr, input, dist, occ, tw, chan_off, scale, want_alpha, want_bits)
         return (a01, alpha, bits) if want_bits else (a01, alpha)
     res = _FlowCtxAlpha.apply(alpha_lr, input, dist, occ, tw, chan_off, scale)
     return (*res, None) if want_bits else res
 
 
+def _flow_ctx_warp_fwd(name, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, scale, layer_max, status_ptr, bits_ptr,
+                       alpha_out, *raw_args):
+    """The forward launch of ``flow_ctx_warp`` (``alpha_out``: alpha_ctx) and of ``flow_ctx_warp_into_raw`` (``alpha_out``:
+    raw and score; ``raw_args``: the raw-slot arguments that follow the shape) on checked, contiguous arguments ->
+    (flow, disocc, amax or None)."""
+    m, nl, _, h, w = flow_lr.shape
+    b, tc, tp = ctx_ts.shape
+    t = occ.shape[1]
+    hd, wd = a01.shape[-2:]
+    flow = flow_lr.new_empty(m, 2, hd, wd)
+    disocc = flow_lr.new_empty(m, hd, wd)
+    amax = flow_lr.new_empty(m, hd, wd) if layer_max else None
+    _lib.launch(name, flow_lr.device, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, flow, *alpha_out, disocc, amax,
+                bits_ptr, status_ptr, b, t, tw, tc, tp, nl, h, w, scale, *raw_args)
+    return flow, disocc, amax
+
+
 class _FlowCtxWarp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, scale, layer_max, status_ptr, bits_ptr=None):
-        m, nl, _, h, w = flow_lr.shape
-        b, tc, tp = ctx_ts.shape
-        t = occ.shape[1]
+        m, nl = flow_lr.shape[:2]
+        tc, tp = ctx_ts.shape[1:]
         hd, wd = a01.shape[-2:]
-        flow = flow_lr.new_empty(m, 2, hd, wd)
         alpha_ctx = flow_lr.new_empty(m, nl, hd, wd)
-        disocc = flow_lr.new_empty(m, hd, wd)
-        amax = flow_lr.new_empty(m, hd, wd) if layer_max else flow_lr.new_empty(0)
-        with _lib.on_device(flow_lr.device):
-            _lib.call("waldo_flow_ctx_warp_fwd", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
-                      _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(alpha_ctx),
-                      _lib.ptr(disocc), _lib.ptr(amax) if layer_max else None, bits_ptr, status_ptr, b, t, tw, tc, tp, nl,
-                      h, w, scale, _lib.current_stream(flow_lr.device))
+        flow, disocc, amax = _flow_ctx_warp_fwd("waldo_flow_ctx_warp_fwd", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw,
+                                                scale, layer_max, status_ptr, bits_ptr, (alpha_ctx,))
+        if amax is None:
+            amax = flow_lr.new_empty(0)
         ctx.save_for_backward(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ)
         ctx.cfg = (tw, scale)
         ctx.det = is_deterministic()
@@ -1021,24 +964,18 @@ class _FlowCtxWarp(torch.autograd.Function):
         g_actx = _c(g_actx) if g_actx is not None else None
         g_dis = _c(g_dis) if g_dis is not None else None
         g_lr = torch.empty_like(flow_lr)
-        if ctx.det:
-            g_a01 = torch.empty_like(a01) if ctx.needs_input_grad[2] else None
-            g_occ = torch.empty_like(occ) if ctx.needs_input_grad[5] else None
-            with _lib.on_device(flow_lr.device):
-                ws, nb = _det_workspace("flow_ctx_warp", "waldo_flow_ctx_warp_bwd_det_workspace_bytes",
-                                        (b, tw, tc, tp, nl, h, w, scale), flow_lr.device)
-                _lib.call("waldo_flow_ctx_warp_bwd_det", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
-                          _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(g_flow), _lib.ptr(g_actx),
-                          _lib.ptr(g_dis), _lib.ptr(g_lr), _lib.ptr(g_a01), _lib.ptr(g_occ), _lib.ptr(ws), nb, b, t, tw,
-                          tc, tp, nl, h, w, scale, _lib.current_stream(flow_lr.device))
-            return g_lr, None, g_a01, None, None, g_occ, None, None, None, None, None
-        g_a01, g_occ = _zeros_like_each(a01 if ctx.needs_input_grad[2] else None, occ if ctx.needs_input_grad[5] else None)
-        ws = flow_lr.new_empty(m, nl, 2, hd, wd) if scale > 1 else None
-        with _lib.on_device(flow_lr.device):
-            _lib.call("waldo_flow_ctx_warp_bwd", _lib.ptr(flow_lr), _lib.ptr(isobj_lr), _lib.ptr(a01),
-                      _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(g_flow), _lib.ptr(g_actx),
-                      _lib.ptr(g_dis), _lib.ptr(g_lr), _lib.ptr(g_a01), _lib.ptr(g_occ), _lib.ptr(ws), b, t, tw,
-                      tc, tp, nl, h, w, scale, _lib.current_stream(flow_lr.device))
+        summed = (a01 if ctx.needs_input_grad[2] else None, occ if ctx.needs_input_grad[5] else None)
+        if ctx.det:  # (the sums are overwritten; the workspace travels with its size)
+            name = "waldo_flow_ctx_warp_bwd_det"
+            g_a01, g_occ = _empty_like_each(*summed)
+            ws = _det_workspace("flow_ctx_warp", "waldo_flow_ctx_warp_bwd_det_workspace_bytes",
+                                (b, tw, tc, tp, nl, h, w, scale), flow_lr.device)
+        else:
+            name = "waldo_flow_ctx_warp_bwd"
+            g_a01, g_occ = _zeros_like_each(*summed)
+            ws = (flow_lr.new_empty(m, nl, 2, hd, wd) if scale > 1 else None,)
+        _lib.launch(name, flow_lr.device, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, g_flow, g_actx, g_dis, g_lr, g_a01,
+                    g_occ, *ws, b, t, tw, tc, tp, nl, h, w, scale)
         return g_lr, None, g_a01, None, None, g_occ, None, None, None, None, None
 
 
@@ -1127,24 +1064,18 @@ def flow_ctx_warp_into_raw(flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, sca
         raise _lib.WaldoHipError("flow_ctx_warp_into_raw: no gradient flows through the raw-slot path; use flow_ctx_warp")
     flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ = _flow_ctx_warp_args("flow_ctx_warp_into_raw", flow_lr, isobj_lr, a01,
                                                                        ctx_ts, pred_ts, occ, tw, scale)
-    m, nl, _, h, w = flow_lr.shape
+    nl = flow_lr.shape[1]
     b, tc, tp = ctx_ts.shape
-    t = occ.shape[1]
     hd, wd = a01.shape[-2:]
     tcx = tc + (1 if include_self else 0)
     st, strict = _status(status)
     with torch.no_grad():
-        flow = flow_lr.new_empty(m, 2, hd, wd)
         raw = flow_lr.new_empty(b, tp, tcx, channels + nl, hd, wd, dtype=raw_dtype)
         score = flow_lr.new_empty(b, tc, tp, hd, wd)
-        disocc = flow_lr.new_empty(m, hd, wd)
-        amax = flow_lr.new_empty(m, hd, wd) if layer_max else None
-        with _lib.on_device(flow_lr.device):
-            _call_dt("waldo_flow_ctx_warp_raw_fwd", (raw_dtype,), _lib.ptr(flow_lr), _lib.ptr(isobj_lr),
-                     _lib.ptr(a01), _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(occ), _lib.ptr(flow), _lib.ptr(raw),
-                     _lib.ptr(score), _lib.ptr(disocc), _lib.ptr(amax),
-                     _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01), st.ptr, b, t, tw, tc, tp, nl, h, w,
-                     scale, int(channels), tcx, _lib.current_stream(flow_lr.device))
+        name, codes = _dt_entry("waldo_flow_ctx_warp_raw_fwd", raw_dtype)
+        flow, disocc, amax = _flow_ctx_warp_fwd(name, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, tw, scale, layer_max,
+                                                st.ptr, _layer_bits_ptr("flow_ctx_warp_into_raw", layer_bits, a01),
+                                                (raw, score), int(channels), tcx, *codes)
         alpha_ctx = raw[:, :, :tc, channels:].permute(0, 2, 1, 3, 4, 5)  # (B, Tc, Tp, L, Hd, Wd), strided
     if strict:
         st.check(sync=True)
@@ -1165,10 +1096,8 @@ class _FrameWarpFuse(torch.autograd.Function):
         # permute(0, 2, 1, ...).contiguous() (wif.py:39) then is a no-op instead of a copy of the
         # pipeline's largest tensor (C4 recipe: 11.8 GB read + written per predict)
         raw = input.new_empty(b, tp, tcx, c + nl, hd, wd)
-        with _lib.on_device(input.device):
-            _lib.call("waldo_frame_warp_fuse_fwd", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(alpha),
-                      _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), status_ptr, b, t, tc, tp, c, nl, hd, wd,
-                      1 if include_self else 0, float(eps), _lib.current_stream(input.device))
+        _lib.launch("waldo_frame_warp_fuse_fwd", input.device, input, flow, alpha, ctx_ts, out, raw, status_ptr, b, t, tc,
+                    tp, c, nl, hd, wd, 1 if include_self else 0, float(eps))
         ctx.save_for_backward(input, flow, alpha, ctx_ts)
         ctx.cfg = (bool(include_self), float(eps))
         # an output the loss does not use comes back as None, not as a zero-filled tensor of its size (raw_output is
@@ -1186,10 +1115,8 @@ class _FrameWarpFuse(torch.autograd.Function):
         g_raw = _c(g_raw) if g_raw is not None else None
         g_flow = torch.empty_like(flow)
         g_alpha = torch.empty_like(alpha)
-        with _lib.on_device(input.device):
-            _lib.call("waldo_frame_warp_fuse_bwd", _lib.ptr(input), _lib.ptr(flow), _lib.ptr(alpha),
-                      _lib.ptr(ctx_ts), _lib.ptr(g_out), _lib.ptr(g_raw), _lib.ptr(g_flow), _lib.ptr(g_alpha), b, t,
-                      tc, tp, c, nl, hd, wd, 1 if include_self else 0, eps, _lib.current_stream(input.device))
+        _lib.launch("waldo_frame_warp_fuse_bwd", input.device, input, flow, alpha, ctx_ts, g_out, g_raw, g_flow, g_alpha,
+                    b, t, tc, tp, c, nl, hd, wd, 1 if include_self else 0, eps)
         return None, g_flow, g_alpha, None, None, None, None
 
 
@@ -1246,16 +1173,15 @@ def frame_warp_fuse_raw(input, flow, slots, ctx_ts, eps=1e-6, status=None):
             f"raw={tuple(raw.shape)} score={tuple(score.shape)} ctx_ts={tuple(ctx_ts.shape)}")
     st, strict = _status(status)
     out = input.new_empty(b, tp, c + 1, hd, wd)
-    with torch.no_grad(), _lib.on_device(input.device):
+    with torch.no_grad():
         if packed:
-            _lib.call("waldo_frame_warp_fuse_raw_packed_fwd", _lib.ptr(_packed_data(input, "frame_warp_fuse_raw")),
-                      _lib.ptr(rgb_table(input.device)), _lib.ptr(flow), _lib.ptr(score), _lib.ptr(ctx_ts), _lib.ptr(out),
-                      _lib.ptr(raw), st.ptr, b, t, tc, tp, input.num_lyt, nl, hd, wd, 1 if slots.include_self else 0,
-                      float(eps), _DTYPE_CODE[raw.dtype], _lib.current_stream(input.device))
+            _lib.launch("waldo_frame_warp_fuse_raw_packed_fwd", input.device, _packed_data(input, "frame_warp_fuse_raw"),
+                        rgb_table(input.device), flow, score, ctx_ts, out, raw, st.ptr, b, t, tc, tp, input.num_lyt, nl,
+                        hd, wd, 1 if slots.include_self else 0, float(eps), _DTYPE_CODE[raw.dtype])
         else:
-            _call_dt("waldo_frame_warp_fuse_raw_fwd", (raw.dtype,), _lib.ptr(input), _lib.ptr(flow), _lib.ptr(score),
-                     _lib.ptr(ctx_ts), _lib.ptr(out), _lib.ptr(raw), st.ptr, b, t, tc, tp, c, nl, hd, wd,
-                     1 if slots.include_self else 0, float(eps), _lib.current_stream(input.device))
+            name, codes = _dt_entry("waldo_frame_warp_fuse_raw_fwd", raw.dtype)
+            _lib.launch(name, input.device, input, flow, score, ctx_ts, out, raw, st.ptr, b, t, tc, tp, c, nl, hd, wd,
+                        1 if slots.include_self else 0, float(eps), *codes)
     if strict:
         st.check(sync=True)
     return out, raw.permute(0, 2, 1, 3, 4, 5)
@@ -1385,9 +1311,7 @@ def unpack_clip(clip):
     data = _packed_data(clip, "unpack_clip")
     b, t, hd, wd, _ = data.shape
     out = torch.empty(clip.shape, dtype=torch.float32, device=data.device)
-    with _lib.on_device(data.device):
-        _lib.call("waldo_unpack_clip_fwd", _lib.ptr(data), _lib.ptr(rgb_table(data.device)), _lib.ptr(out), b, t,
-                  clip.num_lyt, hd, wd, _lib.current_stream(data.device))
+    _lib.launch("waldo_unpack_clip_fwd", data.device, data, rgb_table(data.device), out, b, t, clip.num_lyt, hd, wd)
     return out
 
 
@@ -1478,9 +1402,8 @@ def frames_to_bytes(x, span=(-1.0, 1.0), quantize="trunc", layout="nchw", out=No
         if o is None or not _dense_tail(o, 3):
             raise ValueError(f"{fn}: out must hold dense frames whose leading dimensions flatten by stride "
                              f"(strides {tuple(out.stride())})")
-    with _lib.on_device(d.device):
-        _lib.call("waldo_frames_to_bytes_fwd", _lib.ptr(d), code, *strides, _lib.ptr(table), _lib.ptr(o),
-                  o.stride(0) if n > 1 else c * h * w, lay, n, c, h, w, lo, rng, quant, _lib.current_stream(d.device))
+    _lib.launch("waldo_frames_to_bytes_fwd", d.device, d, code, *strides, table, o, o.stride(0) if n > 1 else c * h * w,
+                lay, n, c, h, w, lo, rng, quant)
     return out if out is not None else o.view(*lead, *frame)
 
 
@@ -1510,9 +1433,8 @@ def wif_fuse_bytes(vid, net_out, ab=True, span=(-1.0, 1.0), quantize="trunc", la
     if tuple(net.shape) != (b, t, tc, co, h, w):
         raise _lib.WaldoHipError(f"{fn}: shapes {tuple(vid.shape)} vs {tuple(net.shape)}")
     out = torch.empty((b, t, h, w, 3) if lay else (b, t, 3, h, w), dtype=torch.uint8, device=vid.device)
-    with _lib.on_device(vid.device):
-        _call_dt("waldo_wif_fuse_bytes_fwd", (vid.dtype, net.dtype), _lib.ptr(vid), _lib.ptr(net), _lib.ptr(out),
-                 b * t, tc, c, co, h * w, int(bool(ab)), lo, rng, quant, lay, _lib.current_stream(vid.device))
+    name, codes = _dt_entry("waldo_wif_fuse_bytes_fwd", vid.dtype, net.dtype)
+    _lib.launch(name, vid.device, vid, net, out, b * t, tc, c, co, h * w, int(bool(ab)), lo, rng, quant, lay, *codes)
     return out
 
 
@@ -1526,9 +1448,8 @@ class _TimeGather(torch.autograd.Function):
         p = math.prod(x.shape[2:]) // 2
         tp = pred_ts.numel()
         out = x.new_empty(b, tc, tp, *((p // hw, 2, hw) if hw else (p, 2)))
-        with _lib.on_device(x.device):
-            _lib.call("waldo_time_gather_fwd", _lib.ptr(x), _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(out),
-                      status_ptr, b, t, tc, tp, p, hw, int(subtract), _lib.current_stream(x.device))
+        _lib.launch("waldo_time_gather_fwd", x.device, x, ctx_ts, pred_ts, out, status_ptr, b, t, tc, tp, p, hw,
+                    int(subtract))
         ctx.save_for_backward(ctx_ts, pred_ts)
         ctx.cfg = (tuple(x.shape), tc, hw, subtract)
         return out
@@ -1540,10 +1461,8 @@ class _TimeGather(torch.autograd.Function):
         grad_out = _c(grad_out)
         gx = grad_out.new_empty(shape)
         b, t = shape[:2]
-        with _lib.on_device(grad_out.device):
-            _lib.call("waldo_time_gather_bwd", _lib.ptr(grad_out), _lib.ptr(ctx_ts), _lib.ptr(pred_ts), _lib.ptr(gx),
-                      b, t, tc, pred_ts.numel(), math.prod(shape[2:]) // 2, hw, int(subtract),
-                      _lib.current_stream(grad_out.device))
+        _lib.launch("waldo_time_gather_bwd", grad_out.device, grad_out, ctx_ts, pred_ts, gx, b, t, tc, pred_ts.numel(),
+                    math.prod(shape[2:]) // 2, hw, int(subtract))
         return gx, None, None, None, None, None, None
 
 
@@ -1609,15 +1528,13 @@ def downscale_frames(input, num_frames, first_channel, factor):
             raise _lib.WaldoHipError(f"downscale_frames: a packed clip's layout channels start at 3, not {first_channel}")
         data = _packed_data(input, "downscale_frames")
         out = torch.empty(b, int(num_frames), c - 3, hd // s, wd // s, device=data.device)
-        with _lib.on_device(data.device):
-            _lib.call("waldo_downscale_frames_packed_fwd", _lib.ptr(data), _lib.ptr(out), b, t, int(num_frames), c - 3,
-                      hd // s, wd // s, s, _lib.current_stream(data.device))
+        _lib.launch("waldo_downscale_frames_packed_fwd", data.device, data, out, b, t, int(num_frames), c - 3, hd // s,
+                    wd // s, s)
         return out
     x = _c(input.detach().float())
     out = x.new_empty(b, int(num_frames), c - int(first_channel), hd // s, wd // s)
-    with _lib.on_device(x.device):
-        _lib.call("waldo_downscale_frames_fwd", _lib.ptr(x), _lib.ptr(out), b, t, int(num_frames), c,
-                  int(first_channel), hd // s, wd // s, s, _lib.current_stream(x.device))
+    _lib.launch("waldo_downscale_frames_fwd", x.device, x, out, b, t, int(num_frames), c, int(first_channel), hd // s,
+                wd // s, s)
     return out
 
 
@@ -1630,7 +1547,6 @@ def points_in_polygon(pts, corners, valid=None):
     ``corners`` may also be a tensor ON THE DEVICE (nothing is read on the host): (K, 2) -> ``pts.shape[:-1]``, or
     (P, K, 2), P polygons tested against the same points -> (P, *pts.shape[:-1]); float64 (float32 is widened
     exactly).  ``valid`` (P,) on the device, any integer or bool type: a polygon whose entry is zero contains nothing."""
-    import ctypes
     _lib.check_cuda(pts)
     if pts.shape[-1] != 2:
         raise _lib.WaldoHipError(f"points_in_polygon: points of shape {tuple(pts.shape)} (..., 2)")
@@ -1646,9 +1562,7 @@ def points_in_polygon(pts, corners, valid=None):
     x = _c(pts.detach())
     n = x.numel() // 2
     out = x.new_empty(x.shape[:-1])
-    with _lib.on_device(x.device):
-        _lib.call("waldo_points_in_polygon_fwd", _lib.ptr(x), ctypes.addressof(host), k, _lib.ptr(out), n,
-                  _lib.current_stream(x.device))
+    _lib.launch("waldo_points_in_polygon_fwd", x.device, x, ctypes.addressof(host), k, out, n)
     return out > 0
 
 
@@ -1672,10 +1586,8 @@ def _polygon_regions(pts, corners, valid):
     x = _c(pts.detach())
     n = x.numel() // 2
     out = x.new_empty((p,) + tuple(x.shape[:-1]))
-    with _lib.on_device(x.device):
-        _lib.call("waldo_points_in_polygon_dev_fwd", _lib.ptr(x), _lib.ptr(cn), cn.stride(0) if p and k else 0,
-                  _lib.ptr(valid), valid.stride(0) if valid is not None else 0, k, _lib.ptr(out), p, n,
-                  _lib.current_stream(x.device))
+    _lib.launch("waldo_points_in_polygon_dev_fwd", x.device, x, cn, cn.stride(0) if p and k else 0, valid,
+                valid.stride(0) if valid is not None else 0, k, out, p, n)
     return out
 
 
@@ -1714,10 +1626,8 @@ def border_objects(pred_flow, ident, alpha_ctx):
     obj_id = torch.empty(b, 2, dtype=torch.int64, device=dev)
     corners = torch.empty(b, 2, 4, 2, dtype=torch.float64, device=dev)
     ws = torch.empty(max(_lib.query("waldo_border_objects_workspace_bytes", b) // 4, 1), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("waldo_border_objects_fwd", _lib.ptr(f), f.stride(0), f.stride(1), _lib.ptr(ident), _lib.ptr(x),
-                  x.stride(0), x.stride(1), x.stride(2), x.stride(3), _lib.ptr(valid), _lib.ptr(obj_id), _lib.ptr(corners),
-                  _lib.ptr(ws), b, tc, tp, nl, h, w, _lib.current_stream(dev))
+    _lib.launch("waldo_border_objects_fwd", dev, f, f.stride(0), f.stride(1), ident, x, x.stride(0), x.stride(1),
+                x.stride(2), x.stride(3), valid, obj_id, corners, ws, b, tc, tp, nl, h, w)
     return valid, obj_id, corners
 
 
@@ -1728,7 +1638,6 @@ def inpaint_propagate(flow, ident, ref_img, ref_mask, shadow, entering, img, tod
     (``entering``: up to two ``(region, look, flow_k)``), the fill of the frame's holes and the inpainter's inputs --
     with the bits of the spelled-out composition.  Returns ``(img, todo, inpainter_img, inpainter_mask)``; with
     ``fix_mask`` the inpainter takes ``img`` itself and ``inpainter_mask`` is the undilated ``1 - (1 - todo)(1 - obj)``."""
-    import ctypes
     _lib.check_cuda(flow, ident, ref_img, ref_mask, shadow, img, todo, obj)
     b, c, h, w = img.shape
     if c != 3 or len(entering) > 2:
@@ -1754,12 +1663,9 @@ def inpaint_propagate(flow, ident, ref_img, ref_mask, shadow, entering, img, tod
     arrs = [(ctypes.c_void_p * 2)(*(lst + [None] * (2 - len(lst)))) for lst in ptrs]
     img_out, todo_out, inp_mask = torch.empty_like(img), torch.empty_like(todo), torch.empty_like(todo)
     inp_img = None if fix_mask else torch.empty_like(img)
-    with _lib.on_device(img.device):
-        _lib.call("waldo_inpaint_propagate_fwd", _lib.ptr(flow), _lib.ptr(ident), _lib.ptr(ref_img), _lib.ptr(ref_mask),
-                  _lib.ptr(shadow), ctypes.addressof(arrs[0]), ctypes.addressof(arrs[1]), ctypes.addressof(arrs[2]),
-                  len(entering), _lib.ptr(img), _lib.ptr(todo), _lib.ptr(obj), _lib.ptr(img_out), _lib.ptr(todo_out),
-                  _lib.ptr(inp_img), _lib.ptr(inp_mask), b, h, w, int(bool(soft_shadow)), int(bool(fix_mask)),
-                  _lib.current_stream(img.device))
+    _lib.launch("waldo_inpaint_propagate_fwd", img.device, flow, ident, ref_img, ref_mask, shadow,
+                ctypes.addressof(arrs[0]), ctypes.addressof(arrs[1]), ctypes.addressof(arrs[2]), len(entering), img, todo,
+                obj, img_out, todo_out, inp_img, inp_mask, b, h, w, int(bool(soft_shadow)), int(bool(fix_mask)))
     return img_out, todo_out, (img_out if fix_mask else inp_img), inp_mask
 
 
@@ -1777,10 +1683,8 @@ def inpaint_holes(alpha_ctx, last_only=False, fix_thresh=True):
         x = x.contiguous()
     mask = x.new_empty(b, tp, 1, h, w)
     obj_mask = x.new_empty(b, tp, 1, h, w)
-    with _lib.on_device(x.device):
-        _lib.call("waldo_inpaint_holes_fwd", _lib.ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), _lib.ptr(mask),
-                  _lib.ptr(obj_mask), b, tc, tp, nl, h * w, int(bool(last_only)), 0.1 if fix_thresh else 0.9,
-                  _lib.current_stream(x.device))
+    _lib.launch("waldo_inpaint_holes_fwd", x.device, x, x.stride(0), x.stride(1), x.stride(2), x.stride(3), mask,
+                obj_mask, b, tc, tp, nl, h * w, int(bool(last_only)), 0.1 if fix_thresh else 0.9)
     return mask, obj_mask
 
 
@@ -1792,9 +1696,7 @@ def inpaint_blend(img, todo, fill):
     if c != 3 or tuple(fill.shape) != tuple(img.shape) or tuple(todo.shape) != (b, 1, h, w):
         raise _lib.WaldoHipError(f"inpaint_blend: shapes {tuple(img.shape)}, {tuple(todo.shape)}, {tuple(fill.shape)}")
     out = torch.empty_like(img)
-    with _lib.on_device(img.device):
-        _lib.call("waldo_inpaint_blend_fwd", _lib.ptr(img), _lib.ptr(todo), _lib.ptr(fill), _lib.ptr(out), b, h * w,
-                  _lib.current_stream(img.device))
+    _lib.launch("waldo_inpaint_blend_fwd", img.device, img, todo, fill, out, b, h * w)
     return out
 
 
@@ -1834,9 +1736,8 @@ def mask_expand(mask, num=1, dir=None, soft=False, alpha=0.97):
         return x.clone() if soft else (x != 0).float()
     out = torch.empty_like(x)
     scratch = torch.empty_like(x) if num > 30 else None
-    with _lib.on_device(x.device):
-        _lib.call("waldo_mask_expand_fwd", _lib.ptr(x), _lib.ptr(out), _lib.ptr(scratch), planes, h, w, num, steps,
-                  1 if soft else 0, float(alpha), _lib.current_stream(x.device))
+    _lib.launch("waldo_mask_expand_fwd", x.device, x, out, scratch, planes, h, w, num, steps, 1 if soft else 0,
+                float(alpha))
     return out
 
 
@@ -1860,10 +1761,8 @@ class _WarpComposite(torch.autograd.Function):
                 f"mapping={tuple(mapping.shape)} occ={tuple(occ.shape)} basis_t={tuple(basis_t.shape)}")
         rgb = layers.new_empty(f, 3, h, w, dtype=torch.float32)
         alpha = layers.new_empty(f, nl, h, w, dtype=torch.float32) if want_alpha else None
-        with _lib.on_device(layers.device):
-            _call_dt("waldo_warp_composite_fwd", (layers.dtype,), _lib.ptr(layers), _lib.ptr(basis_t),
-                     _lib.ptr(mapping), _lib.ptr(occ), _lib.ptr(rgb), _lib.ptr(alpha), f, nl, h,
-                     w, k3, float(delta), _lib.current_stream(layers.device))
+        name, codes = _dt_entry("waldo_warp_composite_fwd", layers.dtype)
+        _lib.launch(name, layers.device, layers, basis_t, mapping, occ, rgb, alpha, f, nl, h, w, k3, float(delta), *codes)
         ctx.save_for_backward(layers, mapping, occ, basis_t)
         ctx.want_alpha = want_alpha
         ctx.delta = float(delta)
@@ -1882,32 +1781,27 @@ class _WarpComposite(torch.autograd.Function):
         grad_rgb = _c(grad_rgb)
         if grad_alpha is not None:
             grad_alpha = _c(grad_alpha)
-        if ctx.det:
-            gm = torch.empty_like(mapping) if ctx.needs_input_grad[1] else None
-            go = torch.empty_like(occ) if ctx.needs_input_grad[2] else None
+        summed = (mapping if ctx.needs_input_grad[1] else None, occ if ctx.needs_input_grad[2] else None)
+        if ctx.det:  # (every gradient overwritten; the dtype code travels in every case)
+            gm, go = _empty_like_each(*summed)
             gl = torch.empty_like(layers)
-            if f > 0:
-                with _lib.on_device(layers.device):
-                    ws, nb = _det_workspace("warp_composite", "waldo_warp_composite_bwd_det_workspace_bytes",
-                                            (f, nl, h, w, k3), layers.device)
-                    _lib.call("waldo_warp_composite_bwd_det", _lib.ptr(layers), _lib.ptr(basis_t), _lib.ptr(mapping),
-                              _lib.ptr(occ), _lib.ptr(grad_rgb), _lib.ptr(grad_alpha), _lib.ptr(gl), _lib.ptr(gm),
-                              _lib.ptr(go), _lib.ptr(ws), nb, f, nl, h, w, k3, ctx.delta, _DTYPE_CODE[layers.dtype],
-                              _lib.current_stream(layers.device))
-            return gl, gm, go, None, None, None
-        gm, go = _zeros_like_each(mapping if ctx.needs_input_grad[1] else None, occ if ctx.needs_input_grad[2] else None)
-        # 0: the shape is served by the generic kernel (or a test asked for it: WALDO_DEBUG_BWD_GENERIC)
-        ws_bytes = _lib.load().waldo_warp_composite_bwd_workspace_bytes(f, nl, h, w, k3)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=layers.device) if ws_bytes else None
-        # with a workspace the two-kernel path writes every texel of grad_layers exactly once;
-        # the generic kernel accumulates with atomics into a zero-filled buffer.  (A 16-bit stack: grad_layers in
-        # its type, from the two-kernel path only.)
-        gl = torch.empty_like(layers) if ws_bytes else torch.zeros_like(layers)
-        with _lib.on_device(layers.device):
-            _call_dt("waldo_warp_composite_bwd", (layers.dtype,), _lib.ptr(layers), _lib.ptr(basis_t),
-                     _lib.ptr(mapping), _lib.ptr(occ), _lib.ptr(grad_rgb), _lib.ptr(grad_alpha),
-                     _lib.ptr(gl), _lib.ptr(gm), _lib.ptr(go), _lib.ptr(ws), ws_bytes, f, nl, h,
-                     w, k3, ctx.delta, _lib.current_stream(layers.device))
+            if f == 0:
+                return gl, gm, go, None, None, None
+            ws, ws_bytes = _det_workspace("warp_composite", "waldo_warp_composite_bwd_det_workspace_bytes",
+                                          (f, nl, h, w, k3), layers.device)
+            name, codes = "waldo_warp_composite_bwd_det", (_DTYPE_CODE[layers.dtype],)
+        else:
+            gm, go = _zeros_like_each(*summed)
+            # 0: the shape is served by the generic kernel (or a test asked for it: WALDO_DEBUG_BWD_GENERIC)
+            ws_bytes = _lib.query("waldo_warp_composite_bwd_workspace_bytes", f, nl, h, w, k3)
+            ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=layers.device) if ws_bytes else None
+            # with a workspace the two-kernel path writes every texel of grad_layers exactly once;
+            # the generic kernel accumulates with atomics into a zero-filled buffer.  (A 16-bit stack: grad_layers in
+            # its type, from the two-kernel path only.)
+            gl = torch.empty_like(layers) if ws_bytes else torch.zeros_like(layers)
+            name, codes = _dt_entry("waldo_warp_composite_bwd", layers.dtype)
+        _lib.launch(name, layers.device, layers, basis_t, mapping, occ, grad_rgb, grad_alpha, gl, gm, go, ws, ws_bytes, f,
+                    nl, h, w, k3, ctx.delta, *codes)
         return gl, gm, go, None, None, None
 
 
@@ -1965,7 +1859,7 @@ def _layers16_served(layers, src_pts, needs_grad):
     n = src_pts.shape[1]
     if nl < 1 or not lib.waldo_warp_composite_pts_supported(nl, h, w, n):
         return False
-    return not needs_grad or lib.waldo_warp_composite_bwd_workspace_bytes(max(f, 1), nl, h, w, n + 3) > 0
+    return not needs_grad or _lib.query("waldo_warp_composite_bwd_workspace_bytes", max(f, 1), nl, h, w, n + 3) > 0
 
 
 def _warp_composite_pts(layers, src_pts, occ, inverse_kernel, basis_t, want_alpha, delta):
@@ -1986,13 +1880,11 @@ def _warp_composite_pts(layers, src_pts, occ, inverse_kernel, basis_t, want_alph
     rgb = layers.new_empty(f, 3, h, w, dtype=torch.float32)
     alpha = layers.new_empty(f, nl, h, w, dtype=torch.float32) if want_alpha else None
     per = max(1, MAX_FL_PER_LAUNCH // nl)
-    with _lib.on_device(layers.device):
-        for i in range(0, f, per):
-            j = min(f, i + per)
-            _call_dt("waldo_warp_composite_pts_fwd", (layers.dtype,), _lib.ptr(layers[i:j]), _lib.ptr(basis_t),
-                     _lib.ptr(inverse_kernel), _lib.ptr(src_pts[i * nl:j * nl]), _lib.ptr(occ[i:j]),
-                     _lib.ptr(rgb[i:j]), _lib.ptr(alpha[i:j]) if want_alpha else None, j - i, nl, h, w, n,
-                     delta, _lib.current_stream(layers.device))
+    name, codes = _dt_entry("waldo_warp_composite_pts_fwd", layers.dtype)
+    for i in range(0, f, per):
+        j = min(f, i + per)
+        _lib.launch(name, layers.device, layers[i:j], basis_t, inverse_kernel, src_pts[i * nl:j * nl], occ[i:j], rgb[i:j],
+                    alpha[i:j] if want_alpha else None, j - i, nl, h, w, n, delta, *codes)
     return (rgb, alpha) if want_alpha else rgb
 
 
@@ -2006,8 +1898,7 @@ def _frames_per_call(f, nl, h, w, k3):
     if f == 0:
         return 1
     per = max(1, MAX_FL_PER_LAUNCH // nl)
-    query = _lib.load().waldo_warp_composite_bwd_workspace_bytes
-    ws1, ws8 = query(1, nl, h, w, k3), query(8, nl, h, w, k3)
+    ws1, ws8 = (_lib.query("waldo_warp_composite_bwd_workspace_bytes", n, nl, h, w, k3) for n in (1, 8))
     per_frame = max((ws8 - ws1) / 7.0, 1.0) if ws8 > 0 else 0.0
     if per_frame:
         per = min(per, max(1, int(MAX_WORKSPACE_BYTES // per_frame)))

@@ -120,9 +120,8 @@ def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc
     dev = pred.device
     if real.device != dev:
         raise ValueError(f"frame_metrics: pred on {dev}, real on {real.device}")
-    lib = _lib.load()
-    part_bytes = lib.waldo_frame_metrics_partial_bytes(b, t, h, w, mask)
-    scratch_bytes = lib.waldo_frame_metrics_scratch_bytes(b, t, h, w, mask)
+    part_bytes = _lib.query("waldo_frame_metrics_partial_bytes", b, t, h, w, mask)
+    scratch_bytes = _lib.query("waldo_frame_metrics_scratch_bytes", b, t, h, w, mask)
     if part_bytes < 0 or scratch_bytes < 0:
         raise ValueError(f"frame_metrics: unsupported shape {shp}")
     da, ea, sa = _descriptor(pred)
@@ -131,11 +130,8 @@ def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc
     scratch = torch.empty(scratch_bytes // 4, dtype=torch.float32, device=dev) if scratch_bytes else None
     out = {m: torch.empty(b, t, dtype=torch.float32, device=dev) for m in metrics}
     table = rgb_table(dev) if _ENC_PACKED in (ea, eb) else None
-    with _lib.on_device(dev):
-        _lib.call("waldo_frame_metrics_fwd", _lib.ptr(da), ea, *sa, _lib.ptr(db), eb, *sb, _lib.ptr(table),
-                  b, t, h, w, lo, hi - lo, QUANTIZE[quantize], mask, _lib.ptr(partials), _lib.ptr(scratch),
-                  _lib.ptr(out.get("psnr")), _lib.ptr(out.get("ssim")), _lib.ptr(out.get("msssim")),
-                  _lib.current_stream(dev))
+    _lib.launch("waldo_frame_metrics_fwd", dev, da, ea, *sa, db, eb, *sb, table, b, t, h, w, lo, hi - lo,
+                QUANTIZE[quantize], mask, partials, scratch, out.get("psnr"), out.get("ssim"), out.get("msssim"))
     return out
 
 
