@@ -749,6 +749,45 @@ int waldo_wif_fuse_bytes_fwd_dt(const void* vid, const void* net, uint8_t* out, 
                                 int net_dtype, waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Renders: the three views of the layered decomposition as bytes, made on the device -- which class or object layer
+ * owns a pixel (the reference's Logger.get_lyt, tools/logger.py:169-202 -> color_transfer, tools/utils.py:202-214) and
+ * the flow that moved it (Logger.get_flow_rgb, tools/logger.py:265-318), without the reference's trip through the host.
+ *
+ * waldo_render_argmax_fwd: N frames of C planes of H x W values -> the class id of every pixel and / or its colour.
+ *   src       src_code WALDO_DTYPE_F32 / _F16 / _BF16: planar frames, element strides ss_n, ss_c, ss_h (W unit-stride:
+ *             the channel slice output[:, :, 3:3+Nl] or a time slice is read in place), aligned to its elements.  A
+ *             packed clip holds its ids already: WALDO_BYTES_SRC_PACKED is WALDO_EINVAL.
+ *   id        the index torch.max(dim) returns on the CPU: scanning c upward, c replaces the best so far when
+ *             v > best || (v != v && best == best) -- the lowest c among the maxima wins, NaN is greater than
+ *             everything and the first NaN wins, -0.0 == +0.0; a 16-bit value is widened exactly first.
+ *   palette   C rows of 3 bytes on the device, read only when rgb != NULL: rgb[pixel] = palette[id].
+ *   ids       (N, H, W) bytes, or NULL;  rgb: WALDO_BYTES_NCHW (N, 3, H, W) or WALDO_BYTES_NHWC (N, H, W, 3), or NULL --
+ *             not both NULL; both come from the one pass.  Each frame dense, frame strides di_n, dr_n in bytes, ANY
+ *             alignment of either base.
+ *   C in [1, 256] (an id fits a byte), H and W in [1, 32768].
+ *
+ * waldo_render_flow_fwd: N flows (2, H, W) (plane 0 = u, plane 1 = v; strides as above) -> RGB bytes.  Per pixel, in fp32
+ * with IEEE division and no contraction of u u + v v into an fma:
+ *     m = sqrtf(u u + v v);  r = min(m / sqrt(2) * mul, 1), a NaN kept (the reference's r[r > 1] = 1)
+ *     theta = (1 + atan2f(v, u) / pi) / 2;  k = min((int)(theta K), K - 1)
+ *     channel c = byte of r * wheel[3 k + c] under the quantisation of "Byte output" with the span (0, 1)
+ * NaN in u or v gives bytes 0 (the NaN rule of "Byte output"; the reference's "bad" colour (0, 0, 0) times NaN); a zero
+ * flow gives bytes 0.  wheel: K rows of 3 fp32 on the device (the reference: hsv with 128 entries), K in [1, 4096];
+ * mul finite; quant WALDO_METRICS_TRUNC / _ROUND (WALDO_METRICS_NONE: WALDO_EINVAL).  rgb as above.
+ *
+ * Both: caller-owned buffers, the caller's stream, no workspace, no allocation, no synchronisation; N == 0: WALDO_OK
+ * without a launch.  WALDO_EINVAL with a message before any launch: an unknown dtype, layout or quantisation code; a
+ * non-finite mul; a bad shape (N < 0, C, K, H or W outside its range); a negative stride; a null src / flow / wheel, ids
+ * and rgb both null, rgb without a palette; a source that is not aligned to its elements; more than 2^31 - 1 workgroups.
+ * ------------------------------------------------------------------------------------- */
+int waldo_render_argmax_fwd(const void* src, int src_code, int64_t ss_n, int64_t ss_c, int64_t ss_h,
+                            const uint8_t* palette, uint8_t* ids, int64_t di_n, uint8_t* rgb, int64_t dr_n,
+                            int layout, int64_t N, int C, int H, int W, waldo_stream_t stream);
+int waldo_render_flow_fwd(const void* flow, int src_code, int64_t ss_n, int64_t ss_c, int64_t ss_h,
+                          const float* wheel, int K, float mul, uint8_t* rgb, int64_t dr_n, int layout, int quant,
+                          int64_t N, int H, int W, waldo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Reproducible gradients (deterministic mode).  The backward entry points above that say "ZERO-FILLED ... atomics"
  * sum with float atomics: the result depends on the order of arrival and differs in its last bits from run to run.
  * Each has a twin, suffix _det, whose result is a function of its inputs alone -- the same bits from run to run,

@@ -82,6 +82,11 @@ SIGNATURES = {
     "waldo_wif_fuse_bytes_fwd": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _flt, _flt, _int, _int, _stream],
     "waldo_wif_fuse_bytes_fwd_dt": [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _i64, _int, _flt, _flt, _int, _int, _int,
                                     _int, _stream],
+    # renders (include/waldo_hip.h "Renders"): source descriptor, table, destination(s), codes, shape
+    "waldo_render_argmax_fwd": [_c_f, _int, _i64, _i64, _i64, _c_f, _c_f, _i64, _c_f, _i64, _int, _i64, _int, _int, _int,
+                                _stream],
+    "waldo_render_flow_fwd": [_c_f, _int, _i64, _i64, _i64, _c_f, _int, _flt, _c_f, _i64, _int, _int, _i64, _int, _int,
+                              _stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],

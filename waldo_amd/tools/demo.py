@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as WF
+from .. import render as WR
 from ..nets import flp
 from ..nets.lvd import Warper, decode_output, decoder_tail, estimate_alpha_grid_occ
 from ..nets.wif import WIF
@@ -221,7 +222,7 @@ def _points_grids_occ(opt, warper, net, nb, nt):
 
 
 def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, shared=None, shared_key=None,
-                  out_alpha=None, raw_dtype=None, out_bytes=None):
+                  out_alpha=None, raw_dtype=None, out_bytes=None, palette=None, out_render=None):
     """One decode of predict() (estimate_alpha_grid_occ -> decode_output -> disocclusion test -> WIF fusion,
     synthesizer.py:434-460 / 464-484) for ``nb`` clips on the compact time axis ``sel`` (frame numbers: the context
     frames 0 .. ctx_len - 1, then the other frames whose poses the decode needs -- a frame may stand there twice, with
@@ -235,7 +236,10 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
     do not depend on which other frames or clips are decoded beside it (tests/test_gpu_pipeline.py).  ``raw_dtype``:
     decode_output's (None = fp32; bf16 / fp16: the WIF input in 16 bits, fused by the 16-bit wif_fuse).  ``out_bytes``
     ("trunc" / "round"): output, disocc and inpainted come back as uint8 (``WF.frames_to_bytes``; the inpainted frames
-    quantised inside the fusion kernel) -- the bytes the reference's save_vid writes of them; flow stays fp32."""
+    quantised inside the fusion kernel) -- the bytes the reference's save_vid writes of them; flow stays fp32.
+    ``out_render`` (a list): receives ``(ids, rgb)``, the class ids (nb, n, Hd, Wd) of the decoded layout channels
+    ``output[:, :, 3:]`` (read in place) and the same ids through ``palette`` (nb, n, 3, Hd, Wd), uint8, from one launch
+    (``render.render_argmax``)."""
     no = opt.num_obj
     dev = real_input.device
     nt, n = len(sel), len(where)
@@ -334,6 +338,9 @@ def _decode_block(opt, warper, wif, real_input, net, ctx_len, nb, sel, where, sh
     dmax = WF.disocc_test(mx)
     if out_alpha is not None:
         out_alpha.append(alpha)
+    if out_render is not None:
+        rgb, ids = WR.render_argmax(output[:, :, 3:], palette, return_ids=True)
+        out_render.append((ids, rgb))
     if out_bytes is not None:  # (the 3-channel slice and the map are read in place)
         return (WF.frames_to_bytes(output[:, :, :3], quantize=out_bytes),
                 WF.frames_to_bytes(dmax.unsqueeze(2), quantize=out_bytes), wif(raw_output, out_bytes=out_bytes), flow)
@@ -345,8 +352,29 @@ def _check_out_bytes(fn, out_bytes):
         raise ValueError(f"{fn}: out_bytes must be None or one of {tuple(WF.BYTE_QUANTIZE)}, got {out_bytes!r}")
 
 
+def _check_render(fn, render):
+    if render is not None and render not in WR.QUANTIZE:
+        raise ValueError(f"{fn}: render must be None or one of {tuple(WR.QUANTIZE)}, got {render!r}")
+
+
+def _render_palette(palette, num_lyt):
+    """The palette of the ``*_sem_lyt`` renders: the caller's (at least ``num_lyt`` rows of 3 bytes; a flat list of
+    3 * Nl integers is a dataset palette as the reference's option holds it) or ``layer_palette(num_lyt)``."""
+    if palette is None:
+        return WR.layer_palette(num_lyt)
+    if not torch.is_tensor(palette) and getattr(palette, "ndim", 1) == 1:
+        palette = WR.semantic_palette(list(palette))
+    if palette.shape[0] < num_lyt:
+        raise ValueError(f"palette: {palette.shape[0]} rows for {num_lyt} layout classes")
+    return palette
+
+
+RENDER_KEYS = {"rec": ("rec_lyt_ids", "rec_sem_lyt"), "pred": ("pred_lyt_ids", "pred_sem_lyt", "pred_flow_rgb")}
+
+
 @torch.no_grad()
-def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, out_bytes=None):
+def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, out_bytes=None, render=None,
+            palette=None):
     """The hot-path part of Synthesizer.predict (models/synthesizer.py:434-480).  real_vid
     (B, T, 3, H, W), real_lyt (B, T, Nl, H, W); ``net`` = synthetic_network_outputs(...).  Or real_vid a
     ``WF.PackedClip`` of frames and class ids (``tools.io.load_clip(..., packed=True)``) and real_lyt None: the same
@@ -357,8 +385,19 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, 
     ``*_disocc`` keys as uint8 with 1 channel -- ``WF.frames_to_bytes`` of what they are without it ("trunc": the bytes
     the reference's save_vid -> dump_video writes of them, synthesizer.py:403-411), quantised on the device; ``pred_flow``
     and ``pred_alpha`` stay as they are.  The context frames in front of ``pred_vid`` / ``inp_pred_vid`` are quantised
-    from the clip (a packed clip's bytes are not copied: "trunc" does not give them back)."""
+    from the clip (a packed clip's bytes are not copied: "trunc" does not give them back).
+    ``render`` (None, "trunc" or "round"): the decomposition as pictures, rendered on the device (``waldo_amd.render``;
+    the reference's log_lyt / log_flow, synthesizer.py:396-401) -- every other key stays what it is without it, and these
+    are added, all uint8: ``rec_lyt_ids`` / ``pred_lyt_ids`` (B, T', Hd, Wd), the argmax of the decoded layout channels
+    ``output[:, :, 3:3 + Nl]`` (with the ``*_vid`` bytes the two tensors ``WF.pack_clip`` takes); ``rec_sem_lyt`` /
+    ``pred_sem_lyt`` (B, T', 3, Hd, Wd), those ids through ``palette`` (``_render_palette``; default
+    ``render.layer_palette(Nl)``) from the same launch; ``pred_flow_rgb`` (B, Tc, Tp, 3, Hd, Wd), ``render.render_flow`` of
+    ``pred_flow`` -- the only one the quantisation mode ``render`` applies to; and, where ``pred_alpha`` is returned,
+    ``ctx_obj_lyt``: its argmax over the layers through ``render.layer_palette(L)``."""
     _check_out_bytes("predict", out_bytes)
+    _check_render("predict", render)
+    pal = _render_palette(palette, opt.num_lyt) if render else None
+    rend_rec, rend_pred = ([], []) if render else (None, None)
     b, t = real_vid.shape[:2]
     every = list(range(t))
     out = {}
@@ -383,22 +422,25 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, 
         # the reference's two calls, one after the other (include_self: every frame is a context of itself)
         shared = SharedContext() if not getattr(opt, "include_self", False) else None
         rec, dis, inp, _ = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every, every, shared=shared,
-                                         raw_dtype=raw_dtype, out_bytes=out_bytes)
+                                         raw_dtype=raw_dtype, out_bytes=out_bytes, palette=pal, out_render=rend_rec)
         out["rec_vid"], out["rec_disocc"], out["inp_rec_vid"] = rec, dis, inp
         if not opt.no_future:
             alpha = []
             pred, dis, inp, flow = _decode_block(opt, warper, wif, real_input, net, ctx_len, b, every,
                                                  list(range(ctx_len, t)), shared=shared, out_alpha=alpha,
-                                                 raw_dtype=raw_dtype, out_bytes=out_bytes)
+                                                 raw_dtype=raw_dtype, out_bytes=out_bytes, palette=pal,
+                                                 out_render=rend_pred)
     else:
         # ONE decode for the reconstruction's and the prediction's units (see decode_units): the context's products once,
         # every full-resolution pass launched once with T + Tp units per clip
         alpha = []
         (rec, dis, inp, _), (pred, dis_p, inp_p, flow) = decode_units(
             opt, warper, wif, real_input, net, ctx_len, b, t, 0, b, every, list(range(ctx_len, t)), out_alpha=alpha,
-            raw_dtype=raw_dtype, out_bytes=out_bytes)
+            raw_dtype=raw_dtype, out_bytes=out_bytes, palette=pal, out_render=rend_rec)
         out["rec_vid"], out["rec_disocc"], out["inp_rec_vid"] = rec, dis, inp
         dis, inp = dis_p, inp_p
+        if render:  # (decode_units leaves the reconstruction's pair, then the prediction's)
+            rend_pred = [rend_rec.pop()]
     if not opt.no_future:
         # the pose generator (net_pg, outside the path) returns full-length pose sequences: the context
         # poses as they came in, the future ones predicted (flp.py:275-290) -- here the synthetic poses
@@ -409,6 +451,13 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, 
         out["pred_flow"] = flow
         out["pred_vid"] = torch.cat([ctx_vid, pred], dim=1)
         out["inp_pred_vid"] = torch.cat([ctx_vid, inp], dim=1)
+    if render:
+        out["rec_lyt_ids"], out["rec_sem_lyt"] = rend_rec[0]
+        if not opt.no_future:
+            out["pred_lyt_ids"], out["pred_sem_lyt"] = rend_pred[0]
+            out["pred_flow_rgb"] = WR.render_flow(flow, quantize=render)
+            if "pred_alpha" in out:
+                out["ctx_obj_lyt"] = WR.render_argmax(out["pred_alpha"], WR.layer_palette(out["pred_alpha"].shape[-3]))
     return out
 
 
@@ -423,19 +472,24 @@ MERGE_DECODES = True
 
 
 def decode_units(opt, warper, wif, real_input, net, ctx_len, b, t, b0, b1, rec_frames, pred_frames, out_alpha=None,
-                 raw_dtype=None, out_bytes=None):
+                 raw_dtype=None, out_bytes=None, palette=None, out_render=None):
     """The reconstruction's frames ``rec_frames`` and the prediction's frames ``pred_frames`` (clip-relative frame numbers,
     ascending) of clips b0:b1 in ONE decode.  Returns the two 4-tuples of ``_decode_block`` (either may be None when its
-    list is empty).  ``raw_dtype``, ``out_bytes``: see ``_decode_block``."""
+    list is empty).  ``raw_dtype``, ``out_bytes``: see ``_decode_block``.  ``out_render`` (a list): receives the
+    reconstruction's ``(ids, rgb)`` pair of ``_decode_block``, then the prediction's (views of the one render)."""
     dev = real_input.device
     rec_new = [f for f in rec_frames if f >= ctx_len]
     sel = list(range(ctx_len)) + rec_new + list(pred_frames)
     where = [f if f < ctx_len else ctx_len + rec_new.index(f) for f in rec_frames] + \
             [ctx_len + len(rec_new) + i for i in range(len(pred_frames))]
     blk = _block_net(opt, net, b, t, b0, b1, sel, dev)
+    both = [] if out_render is not None else None
     vid, dis, inp, flow = _decode_block(opt, warper, wif, real_input, blk, ctx_len, b1 - b0, sel, where, out_alpha=out_alpha,
-                                        raw_dtype=raw_dtype, out_bytes=out_bytes)
+                                        raw_dtype=raw_dtype, out_bytes=out_bytes, palette=palette, out_render=both)
     nr = len(rec_frames)
+    if both:
+        ids, rgb = both[0]
+        out_render += [(ids[:, :nr], rgb[:, :nr]), (ids[:, nr:], rgb[:, nr:])]
 
     def part(lo, hi):
         return (vid[:, lo:hi], dis[:, lo:hi], inp[:, lo:hi], flow[:, :, lo:hi]) if hi > lo else None
@@ -506,7 +560,7 @@ UNIT_KEYS = {"rec": ("rec_vid", "rec_disocc", "inp_rec_vid"), "pred": ("pred_vid
 
 @torch.no_grad()
 def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, world, phases=("rec", "pred"),
-                    raw_dtype=None, out_bytes=None):
+                    raw_dtype=None, out_bytes=None, render=None, palette=None):
     """This rank's share of predict() when ONE job (B clips) is split over ``world`` ranks: the
     (b, t) output units of each decode -- B * T reconstructed frames, B * (T - Tc) predicted ones -- are dealt in
     contiguous blocks of the phase's dealing order (dist.shard_range over ``phase_order``: the reconstruction's spreads
@@ -519,9 +573,13 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
     (``pred_vid`` / ``inp_pred_vid``: the predicted frames only; ``pred_flow``: Tc * 2 channels); ``gather_predict`` puts
     the ranks' blocks together into predict()'s dict.  Reference: the data-parallel split of tools/engine.py:63-64, here
     over frames instead of clips so that one clip can use every GPU.  ``raw_dtype``, ``out_bytes``: see ``predict`` (with
-    ``out_bytes`` the image blocks are uint8 -- a quarter of the bytes the all-gather moves; ``pred_flow`` stays fp32)."""
+    ``out_bytes`` the image blocks are uint8 -- a quarter of the bytes the all-gather moves; ``pred_flow`` stays fp32).
+    ``render``, ``palette``: see ``predict``; the keys of RENDER_KEYS are added as uint8 unit blocks (the ids with one
+    channel, ``pred_flow_rgb`` with Tc * 3)."""
     from ..dist import shard_range
     _check_out_bytes("predict_sharded", out_bytes)
+    _check_render("predict_sharded", render)
+    pal = _render_palette(palette, opt.num_lyt) if render else None
     if opt.include_self:
         raise ValueError("predict_sharded: include_self appends the predicted frame itself as a context "
                          "(lvd.py:842-845): every rank would need every frame")
@@ -531,7 +589,8 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
     out = {}
     inputs, shared = {}, {}  # clips b0:b1 -> cat of their context frames and layouts / their context's products
     job = (net["raw"], net["pred_obj_pose"], net["pred_bg_pose"], net["occ_score"], net["cls"])
-    parts = {k: [] for ph in phases for k in UNIT_KEYS[ph] if not (ph == "pred" and opt.no_future)}
+    parts = {k: [] for ph in phases for k in UNIT_KEYS[ph] + (RENDER_KEYS[ph] if render else ())
+             if not (ph == "pred" and opt.no_future)}
 
     def clip_input(b0, b1):
         if (b0, b1) not in inputs:
@@ -539,9 +598,16 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
             shared[(b0, b1)] = SharedContext()
         return inputs[(b0, b1)]
 
-    def keep(phase, nb, res):
+    def keep(phase, nb, res, rend=None):
         vid, dis, inp, flow = res
         n = vid.shape[1]
+        if rend is not None:
+            ids, rgb = rend
+            parts[phase + "_lyt_ids"].append(ids.reshape(-1, 1, hd, wd))
+            parts[phase + "_sem_lyt"].append(rgb.reshape(-1, 3, hd, wd))
+            if phase == "pred":  # (nb, Tc, n, 3, Hd, Wd) -> units x (Tc * 3)
+                pic = WR.render_flow(flow, quantize=render)
+                parts["pred_flow_rgb"].append(pic.permute(0, 2, 1, 3, 4, 5).reshape(nb * n, -1, hd, wd))
         parts[phase + "_vid"].append(vid.reshape(-1, 3, hd, wd))
         parts[phase + "_disocc"].append(dis.reshape(-1, 1, hd, wd))
         parts["inp_" + phase + "_vid"].append(inp.reshape(-1, 3, hd, wd))
@@ -561,25 +627,30 @@ def predict_sharded(opt, warper, wif, real_vid, real_lyt, net, ctx_len, rank, wo
             segs["rec"][0][:2] == segs["pred"][0][:2]:
         # this rank's reconstruction and prediction units belong to the same clips: ONE decode for both (decode_units)
         b0, b1, rec_frames = segs["rec"][0]
+        rend = [] if render else [None, None]
         rec, pred = decode_units(opt, warper, wif, clip_input(b0, b1), net, ctx_len, b, t, b0, b1, rec_frames,
-                                 segs["pred"][0][2], raw_dtype=raw_dtype, out_bytes=out_bytes)
-        keep("rec", b1 - b0, rec)
-        keep("pred", b1 - b0, pred)
+                                 segs["pred"][0][2], raw_dtype=raw_dtype, out_bytes=out_bytes, palette=pal,
+                                 out_render=rend if render else None)
+        keep("rec", b1 - b0, rec, rend[0])
+        keep("pred", b1 - b0, pred, rend[1])
     else:
         for phase, lst in segs.items():
             for b0, b1, frames in lst:
                 sel = sorted(set(range(ctx_len)) | set(frames))
                 blk = _block_net(opt, net, b, t, b0, b1, sel, dev)
+                rend = [] if render else [None]
                 res = _decode_block(opt, warper, wif, clip_input(b0, b1), blk, ctx_len, b1 - b0, sel,
                                     [sel.index(f) for f in frames], shared=shared[(b0, b1)],
-                                    shared_key=job + (inputs[(b0, b1)],), raw_dtype=raw_dtype, out_bytes=out_bytes)
-                keep(phase, b1 - b0, res)
+                                    shared_key=job + (inputs[(b0, b1)],), raw_dtype=raw_dtype, out_bytes=out_bytes,
+                                    palette=pal, out_render=rend if render else None)
+                keep(phase, b1 - b0, res, rend[0])
     for k, v in parts.items():
         if v:
             out[k] = v[0] if len(v) == 1 else torch.cat(v, dim=0)
         else:  # a rank past the end of a short job holds no unit
-            ch = {"disocc": 1, "flow": 2 * (opt.last_n_ctx or ctx_len)}.get(k.split("_")[-1], 3)
-            as_bytes = out_bytes is not None and k != "pred_flow"
+            ch = {"disocc": 1, "flow": 2 * (opt.last_n_ctx or ctx_len), "ids": 1}.get(k.split("_")[-1], 3)
+            ch = 3 * (opt.last_n_ctx or ctx_len) if k == "pred_flow_rgb" else ch
+            as_bytes = (out_bytes is not None and k != "pred_flow") or k in RENDER_KEYS["rec"] + RENDER_KEYS["pred"]
             out[k] = real_vid.new_empty(0, ch, hd, wd, dtype=torch.uint8 if as_bytes else torch.float32)
     return out
 
@@ -589,9 +660,10 @@ def units_to_clips(key, units, b, t, ctx_len, world, real_vid=None, out_bytes=No
     returns that key: the reconstruction's units go back from dealing order to frame order (one index copy; the
     prediction's are in frame order already), ``pred_flow`` to (B, Tc, Tp, 2, Hd, Wd), the context frames in front of
     ``pred_vid`` / ``inp_pred_vid`` (``real_vid``; with ``out_bytes``, for uint8 units of ``predict_sharded(out_bytes=...)``:
-    quantised the same way -- ``real_vid`` the fp32 clip or a ``WF.PackedClip``)."""
+    quantised the same way -- ``real_vid`` the fp32 clip or a ``WF.PackedClip``).  The keys of RENDER_KEYS: the ids lose
+    their channel, ``pred_flow_rgb`` goes to (B, Tc, Tp, 3, Hd, Wd)."""
     _check_out_bytes("units_to_clips", out_bytes)
-    phase = "rec" if key in UNIT_KEYS["rec"] else "pred"
+    phase = "rec" if key in UNIT_KEYS["rec"] + RENDER_KEYS["rec"] else "pred"
     per_clip = t if phase == "rec" else t - ctx_len
     if phase == "rec" and world > 1:
         ids = [i for r in range(world) for i in local_unit_ids(phase, b, t, ctx_len, r, world)]
@@ -600,9 +672,11 @@ def units_to_clips(key, units, b, t, ctx_len, world, real_vid=None, out_bytes=No
             natural[_cached_index(ids, units.device)] = units
             units = natural
     full = units.view(b, per_clip, *units.shape[1:])
-    if key == "pred_flow":  # units x (Tc * 2) -> (B, Tc, Tp, 2, Hd, Wd)
+    if key in ("pred_flow", "pred_flow_rgb"):  # units x (Tc * 2 | 3) -> (B, Tc, Tp, 2 | 3, Hd, Wd)
         hd, wd = full.shape[-2:]
-        return full.view(b, per_clip, -1, 2, hd, wd).permute(0, 2, 1, 3, 4, 5).contiguous()
+        return full.view(b, per_clip, -1, 2 if key == "pred_flow" else 3, hd, wd).permute(0, 2, 1, 3, 4, 5).contiguous()
+    if key in ("rec_lyt_ids", "pred_lyt_ids"):
+        return full.squeeze(2)
     if key in ("pred_vid", "inp_pred_vid") and real_vid is not None:
         ctx_vid = real_vid[:, :ctx_len]
         if out_bytes is not None:
@@ -623,7 +697,7 @@ def gather_predict(local, real_vid, ctx_len, keys=None, group=None, out_bytes=No
     keys = list(keys or local.keys())
     pending = {}
     for k in keys:
-        per_clip = t if k in UNIT_KEYS["rec"] else t - ctx_len
+        per_clip = t if k in UNIT_KEYS["rec"] + RENDER_KEYS["rec"] else t - ctx_len
         pending[k] = all_gather_frames_async(local[k], b * per_clip, group=group)
     return {k: units_to_clips(k, pending[k].wait(), b, t, ctx_len, world, real_vid, out_bytes=out_bytes) for k in keys}
 
@@ -632,11 +706,13 @@ RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --
 
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
-        device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None):
+        device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None, render=None, palette=None):
     """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
     ``WF.PackedClip``) and predict() reads it as such -- the same results.  ``eval``: also score ``rec_vid`` and
     ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``.  ``out_bytes``
-    ("trunc" / "round"): predict() returns its clips as uint8, and those bytes are what is written and scored."""
+    ("trunc" / "round"): predict() returns its clips as uint8, and those bytes are what is written and scored.
+    ``render`` ("trunc" / "round"), ``palette`` (3 * num_lyt integers): predict()'s renders of the decomposition; the
+    layout pictures, the flow picture of the last context and ``ctx_obj_lyt`` are written as ``.gif`` + ``_last.png``."""
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt)
     size = (dim, int(dim * aspect_ratio))
     clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames, packed=packed)
@@ -648,9 +724,18 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
     warper = Warper(opt).to(dev)
     wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     net = synthetic_network_outputs(opt, 1, vid.shape[1], ctx_len, seed=seed, device=dev)
-    res = predict(opt, warper, wif, vid, lyt, net, ctx_len, raw_dtype=raw_dtype, out_bytes=out_bytes)
+    res = predict(opt, warper, wif, vid, lyt, net, ctx_len, raw_dtype=raw_dtype, out_bytes=out_bytes, render=render,
+                  palette=palette)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
+        pics = {key: res[key][0] for key in ("rec_sem_lyt", "pred_sem_lyt") if key in res}
+        if "pred_flow_rgb" in res:
+            pics["pred_flow_rgb"] = res["pred_flow_rgb"][0, -1]  # (the last context's flows)
+        if "ctx_obj_lyt" in res:
+            pics["ctx_obj_lyt"] = res["ctx_obj_lyt"][0].reshape(-1, *res["ctx_obj_lyt"].shape[-3:])
+        for key, pic in pics.items():  # (uint8 already: written as they are)
+            wio.dump_video(pic.cpu(), os.path.join(out_dir, key + ".gif"))
+            wio.dump_image(pic[-1].cpu(), os.path.join(out_dir, key + "_last.png"))
         for key in ("rec_vid", "inp_rec_vid", "pred_vid", "inp_pred_vid"):
             if key in res:
                 wio.dump_video(res[key][0], os.path.join(out_dir, key + ".gif"))
@@ -688,6 +773,12 @@ def print_evaluation(scores, ctx_len, frame_size):
             print(line)
 
 
+def read_palette_file(path):
+    """``--palette FILE``: integers separated by white space or commas (3 per layout class), as a flat list."""
+    with open(path) as fh:
+        return [int(v) for v in fh.read().replace(",", " ").split()]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--clip", required=True, help="directory with the clip's frame PNGs (demo dataset layout)")
@@ -705,12 +796,19 @@ def main():
     ap.add_argument("--bytes", choices=sorted(WF.BYTE_QUANTIZE), default=None, dest="out_bytes",
                     help="return and write the clips as bytes quantised on the device (trunc: the reference's "
                          "dump_video; round: this package's)")
+    ap.add_argument("--render", nargs="?", const="trunc", choices=sorted(WR.QUANTIZE), default=None,
+                    help="also render the decomposition on the device: layout class ids and pictures, the flow wheel "
+                         "(the value: the quantisation of the flow picture)")
+    ap.add_argument("--palette", default=None, metavar="FILE",
+                    help="with --render: a text file of 3 * num_lyt integers, the layout colours (default: the jet "
+                         "colours of the object layers)")
     ap.add_argument("--eval", action="store_true",
                     help="score rec_vid and inp_pred_vid against the real frames (PSNR, SSIM, MS-SSIM from 161x161)")
     args = ap.parse_args()
+    palette = read_palette_file(args.palette) if args.palette is not None else None
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
-              eval=args.eval, out_bytes=args.out_bytes)
+              eval=args.eval, out_bytes=args.out_bytes, render=args.render, palette=palette)
     scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "
