@@ -788,6 +788,89 @@ int waldo_render_flow_fwd(const void* flow, int src_code, int64_t ss_n, int64_t 
                           int64_t N, int H, int W, waldo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Supervision targets: the data-side target of LVD training and its control-point distance terms -- what the
+ * reference's Synthesizer.extract_object builds from the real flow and layout on every step (models/synthesizer.py:
+ * 907-945, 965-979; models/modules/edge.py).  fp32 throughout; every tensor contiguous NCHW.
+ *
+ * waldo_flow_edges_fwd: EdgeExtractor.forward (edge.py:28-40).  flow (N, C, H, W), C = 1 or 2 -> flow_edge and
+ *   dominant, (N, 1, H, W) each.  Reflection padding k/2; per channel the k x k mean (weight 1.0f / (k k)) and the two
+ *   gradient filters, weights (float)x_i / (float)(x_i x_i + y_j y_j) and (float)y_j / (the same), the centre's divisor
+ *   1 -- divided in fp32 as the reference divides;  e_c = sqrtf(gx gx + gy gy + eps) / (float)sqrt(32);
+ *   flow_edge = 1 - prod_c (1 - e_c);  dominant = [sum_c flow_c^2 > sum_c mean_c^2] as 0.0f / 1.0f.
+ *   One launch: a 16 x 64 tile with its halo per channel in LDS, the weights in the kernel's arguments.
+ *   k odd in [3, 15]; H, W > k/2.
+ *
+ * waldo_gaussian_blur_fwd: the reference's blur (synthesizer.py:1114-1118: GaussianBlur(kernel_size, sigma) with a
+ *   fixed sigma), depthwise over P planes of H x W.  1-D weights exp(-0.5 (t / sigma)^2) at t = -(k-1)/2 .. (k-1)/2,
+ *   normalised to sum 1, in fp32; reflection padding k/2; rows, then columns (the reference multiplies by the outer
+ *   product: the same number up to rounding).  One launch: the row pass into LDS, the column pass from LDS.
+ *   k odd in [3, 31]; H, W > k/2; sigma > 0 and finite.  y must not overlap x.
+ *
+ * waldo_mov_props_fwd: the per-pixel sums over layout channels (synthesizer.py:912-916, 924).  lyt (N, Nl, H, W), flow
+ *   (N, 2, H, W); the channel lists as bit masks (bit c = channel c; Nl <= 32, no bit at or above Nl).
+ *   prop(list) = sum over the list's channels, ascending, of lyt_c / 10 + 0.5.
+ *   fg_prop = prop(fg);  nobg_prop = 1 - prop(bg);  other_prop = prop(other);  all (N, 1, H, W);
+ *   blur_in (N, 3, H, W) = (1 - fg_prop, (1 - fg_prop) flow_0, (1 - fg_prop) flow_1).
+ *
+ * waldo_mov_finish_fwd: synthesizer.py:909, 917-942 (blur_alpha off).  blurred (N, 3, H, W) = the blur of blur_in;
+ *   edge_raw, dominant = waldo_flow_edges_fwd's outputs.  Per pixel:
+ *     edge = [edge_raw > flow_thresh];  sum = blurred_0 + [blurred_0 == 0];  mean_bg_flow = blurred_{1,2} / sum
+ *     delta = fg_prop (|flow_0 - mean_0| + |flow_1 - mean_1|);  mask = [delta > mov_obj_thresh]
+ *     WALDO_MOV_DOMINANT_OTHER: mask = max(mask, other_prop dominant edge)
+ *     WALDO_MOV_FLOW_NOBG:      mask = mask | (edge > 0.1 & nobg_prop > 0)    (not with _DOMINANT_OTHER: the
+ *                               reference's `|` of a float tensor raises there)
+ *     mov_obj = 2 mask - 1;  negative values times reg_bg_mul;  then, in this order, each only where mov_obj < 0:
+ *     WALDO_MOV_USE_FG:    fg_prop > 0 -> 0;   WALDO_MOV_USE_NOBG: nobg_prop > 0 -> 0;
+ *     WALDO_MOV_USE_NOBG_EDGE: nobg_prop > 0 & edge > 0.1 -> nobg_edge_mul
+ *   Writes edge, mask, mov_obj (N, 1, H, W) and mean_bg_flow (N, 2, H, W).
+ *
+ * waldo_cell_distance_fwd / _bwd: synthesizer.py:965-979 without its (B, T, No, K, H, W) tensor.  Per frame f and object
+ *   n the caller passes the moments of the object's K points c_nk, moments (F, No, 3) = (sum_k c_x, sum_k c_y,
+ *   sum_k |c|^2), so that  dis_n(g) = sum_k |g - c_nk|^2 = K |g|^2 - 2 g . S1_n + S2_n  at the pixel's coordinate
+ *   g = (gx[x], gy[y]) (gx (W), gy (H): the columns and rows of get_grid).
+ *     w = (mov_mask + eps) (1 - fg_mask)   with fg_mask;   w = mov_mask   with fg_mask == NULL (the centre term)
+ *     out[0] = mean over F H W of min_n w dis_n;   chosen (F, H, W) bytes: the n of the minimum -- scanning n upward,
+ *     n replaces the best when v < best || (v != v && best == best): ties go to the lowest index, as torch.min(dim) on
+ *     the CPU; No <= 31.
+ *   Backward, grad_out a device scalar:  grad_moments (F, No, 3) = grad_out / (F H W) * sum over the pixels that chose n
+ *   of (-2 w gx, -2 w gy, w);  grad_fg (F, 1, H, W) = -grad_out (mov_mask + eps) dis_chosen / (F H W), or NULL.
+ *   Both are OVERWRITTEN.  NO FLOAT ATOMICS: every sum is a partial per workgroup, stored to the workspace, then one
+ *   pass over the partials in a fixed order -- out and both gradients are the same bits from run to run, whatever
+ *   the deterministic mode of the caller.  workspace: waldo_cell_distance_workspace_bytes(F, No, H W) for either call.
+ *
+ * All: caller-owned buffers and workspace, the caller's stream, no allocation, no synchronisation; N == 0 (F == 0):
+ * WALDO_OK without a launch.  WALDO_EINVAL with a message before any launch: k even or outside its range; H or W
+ * <= k/2; C outside [1, 2]; Nl outside [1, 32] or a mask bit at or above Nl; No outside [1, 31]; unknown flag bits or
+ * both _DOMINANT_OTHER and _FLOW_NOBG; a bad sigma, eps or K; a null pointer; a workspace that is too small; more
+ * than 2^31 - 1 workgroups.
+ * ------------------------------------------------------------------------------------- */
+#define WALDO_MOV_USE_FG 1
+#define WALDO_MOV_USE_NOBG 2
+#define WALDO_MOV_USE_NOBG_EDGE 4
+#define WALDO_MOV_FLOW_NOBG 8
+#define WALDO_MOV_DOMINANT_OTHER 16
+int waldo_flow_edges_fwd(const float* flow, float* flow_edge, float* dominant, int64_t N, int C, int H, int W, int k,
+                         float eps, waldo_stream_t stream);
+int waldo_gaussian_blur_fwd(const float* x, float* y, int64_t P, int H, int W, int k, float sigma,
+                            waldo_stream_t stream);
+int waldo_mov_props_fwd(const float* lyt, const float* flow, uint32_t fg_bits, uint32_t bg_bits, uint32_t other_bits,
+                        float* fg_prop, float* nobg_prop, float* other_prop, float* blur_in, int64_t N, int Nl,
+                        int64_t HW, waldo_stream_t stream);
+int waldo_mov_finish_fwd(const float* flow, const float* blurred, const float* fg_prop, const float* nobg_prop,
+                         const float* other_prop, const float* edge_raw, const float* dominant, float flow_thresh,
+                         float mov_obj_thresh, float reg_bg_mul, float nobg_edge_mul, int flags, float* edge,
+                         float* mean_bg_flow, float* mask, float* mov_obj, int64_t N, int64_t HW,
+                         waldo_stream_t stream);
+int64_t waldo_cell_distance_workspace_bytes(int64_t F, int No, int64_t HW);
+int waldo_cell_distance_fwd(const float* moments, const float* mov_mask, const float* fg_mask, const float* gx,
+                            const float* gy, float* out, uint8_t* chosen, void* workspace, int64_t workspace_bytes,
+                            int64_t F, int No, int H, int W, float K, float eps, waldo_stream_t stream);
+int waldo_cell_distance_bwd(const float* moments, const float* mov_mask, const float* fg_mask, const float* gx,
+                            const float* gy, const uint8_t* chosen, const float* grad_out, float* grad_moments,
+                            float* grad_fg, void* workspace, int64_t workspace_bytes, int64_t F, int No, int H, int W,
+                            float K, float eps, waldo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * Reproducible gradients (deterministic mode).  The backward entry points above that say "ZERO-FILLED ... atomics"
  * sum with float atomics: the result depends on the order of arrival and differs in its last bits from run to run.
  * Each has a twin, suffix _det, whose result is a function of its inputs alone -- the same bits from run to run,

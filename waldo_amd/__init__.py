@@ -5,6 +5,7 @@ binding (``_lib``), autograd wrappers (``functional``) and host-side mirrors of 
 operator modules (``modules.warp``, ``nets.lvd``, ``nets.wif``).
 """
 from . import functional  # noqa: F401
+from . import supervision  # noqa: F401
 from .functional import set_deterministic, is_deterministic, deterministic  # noqa: F401
 from .modules.warp import TPSWarp, InverseWarp  # noqa: F401
 

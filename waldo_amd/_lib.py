@@ -21,6 +21,7 @@ _c_f = ctypes.c_void_p  # device pointers travel as integers
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _flt = ctypes.c_float
+_u32 = ctypes.c_uint32
 _stream = ctypes.c_void_p
 
 # name -> argtypes; mirrors include/waldo_hip.h one to one (tests check the header against this)
@@ -87,6 +88,13 @@ SIGNATURES = {
                                 _stream],
     "waldo_render_flow_fwd": [_c_f, _int, _i64, _i64, _i64, _c_f, _int, _flt, _c_f, _i64, _int, _int, _i64, _int, _int,
                               _stream],
+    # supervision targets (include/waldo_hip.h "Supervision targets")
+    "waldo_flow_edges_fwd": [_c_f] * 3 + [_i64, _int, _int, _int, _int, _flt, _stream],
+    "waldo_gaussian_blur_fwd": [_c_f, _c_f, _i64, _int, _int, _int, _flt, _stream],
+    "waldo_mov_props_fwd": [_c_f, _c_f, _u32, _u32, _u32] + [_c_f] * 4 + [_i64, _int, _i64, _stream],
+    "waldo_mov_finish_fwd": [_c_f] * 7 + [_flt] * 4 + [_int] + [_c_f] * 4 + [_i64, _i64, _stream],
+    "waldo_cell_distance_fwd": [_c_f] * 8 + [_i64, _i64, _int, _int, _int, _flt, _flt, _stream],
+    "waldo_cell_distance_bwd": [_c_f] * 10 + [_i64, _i64, _int, _int, _int, _flt, _flt, _stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],
@@ -133,6 +141,7 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_warp_composite_bwd_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int]),
          "waldo_lyt_dist_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int, _int]),
          "waldo_border_objects_workspace_bytes": (_i64, [_i64]),
+         "waldo_cell_distance_workspace_bytes": (_i64, [_i64, _int, _i64]),
          "waldo_frame_metrics_partial_bytes": (_i64, [_int] * 5),
          "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),

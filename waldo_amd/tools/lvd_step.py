@@ -8,12 +8,18 @@ layout filtering with weighted classes):
 
 with the tensors the networks outside the path would hand over as seeded leaves (decoder logits, pose head
 outputs, occlusion scores, class logits).  ``bench.py --config LVD`` times it.
+
+``objective="stand-in"`` (the default) closes the step with a plain quadratic of the outputs;
+``objective="recipe"`` with the recipe's own four terms (``--s_vid_object_extractor_losses "ent_flt_edge" "l1_flow"
+"cell_dis" "reg_mov"``, train_lvd.sh:15) on a seeded real flow: the moving-object target is built on the device at
+every call, as the reference builds it at every step (``waldo_amd.supervision``).
 """
 import types
 
 import torch
 
 from .. import functional as WF
+from .. import supervision
 from ..nets import Warper, decode_output, estimate_alpha_grid_occ, flp
 from ..nets.lvd import decoder_tail
 from .utils import get_grid
@@ -27,13 +33,26 @@ def lvd_opt(**over):
     return types.SimpleNamespace(**d)
 
 
+# the recipe's options of the moving-object target (scripts/cityscapes/train_lvd.sh:28-35; the Cityscapes channel lists
+# of tools/options.py:628-630) and the weights of its four terms (train_lvd.sh:29-31; ent_flt_edge at the default of
+# --s_lambda_ent_flt_edge, tools/options.py:461)
+RECIPE_TARGET = dict(fg_idx=[0, 4, 5, 6, 7, 8, 12, 13, 14, 15, 16, 17, 18, 19], bg_idx=[1, 2, 3, 10, 11], other_idx=[9],
+                     flow_thresh=0.02, mov_obj_thresh=0.005, blur_sigma=2.0, edge_size=15, reg_bg_mul=0.25, use_fg=True,
+                     use_dominant_flow_other=True)
+RECIPE_WEIGHTS = {"cell_dis": 10.0, "l1_flow": 1000.0, "reg_mov": 10.0, "ent_flt_edge": 1.0}
+OBJECTIVES = ("stand-in", "recipe")
+
+
 class LvdStep:
     """``clips`` clips of 5 frames resident on ``device``; ``__call__`` runs forward, loss and backward once and
     returns the loss (the leaves' ``.grad`` hold the gradients)."""
 
     frames, num_lyt = 5, 20
 
-    def __init__(self, clips, device, seed=0):
+    def __init__(self, clips, device, seed=0, objective="stand-in"):
+        if objective not in OBJECTIVES:
+            raise ValueError(f"LvdStep: objective must be one of {OBJECTIVES}, got {objective!r}")
+        self.objective = objective
         self.opt = o = lvd_opt()
         self.clips = b = clips
         t, no, nl = self.frames, o.num_obj, self.num_lyt
@@ -58,6 +77,8 @@ class LvdStep:
         self.ctx_ts = torch.roll(torch.arange(t, device=device), 1).view(1, 1, t).expand(b, -1, -1).contiguous()
         # (every frame is predicted, in order: an index MARKED as 0 .. T-1 lets time_gather hand out the clip itself)
         self.pred_ts = WF.arange_index(t, device)
+        # (drawn after everything else: the leaves above are the same values with either objective)
+        self.real_flow = (0.05 * torch.randn(b, t, 2, h, w, generator=g, device=device)) if objective == "recipe" else None
         self.leaves = [self.raw, self.pose_o, self.pose_b, self.score, self.cls_logit]
         self.shape = (b, t, no, lo, lb, ho)
 
@@ -73,7 +94,15 @@ class LvdStep:
                                                     self.score)
         out = decode_output(self.warper, self.inp, grid, occ, oa, ba, self.cls_logit.softmax(-1), self.ctx_ts,
                             self.pred_ts, restrict_to_ctx=False)
-        loss = out[0].square().mean() + out[1].square().mean() + out[3].mean()
+        if self.objective == "recipe":
+            real_lyt = self.inp[:, :, 3:]
+            target = supervision.moving_object_target(self.real_flow, real_lyt, **RECIPE_TARGET)
+            # ctx_mode "prev" (synthesizer.py:849): the flow from the previous frame, for every frame but the first
+            self.terms = supervision.recipe_terms(out[3], out[1][:, 0, 1:], self.real_flow, real_lyt,
+                                                  obj_pose.view(b, t, no, lo, 2), self.opt.obj_shape, target)
+            loss = sum(RECIPE_WEIGHTS[k] * v for k, v in self.terms.items())
+        else:
+            loss = out[0].square().mean() + out[1].square().mean() + out[3].mean()
         loss.backward()
         return loss
 
