@@ -972,6 +972,50 @@ int waldo_warp_composite_bwd_det(const void* layers, const float* basis_t, const
                                  int64_t F, int L, int H, int W, int K3, float delta, int layers_dtype,
                                  waldo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Plane norm: the work between the convolutions of one UNet level (the reference's models/modules/conv.py:19-25,
+ * 59: conv -> CustomNorm("ln2d") = GroupNorm(C, C) -> GELU, then torch.cat([y, y_skip], dim=1)) in one call each way.
+ *
+ * waldo_plane_norm_gelu_fwd: x (N, C, H, W) fp32, every plane dense (H W consecutive values), planes xs_c and frames
+ *   xs_n elements apart; gamma, beta (C); skip (N, Cs, H, W) with strides ss_n, ss_c, or NULL with Cs == 0;
+ *   out (N, C + Cs, H, W), frames os_n >= (C + Cs) H W elements apart, channels dense.  Per plane (n, c):
+ *     mean = sum x / (H W);  var = sum (x - mean)^2 / (H W)  (biased);  rstd = 1 / sqrt(var + eps)
+ *     z = (x - mean) rstd gamma[c] + beta[c];  out[n, c] = 0.5 z (1 + erf(z / sqrt 2))   (the exact GELU)
+ *   out[n, C + cs] = the bits of skip[n, cs].  mean, rstd (N C) are written for the backward.
+ *   The variance is NEVER E[x^2] - E[x]^2: a thread holds its values in registers, subtracts the mean and sums the
+ *   squares; a plane larger than one workgroup's registers is cut into chunks whose (mean, M2) are combined pairwise
+ *   (Chan et al.).  A constant plane gives gelu(beta[c]); H W == 1 gives z = beta[c].
+ *
+ * waldo_plane_norm_gelu_bwd: grad_out is the gradient of the WHOLE out; its first C channels are read through gs_n,
+ *   gs_c (the gradient of skip is the other channel slice: a view, no kernel).  With xhat = (x - mean) rstd,
+ *   dz = grad_out gelu'(z),  gelu'(z) = Phi(z) + z phi(z):
+ *     sums[n C + c] = (sum dz, sum dz xhat)                            (N C, 2): grad_beta, grad_gamma summed over n
+ *     grad_x = rstd gamma (dz - sum dz / (H W) - xhat sum dz xhat / (H W))           (N, C, H, W) dense
+ *
+ * NO FLOAT ATOMICS: every sum is taken in an order fixed by the shapes -- all results are the same bits from run to
+ * run.  Traffic: H W <= 8192: x (and grad_out) read once, one write; above: read twice, one write; nothing
+ * tensor-sized in between.  workspace: waldo_plane_norm_workspace_bytes(N, C, H, W) for either call (0 for
+ * H W <= 8192; -1 for a bad shape).  waldo_plane_norm_limits(out, n): writes the first n of the launcher's regime
+ * boundaries, ascending (H W <= out[i] takes regime i; above the last: chunked), and returns how many there are.
+ *
+ * Caller-owned buffers and workspace, the caller's stream, no allocation, no synchronisation; N == 0: WALDO_OK
+ * without a launch.  WALDO_EINVAL with a message before any launch: "bad shape" (N, Cs < 0; C, H, W < 1),
+ * "too large" (H W > 2^30, or more than 2^31 - 1 workgroups), "negative stride", "bad stride" (os_n below
+ * (C + Cs) H W), "bad eps", "null pointer", "not aligned" (a pointer off a 4-byte boundary; 16-byte loads and stores
+ * are used when every pointer is 16-byte aligned and H W and the strides are multiples of 4, element accesses
+ * otherwise), "workspace too small".
+ * ------------------------------------------------------------------------------------- */
+int waldo_plane_norm_limits(int* out, int n);
+int64_t waldo_plane_norm_workspace_bytes(int64_t N, int C, int H, int W);
+int waldo_plane_norm_gelu_fwd(const float* x, int64_t xs_n, int64_t xs_c, const float* gamma, const float* beta,
+                              float eps, const float* skip, int64_t ss_n, int64_t ss_c, float* out, int64_t os_n,
+                              float* mean, float* rstd, void* workspace, int64_t workspace_bytes, int64_t N, int C,
+                              int Cs, int H, int W, waldo_stream_t stream);
+int waldo_plane_norm_gelu_bwd(const float* x, int64_t xs_n, int64_t xs_c, const float* gamma, const float* beta,
+                              const float* mean, const float* rstd, const float* grad_out, int64_t gs_n, int64_t gs_c,
+                              float* grad_x, float* sums, void* workspace, int64_t workspace_bytes, int64_t N, int C,
+                              int H, int W, waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,11 @@ SIGNATURES = {
     "waldo_flow_ctx_alpha_bwd_det": [_c_f] * 10 + [_i64] + [_int] * 10 + [_stream],
     "waldo_flow_ctx_warp_bwd_det": [_c_f] * 13 + [_i64] + [_int] * 9 + [_stream],
     "waldo_warp_composite_bwd_det": [_c_f] * 10 + [_i64, _i64, _int, _int, _int, _int, _flt, _int, _stream],
+    # plane norm (include/waldo_hip.h "Plane norm"): x and its strides, the affine, ..., workspace and its size, shape
+    "waldo_plane_norm_gelu_fwd": [_c_f, _i64, _i64, _c_f, _c_f, _flt, _c_f, _i64, _i64, _c_f, _i64, _c_f, _c_f, _c_f, _i64,
+                                  _i64, _int, _int, _int, _int, _stream],
+    "waldo_plane_norm_gelu_bwd": [_c_f, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _c_f, _c_f, _c_f, _i64, _i64,
+                                  _int, _int, _int, _stream],
 }
 # workspace size of each *_det entry point (0: no deterministic kernel for the shape)
 DET_QUERIES = {
@@ -144,6 +149,8 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_cell_distance_workspace_bytes": (_i64, [_i64, _int, _i64]),
          "waldo_frame_metrics_partial_bytes": (_i64, [_int] * 5),
          "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
+         "waldo_plane_norm_workspace_bytes": (_i64, [_i64, _int, _int, _int]),
+         "waldo_plane_norm_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),
          "waldo_last_error_string": (ctypes.c_char_p, []),
          "waldo_set_debug_option": (_int, [_int, _int]),

@@ -1903,3 +1903,130 @@ def _frames_per_call(f, nl, h, w, k3):
     if per_frame:
         per = min(per, max(1, int(MAX_WORKSPACE_BYTES // per_frame)))
     return per
+
+
+# --------------------------------------------------------------------------------------
+# plane norm + GELU (+ the concatenation with a skip): what lies between the UNet's convolutions
+# --------------------------------------------------------------------------------------
+# The launcher's gate: with a gradient required, planes whose H W lies in one of these ranges (lo, hi),
+# inclusive, take the framework ops although the tensors are on the GPU -- the level shapes where tools_dev/ab_unet.py
+# measured forward + backward of the op slower than GroupNorm + GELU + cat (a few megabytes per call: the time is the
+# host's, and the autograd node of a Python op costs more of it than three framework nodes).  Forward without
+# autograd: the kernel at every shape.
+PLANE_NORM_GRAD_FRAMEWORK_HW = ((1, 512),)           # with a skip to concatenate: the decoder's 16 x 32 level
+PLANE_NORM_GRAD_FRAMEWORK_HW_NO_SKIP = ((1, 8192),)  # without: the encoder's 8 x 16 to 64 x 128 levels
+
+
+def plane_norm_limits():
+    """The launcher's regime boundaries in H W, ascending (``waldo_plane_norm_limits``): planes of at most ``[0]``
+    values take a wavefront each, up to ``[-1]`` a workgroup each, larger ones are cut into chunks of ``[-1]``."""
+    buf = (ctypes.c_int * 8)()
+    n = _lib.load().waldo_plane_norm_limits(buf, 8)
+    return [int(buf[i]) for i in range(n)]
+
+
+def plane_norm_gelu_framework(x, weight, bias, skip=None, eps=1e-5):
+    """``plane_norm_gelu`` spelled out in framework ops, as the reference runs it (models/modules/conv.py:19-25, 59):
+    GroupNorm with one group per channel, the exact GELU, ``torch.cat`` with the skip.  The CPU route of
+    ``plane_norm_gelu`` and the ``fused = False`` route of ``modules.UNet``."""
+    # (torch.group_norm itself: F.group_norm first refuses N H W == 1, which is a legal plane here -- z = beta)
+    y = torch.nn.functional.gelu(torch.group_norm(x, x.shape[1], weight, bias, eps, torch.backends.cudnn.enabled))
+    return y if skip is None else torch.cat([y, skip], dim=1)
+
+
+def _dense_planes(t):
+    """``t`` (N, C, H, W) with every (n, c) plane dense -- any batch and channel stride: itself, else a dense copy."""
+    if t.is_contiguous():
+        return t
+    h, w = t.shape[2:]
+    if (w == 1 or t.stride(3) == 1) and (h == 1 or t.stride(2) == w):
+        return t
+    return t.contiguous()
+
+
+_plane_norm_chunk = None
+
+
+def _plane_norm_workspace(x):
+    """(buffer or None, bytes): what ``waldo_plane_norm_workspace_bytes`` returns for x's shape -- two floats per chunk
+    of a plane above the last regime boundary, nothing below -- worked out here from the limits (queried once): the
+    host's work per call is what a small level costs."""
+    global _plane_norm_chunk
+    if _plane_norm_chunk is None:
+        _plane_norm_chunk = plane_norm_limits()[-1]
+    n, c, h, w = x.shape
+    if h * w <= _plane_norm_chunk:
+        return None, 0
+    words = n * c * (-(-h * w // _plane_norm_chunk)) * 2
+    return x.new_empty(words), words * 4
+
+
+class _PlaneNormGelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, skip, eps):
+        _lib.check_cuda(x, weight, bias, skip)
+        n, c, h, w = x.shape
+        x, weight, bias = _dense_planes(x), _c(weight), _c(bias)
+        cs = ss_n = ss_c = 0
+        if skip is not None:
+            skip = _dense_planes(skip)
+            cs, ss_n, ss_c = skip.shape[1], skip.stride(0), skip.stride(1)
+        out = x.new_empty(n, c + cs, h, w)
+        stats = x.new_empty(2, n * c)  # mean, rstd
+        ws, nbytes = _plane_norm_workspace(x)
+        _lib.launch("waldo_plane_norm_gelu_fwd", x.device, x, x.stride(0), x.stride(1), weight, bias, float(eps), skip,
+                    ss_n, ss_c, out, (c + cs) * h * w, stats, stats.data_ptr() + 4 * n * c, ws, nbytes, n, c, cs, h, w)
+        ctx.save_for_backward(x, weight, bias, stats)
+        ctx.has_skip = skip is not None
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, weight, bias, stats = ctx.saved_tensors
+        n, c, h, w = x.shape
+        gx = gw = gb = gs = None
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            grad_out = _dense_planes(grad_out)  # (its first C channels are read through the strides: no copy)
+            gx = x.new_empty(n, c, h, w)
+            sums = x.new_empty(n, c, 2)
+            ws, nbytes = _plane_norm_workspace(x)
+            _lib.launch("waldo_plane_norm_gelu_bwd", x.device, x, x.stride(0), x.stride(1), weight, bias, stats,
+                        stats.data_ptr() + 4 * n * c, grad_out, grad_out.stride(0), grad_out.stride(1), gx, sums, ws,
+                        nbytes, n, c, h, w)
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                # (over n: a framework reduction with a fixed order, no atomics)
+                gb, gw = (sums[0] if n == 1 else sums.sum(dim=0)).unbind(1)
+        if ctx.has_skip and ctx.needs_input_grad[3]:
+            gs = grad_out[:, c:]
+        return gx, gw, gb, gs, None
+
+
+def plane_norm_gelu(x, weight, bias, skip=None, eps=1e-5):
+    """``cat([gelu(group_norm(x, C, weight, bias, eps)), skip], dim=1)`` -- one UNet level's work between two
+    convolutions (include/waldo_hip.h "Plane norm") as one op: x (N, C, H, W), weight / bias (C), skip (N, Cs, H, W) or
+    None -> (N, C + Cs, H, W).  Differentiable in x, weight, bias and skip; keeps x and two floats per plane for the
+    backward, which is free of atomics (the same bits from run to run in either deterministic mode).  fp32; under
+    autocast the inputs are cast to fp32, as ``group_norm``'s are.  Tensors on the CPU take the same arithmetic in
+    framework ops (``plane_norm_gelu_framework``), as do, under autograd, the planes of
+    ``PLANE_NORM_GRAD_FRAMEWORK_HW`` (``_NO_SKIP``)."""
+    if x.dim() != 4:
+        raise ValueError(f"plane_norm_gelu: x must be (N, C, H, W), got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    if tuple(weight.shape) != (c,) or tuple(bias.shape) != (c,):
+        raise ValueError(f"plane_norm_gelu: weight and bias must be ({c},), got {tuple(weight.shape)}, {tuple(bias.shape)}")
+    if skip is not None and (skip.dim() != 4 or skip.shape[0] != n or tuple(skip.shape[2:]) != (h, w)):
+        raise ValueError(f"plane_norm_gelu: skip must be ({n}, Cs, {h}, {w}), got {tuple(skip.shape)}")
+    if not x.is_cuda or x.numel() == 0:
+        return plane_norm_gelu_framework(x, weight, bias, skip, eps)
+    gate = PLANE_NORM_GRAD_FRAMEWORK_HW_NO_SKIP if skip is None else PLANE_NORM_GRAD_FRAMEWORK_HW
+    if gate and any(lo <= h * w <= hi for lo, hi in gate) and torch.is_grad_enabled() \
+            and (x.requires_grad or weight.requires_grad or bias.requires_grad or (skip is not None and skip.requires_grad)):
+        return plane_norm_gelu_framework(x, weight, bias, skip, eps)
+    if torch.is_autocast_enabled("cuda"):  # fp32 inside, as group_norm: the casts carry the gradients back
+        with torch.autocast("cuda", enabled=False):
+            return _PlaneNormGelu.apply(x.float(), weight.float(), bias.float(), None if skip is None else skip.float(),
+                                        eps)
+    return _PlaneNormGelu.apply(x, weight, bias, skip, eps)

@@ -1,14 +1,17 @@
 """Drop-in for the hot-path part of the reference's models/nets/wif.py: ``WIF.forward`` and the
 warp / mask arithmetic of ``WIF.inpaint``.
 
-The UNet itself (models/modules/conv.py, MIOpen convolutions) is out of scope: the constructor
-takes any ``nn.Module`` mapping (N, C_in, H, W) -> (N, 4|5, H, W) (or builds nothing when None is
-given and ``forward`` is called with precomputed network outputs through ``fuse``).  The fusion
-arithmetic around it runs in one hand-written gfx950 kernel (``waldo_wif_fuse_*``)."""
+The UNet's convolutions stay MIOpen; the rest is ours: ``WIF.with_unet(opt)`` builds the reference's network
+(``waldo_amd.modules.UNet``: its norm, GELU and skip concatenation in one hand-written kernel per level,
+``waldo_plane_norm_gelu_*``) from the option fields the reference reads, and a reference checkpoint loads into it
+strictly.  The plain constructor takes any ``nn.Module`` mapping (N, C_in, H, W) -> (N, 4|5, H, W) (or builds
+nothing when None is given and ``forward`` is called with precomputed network outputs through ``fuse``).  The
+fusion arithmetic around the network runs in one hand-written gfx950 kernel (``waldo_wif_fuse_*``)."""
 import torch
 import torch.nn as nn
 
 from .. import functional as WF
+from ..modules.conv import UNet
 from ..tools.utils import get_grid
 
 expand = WF.mask_expand  # tools/utils.py:300-323 as one launch (waldo_amd.tools.utils.expand states the steps)
@@ -53,6 +56,27 @@ class WIF(nn.Module):
             if getattr(opt, "load_dim", 0) > 0:
                 shape = [opt.load_dim, int(opt.load_dim * opt.aspect_ratio)]
             self.register_buffer("src_grid_hd", get_grid(*shape), persistent=False)
+
+    @staticmethod
+    def unet_arguments(opt):
+        """The arguments the reference's constructor derives for its UNet (wif.py:18-28), as a dict."""
+        scale_hd = opt.load_dim / opt.dim if (opt.load_dim > 0 and opt.ii_ft_hd) else 1
+        per_ctx = 3 + opt.num_lyt + opt.num_obj + 1 + (1 if opt.use_disocc else 0)
+        if opt.ii_score:
+            cin, cout, zero_init = per_ctx, 5 if opt.ii_ab else 4, bool(opt.ii_ab)
+        else:
+            cin, cout, zero_init = per_ctx * opt.ctx_len, 3, False
+        return dict(num_channels_in=cin, num_channels_out=cout, embed_dim=opt.ii_embed_dim,
+                    norm_layer=opt.norm_layer_patch, depth=opt.ii_depth, scale_hd=scale_hd, zero_init=zero_init,
+                    upmode=opt.ii_upmode)
+
+    @classmethod
+    def with_unet(cls, opt):
+        """``WIF`` with the reference's own network built from ``opt`` as its constructor does (wif.py:18-28: the channel
+        counts from num_lyt, num_obj, use_disocc, ii_score, ii_ab, ctx_len; the rest from ii_embed_dim,
+        norm_layer_patch, ii_depth, ii_upmode, load_dim / dim / ii_ft_hd).  The reference WIF's ``state_dict()`` -- only
+        ``unet.*`` keys -- loads into it with ``strict=True``."""
+        return cls(opt, unet=UNet(**cls.unet_arguments(opt)))
 
     def get_last_layer(self):
         return self.unet.from_emb.weight

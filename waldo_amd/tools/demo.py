@@ -30,13 +30,16 @@ from .utils import get_grid
 
 
 def demo_opt(dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, **over):
-    """The option fields the path reads (Warper: models/nets/lvd.py:472-499; WIF: ii_score, ii_ab),
-    at the C1 size: 128 x 128, 4 layers (3 objects + background)."""
+    """The option fields the path reads (Warper: models/nets/lvd.py:472-499; WIF: ii_score, ii_ab, and what
+    ``WIF.with_unet`` builds the network from: the ii_* fields at the reference's defaults, tools/options.py:235,
+    309-316, 392), at the C1 size: 128 x 128, 4 layers (3 objects + background)."""
     d = dict(latent_shape=[4, 4], obj_shape=[2, 2], time_dropout=0.0, num_obj=num_obj, patch_size=8,
              scale_factor=2, dim=dim, aspect_ratio=aspect_ratio, load_dim=0, num_perm_grid=1,
              normalize_alpha=False, use_lyt_filtering=True, use_lyt_opacity=False, weight_cls=True,
              min_cls=0.05, include_self=False, no_filter=False, allow_ghost=False, num_lyt=num_lyt,
-             ii_score=True, ii_ab=True, last_n_ctx=0, no_future=False, pad_obj_alpha=2, use_inpainter=False)
+             ii_score=True, ii_ab=True, last_n_ctx=0, no_future=False, pad_obj_alpha=2, use_inpainter=False,
+             ii_embed_dim=512, ii_depth=4, ii_upmode="bilinear", ii_ft_hd=False, norm_layer_patch="ln2d",
+             use_disocc=False, ctx_len=4)
     d.update(over)
     return types.SimpleNamespace(**d)
 
@@ -706,14 +709,17 @@ RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --
 
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
-        device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None, render=None, palette=None):
+        device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None, render=None, palette=None,
+        wif_ckpt=None, ii_depth=4, ii_embed_dim=512):
     """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
     ``WF.PackedClip``) and predict() reads it as such -- the same results.  ``eval``: also score ``rec_vid`` and
     ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``.  ``out_bytes``
     ("trunc" / "round"): predict() returns its clips as uint8, and those bytes are what is written and scored.
     ``render`` ("trunc" / "round"), ``palette`` (3 * num_lyt integers): predict()'s renders of the decomposition; the
-    layout pictures, the flow picture of the last context and ``ctx_obj_lyt`` are written as ``.gif`` + ``_last.png``."""
-    opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt)
+    layout pictures, the flow picture of the last context and ``ctx_obj_lyt`` are written as ``.gif`` + ``_last.png``.
+    ``wif_ckpt``: a reference ``ii`` state dict (``load_wif_checkpoint``) run through ``WIF.with_unet`` at ``ii_depth`` /
+    ``ii_embed_dim`` in place of the stand-in network."""
+    opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt, ctx_len=ctx_len, ii_depth=ii_depth, ii_embed_dim=ii_embed_dim)
     size = (dim, int(dim * aspect_ratio))
     clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames, packed=packed)
     dev = torch.device(device)
@@ -722,7 +728,10 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
     else:
         vid, lyt = clip["vid"].unsqueeze(0).to(dev), clip["lyt"].unsqueeze(0).to(dev)
     warper = Warper(opt).to(dev)
-    wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
+    if wif_ckpt is not None:
+        wif = load_wif_checkpoint(WIF.with_unet(opt), wif_ckpt).to(dev).eval()
+    else:
+        wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     net = synthetic_network_outputs(opt, 1, vid.shape[1], ctx_len, seed=seed, device=dev)
     res = predict(opt, warper, wif, vid, lyt, net, ctx_len, raw_dtype=raw_dtype, out_bytes=out_bytes, render=render,
                   palette=palette)
@@ -746,6 +755,17 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
     if eval:
         res["metrics"] = evaluate_prediction(res, vid)
     return res
+
+
+def load_wif_checkpoint(wif, path):
+    """Load a reference ``ii`` state dict (the file, or a tensor-only dict in it under "state_dict") into ``wif``
+    (``WIF.with_unet``), strictly; a ``module.`` prefix (DistributedDataParallel) is stripped."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(state, dict) and "state_dict" in state:
+        state = state["state_dict"]
+    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    wif.load_state_dict(state, strict=True)
+    return wif
 
 
 EVAL_KEYS = ("rec_vid", "inp_pred_vid")
@@ -804,11 +824,17 @@ def main():
                          "colours of the object layers)")
     ap.add_argument("--eval", action="store_true",
                     help="score rec_vid and inp_pred_vid against the real frames (PSNR, SSIM, MS-SSIM from 161x161)")
+    ap.add_argument("--wif-ckpt", default=None, metavar="FILE",
+                    help="a reference `ii` checkpoint (state dict): run the reference's UNet (WIF.with_unet) in place of "
+                         "the stand-in network")
+    ap.add_argument("--ii-depth", type=int, default=4, help="with --wif-ckpt: the checkpoint's --s_ii_depth")
+    ap.add_argument("--ii-embed-dim", type=int, default=512, help="with --wif-ckpt: the checkpoint's --s_ii_embed_dim")
     args = ap.parse_args()
     palette = read_palette_file(args.palette) if args.palette is not None else None
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
-              eval=args.eval, out_bytes=args.out_bytes, render=args.render, palette=palette)
+              eval=args.eval, out_bytes=args.out_bytes, render=args.render, palette=palette, wif_ckpt=args.wif_ckpt,
+              ii_depth=args.ii_depth, ii_embed_dim=args.ii_embed_dim)
     scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "

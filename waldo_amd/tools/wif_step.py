@@ -14,7 +14,8 @@ classes, 128 x 256 layers, 512 x 1024 frames):
 The networks outside the path are stand-ins: seeded decoder logits / pose head outputs / occlusion scores / class
 distributions, and a 1 x 1 convolution (40 -> 5 channels, the UNet's widths at ``ii_score`` + ``ii_ab``, wif.py:19-23)
 in the UNet's place so that ``waldo_wif_fuse_bwd`` receives and produces real gradients.  ``bench.py --config WIF``
-times it.
+times it.  ``WifStep(..., unet="reference")`` puts the real network there (``WIF.with_unet`` at the recipe's widths:
+``ii_depth 6``, ``ii_embed_dim 512``).
 """
 import torch
 import torch.nn as nn
@@ -30,7 +31,7 @@ def wif_opt(**over):
     """The option fields the path reads, at the Cityscapes WIF recipe (train_wif.sh:12-16, 25-37)."""
     return demo.demo_opt(dim=128, aspect_ratio=2.0, num_obj=16, num_lyt=20, load_dim=512, latent_shape=[8, 16],
                          obj_shape=[4, 4], patch_size=16, scale_factor=1, min_cls=0.1, use_lyt_opacity=True,
-                         pad_obj_alpha=3, **over)
+                         pad_obj_alpha=3, **dict(dict(ii_depth=6), **over))
 
 
 class WifStep:
@@ -39,13 +40,19 @@ class WifStep:
 
     frames, ctx_len = 5, 4
 
-    def __init__(self, clips, device, seed=0, motion="calibrated"):
+    def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in"):
+        if unet not in ("stand-in", "reference"):
+            raise ValueError(f"WifStep: unet must be 'stand-in' or 'reference', got {unet!r}")
         self.opt = o = wif_opt()
         self.clips, self.device = clips, device
         self.warper = Warper(o).to(device)
         torch.manual_seed(seed)
-        self.unet = nn.Conv2d(3 + o.num_lyt + o.num_obj + 1, 5, 1).to(device)
-        self.wif = WIF(o, unet=self.unet).to(device)
+        if unet == "reference":
+            self.wif = WIF.with_unet(o).to(device)
+            self.unet = self.wif.unet
+        else:
+            self.unet = nn.Conv2d(3 + o.num_lyt + o.num_obj + 1, 5, 1).to(device)
+            self.wif = WIF(o, unet=self.unet).to(device)
         self.net = demo.synthetic_network_outputs(o, clips, self.frames, self.ctx_len, seed=seed, device=device,
                                                   motion=motion)
         self.vid, self.lyt = synthetic_clip(o, clips, self.frames, seed, device)
