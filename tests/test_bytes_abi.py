@@ -100,6 +100,11 @@ def test_both_units_use_the_one_quantisation_text():
         text = open(os.path.join(csrc, name)).read()
         assert '#include "quantize.hip.h"' in text, name
         assert "/ range" not in text and "* 255.0f" not in text, name
+    # the renders take it through the row scheme's header; the formula is in neither
+    rows, render = (open(os.path.join(csrc, name)).read() for name in ("byte_rows.hip.h", "render.hip"))
+    assert '#include "quantize.hip.h"' in rows and '#include "byte_rows.hip.h"' in render
+    for text in (rows, render):
+        assert "/ range" not in text and "* 255.0f" not in text
 
 
 def test_wrappers_have_no_cpu_fallback():

@@ -14,8 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DTYPES = [torch.float32, torch.bfloat16, torch.float16]
 CLASSES = [1, 2, 12, 20, 33]
 # 5 x 37 and 3 x 129: dense rows merge into one of 185 / 387 pixels -- head, full 16-pixel groups and a 4 + 1 / 3 tail
-# (and, as non-dense rows of 37 / 129, groups and a 4 + 1 / 1 tail per row); 12 x 20: no full group in a row
-SIZES = [(5, 37), (12, 20), (3, 129)]
+# (and, as non-dense rows of 37 / 129, groups and a 4 + 1 / 1 tail per row); 12 x 20: no full group in a row; 3 x 1400:
+# one row of 4200 pixels, past a workgroup's 4096 -- a second workgroup whose lanes hold a body and a 4 + 4 tail (and, as
+# non-dense rows of 1400, 87 groups and an 8-pixel tail per row)
+SIZES = [(5, 37), (12, 20), (3, 129), (3, 1400)]
 
 
 @pytest.fixture(scope="module")

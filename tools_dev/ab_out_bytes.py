@@ -12,7 +12,7 @@ fusion shape (40-channel ``raw_output``, 5-channel network output, Tc = 4, 10 fr
 The forms of a group are interleaved in ONE process, timed with events on the launch stream, median of 7 after 3
 warm-ups (best and worst reported with it).  One GPU process: run it under a time limit,
 
-    timeout -k 10 600 python tools_dev/ab_out_bytes.py [--out profiles/out_bytes.json] [--clips 4]"""
+    timeout -k 10 600 python tools_dev/ab_out_bytes.py [--out profiles/out_bytes.json] [--clips 4] [--lib PATH]"""
 import argparse
 import json
 import os
@@ -22,6 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from waldo_amd import _lib  # noqa: E402
 from waldo_amd import functional as WF  # noqa: E402
 from waldo_amd.tools import demo  # noqa: E402
 from waldo_amd.tools.pipeline import Pipeline  # noqa: E402
@@ -79,7 +80,10 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=os.path.join("profiles", "out_bytes.json"))
     ap.add_argument("--clips", type=int, default=4)
+    ap.add_argument("--lib", default=None, help="another build of the library, timed under this script")
     args = ap.parse_args()
+    if args.lib:
+        _lib.use_library(args.lib)
     dev = torch.device("cuda:0")
     doc = {"what": f"byte output at C5 predict ({args.clips} clips x 14 frames, 512x1024, Tc=4, 12 layers, stand-in "
                    "networks) and at the WIF recipe's fusion (40-channel raw_output, Tc=4, 10 frames of 512x1024)",

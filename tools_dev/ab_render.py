@@ -2,7 +2,7 @@
 classes, L = 12 object layers, Tc = 4 contexts -- against the same results spelled in framework ops on the device and
 against the reference's host route.  Writes profiles/render.json.
 
-    python tools_dev/ab_render.py [--out profiles/render.json] [--frames 56] [--height 512] [--width 1024]
+    python tools_dev/ab_render.py [--out profiles/render.json] [--frames 56] [--height 512] [--width 1024] [--lib PATH]
 
 Routes, each producing the SAME bytes (checked here, at the timed size, before anything is timed):
   new        one library call: render_argmax(..., return_ids=True) / class_ids / render_flow;
@@ -29,6 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from waldo_amd import _lib  # noqa: E402
 from waldo_amd import render as R  # noqa: E402
 
 
@@ -106,7 +107,10 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--host-frames", type=int, default=4)
+    ap.add_argument("--lib", default=None, help="another build of the library, timed under this script")
     args = ap.parse_args()
+    if args.lib:
+        _lib.use_library(args.lib)
     if not torch.cuda.is_available():
         raise SystemExit("ab_render: needs a GPU (no timing is taken without one)")
     dev = torch.device("cuda:0")

@@ -5,31 +5,25 @@
 //   waldo_render_flow_fwd     N flows (2, H, W) -> the colour-wheel picture of Logger.get_flow_rgb (tools/logger.py:310-318),
 //                             quantised with the library's one quantisation (quantize.hip.h), span (0, 1).
 //
-// Both are streaming passes laid out as frames_to_bytes.hip (sub-dword stores cost ~12 x a 16-byte store per byte on this
-// part): a lane owns 16 consecutive pixels of a ROW (H merged into the row where the source rows are dense), keeps their
-// running maxima and ids in registers while it walks the C planes -- kAhead planes' 16-byte loads in flight -- and writes
-// 16 ids as one 16-byte store, an interleaved group as three.  Per row:
-//   head   the pixels up to the first 16-byte boundary of the row's PRIMARY destination (the id map where there is one,
-//          else the RGB bytes; at most 15; any base alignment is accepted): single bytes, one lane each;
-//   body   groups of 16 pixels: 16-byte loads where every plane's row is 16-byte aligned at the head's end, element loads
-//          otherwise;
-//   tail   the last, partial group: 4 pixels per dword store (three dwords interleaved), then single bytes.
+// Both are streaming passes over the rows of byte_rows.hip.h (H merged into the row where the source rows are dense): a
+// lane keeps its 16 pixels' running maxima and ids in registers while it walks the C planes -- kAhead planes' 16-byte
+// loads in flight -- and writes 16 ids as one 16-byte store, an interleaved group as three.  The head reaches the first
+// 16-byte boundary of the row's PRIMARY destination: the id map where there is one, else the RGB bytes.  The body's loads
+// are 16-byte ones where every plane's row is 16-byte aligned at the head's end.
 // With two destinations (ids AND rgb) or a planar one whose planes are not a multiple of 16 bytes apart, the others may
 // sit at another alignment than the primary: every store checks its own address (store_words: 16-byte, else dword, else
 // byte stores -- uniform over a row), so any alignment is correct and the aligned case pays one compare.
 // The palette lives in LDS as one packed word per class (0x00BBGGRR), filled by the workgroup at entry; the flow wheel
 // too while it has at most kWheelLds rows.  No atomics, no workspace, no allocation; the caller's stream.
-#include "quantize.hip.h"
+#include "byte_rows.hip.h"
 
 namespace waldo {
 
 namespace {
 
-constexpr int kPx = 16;          // pixels of a lane
 constexpr int kMaxClasses = 256; // an id fits a byte
 constexpr int kWheelLds = 256;   // rows of a flow wheel kept in LDS (a larger one is read from global memory)
 constexpr int kMaxWheel = 4096;
-typedef uint32_t bytes_u32x4 __attribute__((ext_vector_type(4)));
 
 struct Dest {
   uint8_t* ids;   // this row of the id map, or null
@@ -47,47 +41,11 @@ struct RenderArgs {
   int64_t di_n;
   uint8_t* rgb;
   int64_t dr_n;
-  int64_t Wr;  // pixels of a row (after merging)
-  int Hr;      // rows of a frame
-  int chunks;  // workgroups of a row
+  Rows R;  // (rows of a frame: Hr)
   int C, K, quant;
   float mul;
   bool nhwc;
 };
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-// 16 consecutive elements at p; vec: p is 16-byte aligned
-template <typename T>
-__device__ __forceinline__ void load16(const T* __restrict__ p, bool vec, T (&v)[kPx]) {
-  if (vec) {
-    constexpr int kQ = (int)sizeof(T) * kPx / 16;
-    bytes_u32x4 q[kQ];
-#pragma unroll
-    for (int k = 0; k < kQ; ++k) q[k] = reinterpret_cast<const bytes_u32x4*>(p)[k];
-    __builtin_memcpy(v, q, sizeof(v));
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPx; ++k) v[k] = p[k];
-  }
-}
-
-// NW words at p, whatever its alignment, with the widest store that alignment allows
-template <int NW>
-__device__ __forceinline__ void store_words(uint8_t* p, const uint32_t (&w)[NW]) {
-  const unsigned a = (unsigned)((uintptr_t)p & 15u);
-  if (NW % 4 == 0 && a == 0) {
-#pragma unroll
-    for (int q = 0; q < NW / 4; ++q)
-      reinterpret_cast<bytes_u32x4*>(p)[q] = (bytes_u32x4){w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
-  } else if ((a & 3u) == 0) {
-#pragma unroll
-    for (int j = 0; j < NW; ++j) reinterpret_cast<uint32_t*>(p)[j] = w[j];
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4 * NW; ++i) p[i] = (uint8_t)(w[i / 4] >> (8 * (i % 4)));
-  }
-}
 
 // NP consecutive pixels from pixel x of the row on: ids id[] and colours col[] (0x00BBGGRR) to whatever the row writes.
 // NP = 16 (a lane's group), 4 or 1 (the tail and the head).
@@ -102,55 +60,33 @@ __device__ __forceinline__ void emit(const Dest& d, int64_t x, const uint32_t (&
   } else {
     if (d.ids) {
       uint32_t w[NP / 4];
-#pragma unroll
-      for (int j = 0; j < NP / 4; ++j) w[j] = id[4 * j] | (id[4 * j + 1] << 8) | (id[4 * j + 2] << 16) | (id[4 * j + 3] << 24);
+      pack_planar<NP>(w, [&](int k) { return id[k]; });
       store_words(d.ids + x, w);
     }
-    if (d.rgb && d.nhwc) {  // byte i of the group's 3 NP: channel i % 3 of pixel i / 3
+    if (d.rgb && d.nhwc) {
       uint32_t w[3 * NP / 4];
-#pragma unroll
-      for (int j = 0; j < 3 * NP / 4; ++j) {
-        uint32_t word = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const int i = 4 * j + b;
-          word |= ((col[i / 3] >> (8 * (i % 3))) & 255u) << (8 * b);
-        }
-        w[j] = word;
-      }
+      pack_interleaved<NP>(w, [&](int c, int k) { return (col[k] >> (8 * c)) & 255u; });
       store_words(d.rgb + 3 * x, w);
     } else if (d.rgb) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         uint32_t w[NP / 4];
-#pragma unroll
-        for (int j = 0; j < NP / 4; ++j) {
-          uint32_t word = 0;
-#pragma unroll
-          for (int b = 0; b < 4; ++b) word |= ((col[4 * j + b] >> (8 * c)) & 255u) << (8 * b);
-          w[j] = word;
-        }
+        pack_planar<NP>(w, [&](int k) { return (col[k] >> (8 * c)) & 255u; });
         store_words(d.rgb + c * d.plane + x, w);
       }
     }
   }
 }
 
-// workgroup -> (frame, row of the frame, chunk of the row); the row's destinations and its head
-__device__ __forceinline__ void decode_row(const RenderArgs& A, int64_t& n, int& r, int& chunk, Dest& d, int& head) {
-  const unsigned row_id = blockIdx.x / (unsigned)A.chunks;
-  chunk = (int)(blockIdx.x - row_id * (unsigned)A.chunks);
-  n = row_id / (unsigned)A.Hr;
-  r = (int)(row_id - (unsigned)n * (unsigned)A.Hr);
+// the destinations of row r of frame n, and the row's head
+__device__ __forceinline__ Dest row_dest(const RenderArgs& A, int64_t n, int r, int& head) {
+  Dest d;
   d.nhwc = A.nhwc;
-  d.plane = (int64_t)A.Hr * A.Wr;
-  d.ids = A.ids ? A.ids + n * A.di_n + (int64_t)r * A.Wr : nullptr;
-  d.rgb = A.rgb ? A.rgb + n * A.dr_n + (int64_t)r * A.Wr * (A.nhwc ? 3 : 1) : nullptr;
-  unsigned h;
-  if (d.ids || !d.nhwc) h = (16u - (unsigned)((uintptr_t)(d.ids ? d.ids : d.rgb) & 15u)) & 15u;
-  // the first pixel whose 3 bytes start a 16-byte line: 3 h = -address (mod 16), 3 * 11 = 1 (mod 16)
-  else h = ((16u - (unsigned)((uintptr_t)d.rgb & 15u)) * 11u) & 15u;
-  head = (int)min((int64_t)h, A.Wr);
+  d.plane = (int64_t)A.R.Hr * A.R.Wr;
+  d.ids = A.ids ? A.ids + n * A.di_n + (int64_t)r * A.R.Wr : nullptr;
+  d.rgb = A.rgb ? A.rgb + n * A.dr_n + (int64_t)r * A.R.Wr * (A.nhwc ? 3 : 1) : nullptr;
+  head = row_head(d.ids ? d.ids : d.rgb, !d.ids && d.nhwc, A.R.Wr);
+  return d;
 }
 
 // torch.max's index on the CPU: the lowest c among the maxima, NaN above everything and the first NaN kept
@@ -159,15 +95,6 @@ __device__ __forceinline__ void take(float v, uint32_t c, float& best, uint32_t&
     best = v;
     id = c;
   }
-}
-
-// one pixel: p at its plane 0
-template <typename T>
-__device__ __forceinline__ uint32_t argmax_px(const T* __restrict__ p, int64_t ss_c, int C) {
-  float best = widen(p[0]);
-  uint32_t id = 0;
-  for (int c = 1; c < C; ++c) take(widen(p[c * ss_c]), (uint32_t)c, best, id);
-  return id;
 }
 
 template <typename T>
@@ -184,72 +111,49 @@ __global__ __launch_bounds__(kBlock) void render_argmax_kernel(RenderArgs A) {
   }
   int64_t n;
   int r, chunk, head;
-  Dest d;
-  decode_row(A, n, r, chunk, d, head);
+  decode_row(A.R, n, r, chunk);
+  const Dest d = row_dest(A, n, r, head);
   const T* __restrict__ s0 = static_cast<const T*>(A.src) + n * A.ss_n + (int64_t)r * A.ss_h;
-  const int64_t sc = A.ss_c, Wr = A.Wr;
+  const int64_t sc = A.ss_c;
   const int C = A.C;
-  if (chunk == 0 && (int)threadIdx.x < head) {
-    const uint32_t id[1] = {argmax_px(s0 + threadIdx.x, sc, C)};
-    const uint32_t col[1] = {want_rgb ? pal[id[0]] : 0u};
-    emit<1>(d, threadIdx.x, id, col);
-  }
-  const int64_t x = head + ((int64_t)chunk * kBlock + threadIdx.x) * kPx;
-  if (x + kPx <= Wr) {
-    // every plane's row is 16-byte aligned at the head's end (then at every group: 16 elements are 32 or 64 bytes)
-    const bool vec = aligned16(s0 + head) && (C == 1 || ((uint64_t)sc * sizeof(T)) % 16 == 0);
-    constexpr int kAhead = sizeof(T) == 4 ? 2 : 4;  // planes in flight: 8 16-byte loads of a lane
+  // every plane's row is 16-byte aligned at the head's end (then at every group: 16 elements are 32 or 64 bytes)
+  const bool vec = aligned16(s0 + head) && (C == 1 || ((uint64_t)sc * sizeof(T)) % 16 == 0);
+  walk_row(head, chunk, A.R.Wr, [&](auto np, int64_t x) {
+    constexpr int NP = decltype(np)::value;
+    constexpr int kAhead = NP != kPx ? 1 : sizeof(T) == 4 ? 2 : 4;  // planes in flight: 8 16-byte loads of a lane
     const T* __restrict__ p = s0 + x;
-    float best[kPx];
-    uint32_t id[kPx];
+    float best[NP];
+    uint32_t id[NP];
     {
-      T v[kPx];
-      load16(p, vec, v);
+      T v[NP];
+      load_px(p, vec, v);
 #pragma unroll
-      for (int k = 0; k < kPx; ++k) {
+      for (int k = 0; k < NP; ++k) {
         best[k] = widen(v[k]);
         id[k] = 0;
       }
     }
     int c = 1;
     for (; c + kAhead <= C; c += kAhead) {
-      T v[kAhead][kPx];
+      T v[kAhead][NP];
 #pragma unroll
-      for (int u = 0; u < kAhead; ++u) load16(p + (c + u) * sc, vec, v[u]);
+      for (int u = 0; u < kAhead; ++u) load_px(p + (c + u) * sc, vec, v[u]);
 #pragma unroll
       for (int u = 0; u < kAhead; ++u)
 #pragma unroll
-        for (int k = 0; k < kPx; ++k) take(widen(v[u][k]), (uint32_t)(c + u), best[k], id[k]);
+        for (int k = 0; k < NP; ++k) take(widen(v[u][k]), (uint32_t)(c + u), best[k], id[k]);
     }
     for (; c < C; ++c) {
-      T v[kPx];
-      load16(p + c * sc, vec, v);
+      T v[NP];
+      load_px(p + c * sc, vec, v);
 #pragma unroll
-      for (int k = 0; k < kPx; ++k) take(widen(v[k]), (uint32_t)c, best[k], id[k]);
+      for (int k = 0; k < NP; ++k) take(widen(v[k]), (uint32_t)c, best[k], id[k]);
     }
-    uint32_t col[kPx];
+    uint32_t col[NP];
 #pragma unroll
-    for (int k = 0; k < kPx; ++k) col[k] = want_rgb ? pal[id[k]] : 0u;
-    emit<kPx>(d, x, id, col);
-  } else if (x < Wr) {
-    for (int64_t xs = x; xs < Wr; xs += 4) {
-      if (xs + 4 <= Wr) {
-        uint32_t id[4], col[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          id[k] = argmax_px(s0 + xs + k, sc, C);
-          col[k] = want_rgb ? pal[id[k]] : 0u;
-        }
-        emit<4>(d, xs, id, col);
-      } else {
-        for (int64_t k = xs; k < Wr; ++k) {
-          const uint32_t id[1] = {argmax_px(s0 + k, sc, C)};
-          const uint32_t col[1] = {want_rgb ? pal[id[0]] : 0u};
-          emit<1>(d, k, id, col);
-        }
-      }
-    }
-  }
+    for (int k = 0; k < NP; ++k) col[k] = want_rgb ? pal[id[k]] : 0u;
+    emit<NP>(d, x, id, col);
+  });
 }
 
 constexpr float kSqrt2 = 1.41421356237309504880f, kPi = 3.14159265358979323846f;
@@ -279,77 +183,37 @@ __global__ __launch_bounds__(kBlock) void render_flow_kernel(RenderArgs A) {
   }
   int64_t n;
   int r, chunk, head;
-  Dest d;
-  decode_row(A, n, r, chunk, d, head);
+  decode_row(A.R, n, r, chunk);
+  const Dest d = row_dest(A, n, r, head);
   const T* __restrict__ su = static_cast<const T*>(A.src) + n * A.ss_n + (int64_t)r * A.ss_h;
   const T* __restrict__ sv = su + A.ss_c;
-  const int64_t Wr = A.Wr;
   const int K = A.K, quant = A.quant;
   const float mul = A.mul;
-  const uint32_t none[1] = {0u};
-  if (chunk == 0 && (int)threadIdx.x < head) {
-    const uint32_t col[1] = {flow_colour(widen(su[threadIdx.x]), widen(sv[threadIdx.x]), wheel, K, mul, quant)};
-    emit<1>(d, threadIdx.x, none, col);
-  }
-  const int64_t x = head + ((int64_t)chunk * kBlock + threadIdx.x) * kPx;
-  if (x + kPx <= Wr) {
-    const bool vec = aligned16(su + head) && aligned16(sv + head);
-    T u[kPx], v[kPx];
-    load16(su + x, vec, u);
-    load16(sv + x, vec, v);
-    uint32_t id[kPx], col[kPx];
+  const bool vec = aligned16(su + head) && aligned16(sv + head);
+  walk_row(head, chunk, A.R.Wr, [&](auto np, int64_t x) {
+    constexpr int NP = decltype(np)::value;
+    T u[NP], v[NP];
+    load_px(su + x, vec, u);
+    load_px(sv + x, vec, v);
+    uint32_t id[NP], col[NP];
 #pragma unroll
-    for (int k = 0; k < kPx; ++k) {
+    for (int k = 0; k < NP; ++k) {
       id[k] = 0;
       col[k] = flow_colour(widen(u[k]), widen(v[k]), wheel, K, mul, quant);
     }
-    emit<kPx>(d, x, id, col);
-  } else if (x < Wr) {
-    for (int64_t xs = x; xs < Wr; xs += 4) {
-      if (xs + 4 <= Wr) {
-        uint32_t id[4], col[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          id[k] = 0;
-          col[k] = flow_colour(widen(su[xs + k]), widen(sv[xs + k]), wheel, K, mul, quant);
-        }
-        emit<4>(d, xs, id, col);
-      } else {
-        for (int64_t k = xs; k < Wr; ++k) {
-          const uint32_t col[1] = {flow_colour(widen(su[k]), widen(sv[k]), wheel, K, mul, quant)};
-          emit<1>(d, k, none, col);
-        }
-      }
-    }
-  }
+    emit<NP>(d, x, id, col);
+  });
 }
 
-// what the two entry points check alike; fills the row geometry of A.  false: refused (the message is set)
-bool render_geometry(const char* fn, RenderArgs& A, const void* src, int src_code, int64_t ss_n, int64_t ss_c,
-                     int64_t ss_h, int64_t N, int H, int W, unsigned& grid) {
-  const unsigned elem = src_code == WALDO_DTYPE_F32 ? 4u : 2u;
-  if ((uintptr_t)src % elem) {
-    set_error("%s: the source is not aligned to its %u-byte elements", fn, elem);
-    return false;
-  }
-  const bool dense_h = H == 1 || ss_h == W;  // (the destinations' frames are dense: H merges into the row)
+// the source and the row geometry, which the two entry points take alike.  false: refused (the message is set)
+bool render_rows(const char* fn, RenderArgs& A, const void* src, int src_code, int64_t ss_n, int64_t ss_c, int64_t ss_h,
+                 int64_t N, int H, int W, unsigned& grid) {
   A.src = src;
   A.ss_n = ss_n;
   A.ss_c = ss_c;
   A.ss_h = ss_h;
-  A.Hr = dense_h ? 1 : H;
-  A.Wr = dense_h ? (int64_t)H * W : W;
-  const int64_t chunks = (A.Wr + kBlock * kPx - 1) / (kBlock * kPx);
-  if (N > 2147483647 / ((int64_t)A.Hr * chunks)) {
-    set_error("%s: problem too large for one launch", fn);
-    return false;
-  }
-  A.chunks = (int)chunks;
-  grid = (unsigned)(N * A.Hr * chunks);
-  return true;
+  return check_aligned(fn, src, elem_bytes(src_code), "the source") && row_geometry(fn, N, H, W, ss_h, 1, false, A.R, grid);
 }
-
-bool known_dtype(int code) { return code == WALDO_DTYPE_F32 || code == WALDO_DTYPE_F16 || code == WALDO_DTYPE_BF16; }
 
 }  // namespace
 
@@ -361,19 +225,9 @@ extern "C" int waldo_render_argmax_fwd(const void* src, int src_code, int64_t ss
                                        const uint8_t* palette, uint8_t* ids, int64_t di_n, uint8_t* rgb, int64_t dr_n,
                                        int layout, int64_t N, int C, int H, int W, waldo_stream_t stream) {
   const char* fn = "waldo_render_argmax_fwd";
-  if (!known_dtype(src_code)) {
-    set_error("%s: unknown dtype %d of the source (WALDO_DTYPE_F32 / _F16 / _BF16; a packed clip holds its ids)", fn,
-              src_code);
+  if (!check_dtype(fn, src_code, false, "the source", "; a packed clip holds its ids") || !check_layout(fn, layout) ||
+      !check_shape(fn, N, "C", C, kMaxClasses, H, W))
     return WALDO_EINVAL;
-  }
-  if (layout != WALDO_BYTES_NCHW && layout != WALDO_BYTES_NHWC) {
-    set_error("%s: unknown layout %d (WALDO_BYTES_NCHW / WALDO_BYTES_NHWC)", fn, layout);
-    return WALDO_EINVAL;
-  }
-  if (N < 0 || C < 1 || C > kMaxClasses || H < 1 || W < 1 || H > 32768 || W > 32768) {
-    set_error("%s: bad shape N=%lld C=%d H=%d W=%d (1 <= H, W <= 32768, 1 <= C <= 256)", fn, (long long)N, C, H, W);
-    return WALDO_EINVAL;
-  }
   if (ss_n < 0 || ss_c < 0 || ss_h < 0 || di_n < 0 || dr_n < 0) {
     set_error("%s: negative stride (source n=%lld c=%lld h=%lld, ids n=%lld, rgb n=%lld)", fn, (long long)ss_n,
               (long long)ss_c, (long long)ss_h, (long long)di_n, (long long)dr_n);
@@ -386,7 +240,7 @@ extern "C" int waldo_render_argmax_fwd(const void* src, int src_code, int64_t ss
   }
   RenderArgs A{};
   unsigned grid;
-  if (!render_geometry(fn, A, src, src_code, ss_n, ss_c, ss_h, N, H, W, grid)) return WALDO_EINVAL;
+  if (!render_rows(fn, A, src, src_code, ss_n, ss_c, ss_h, N, H, W, grid)) return WALDO_EINVAL;
   A.palette = palette;
   A.ids = ids;
   A.di_n = di_n;
@@ -414,26 +268,13 @@ extern "C" int waldo_render_flow_fwd(const void* flow, int src_code, int64_t ss_
                                      const float* wheel, int K, float mul, uint8_t* rgb, int64_t dr_n, int layout,
                                      int quant, int64_t N, int H, int W, waldo_stream_t stream) {
   const char* fn = "waldo_render_flow_fwd";
-  if (!known_dtype(src_code)) {
-    set_error("%s: unknown dtype %d of the flow (WALDO_DTYPE_F32 / _F16 / _BF16)", fn, src_code);
+  if (!check_dtype(fn, src_code, false, "the flow", "") || !check_layout(fn, layout) || !check_quant(fn, quant))
     return WALDO_EINVAL;
-  }
-  if (layout != WALDO_BYTES_NCHW && layout != WALDO_BYTES_NHWC) {
-    set_error("%s: unknown layout %d (WALDO_BYTES_NCHW / WALDO_BYTES_NHWC)", fn, layout);
-    return WALDO_EINVAL;
-  }
-  if (quant != WALDO_METRICS_TRUNC && quant != WALDO_METRICS_ROUND) {
-    set_error("%s: unknown quantisation %d (WALDO_METRICS_TRUNC / WALDO_METRICS_ROUND)", fn, quant);
-    return WALDO_EINVAL;
-  }
   if (!(mul >= -3.4028234664e38f && mul <= 3.4028234664e38f)) {
     set_error("%s: bad multiplier mul=%g (must be finite)", fn, (double)mul);
     return WALDO_EINVAL;
   }
-  if (N < 0 || K < 1 || K > kMaxWheel || H < 1 || W < 1 || H > 32768 || W > 32768) {
-    set_error("%s: bad shape N=%lld K=%d H=%d W=%d (1 <= H, W <= 32768, 1 <= K <= 4096)", fn, (long long)N, K, H, W);
-    return WALDO_EINVAL;
-  }
+  if (!check_shape(fn, N, "K", K, kMaxWheel, H, W)) return WALDO_EINVAL;
   if (ss_n < 0 || ss_c < 0 || ss_h < 0 || dr_n < 0) {
     set_error("%s: negative stride (flow n=%lld c=%lld h=%lld, rgb n=%lld)", fn, (long long)ss_n, (long long)ss_c,
               (long long)ss_h, (long long)dr_n);
@@ -446,7 +287,7 @@ extern "C" int waldo_render_flow_fwd(const void* flow, int src_code, int64_t ss_
   }
   RenderArgs A{};
   unsigned grid;
-  if (!render_geometry(fn, A, flow, src_code, ss_n, ss_c, ss_h, N, H, W, grid)) return WALDO_EINVAL;
+  if (!render_rows(fn, A, flow, src_code, ss_n, ss_c, ss_h, N, H, W, grid)) return WALDO_EINVAL;
   A.wheel = wheel;
   A.K = K;
   A.mul = mul;

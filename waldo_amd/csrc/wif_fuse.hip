@@ -11,6 +11,7 @@
 // the fp32 one rounded to nearest-even.
 #include <type_traits>
 
+#include "byte_rows.hip.h"
 #include "quantize.hip.h"
 #include "waldo_common.hip.h"
 
@@ -174,10 +175,9 @@ __global__ __launch_bounds__(kBlock) void wif_fuse_bytes_kernel(const VT* __rest
   if (nhwc) {
     uint8_t* d = out + (n * HW + p) * 3;
     if (valid == 4 && ((uintptr_t)d & 3u) == 0) {
-      uint32_t* w = reinterpret_cast<uint32_t*>(d);
-      w[0] = q[0][0] | (q[1][0] << 8) | (q[2][0] << 16) | (q[0][1] << 24);
-      w[1] = q[1][1] | (q[2][1] << 8) | (q[0][2] << 16) | (q[1][2] << 24);
-      w[2] = q[2][2] | (q[0][3] << 8) | (q[1][3] << 16) | (q[2][3] << 24);
+      uint32_t w[3];
+      pack_interleaved<4>(w, [&](int c, int j) { return q[c][j]; });
+      store_aligned(d, w);
     } else {
       for (int j = 0; j < valid; ++j)
 #pragma unroll
@@ -188,7 +188,9 @@ __global__ __launch_bounds__(kBlock) void wif_fuse_bytes_kernel(const VT* __rest
     for (int c = 0; c < 3; ++c) {
       uint8_t* d = out + (n * 3 + c) * HW + p;
       if (valid == 4 && ((uintptr_t)d & 3u) == 0) {
-        *reinterpret_cast<uint32_t*>(d) = q[c][0] | (q[c][1] << 8) | (q[c][2] << 16) | (q[c][3] << 24);
+        uint32_t w[1];
+        pack_planar<4>(w, [&](int j) { return q[c][j]; });
+        store_aligned(d, w);
       } else {
         for (int j = 0; j < valid; ++j) d[j] = (uint8_t)q[c][j];
       }
@@ -252,17 +254,7 @@ static int wif_bytes_launch(const char* fn, const void* vid, const void* net, ui
                             waldo_stream_t stream) {
   int rc = check_wif(fn, N, Tc, C, Co, HW);
   if (rc) return rc;
-  if ((quant != WALDO_METRICS_TRUNC && quant != WALDO_METRICS_ROUND) ||
-      (layout != WALDO_BYTES_NCHW && layout != WALDO_BYTES_NHWC)) {
-    set_error("%s: unknown quantisation %d (WALDO_METRICS_TRUNC / _ROUND) or layout %d (WALDO_BYTES_NCHW / _NHWC)", fn,
-              quant, layout);
-    return WALDO_EINVAL;
-  }
-  if (!(range > 0.0f) || !(range <= 3.4028234664e38f) || !(lo >= -3.4028234664e38f && lo <= 3.4028234664e38f)) {
-    set_error("%s: bad span lo=%g range=%g (range = hi - lo must be positive and finite)", fn, (double)lo,
-              (double)range);
-    return WALDO_EINVAL;
-  }
+  if (!check_quant(fn, quant) || !check_layout(fn, layout) || !check_span(fn, lo, range)) return WALDO_EINVAL;
   if (N == 0) return WALDO_OK;
   if (!vid || !net || !out) {
     set_error("%s: null pointer", fn);

@@ -1349,6 +1349,45 @@ def _dense_tail(t, k):
     return True
 
 
+def _flat_frames(d):
+    """(..., C, H, W) as (N, C, H, W) with W unit-stride: a view where the strides allow it, one copy otherwise."""
+    c, h, w = d.shape[-3:]
+    if d.stride(-1) != 1 and w > 1:
+        d = d.contiguous()
+    return d.reshape(-1, c, h, w)
+
+
+def _check_out(fn, out, lead, frame, name="out"):
+    """``out=`` of a byte output, where given: a uint8 tensor of the result's shape."""
+    if out is None:
+        return
+    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (*lead, *frame):
+        raise ValueError(f"{fn}: {name} must be a uint8 tensor of shape {(*lead, *frame)}, got "
+                         f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
+
+
+def _dest(fn, out, n, frame, device, name="out"):
+    """The (n, *frame) destination of a byte output: a new tensor, or ``out`` (past ``_check_out``) viewed so -- dense
+    frames, leading dimensions flattened by stride, any alignment."""
+    if out is None:
+        return torch.empty((n, *frame), dtype=torch.uint8, device=device)
+    if out.device != device:
+        raise ValueError(f"{fn}: the input on {device}, {name} on {out.device}")
+    try:
+        o = out.view(n, *frame)
+    except RuntimeError:
+        o = None
+    if o is None or not _dense_tail(o, len(frame)):
+        raise ValueError(f"{fn}: {name} must hold dense frames whose leading dimensions flatten by stride "
+                         f"(strides {tuple(out.stride())})")
+    return o
+
+
+def _frame_stride(o, frame_bytes):
+    """The stride between the frames of ``o``; of one frame alone, its size (the stride of a dimension of 1 is free)."""
+    return o.stride(0) if o.shape[0] > 1 else frame_bytes
+
+
 def frames_to_bytes(x, span=(-1.0, 1.0), quantize="trunc", layout="nchw", out=None):
     """Frames as bytes (``waldo_frames_to_bytes_fwd``): with ``u = clamp((x - lo) / (hi - lo), 0, 1)`` in fp32,
     ``"trunc"``: ``uint8(trunc(u * 255))``, what the reference's ``dump_video`` writes (tools/utils.py:246-264);
@@ -1379,31 +1418,16 @@ def frames_to_bytes(x, span=(-1.0, 1.0), quantize="trunc", layout="nchw", out=No
         lead, (c, h, w) = tuple(d.shape[:-3]), d.shape[-3:]
         if min(c, h, w) < 1:
             raise ValueError(f"{fn}: empty frames {tuple(x.shape)}")
-        if d.stride(-1) != 1 and w > 1:
-            d = d.contiguous()
-        d = d.reshape(-1, c, h, w)  # (a view where the strides allow it)
+        d = _flat_frames(d)
         code, strides, table = _DTYPE_CODE[d.dtype], (d.stride(0), d.stride(1), d.stride(2)), None
     if lay and c != 3:
         raise ValueError(f"{fn}: layout 'nhwc' takes 3 channels, got {c}")
     n = d.shape[0]
     frame = (h, w, 3) if lay else (c, h, w)
-    if out is None:
-        o = torch.empty((n, *frame), dtype=torch.uint8, device=d.device)
-    else:
-        if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (*lead, *frame):
-            raise ValueError(f"{fn}: out must be a uint8 tensor of shape {(*lead, *frame)}, got "
-                             f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
-        if out.device != d.device:
-            raise ValueError(f"{fn}: x on {d.device}, out on {out.device}")
-        try:
-            o = out.view(n, *frame)
-        except RuntimeError:
-            o = None
-        if o is None or not _dense_tail(o, 3):
-            raise ValueError(f"{fn}: out must hold dense frames whose leading dimensions flatten by stride "
-                             f"(strides {tuple(out.stride())})")
-    _lib.launch("waldo_frames_to_bytes_fwd", d.device, d, code, *strides, table, o, o.stride(0) if n > 1 else c * h * w,
-                lay, n, c, h, w, lo, rng, quant)
+    _check_out(fn, out, lead, frame)
+    o = _dest(fn, out, n, frame, d.device)
+    _lib.launch("waldo_frames_to_bytes_fwd", d.device, d, code, *strides, table, o, _frame_stride(o, c * h * w), lay, n,
+                c, h, w, lo, rng, quant)
     return out if out is not None else o.view(*lead, *frame)
 
 

@@ -17,12 +17,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from .functional import BYTE_LAYOUT as LAYOUT
+from .functional import BYTE_QUANTIZE as QUANTIZE
+from .functional import _DTYPE_CODE, _byte_args, _check_out, _dest, _flat_frames, _frame_stride
 
-QUANTIZE = {"trunc": 0, "round": 1}  # WALDO_METRICS_TRUNC / _ROUND
-LAYOUT = {"nchw": 0, "nhwc": 1}  # WALDO_BYTES_NCHW / _NHWC
 MAX_CLASSES = 256  # an id fits a byte
 MAX_WHEEL = 4096
-_DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 # --------------------------------------------------------------------------------------
 # Colour tables.  matplotlib's segment data of the two maps: per channel, rows (x, y below x, y above x); a map with N
@@ -143,11 +143,8 @@ def _on_device(fn, table, device, dtype, what):
 
 
 def _codes(fn, layout, quantize="trunc"):
-    if layout not in LAYOUT:
-        raise ValueError(f"{fn}: layout must be one of {tuple(LAYOUT)}, got {layout!r}")
-    if quantize not in QUANTIZE:
-        raise ValueError(f"{fn}: quantize must be one of {tuple(QUANTIZE)}, got {quantize!r}")
-    return LAYOUT[layout], QUANTIZE[quantize]
+    _, _, quant, lay = _byte_args(fn, (0.0, 1.0), quantize, layout)
+    return lay, quant
 
 
 def _source(fn, x, what, channels=None):
@@ -165,55 +162,9 @@ def _source(fn, x, what, channels=None):
     return x.detach(), tuple(x.shape[:-3]), (c, h, w)
 
 
-def _flat(d):
-    """(N, C, H, W) with W unit-stride: a view where the strides allow it, one copy otherwise."""
-    c, h, w = d.shape[-3:]
-    if d.stride(-1) != 1 and w > 1:
-        d = d.contiguous()
-    return d.reshape(-1, c, h, w)
-
-
-def _dense_tail(t, k):
-    expect = 1
-    for i in range(t.ndim - 1, t.ndim - 1 - k, -1):
-        if t.shape[i] != 1 and t.stride(i) != expect:
-            return False
-        expect *= t.shape[i]
-    return True
-
-
-def _check_out(fn, out, lead, frame, name="out"):
-    if out is None:
-        return
-    if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (*lead, *frame):
-        raise ValueError(f"{fn}: {name} must be a uint8 tensor of shape {(*lead, *frame)}, got "
-                         f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
-
-
-def _dest(fn, out, n, frame, device, name="out"):
-    """The (n, *frame) destination: a new tensor, or ``out`` viewed so -- dense frames, leading dimensions flattened by
-    stride, any alignment (the rules of ``functional.frames_to_bytes``)."""
-    if out is None:
-        return torch.empty((n, *frame), dtype=torch.uint8, device=device)
-    if out.device != device:
-        raise ValueError(f"{fn}: the input on {device}, {name} on {out.device}")
-    try:
-        o = out.view(n, *frame)
-    except RuntimeError:
-        o = None
-    if o is None or not _dense_tail(o, len(frame)):
-        raise ValueError(f"{fn}: {name} must hold dense frames whose leading dimensions flatten by stride "
-                         f"(strides {tuple(out.stride())})")
-    return o
-
-
 def _need_gpu(fn, x, what):
     if not x.is_cuda:
         raise _lib.WaldoHipError(f"{fn}: {what} must be on the GPU (cuda device); there is no CPU fallback")
-
-
-def _frame_stride(o, frame_bytes):
-    return o.stride(0) if o.shape[0] > 1 else frame_bytes
 
 
 def _argmax(fn, x, palette, layout, out, want_ids, ids_out):
@@ -228,7 +179,7 @@ def _argmax(fn, x, palette, layout, out, want_ids, ids_out):
         _check_out(fn, out, lead, frame)
     _check_out(fn, ids_out, lead, (h, w), "ids")
     _need_gpu(fn, d, "x")
-    d = _flat(d)
+    d = _flat_frames(d)
     n = d.shape[0]
     rgb = _dest(fn, out, n, frame, d.device) if want_rgb else None
     ids = _dest(fn, ids_out, n, (h, w), d.device, "ids") if want_ids else None
@@ -282,7 +233,7 @@ def render_flow(flow, mul=10.0, wheel=None, quantize="trunc", layout="nchw", out
     frame = (h, w, 3) if lay else (3, h, w)
     _check_out(fn, out, lead, frame)
     _need_gpu(fn, d, "flow")
-    d = _flat(d)
+    d = _flat_frames(d)
     n = d.shape[0]
     o = _dest(fn, out, n, frame, d.device)
     _lib.launch("waldo_render_flow_fwd", d.device, d, _DTYPE_CODE[d.dtype], d.stride(0), d.stride(1), d.stride(2), tab,
