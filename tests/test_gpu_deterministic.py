@@ -606,3 +606,153 @@ def test_default_mode_calls_no_det_entry_point(dev, calls):
     assert not det_names(calls), det_names(calls)
     for name in ("waldo_flow_ctx_warp_bwd", "waldo_flow_ctx_alpha_bwd", "waldo_grid_sample2d_ex_bwd", "waldo_tps_grid_bwd"):
         assert name in calls, name
+
+
+# ------------------------------------------------------------------------------------------------ 10. one body, two modes
+# The atomic and the deterministic entry point of an op share one host body: the branches of those bodies that no test
+# above reaches, each on both paths, against the oracle in float64 (autograd on the CPU, from the same fp32 inputs).
+def _oracle64(fn, inputs, wrt, weights):
+    """Gradients of sum_k (fn(*inputs)[k] * weights[k]).sum() with respect to inputs[i], i in wrt, in float64."""
+    xs = [x.double() if torch.is_tensor(x) and x.is_floating_point() else x for x in inputs]
+    for i in wrt:
+        xs[i].requires_grad_()
+    outs = fn(*xs)
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    sum((o * w.double()).sum() for o, w in zip(outs, weights)).backward()
+    grads = [xs[i].grad for i in wrt]
+    assert all(torch.isfinite(g).all() and g.abs().sum() > 0 for g in grads), "the oracle's gradients must say something"
+    return grads
+
+
+def _both_paths(what, run, want, calls, names):
+    """``run() -> gradients`` on the atomic and on the deterministic path, each against ``want``; the deterministic one
+    gives the same bits twice."""
+    from waldo_amd import functional as WF
+    for det in (False, True):
+        with WF.deterministic(det):
+            got = run()
+            for i, (g, w) in enumerate(zip(got, want)):
+                close(g, w, rel=True, what=f"{what}, {'deterministic' if det else 'atomic'}: gradient {i}")
+            if det:
+                for i, (a, b) in enumerate(zip(run(), got)):
+                    assert torch.equal(a, b), f"{what}: gradient {i} differs between two deterministic calls"
+    for name in names:
+        assert name in calls and name + "_det" in calls, name
+
+
+def _flow_ctx_alpha_spelled_out(alpha_lr, inp, dist, occ, tw, s):
+    """lvd.py:731-766 with framework ops (tests/test_gpu_warper.py::test_flow_ctx_alpha_skips_absent_layers_exactly's
+    statement; ``dist`` None: no layout filter)."""
+    import torch.nn.functional as F
+    b = inp.shape[0]
+    n, nl, h, w = alpha_lr.shape
+    a = F.interpolate(alpha_lr, scale_factor=s, mode="bilinear") if s > 1 else alpha_lr
+    if dist is not None:
+        ncls = dist.shape[2]
+        prob = inp[:, :tw, 3:].softmax(dim=2).reshape(n, 1, ncls, h * s, w * s)
+        d = dist.view(b, 1, nl - 1, ncls, 1, 1).expand(-1, tw, -1, -1, -1, -1).reshape(n, nl - 1, ncls, 1, 1)
+        a = torch.cat([a[:, :1], a[:, 1:] * (1 - (d - prob).abs().sum(dim=2) / 2)], dim=1)
+    oc = occ[:, :tw].reshape(n, nl, nl)
+    prod = torch.ones_like(a)
+    for i in range(nl):
+        prod = prod * (1 - a[:, i:i + 1] * oc[:, i].view(n, nl, 1, 1))
+    return a * prod, a * prod * 2 - 1
+
+
+def _short_window_clip(s, seed):
+    """One clip of T = 3 frames of which the window holds Tw = 2; L = 3 layers; 4 x 6 pixels upsampled x s."""
+    b, t, tw, nl, h, w, ncls = 1, 3, 2, 3, 4, 6, 5
+    hd, wd = h * s, w * s
+    g = torch.Generator().manual_seed(seed)
+    alpha_lr = torch.rand(b * tw, nl, h, w, generator=g)
+    inp = torch.randn(b, t, 3 + ncls, hd, wd, generator=g) * 2
+    dist = torch.rand(b, nl - 1, ncls, generator=g).softmax(dim=2)
+    occ = torch.rand(b, t, nl, nl, generator=g) * 0.5
+    return (b, t, tw, nl, h, w, hd, wd), g, alpha_lr, inp, dist, occ
+
+
+def test_one_body_grid_sample_gradient_of_the_grid_alone(dev, calls):
+    from waldo_amd import functional as WF
+    g = torch.Generator().manual_seed(61)
+    x = torch.randn(3, 2, 5, 7, generator=g)
+    grid = torch.rand(3, 6, 5, 2, generator=g) * 2.4 - 1.2
+    wgt = torch.randn(3, 2, 6, 5, generator=g)
+    want = _oracle64(lambda a, b: O.grid_sample_delta(a, b, 0.5), (x, grid), (1,), (wgt,))
+
+    def run():
+        gr = grid.to(dev).requires_grad_()
+        (WF.grid_sample(x.to(dev), gr, delta=0.5) * wgt.to(dev)).sum().backward()
+        return [gr.grad]
+
+    _both_paths("grid_sample, grad_grid alone", run, want, calls, ("waldo_grid_sample2d_bwd",))
+
+
+def test_one_body_occ_composite_last_matrix_read_by_one_map(dev, calls):
+    from waldo_amd import functional as WF
+    g = torch.Generator().manual_seed(62)
+    alpha = torch.rand(3, 3, 300, generator=g)       # M = 3 maps of two tiles, the second partial
+    occ = torch.rand(2, 3, 3, generator=g)           # occ_div = 2: matrix 1 is read by map 2 alone
+    wgt = torch.randn(3, 3, 300, generator=g)
+    want = _oracle64(lambda a, o: O.occlusion_product(a.unsqueeze(-1), o.repeat_interleave(2, dim=0)[:3]).squeeze(-1),
+                     (alpha, occ), (0, 1), (wgt,))
+
+    def run():
+        a, o = alpha.to(dev).requires_grad_(), occ.to(dev).requires_grad_()
+        (WF.occ_composite(a, o, occ_div=2) * wgt.to(dev)).sum().backward()
+        return [a.grad, o.grad]
+
+    _both_paths("occ_composite, occ_div 2 of 3 maps", run, want, calls, ("waldo_occ_composite_bwd",))
+
+
+@pytest.mark.parametrize("s", [1, 2])
+@pytest.mark.parametrize("filtered", [False, True])
+def test_one_body_flow_ctx_alpha_window_shorter_than_the_clip(dev, calls, s, filtered):
+    from waldo_amd import functional as WF
+    (b, t, tw, nl, h, w, hd, wd), g, alpha_lr, inp, dist, occ = _short_window_clip(s, 63)
+    w1, w2 = torch.randn(b * tw, nl, hd, wd, generator=g), torch.randn(b * tw, nl, hd, wd, generator=g)
+    if filtered:
+        want = _oracle64(lambda a, d, o: _flow_ctx_alpha_spelled_out(a, inp.double(), d, o, tw, s), (alpha_lr, dist, occ),
+                         (0, 1, 2), (w1, w2))
+    else:
+        want = _oracle64(lambda a, o: _flow_ctx_alpha_spelled_out(a, inp.double(), None, o, tw, s), (alpha_lr, occ), (0, 1),
+                         (w1, w2))
+    assert want[-1][:, tw:].abs().sum() == 0 and want[-1][:, :tw].abs().sum() > 0
+
+    def run():
+        leaves = [x.to(dev).requires_grad_() for x in ((alpha_lr, dist, occ) if filtered else (alpha_lr, occ))]
+        a01, alpha = WF.flow_ctx_alpha(leaves[0], inp.to(dev), leaves[1] if filtered else None, leaves[-1], tw, 3, s)
+        ((a01 * w1.to(dev)).sum() + (alpha * w2.to(dev)).sum()).backward()
+        assert torch.equal(leaves[-1].grad[:, tw:], torch.zeros_like(leaves[-1].grad[:, tw:])), \
+            "grad_occ: a frame outside the window receives nothing"
+        return [x.grad for x in leaves]
+
+    _both_paths(f"flow_ctx_alpha x{s}, Tw < T, {'layout filter' if filtered else 'no filter'}", run, want, calls,
+                ("waldo_flow_ctx_alpha_bwd",))
+
+
+@pytest.mark.parametrize("s", [1, 2])
+@pytest.mark.parametrize("leaf", ["a01", "occ"])
+def test_one_body_flow_ctx_warp_one_gradient_required(dev, calls, s, leaf):
+    import test_gpu_warper as tw_
+    from waldo_amd import functional as WF
+    (b, t, tw, nl, h, w, hd, wd), g, _, _, _, occ = _short_window_clip(s, 64)
+    tc, tp = 2, 2
+    m = b * tc * tp
+    flow_lr = 0.3 * torch.randn(m, nl, 2, h, w, generator=g)
+    isobj = (torch.rand(m, nl - 1, h, w, generator=g) > 0.3).float()
+    a01 = torch.rand(b * tw, nl, hd, wd, generator=g)
+    ctx_ts, pred_ts = torch.tensor([[[0, 1], [1, 0]]]), torch.tensor([2, 0])
+    ws = (torch.randn(m, 2, hd, wd, generator=g), torch.randn(m, nl, hd, wd, generator=g),
+          torch.randn(m, hd, wd, generator=g))
+    args = (flow_lr, isobj, a01, ctx_ts, pred_ts, occ, tw, s)
+    at = 2 if leaf == "a01" else 5
+    want = _oracle64(tw_._flow_ctx_warp_spelled_out, args, (at,), ws)
+
+    def run():
+        xs = [x.to(dev) if torch.is_tensor(x) else x for x in args]
+        xs[at] = xs[at].requires_grad_()
+        outs = WF.flow_ctx_warp(*xs)[:3]
+        sum((o * wk.to(dev)).sum() for o, wk in zip(outs, ws)).backward()
+        return [xs[at].grad]
+
+    _both_paths(f"flow_ctx_warp x{s}, only {leaf} requires a gradient", run, want, calls, ("waldo_flow_ctx_warp_bwd",))

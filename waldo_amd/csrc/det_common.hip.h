@@ -18,6 +18,9 @@
 //           The scale is a power of two that follows the maximum: doubling the incoming gradient doubles the result
 //           exactly.  A plane whose maximum is infinite or NaN comes back all NaN (float -> integer is undefined there).
 #pragma once
+#include <cstdarg>
+#include <cstdio>
+
 #include "waldo_common.hip.h"
 
 namespace waldo {
@@ -92,13 +95,66 @@ static void slab_reduce(const float* slab, float* out, int64_t D, int nparts, in
                      egroups, map);
 }
 
+// ---- workspaces (host) ---------------------------------------------------------------------------------------------
+// Segments of a workspace in the order given, each rounded up to 256 bytes.  An op builds ONE of these from its shapes;
+// its *_workspace_bytes query returns total() and its entry point takes its pointers from at().
+template <int N>
+struct Carved {
+  int64_t off[N + 1];  // off[N]: the total
+  int64_t total() const { return off[N]; }
+  template <typename T>
+  T* at(void* workspace, int i) const { return reinterpret_cast<T*>(static_cast<char*>(workspace) + off[i]); }
+};
+
+template <typename... S>
+Carved<(int)sizeof...(S)> carve(S... bytes) {
+  constexpr int N = (int)sizeof...(S);
+  const int64_t size[N] = {(int64_t)bytes...};
+  Carved<N> c;
+  c.off[0] = 0;
+  for (int i = 0; i < N; ++i) c.off[i + 1] = c.off[i] + round256(size[i]);
+  return c;
+}
+
+// the refusal of a missing or short workspace (a null one counts as 0 bytes)
+inline int check_workspace(const char* fn, const void* workspace, int64_t workspace_bytes, int64_t need,
+                           const char* note = "") {
+  if (workspace != nullptr && workspace_bytes >= need) return WALDO_OK;
+  set_error("%s: workspace of %lld bytes given, %lld needed%s", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
+            (long long)need, note);
+  return WALDO_EINVAL;
+}
+
 // ---- splats ------------------------------------------------------------------------------------------------------
 constexpr int kSplatMaxLog = 32;  // a texel may receive at most 2^32 contributions
 
-inline int splat_count_log(int64_t count) {  // ceil(log2(count)), count >= 1
+// clog of the header comment: ceil(log2(count)) for the largest number of contributions one texel can receive;
+// -1: more than 2^32, no deterministic sum
+inline int splat_clog(int64_t count) {
   int c = 0;
   while (c < 63 && ((int64_t)1 << c) < count) ++c;
-  return c;
+  return c <= kSplatMaxLog ? c : -1;
+}
+
+// the refusal that goes with splat_clog() < 0; `grad`: the gradient's name, then the caller's sizes (printf style)
+__attribute__((format(printf, 3, 4))) inline int splat_refuse(const char* fn, const char* grad, const char* sizes, ...) {
+  char text[160];
+  va_list ap;
+  va_start(ap, sizes);
+  vsnprintf(text, sizeof(text), sizes, ap);
+  va_end(ap);
+  set_error("%s: a texel of %s may receive more than 2^%d contributions (%s): no deterministic sum for this shape", fn,
+            grad, kSplatMaxLog, text);
+  return WALDO_EINVAL;
+}
+
+// grids of the maximum pass (the caller's workgroups) and of the conversion (one thread per texel of the gradient)
+inline int check_splat_launches(const char* fn, int64_t max_blocks, int64_t texels) {
+  if (max_blocks > 2147483647 || (texels + kBlock - 1) / kBlock > 2147483647) {
+    set_error("%s: problem too large for one launch", fn);
+    return WALDO_EINVAL;
+  }
+  return WALDO_OK;
 }
 
 __device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
@@ -136,6 +192,32 @@ static __global__ __launch_bounds__(kBlock) void splat_convert_kernel(const unsi
   if (mb >= kInfBits) v = __uint_as_float(0x7fc00000u);
   else if (mb != 0u) v = ldexpf((float)(long long)acc[i], -splat_shift(mb, clog));
   out[i] = v;
+}
+
+// The passes of one splat, in stream order: zero fill, the caller's maximum pass, the caller's splat pass, and the
+// conversion that overwrites out (planes x plane_elems).  Segments i (the 64-bit sums, 8 bytes per texel) and i + 1 (the
+// maxima, 4 bytes per plane) of the op's workspace are adjacent: one fill zeroes both.  `live` false: nothing
+// contributes (no source maps), out = 0.  An op whose stream order puts launches of its own between these passes hands
+// them over as `before_max` (after the fill) and `after_splat` (before the conversion); they run when `live`, too.
+struct NoLaunch {
+  void operator()() const {}
+};
+template <int N, typename MaxPass, typename SplatPass, typename Before = NoLaunch, typename After = NoLaunch>
+void splat_passes(const Carved<N>& lo, void* workspace, int i, float* out, int64_t planes, int64_t plane_elems, int clog,
+                  bool live, hipStream_t st, MaxPass&& max_pass, SplatPass&& splat_pass, Before&& before_max = Before{},
+                  After&& after_splat = After{}) {
+  unsigned long long* acc = lo.template at<unsigned long long>(workspace, i);
+  unsigned* plane_max = lo.template at<unsigned>(workspace, i + 1);
+  fill_words(acc, 0u, (size_t)(lo.off[i + 2] - lo.off[i]), st);
+  if (live) {
+    before_max();
+    max_pass(plane_max);
+    splat_pass(acc, plane_max);
+    after_splat();
+  }
+  const int64_t total = planes * plane_elems;
+  hipLaunchKernelGGL(splat_convert_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, acc,
+                     plane_max, out, plane_elems, total, clog);
 }
 
 }  // namespace waldo

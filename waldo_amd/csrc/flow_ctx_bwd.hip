@@ -602,44 +602,184 @@ static int check_bwd_shape(const char* fn, int64_t N, int L, int H, int W, int s
   return WALDO_OK;
 }
 
+// ---- flow_ctx_alpha_bwd and flow_ctx_warp_bwd: one body each for the atomic and the deterministic entry point.
+// det (a template flag: it picks the pixel kernel's DET instance, and the instances keep their order in the object file):
+// the *_det entry point (det_common.hip.h) -- ONE sized workspace that also holds what the atomic form keeps in its
+// unsized `workspace` (the HD gradient before the upsample's transpose, scale > 1: first in both); grad_dist / grad_occ /
+// grad_a01 are OVERWRITTEN.  The atomic form's workspace arrives with no size and is not checked against one.
+static int pixel_tiles(int H, int W, int scale) { return (int)(((int64_t)H * scale * W * scale + kBlock - 1) / kBlock); }
+static int pixel_groups(int tiles, int tpb) { return (tiles + tpb - 1) / tpb; }  // workgroups per unit at tpb tiles each
+static int64_t det_slab_rows(int64_t N, int H, int W, int scale) {  // one per workgroup of a DET pixel kernel
+  return N * pixel_groups(pixel_tiles(H, W, scale), kDetTilesPerBlock);
+}
+
+// HD gradient (scale > 1) | grad_occ slab | grad_dist slab
+static Carved<3> alpha_det_workspace(int64_t N, int L, int Nl, int H, int W, int scale) {
+  const int64_t HWd = (int64_t)H * scale * W * scale, rows = det_slab_rows(N, H, W, scale);
+  return carve(scale > 1 ? N * L * HWd * 4 : 0, rows * L * L * 4, rows * (int64_t)(L - 1) * Nl * 4);
+}
+
+// HD gradient (scale > 1) | vals | sums of grad_a01 | maxima of its planes | grad_occ slab
+static Carved<5> warp_det_workspace(int64_t B, int Tw, int Tc, int Tp, int L, int H, int W, int scale) {
+  const int64_t N = B * Tc * Tp, HWd = (int64_t)H * scale * W * scale;
+  return carve(scale > 1 ? N * L * 2 * HWd * 4 : 0, N * L * HWd * 4, B * Tw * L * HWd * 8, B * Tw * L * 4,
+               det_slab_rows(N, H, W, scale) * L * L * 4);
+}
+
+static void upsample_bwd(const float* g_hd, float* g_lr, int64_t P, int H, int W, int scale, hipStream_t st) {
+  hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g_hd,
+                     g_lr, P, H, W, scale);
+}
+
+template <bool det>
+static int flow_ctx_alpha_bwd(const char* fn, const float* alpha_lr, const float* input, const float* dist,
+                              const float* occ, const float* grad_a01, const float* grad_alpha_out,
+                              float* grad_alpha_lr, float* grad_dist, float* grad_occ, void* workspace,
+                              int64_t workspace_bytes, int B, int T, int Tw, int L, int Nl, int C, int chan_off, int H,
+                              int W, int scale, waldo_stream_t stream) {
+  const int64_t N = (int64_t)B * Tw;
+  if (int rc = check_bwd_shape(fn, N, L, H, W, scale)) return rc;
+  if (B < 0 || T < 1 || Tw < 1 || Tw > T ||
+      (dist != nullptr && (Nl < 1 || Nl > kMaxCls || chan_off < 0 || chan_off + Nl > C))) {
+    set_error("%s: bad frame window Tw=%d of T=%d or class channels", fn, Tw, T);
+    return WALDO_EINVAL;
+  }
+  if (N == 0) return WALDO_OK;
+  Carved<3> lo{};
+  if (det) {
+    lo = alpha_det_workspace(N, L, dist != nullptr ? Nl : 0, H, W, scale);
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, lo.total())) return rc;
+  }
+  if (!alpha_lr || !occ || (!grad_a01 && !grad_alpha_out) || !grad_alpha_lr || (dist != nullptr && !input) ||
+      (!det && scale > 1 && !workspace)) {
+    set_error("%s: null pointer (one of grad_a01 / grad_alpha_out%s)", fn,
+              det ? "" : "; scale > 1 needs the (B*Tw, L, Hd, Wd) workspace");
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = pixel_tiles(H, W, scale);
+  const int tpb = det ? kDetTilesPerBlock : acc_tiles(N, tiles), groups = pixel_groups(tiles, tpb);
+  float* up = static_cast<float*>(workspace);
+  float* gup = scale > 1 ? up : grad_alpha_lr;
+  // the pixel kernel's two small tables: the gradients themselves (atomics), or their slabs where they are wanted
+  float *table_o = grad_occ, *table_d = grad_dist;
+  if (det) {
+    table_o = grad_occ != nullptr ? lo.at<float>(workspace, 1) : nullptr;
+    table_d = dist != nullptr && grad_dist != nullptr ? lo.at<float>(workspace, 2) : nullptr;
+  }
+  // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
+  with_padded_layers(L, [&](auto lp) {
+    auto launch = [&](auto ncp) {
+      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<decltype(lp)::value, decltype(ncp)::value, det>),
+                         dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, alpha_lr, input, dist, occ, grad_a01,
+                         grad_alpha_out, gup, table_d, table_o, T, Tw, L, Nl, C, chan_off, H, W, scale, tiles, tpb, groups);
+    };
+    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
+    else launch(std::integral_constant<int, kMaxCls>{});
+  });
+  if constexpr (det) {
+    if (table_o != nullptr) {
+      // frames Tw .. T - 1 of a batch element receive nothing
+      if (Tw < T) fill_words(grad_occ, 0u, sizeof(float) * (size_t)B * T * L * L, st);
+      slab_reduce(table_o, grad_occ, N, groups, L * L, SlabPlain{N * groups, Tw, T}, st);
+    }
+    if (table_d != nullptr)  // a batch element's Tw * groups workgroups: consecutive rows
+      slab_reduce(table_d, grad_dist, B, Tw * groups, (L - 1) * Nl, SlabPlain{N * groups, B, B}, st);
+  }
+  if (scale > 1) upsample_bwd(up, grad_alpha_lr, N * L, H, W, scale, st);
+  return launch_status(fn);
+}
+
+template <bool det>
+static int flow_ctx_warp_bwd(const char* fn, const float* flow_lr, const float* isobj_lr, const float* a01,
+                             const int64_t* ctx_ts, const int64_t* pred_ts, const float* occ, const float* grad_flow,
+                             const float* grad_alpha_ctx, const float* grad_disocc, float* grad_flow_lr, float* grad_a01,
+                             float* grad_occ, void* workspace, int64_t workspace_bytes, int B, int T, int Tw, int Tc,
+                             int Tp, int L, int H, int W, int scale, waldo_stream_t stream) {
+  const int64_t N = (int64_t)B * Tc * Tp;
+  if (int rc = check_bwd_shape(fn, N, L, H, W, scale)) return rc;
+  if (B < 0 || T < 1 || Tw < 1 || Tw > T || Tc < 0 || Tp < 0) {
+    set_error("%s: bad frame counts T=%d Tw=%d Tc=%d Tp=%d", fn, T, Tw, Tc, Tp);
+    return WALDO_EINVAL;
+  }
+  const int64_t HWd = (int64_t)H * scale * W * scale;
+  const int chunks = (int)((HWd + kFcwMaxChunk - 1) / kFcwMaxChunk);
+  Carved<5> lo{};
+  int clog = 0;
+  if (det) {
+    lo = warp_det_workspace(B, Tw, Tc, Tp, L, H, W, scale);
+    // a texel of a context plane receives at most one contribution per (unit of the batch element, pixel)
+    clog = splat_clog((int64_t)Tc * Tp * HWd);
+    if (grad_a01 != nullptr && clog < 0)
+      return splat_refuse(fn, "grad_a01", "Tc=%d Tp=%d Hd*Wd=%lld", Tc, Tp, (long long)HWd);
+    if (int rc = check_splat_launches(fn, N * L * chunks, (int64_t)B * Tw * L * HWd)) return rc;
+    if (B == 0) return WALDO_OK;
+    if (int rc = check_workspace(fn, workspace, workspace_bytes, lo.total())) return rc;
+  } else if (N == 0) {
+    return WALDO_OK;
+  }
+  // (the deterministic form goes on without units: it still overwrites grad_a01 and grad_occ)
+  if (!a01 || !occ || (N > 0 && (!flow_lr || !ctx_ts || !pred_ts || !grad_flow_lr)) ||
+      (!det && scale > 1 && !workspace)) {
+    set_error("%s: null pointer%s", fn, det ? "" : " (scale > 1 needs the (M, L, 2, Hd, Wd) workspace)");
+    return WALDO_EINVAL;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = pixel_tiles(H, W, scale);
+  const int tpb = det ? kDetTilesPerBlock : acc_tiles(N, tiles), groups = pixel_groups(tiles, tpb);
+  float* up = static_cast<float*>(workspace);
+  float* gup = scale > 1 ? up : grad_flow_lr;
+  // the pixel kernel adds to grad_a01 and grad_occ themselves (atomics), or stores `vals` and the slab where wanted
+  float *vals = grad_a01, *table_o = grad_occ;
+  if (det) {
+    vals = grad_a01 != nullptr ? lo.at<float>(workspace, 1) : nullptr;
+    table_o = grad_occ != nullptr ? lo.at<float>(workspace, 4) : nullptr;
+  }
+  auto pixels = [&] {
+    with_padded_layers(L, [&](auto lp) {
+      hipLaunchKernelGGL((flow_ctx_warp_bwd_kernel<decltype(lp)::value, det>), dim3((unsigned)(N * groups)), dim3(kBlock),
+                         0, st, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup,
+                         vals, table_o, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups);
+    });
+  };
+  auto upsample = [&] {
+    if (scale > 1) upsample_bwd(up, grad_flow_lr, N * L * 2, H, W, scale, st);
+  };
+  if (det && grad_a01 != nullptr) {
+    // stream order: fill, pixels, maxima, splat, upsample, conversion
+    splat_passes(
+        lo, workspace, 2, grad_a01, (int64_t)B * Tw * L, HWd, clog, N > 0, st,
+        [&](unsigned* plane_max) {
+          hipLaunchKernelGGL(flow_ctx_warp_det_max_kernel, dim3((unsigned)(N * L * chunks)), dim3(kBlock), 0, st, vals,
+                             ctx_ts, plane_max, Tw, Tc, Tp, L, HWd, chunks);
+        },
+        [&](unsigned long long* acc, unsigned* plane_max) {
+          hipLaunchKernelGGL(flow_ctx_warp_det_splat_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st, flow_lr,
+                             vals, ctx_ts, acc, plane_max, Tw, Tc, Tp, L, H, W, scale, tiles, clog);
+        },
+        pixels, upsample);
+  } else if (N > 0) {
+    pixels();
+    upsample();
+  }
+  if constexpr (det) {
+    if (table_o != nullptr && N > 0)  // matrix (b, t) sums the workgroups of the units (b, tc, tp) whose predicted frame is t
+      slab_reduce(table_o, grad_occ, (int64_t)B * T, Tc * Tp * groups, L * L, SlabByPredFrame{pred_ts, T, Tc, Tp, groups},
+                  st);
+    else if (table_o != nullptr)
+      fill_words(grad_occ, 0u, sizeof(float) * (size_t)B * T * L * L, st);
+  }
+  return launch_status(fn);
+}
+
 extern "C" int waldo_flow_ctx_alpha_bwd(const float* alpha_lr, const float* input, const float* dist,
                                         const float* occ, const float* grad_a01, const float* grad_alpha_out,
                                         float* grad_alpha_lr, float* grad_dist, float* grad_occ, float* workspace,
                                         int B, int T, int Tw, int L, int Nl, int C, int chan_off, int H, int W,
                                         int scale, waldo_stream_t stream) {
-  const int64_t N = (int64_t)B * Tw;
-  if (int rc = check_bwd_shape("waldo_flow_ctx_alpha_bwd", N, L, H, W, scale)) return rc;
-  if (B < 0 || T < 1 || Tw < 1 || Tw > T ||
-      (dist != nullptr && (Nl < 1 || Nl > kMaxCls || chan_off < 0 || chan_off + Nl > C))) {
-    set_error("waldo_flow_ctx_alpha_bwd: bad frame window Tw=%d of T=%d or class channels", Tw, T);
-    return WALDO_EINVAL;
-  }
-  if (N == 0) return WALDO_OK;
-  if (!alpha_lr || !occ || (!grad_a01 && !grad_alpha_out) || !grad_alpha_lr || (dist != nullptr && !input) || (scale > 1 && !workspace)) {
-    set_error("waldo_flow_ctx_alpha_bwd: null pointer (one of grad_a01 / grad_alpha_out; scale > 1 needs the (B*Tw, L, Hd, Wd) workspace)");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = (int)(((int64_t)H * scale * W * scale + kBlock - 1) / kBlock);
-  const int tpb = acc_tiles(N, tiles), groups = (tiles + tpb - 1) / tpb;
-  float* gup = scale > 1 ? workspace : grad_alpha_lr;
-  // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
-  with_padded_layers(L, [&](auto lp) {
-    auto launch = [&](auto ncp) {
-      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<decltype(lp)::value, decltype(ncp)::value>),
-                         dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, alpha_lr, input, dist, occ, grad_a01,
-                         grad_alpha_out, gup, grad_dist, grad_occ, T, Tw, L, Nl, C, chan_off, H, W, scale, tiles, tpb,
-                         groups);
-    };
-    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
-    else launch(std::integral_constant<int, kMaxCls>{});
-  });
-  if (scale > 1) {
-    const int64_t P = N * L;
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       st, workspace, grad_alpha_lr, P, H, W, scale);
-  }
-  return launch_status("waldo_flow_ctx_alpha_bwd");
+  return flow_ctx_alpha_bwd<false>("waldo_flow_ctx_alpha_bwd", alpha_lr, input, dist, occ, grad_a01, grad_alpha_out,
+                                   grad_alpha_lr, grad_dist, grad_occ, workspace, 0, B, T, Tw, L, Nl, C, chan_off, H, W,
+                                   scale, stream);
 }
 
 extern "C" int waldo_flow_ctx_warp_bwd(const float* flow_lr, const float* isobj_lr, const float* a01,
@@ -648,32 +788,9 @@ extern "C" int waldo_flow_ctx_warp_bwd(const float* flow_lr, const float* isobj_
                                        const float* grad_disocc, float* grad_flow_lr, float* grad_a01,
                                        float* grad_occ, float* workspace, int B, int T, int Tw, int Tc,
                                        int Tp, int L, int H, int W, int scale, waldo_stream_t stream) {
-  const int64_t N = (int64_t)B * Tc * Tp;
-  if (int rc = check_bwd_shape("waldo_flow_ctx_warp_bwd", N, L, H, W, scale)) return rc;
-  if (B < 0 || T < 1 || Tw < 1 || Tw > T || Tc < 0 || Tp < 0) {
-    set_error("waldo_flow_ctx_warp_bwd: bad frame counts T=%d Tw=%d Tc=%d Tp=%d", T, Tw, Tc, Tp);
-    return WALDO_EINVAL;
-  }
-  if (N == 0) return WALDO_OK;
-  if (!flow_lr || !a01 || !ctx_ts || !pred_ts || !occ || !grad_flow_lr || (scale > 1 && !workspace)) {
-    set_error("waldo_flow_ctx_warp_bwd: null pointer (scale > 1 needs the (M, L, 2, Hd, Wd) workspace)");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = (int)(((int64_t)H * scale * W * scale + kBlock - 1) / kBlock);
-  const int tpb = acc_tiles(N, tiles), groups = (tiles + tpb - 1) / tpb;
-  float* gup = scale > 1 ? workspace : grad_flow_lr;
-  with_padded_layers(L, [&](auto lp) {
-    hipLaunchKernelGGL((flow_ctx_warp_bwd_kernel<decltype(lp)::value>), dim3((unsigned)(N * groups)), dim3(kBlock), 0,
-                       st, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx, grad_disocc, gup,
-                       grad_a01, grad_occ, T, Tw, Tc, Tp, L, H, W, scale, tiles, tpb, groups);
-  });
-  if (scale > 1) {
-    const int64_t P = N * L * 2;
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       st, workspace, grad_flow_lr, P, H, W, scale);
-  }
-  return launch_status("waldo_flow_ctx_warp_bwd");
+  return flow_ctx_warp_bwd<false>("waldo_flow_ctx_warp_bwd", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow,
+                                  grad_alpha_ctx, grad_disocc, grad_flow_lr, grad_a01, grad_occ, workspace, 0, B, T, Tw,
+                                  Tc, Tp, L, H, W, scale, stream);
 }
 
 extern "C" int waldo_frame_warp_fuse_bwd(const float* input, const float* flow, const float* alpha,
@@ -711,56 +828,10 @@ extern "C" int waldo_frame_warp_fuse_bwd(const float* input, const float* flow, 
   return launch_status("waldo_frame_warp_fuse_bwd");
 }
 
-// ---- deterministic mode (det_common.hip.h).  The same arguments as the entry points above, with ONE workspace that
-// also holds what they keep there; grad_dist / grad_occ / grad_a01 are OVERWRITTEN.
-namespace {
-
-struct AlphaDetLayout {
-  int64_t up_bytes, occ_bytes, dist_bytes, total;
-  int tiles, tpb, groups;
-};
-
-AlphaDetLayout alpha_det_layout(int64_t N, int L, int Nl, int H, int W, int scale) {
-  AlphaDetLayout o;
-  const int64_t HWd = (int64_t)H * scale * W * scale;
-  o.tiles = (int)((HWd + kBlock - 1) / kBlock);
-  o.tpb = kDetTilesPerBlock;
-  o.groups = (o.tiles + o.tpb - 1) / o.tpb;
-  o.up_bytes = scale > 1 ? round256(N * L * HWd * 4) : 0;
-  o.occ_bytes = round256(N * o.groups * L * L * 4);
-  o.dist_bytes = round256(N * o.groups * (int64_t)(L - 1) * Nl * 4);
-  o.total = o.up_bytes + o.occ_bytes + o.dist_bytes;
-  return o;
-}
-
-struct WarpDetLayout {
-  int64_t up_bytes, vals_bytes, acc_bytes, max_bytes, occ_bytes, total;
-  int tiles, tpb, groups, clog;  // clog -1: a texel could receive more than 2^32 contributions
-};
-
-WarpDetLayout warp_det_layout(int64_t B, int Tw, int Tc, int Tp, int L, int H, int W, int scale) {
-  WarpDetLayout o;
-  const int64_t N = B * Tc * Tp, HWd = (int64_t)H * scale * W * scale;
-  o.tiles = (int)((HWd + kBlock - 1) / kBlock);
-  o.tpb = kDetTilesPerBlock;
-  o.groups = (o.tiles + o.tpb - 1) / o.tpb;
-  o.up_bytes = scale > 1 ? round256(N * L * 2 * HWd * 4) : 0;
-  o.vals_bytes = round256(N * L * HWd * 4);
-  o.acc_bytes = round256(B * Tw * L * HWd * 8);
-  o.max_bytes = round256(B * Tw * L * 4);
-  o.occ_bytes = round256(N * o.groups * L * L * 4);
-  o.total = o.up_bytes + o.vals_bytes + o.acc_bytes + o.max_bytes + o.occ_bytes;
-  const int64_t count = (int64_t)Tc * Tp * HWd;
-  const int clog = splat_count_log(count > 1 ? count : 1);
-  o.clog = clog <= kSplatMaxLog ? clog : -1;
-  return o;
-}
-
-}  // namespace
-
+// ---- deterministic mode (det_common.hip.h): the workspace queries and the entry points; the bodies are above
 extern "C" int64_t waldo_flow_ctx_alpha_bwd_det_workspace_bytes(int B, int Tw, int L, int Nl, int H, int W, int scale) {
   if (B < 0 || Tw < 1 || Nl < 0 || Nl > kMaxCls || check_bwd_shape("", (int64_t)B * Tw, L, H, W, scale)) return 0;
-  return alpha_det_layout((int64_t)B * Tw, L, Nl, H, W, scale).total;
+  return alpha_det_workspace((int64_t)B * Tw, L, Nl, H, W, scale).total();
 }
 
 extern "C" int waldo_flow_ctx_alpha_bwd_det(const float* alpha_lr, const float* input, const float* dist,
@@ -768,61 +839,15 @@ extern "C" int waldo_flow_ctx_alpha_bwd_det(const float* alpha_lr, const float* 
                                             float* grad_alpha_lr, float* grad_dist, float* grad_occ, void* workspace,
                                             int64_t workspace_bytes, int B, int T, int Tw, int L, int Nl, int C,
                                             int chan_off, int H, int W, int scale, waldo_stream_t stream) {
-  const char* fn = "waldo_flow_ctx_alpha_bwd_det";
-  const int64_t N = (int64_t)B * Tw;
-  if (int rc = check_bwd_shape(fn, N, L, H, W, scale)) return rc;
-  if (B < 0 || T < 1 || Tw < 1 || Tw > T ||
-      (dist != nullptr && (Nl < 1 || Nl > kMaxCls || chan_off < 0 || chan_off + Nl > C))) {
-    set_error("%s: bad frame window Tw=%d of T=%d or class channels", fn, Tw, T);
-    return WALDO_EINVAL;
-  }
-  if (N == 0) return WALDO_OK;
-  const AlphaDetLayout lo = alpha_det_layout(N, L, dist != nullptr ? Nl : 0, H, W, scale);
-  if (workspace == nullptr || workspace_bytes < lo.total) {
-    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
-              (long long)lo.total);
-    return WALDO_EINVAL;
-  }
-  if (!alpha_lr || !occ || (!grad_a01 && !grad_alpha_out) || !grad_alpha_lr || (dist != nullptr && !input)) {
-    set_error("%s: null pointer (one of grad_a01 / grad_alpha_out)", fn);
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = reinterpret_cast<char*>(workspace);
-  float* up = reinterpret_cast<float*>(ws);
-  float* slab_o = reinterpret_cast<float*>(ws + lo.up_bytes);
-  float* slab_d = reinterpret_cast<float*>(ws + lo.up_bytes + lo.occ_bytes);
-  float* gup = scale > 1 ? up : grad_alpha_lr;
-  const bool want_d = dist != nullptr && grad_dist != nullptr;
-  with_padded_layers(L, [&](auto lp) {
-    auto launch = [&](auto ncp) {
-      hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<decltype(lp)::value, decltype(ncp)::value, true>),
-                         dim3((unsigned)(N * lo.groups)), dim3(kBlock), 0, st, alpha_lr, input, dist, occ, grad_a01,
-                         grad_alpha_out, gup, want_d ? slab_d : nullptr, grad_occ != nullptr ? slab_o : nullptr, T, Tw,
-                         L, Nl, C, chan_off, H, W, scale, lo.tiles, lo.tpb, lo.groups);
-    };
-    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
-    else launch(std::integral_constant<int, kMaxCls>{});
-  });
-  if (grad_occ != nullptr) {
-    // frames Tw .. T - 1 of a batch element receive nothing
-    if (Tw < T) fill_words(grad_occ, 0u, sizeof(float) * (size_t)B * T * L * L, st);
-    slab_reduce(slab_o, grad_occ, N, lo.groups, L * L, SlabPlain{N * lo.groups, Tw, T}, st);
-  }
-  if (want_d)  // a batch element's Tw * groups workgroups: consecutive rows
-    slab_reduce(slab_d, grad_dist, B, Tw * lo.groups, (L - 1) * Nl, SlabPlain{N * lo.groups, B, B}, st);
-  if (scale > 1) {
-    const int64_t P = N * L;
-    hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       st, up, grad_alpha_lr, P, H, W, scale);
-  }
-  return launch_status(fn);
+  return flow_ctx_alpha_bwd<true>("waldo_flow_ctx_alpha_bwd_det", alpha_lr, input, dist, occ, grad_a01, grad_alpha_out,
+                                  grad_alpha_lr, grad_dist, grad_occ, workspace, workspace_bytes, B, T, Tw, L, Nl, C,
+                                  chan_off, H, W, scale, stream);
 }
 
 extern "C" int64_t waldo_flow_ctx_warp_bwd_det_workspace_bytes(int B, int Tw, int Tc, int Tp, int L, int H, int W,
                                                                int scale) {
   if (B < 0 || Tw < 1 || Tc < 0 || Tp < 0 || check_bwd_shape("", (int64_t)B * Tc * Tp, L, H, W, scale)) return 0;
-  return warp_det_layout(B, Tw, Tc, Tp, L, H, W, scale).total;
+  return warp_det_workspace(B, Tw, Tc, Tp, L, H, W, scale).total();
 }
 
 extern "C" int waldo_flow_ctx_warp_bwd_det(const float* flow_lr, const float* isobj_lr, const float* a01,
@@ -832,74 +857,7 @@ extern "C" int waldo_flow_ctx_warp_bwd_det(const float* flow_lr, const float* is
                                            float* grad_occ, void* workspace, int64_t workspace_bytes, int B, int T,
                                            int Tw, int Tc, int Tp, int L, int H, int W, int scale,
                                            waldo_stream_t stream) {
-  const char* fn = "waldo_flow_ctx_warp_bwd_det";
-  const int64_t N = (int64_t)B * Tc * Tp;
-  if (int rc = check_bwd_shape(fn, N, L, H, W, scale)) return rc;
-  if (B < 0 || T < 1 || Tw < 1 || Tw > T || Tc < 0 || Tp < 0) {
-    set_error("%s: bad frame counts T=%d Tw=%d Tc=%d Tp=%d", fn, T, Tw, Tc, Tp);
-    return WALDO_EINVAL;
-  }
-  const WarpDetLayout lo = warp_det_layout(B, Tw, Tc, Tp, L, H, W, scale);
-  const int64_t HWd = (int64_t)H * scale * W * scale;
-  if (grad_a01 != nullptr && lo.clog < 0) {
-    set_error("%s: a texel of grad_a01 may receive more than 2^%d contributions (Tc=%d Tp=%d Hd*Wd=%lld): no "
-              "deterministic sum for this shape", fn, kSplatMaxLog, Tc, Tp, (long long)HWd);
-    return WALDO_EINVAL;
-  }
-  const int chunks = (int)((HWd + kFcwMaxChunk - 1) / kFcwMaxChunk);
-  if (N * L * chunks > 2147483647 || ((int64_t)B * Tw * L * HWd + kBlock - 1) / kBlock > 2147483647) {
-    set_error("%s: problem too large for one launch", fn);
-    return WALDO_EINVAL;
-  }
-  if (B == 0) return WALDO_OK;
-  if (workspace == nullptr || workspace_bytes < lo.total) {
-    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
-              (long long)lo.total);
-    return WALDO_EINVAL;
-  }
-  if (!a01 || !occ || (N > 0 && (!flow_lr || !ctx_ts || !pred_ts || !grad_flow_lr))) {
-    set_error("%s: null pointer", fn);
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  char* ws = reinterpret_cast<char*>(workspace);
-  float* up = reinterpret_cast<float*>(ws);
-  float* vals = reinterpret_cast<float*>(ws + lo.up_bytes);
-  unsigned long long* acc = reinterpret_cast<unsigned long long*>(ws + lo.up_bytes + lo.vals_bytes);
-  unsigned* plane_max = reinterpret_cast<unsigned*>(ws + lo.up_bytes + lo.vals_bytes + lo.acc_bytes);
-  float* slab_o = reinterpret_cast<float*>(ws + lo.up_bytes + lo.vals_bytes + lo.acc_bytes + lo.max_bytes);
-  float* gup = scale > 1 ? up : grad_flow_lr;
-  if (grad_a01 != nullptr) fill_words(acc, 0u, (size_t)(lo.acc_bytes + lo.max_bytes), st);
-  if (N > 0) {
-    with_padded_layers(L, [&](auto lp) {
-      hipLaunchKernelGGL((flow_ctx_warp_bwd_kernel<decltype(lp)::value, true>), dim3((unsigned)(N * lo.groups)),
-                         dim3(kBlock), 0, st, flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow, grad_alpha_ctx,
-                         grad_disocc, gup, grad_a01 != nullptr ? vals : nullptr, grad_occ != nullptr ? slab_o : nullptr, T,
-                         Tw, Tc, Tp, L, H, W, scale, lo.tiles, lo.tpb, lo.groups);
-    });
-    if (grad_a01 != nullptr) {
-      hipLaunchKernelGGL(flow_ctx_warp_det_max_kernel, dim3((unsigned)(N * L * chunks)), dim3(kBlock), 0, st, vals,
-                         ctx_ts, plane_max, Tw, Tc, Tp, L, HWd, chunks);
-      hipLaunchKernelGGL(flow_ctx_warp_det_splat_kernel, dim3((unsigned)(N * lo.tiles)), dim3(kBlock), 0, st, flow_lr,
-                         vals, ctx_ts, acc, plane_max, Tw, Tc, Tp, L, H, W, scale, lo.tiles, lo.clog);
-    }
-    if (scale > 1) {
-      const int64_t P = N * L * 2;
-      hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((P * H * W + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                         st, up, grad_flow_lr, P, H, W, scale);
-    }
-  }
-  if (grad_a01 != nullptr) {
-    const int64_t total = (int64_t)B * Tw * L * HWd;
-    hipLaunchKernelGGL(splat_convert_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, acc,
-                       plane_max, grad_a01, HWd, total, lo.clog);
-  }
-  if (grad_occ != nullptr) {
-    if (N > 0)  // matrix (b, t) sums the workgroups of the units (b, tc, tp) whose predicted frame is t
-      slab_reduce(slab_o, grad_occ, (int64_t)B * T, Tc * Tp * lo.groups, L * L,
-                  SlabByPredFrame{pred_ts, T, Tc, Tp, lo.groups}, st);
-    else
-      fill_words(grad_occ, 0u, sizeof(float) * (size_t)B * T * L * L, st);
-  }
-  return launch_status(fn);
+  return flow_ctx_warp_bwd<true>("waldo_flow_ctx_warp_bwd_det", flow_lr, isobj_lr, a01, ctx_ts, pred_ts, occ, grad_flow,
+                                 grad_alpha_ctx, grad_disocc, grad_flow_lr, grad_a01, grad_occ, workspace, workspace_bytes,
+                                 B, T, Tw, Tc, Tp, L, H, W, scale, stream);
 }

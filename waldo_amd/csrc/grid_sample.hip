@@ -330,23 +330,9 @@ __global__ __launch_bounds__(kBlock) void grid_sample2d_det_splat_kernel(
   }
 }
 
-struct GsDetLayout {
-  int64_t acc_bytes, max_bytes, total;
-  int clog;  // -1: a texel could receive more than 2^32 contributions
-};
-
-static GsDetLayout gs_det_layout(int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho, int Wo, int64_t outer_div,
-                                 int64_t inner) {
-  GsDetLayout o;
-  o.acc_bytes = round256(Nin * C * (int64_t)Hi * Wi * 8);
-  o.max_bytes = round256(Nin * C * 4);
-  o.total = o.acc_bytes + o.max_bytes;
-  // output maps that read one input map: n / outer_div fixed, n % inner fixed
-  const int64_t per_map = (outer_div + inner - 1) / inner;
-  const int64_t copies = N < 1 ? 1 : (N < per_map ? N : per_map);
-  const int clog = splat_count_log(copies * (int64_t)Ho * Wo);
-  o.clog = clog <= kSplatMaxLog ? clog : -1;
-  return o;
+// workspace of the *_det entry points: the sums of the Nin * C planes of grad_input, then their maxima
+static Carved<2> gs_det_workspace(int64_t Nin, int C, int Hi, int Wi) {
+  return carve(Nin * C * (int64_t)Hi * Wi * 8, Nin * C * 4);
 }
 
 }  // namespace waldo
@@ -408,10 +394,13 @@ extern "C" int waldo_grid_sample2d_ex_fwd(const float* input, const float* grid,
                                   OutSlots{out_group, out_stride, out_offset}, PreAffine{pre_scale, pre_bias}, stream);
 }
 
+// det: the *_det entry points -- grad_input (all Nin maps; the atomic form is not told Nin) is OVERWRITTEN through the
+// fixed-point splat in the workspace instead of being added to with float atomics
 static int grid_sample2d_bwd_launch(const char* fn, const float* input, const float* grid, const float* grad_output,
-                                    float* grad_input, float* grad_grid, int64_t N, int C, int Hi, int Wi, int Ho,
-                                    int Wo, float delta, int64_t outer_div, int64_t inner, OutSlots gos, PreAffine pre,
-                                    waldo_stream_t stream) {
+                                    float* grad_input, float* grad_grid, int64_t N, int64_t Nin, int C, int Hi, int Wi,
+                                    int Ho, int Wo, float delta, int64_t outer_div, int64_t inner, OutSlots gos,
+                                    PreAffine pre, void* workspace, int64_t workspace_bytes, waldo_stream_t stream,
+                                    bool det) {
   if (gos.group < 1 || gos.stride < gos.group || gos.offset < 0 || gos.offset + gos.group > gos.stride) {
     set_error("%s: bad gradient slots (group %lld, stride %lld, offset %lld)", fn, (long long)gos.group,
               (long long)gos.stride, (long long)gos.offset);
@@ -419,82 +408,27 @@ static int grid_sample2d_bwd_launch(const char* fn, const float* input, const fl
   }
   int rc = check_gs(fn, N, C, Hi, Wi, Ho, Wo, outer_div, inner);
   if (rc) return rc;
-  if (N == 0) return WALDO_OK;
-  if (!input || !grid || !grad_output) {
-    set_error("%s: null pointer", fn);
-    return WALDO_EINVAL;
-  }
-  if (!grad_input && !grad_grid) return WALDO_OK;
-  const int64_t HWo = (int64_t)Ho * Wo;
-  const int tiles = (int)((HWo + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(grid_sample2d_bwd_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0,
-                     (hipStream_t)stream, input, grid, grad_output, grad_input, grad_grid, N, C,
-                     Hi, Wi, HWo, tiles, delta, outer_div, inner, gos, pre);
-  return launch_status(fn);
-}
-
-extern "C" int waldo_grid_sample2d_bwd(const float* input, const float* grid,
-                                       const float* grad_output, float* grad_input,
-                                       float* grad_grid, int64_t N, int C, int Hi, int Wi, int Ho,
-                                       int Wo, float delta, int64_t outer_div, int64_t inner,
-                                       waldo_stream_t stream) {
-  return grid_sample2d_bwd_launch("waldo_grid_sample2d_bwd", input, grid, grad_output, grad_input, grad_grid, N, C, Hi,
-                                  Wi, Ho, Wo, delta, outer_div, inner, OutSlots{N > 0 ? N : 1, N > 0 ? N : 1, 0},
-                                  PreAffine{1.0f, 0.0f}, stream);
-}
-
-extern "C" int waldo_grid_sample2d_ex_bwd(const float* input, const float* grid, const float* grad_output,
-                                          float* grad_input, float* grad_grid, int64_t N, int C, int Hi, int Wi,
-                                          int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
-                                          int64_t gout_group, int64_t gout_stride, int64_t gout_offset,
-                                          float pre_scale, float pre_bias, waldo_stream_t stream) {
-  return grid_sample2d_bwd_launch("waldo_grid_sample2d_ex_bwd", input, grid, grad_output, grad_input, grad_grid, N, C,
-                                  Hi, Wi, Ho, Wo, delta, outer_div, inner,
-                                  OutSlots{gout_group, gout_stride, gout_offset}, PreAffine{pre_scale, pre_bias}, stream);
-}
-
-// ---- deterministic mode: grad_input OVERWRITTEN (all Nin maps), the same bits whatever the order of arrival
-extern "C" int64_t waldo_grid_sample2d_bwd_det_workspace_bytes(int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho,
-                                                               int Wo) {
-  if (N < 0 || Nin < 0 || C < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return 0;
-  return gs_det_layout(N, Nin, C, Hi, Wi, Ho, Wo, 1, 1).total;
-}
-
-static int grid_sample2d_bwd_det_launch(const char* fn, const float* input, const float* grid, const float* grad_output,
-                                        float* grad_input, float* grad_grid, int64_t N, int64_t Nin, int C, int Hi,
-                                        int Wi, int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
-                                        OutSlots gos, PreAffine pre, void* workspace, int64_t workspace_bytes,
-                                        waldo_stream_t stream) {
-  if (gos.group < 1 || gos.stride < gos.group || gos.offset < 0 || gos.offset + gos.group > gos.stride) {
-    set_error("%s: bad gradient slots (group %lld, stride %lld, offset %lld)", fn, (long long)gos.group,
-              (long long)gos.stride, (long long)gos.offset);
-    return WALDO_EINVAL;
-  }
-  int rc = check_gs(fn, N, C, Hi, Wi, Ho, Wo, outer_div, inner);
-  if (rc) return rc;
-  if (Nin < 0 || (N > 0 && ((N - 1) / outer_div) * inner + (inner < N ? inner : N) > Nin)) {
-    set_error("%s: Nin=%lld input maps, the broadcast (%lld, %lld) of N=%lld outputs reads more", fn, (long long)Nin,
-              (long long)outer_div, (long long)inner, (long long)N);
-    return WALDO_EINVAL;
-  }
   const int64_t HWo = (int64_t)Ho * Wo, HWi = (int64_t)Hi * Wi;
   const int chunks = (int)((HWo + kGsMaxChunk - 1) / kGsMaxChunk);
-  const GsDetLayout lo = gs_det_layout(N, Nin, C, Hi, Wi, Ho, Wo, outer_div, inner);
-  if (grad_input != nullptr) {
-    if (lo.clog < 0) {
-      set_error("%s: a texel of grad_input may receive more than 2^%d contributions (N=%lld Ho=%d Wo=%d): no "
-                "deterministic sum for this shape", fn, kSplatMaxLog, (long long)N, Ho, Wo);
+  Carved<2> lo{};
+  int clog = 0;
+  if (det) {
+    lo = gs_det_workspace(Nin, C, Hi, Wi);
+    if (Nin < 0 || (N > 0 && ((N - 1) / outer_div) * inner + (inner < N ? inner : N) > Nin)) {
+      set_error("%s: Nin=%lld input maps, the broadcast (%lld, %lld) of N=%lld outputs reads more", fn, (long long)Nin,
+                (long long)outer_div, (long long)inner, (long long)N);
       return WALDO_EINVAL;
     }
-    if (N * C * chunks > 2147483647 || (Nin * C * HWi + kBlock - 1) / kBlock > 2147483647) {
-      set_error("%s: problem too large for one launch", fn);
-      return WALDO_EINVAL;
+    if (grad_input != nullptr) {
+      // output maps that read one input map: n / outer_div fixed, n % inner fixed
+      const int64_t per_map = (outer_div + inner - 1) / inner;
+      clog = splat_clog((N < 1 ? 1 : (N < per_map ? N : per_map)) * HWo);
+      if (clog < 0) return splat_refuse(fn, "grad_input", "N=%lld Ho=%d Wo=%d", (long long)N, Ho, Wo);
+      if ((rc = check_splat_launches(fn, N * C * chunks, Nin * C * HWi))) return rc;
+      if (Nin > 0 && (rc = check_workspace(fn, workspace, workspace_bytes, lo.total()))) return rc;
     }
-    if (Nin > 0 && (workspace == nullptr || workspace_bytes < lo.total)) {
-      set_error("%s: workspace of %lld bytes given, %lld needed", fn,
-                (long long)(workspace == nullptr ? 0 : workspace_bytes), (long long)lo.total);
-      return WALDO_EINVAL;
-    }
+  } else if (N == 0) {
+    return WALDO_OK;
   }
   if (N > 0 && (!input || !grid || !grad_output)) {
     set_error("%s: null pointer", fn);
@@ -503,35 +437,61 @@ static int grid_sample2d_bwd_det_launch(const char* fn, const float* input, cons
   if (!grad_input && !grad_grid) return WALDO_OK;
   hipStream_t st = (hipStream_t)stream;
   const int tiles = (int)((HWo + kBlock - 1) / kBlock);
-  if (grad_grid != nullptr && N > 0)
+  // the pixel kernel: grad_grid and, in the atomic form, the scatter into grad_input
+  float* scatter = det ? nullptr : grad_input;
+  if (N > 0 && (grad_grid != nullptr || scatter != nullptr))
     hipLaunchKernelGGL(grid_sample2d_bwd_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st, input, grid,
-                       grad_output, (float*)nullptr, grad_grid, N, C, Hi, Wi, HWo, tiles, delta, outer_div, inner, gos,
-                       pre);
-  if (grad_input != nullptr && Nin > 0) {
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(workspace);
-    unsigned* plane_max = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + lo.acc_bytes);
-    fill_words(workspace, 0u, (size_t)lo.total, st);
-    if (N > 0) {
-      hipLaunchKernelGGL(grid_sample2d_det_max_kernel, dim3((unsigned)(N * C * chunks)), dim3(kBlock), 0, st,
-                         grad_output, plane_max, C, HWo, chunks, outer_div, inner, gos, pre.scale);
-      hipLaunchKernelGGL(grid_sample2d_det_splat_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st, grid,
-                         grad_output, acc, plane_max, C, Hi, Wi, HWo, tiles, outer_div, inner, gos, pre.scale, lo.clog);
-    }
-    const int64_t total = Nin * C * HWi;
-    hipLaunchKernelGGL(splat_convert_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, acc,
-                       plane_max, grad_input, HWi, total, lo.clog);
-  }
+                       grad_output, scatter, grad_grid, N, C, Hi, Wi, HWo, tiles, delta, outer_div, inner, gos, pre);
+  if (det && grad_input != nullptr && Nin > 0)
+    splat_passes(
+        lo, workspace, 0, grad_input, Nin * C, HWi, clog, N > 0, st,
+        [&](unsigned* plane_max) {
+          hipLaunchKernelGGL(grid_sample2d_det_max_kernel, dim3((unsigned)(N * C * chunks)), dim3(kBlock), 0, st,
+                             grad_output, plane_max, C, HWo, chunks, outer_div, inner, gos, pre.scale);
+        },
+        [&](unsigned long long* acc, unsigned* plane_max) {
+          hipLaunchKernelGGL(grid_sample2d_det_splat_kernel, dim3((unsigned)(N * tiles)), dim3(kBlock), 0, st, grid,
+                             grad_output, acc, plane_max, C, Hi, Wi, HWo, tiles, outer_div, inner, gos, pre.scale, clog);
+        });
   return launch_status(fn);
+}
+
+extern "C" int waldo_grid_sample2d_bwd(const float* input, const float* grid,
+                                       const float* grad_output, float* grad_input,
+                                       float* grad_grid, int64_t N, int C, int Hi, int Wi, int Ho,
+                                       int Wo, float delta, int64_t outer_div, int64_t inner,
+                                       waldo_stream_t stream) {
+  return grid_sample2d_bwd_launch("waldo_grid_sample2d_bwd", input, grid, grad_output, grad_input, grad_grid, N, 0, C,
+                                  Hi, Wi, Ho, Wo, delta, outer_div, inner, OutSlots{N > 0 ? N : 1, N > 0 ? N : 1, 0},
+                                  PreAffine{1.0f, 0.0f}, nullptr, 0, stream, false);
+}
+
+extern "C" int waldo_grid_sample2d_ex_bwd(const float* input, const float* grid, const float* grad_output,
+                                          float* grad_input, float* grad_grid, int64_t N, int C, int Hi, int Wi,
+                                          int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
+                                          int64_t gout_group, int64_t gout_stride, int64_t gout_offset,
+                                          float pre_scale, float pre_bias, waldo_stream_t stream) {
+  return grid_sample2d_bwd_launch("waldo_grid_sample2d_ex_bwd", input, grid, grad_output, grad_input, grad_grid, N, 0,
+                                  C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
+                                  OutSlots{gout_group, gout_stride, gout_offset}, PreAffine{pre_scale, pre_bias}, nullptr,
+                                  0, stream, false);
+}
+
+// ---- deterministic mode: grad_input OVERWRITTEN (all Nin maps), the same bits whatever the order of arrival
+extern "C" int64_t waldo_grid_sample2d_bwd_det_workspace_bytes(int64_t N, int64_t Nin, int C, int Hi, int Wi, int Ho,
+                                                               int Wo) {
+  if (N < 0 || Nin < 0 || C < 1 || Hi < 1 || Wi < 1 || Ho < 1 || Wo < 1) return 0;
+  return gs_det_workspace(Nin, C, Hi, Wi).total();
 }
 
 extern "C" int waldo_grid_sample2d_bwd_det(const float* input, const float* grid, const float* grad_output,
                                            float* grad_input, float* grad_grid, int64_t N, int64_t Nin, int C, int Hi,
                                            int Wi, int Ho, int Wo, float delta, int64_t outer_div, int64_t inner,
                                            void* workspace, int64_t workspace_bytes, waldo_stream_t stream) {
-  return grid_sample2d_bwd_det_launch("waldo_grid_sample2d_bwd_det", input, grid, grad_output, grad_input, grad_grid,
-                                      N, Nin, C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
-                                      OutSlots{N > 0 ? N : 1, N > 0 ? N : 1, 0}, PreAffine{1.0f, 0.0f}, workspace,
-                                      workspace_bytes, stream);
+  return grid_sample2d_bwd_launch("waldo_grid_sample2d_bwd_det", input, grid, grad_output, grad_input, grad_grid, N,
+                                  Nin, C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
+                                  OutSlots{N > 0 ? N : 1, N > 0 ? N : 1, 0}, PreAffine{1.0f, 0.0f}, workspace,
+                                  workspace_bytes, stream, true);
 }
 
 extern "C" int waldo_grid_sample2d_ex_bwd_det(const float* input, const float* grid, const float* grad_output,
@@ -540,8 +500,8 @@ extern "C" int waldo_grid_sample2d_ex_bwd_det(const float* input, const float* g
                                               int64_t inner, int64_t gout_group, int64_t gout_stride,
                                               int64_t gout_offset, float pre_scale, float pre_bias, void* workspace,
                                               int64_t workspace_bytes, waldo_stream_t stream) {
-  return grid_sample2d_bwd_det_launch("waldo_grid_sample2d_ex_bwd_det", input, grid, grad_output, grad_input,
-                                      grad_grid, N, Nin, C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
-                                      OutSlots{gout_group, gout_stride, gout_offset}, PreAffine{pre_scale, pre_bias},
-                                      workspace, workspace_bytes, stream);
+  return grid_sample2d_bwd_launch("waldo_grid_sample2d_ex_bwd_det", input, grid, grad_output, grad_input, grad_grid,
+                                  N, Nin, C, Hi, Wi, Ho, Wo, delta, outer_div, inner,
+                                  OutSlots{gout_group, gout_stride, gout_offset}, PreAffine{pre_scale, pre_bias},
+                                  workspace, workspace_bytes, stream, true);
 }

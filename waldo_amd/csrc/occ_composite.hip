@@ -165,28 +165,6 @@ static int occ_bwd_tiles_per_block(int64_t M, int tiles, bool want_occ) {
   return tpb;
 }
 
-extern "C" int waldo_occ_composite_bwd(const float* alpha, const float* occ,
-                                       const float* grad_out, float* grad_alpha, float* grad_occ,
-                                       int64_t M, int L, int64_t HW, int64_t occ_div,
-                                       waldo_stream_t stream) {
-  int rc = check_occ("waldo_occ_composite_bwd", M, L, HW, occ_div);
-  if (rc) return rc;
-  if (M == 0) return WALDO_OK;
-  if (!alpha || !occ || !grad_out || !grad_alpha) {
-    set_error("waldo_occ_composite_bwd: null pointer");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = (int)((HW + kBlock - 1) / kBlock);
-  const int tpb = occ_bwd_tiles_per_block(M, tiles, grad_occ != nullptr);
-  const int groups = (tiles + tpb - 1) / tpb;
-  with_padded_layers(L, [&](auto lp) {
-    hipLaunchKernelGGL((occ_composite_bwd_kernel<decltype(lp)::value>), dim3((unsigned)(M * groups)), dim3(kBlock), 0,
-                       st, alpha, occ, grad_out, grad_alpha, grad_occ, L, HW, tiles, tpb, groups, occ_div);
-  });
-  return launch_status("waldo_occ_composite_bwd");
-}
-
 // ---- deterministic mode: grad_occ (ceil(M / occ_div) matrices) OVERWRITTEN; slab form
 extern "C" int64_t waldo_occ_composite_bwd_det_workspace_bytes(int64_t M, int L, int64_t HW) {
   if (M < 0 || L < 1 || L > 32 || HW < 1) return 0;
@@ -194,19 +172,16 @@ extern "C" int64_t waldo_occ_composite_bwd_det_workspace_bytes(int64_t M, int L,
   return round256(M * ((tiles + kDetTilesPerBlock - 1) / kDetTilesPerBlock) * L * L * 4);
 }
 
-extern "C" int waldo_occ_composite_bwd_det(const float* alpha, const float* occ, const float* grad_out,
-                                           float* grad_alpha, float* grad_occ, int64_t M, int L, int64_t HW,
-                                           int64_t occ_div, void* workspace, int64_t workspace_bytes,
-                                           waldo_stream_t stream) {
-  const char* fn = "waldo_occ_composite_bwd_det";
+// det: the *_det entry point -- the workgroups store their partial matrices to a slab in the workspace and a reduction
+// overwrites grad_occ; without grad_occ the two modes are the same launch
+static int occ_composite_bwd(const char* fn, const float* alpha, const float* occ, const float* grad_out,
+                             float* grad_alpha, float* grad_occ, int64_t M, int L, int64_t HW, int64_t occ_div,
+                             void* workspace, int64_t workspace_bytes, waldo_stream_t stream, bool det) {
   int rc = check_occ(fn, M, L, HW, occ_div);
   if (rc) return rc;
-  const int64_t need = grad_occ != nullptr ? waldo_occ_composite_bwd_det_workspace_bytes(M, L, HW) : 0;
-  if (need > 0 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
-              (long long)need);
-    return WALDO_EINVAL;
-  }
+  const bool slabs = det && grad_occ != nullptr;
+  const int64_t need = slabs ? waldo_occ_composite_bwd_det_workspace_bytes(M, L, HW) : 0;
+  if (need > 0 && (rc = check_workspace(fn, workspace, workspace_bytes, need))) return rc;
   if (M == 0) return WALDO_OK;
   if (!alpha || !occ || !grad_out || !grad_alpha) {
     set_error("%s: null pointer", fn);
@@ -214,23 +189,38 @@ extern "C" int waldo_occ_composite_bwd_det(const float* alpha, const float* occ,
   }
   hipStream_t st = (hipStream_t)stream;
   const int tiles = (int)((HW + kBlock - 1) / kBlock);
-  const int tpb = grad_occ != nullptr ? kDetTilesPerBlock : 1;
+  const int tpb = slabs ? kDetTilesPerBlock : occ_bwd_tiles_per_block(M, tiles, grad_occ != nullptr);
   const int groups = (tiles + tpb - 1) / tpb;
   float* slab = reinterpret_cast<float*>(workspace);
-  with_padded_layers(L, [&](auto lp) {
-    constexpr int LP = decltype(lp)::value;
-    if (grad_occ != nullptr)
-      hipLaunchKernelGGL((occ_composite_bwd_kernel<LP, true>), dim3((unsigned)(M * groups)), dim3(kBlock), 0, st, alpha,
-                         occ, grad_out, grad_alpha, slab, L, HW, tiles, tpb, groups, occ_div);
-    else
-      hipLaunchKernelGGL((occ_composite_bwd_kernel<LP>), dim3((unsigned)(M * groups)), dim3(kBlock), 0, st, alpha, occ,
-                         grad_out, grad_alpha, grad_occ, L, HW, tiles, tpb, groups, occ_div);
-  });
-  if (grad_occ != nullptr) {
+  auto pixels = [&](auto dt, float* table) {  // table: grad_occ itself (atomics), or the slab
+    with_padded_layers(L, [&](auto lp) {
+      hipLaunchKernelGGL((occ_composite_bwd_kernel<decltype(lp)::value, decltype(dt)::value>), dim3((unsigned)(M * groups)),
+                         dim3(kBlock), 0, st, alpha, occ, grad_out, grad_alpha, table, L, HW, tiles, tpb, groups, occ_div);
+    });
+  };
+  if (!slabs) pixels(std::false_type{}, grad_occ);
+  else pixels(std::true_type{}, slab);
+  if (slabs) {
     // matrix d sums the workgroups of maps d * occ_div .. (d + 1) * occ_div - 1: consecutive rows of the slab
     const int64_t D = (M + occ_div - 1) / occ_div;
     const int nparts = (int)((occ_div < M ? occ_div : M) * groups);
     slab_reduce(slab, grad_occ, D, nparts, L * L, SlabPlain{M * groups, D, D}, st);
   }
   return launch_status(fn);
+}
+
+extern "C" int waldo_occ_composite_bwd(const float* alpha, const float* occ,
+                                       const float* grad_out, float* grad_alpha, float* grad_occ,
+                                       int64_t M, int L, int64_t HW, int64_t occ_div,
+                                       waldo_stream_t stream) {
+  return occ_composite_bwd("waldo_occ_composite_bwd", alpha, occ, grad_out, grad_alpha, grad_occ, M, L, HW, occ_div,
+                           nullptr, 0, stream, false);
+}
+
+extern "C" int waldo_occ_composite_bwd_det(const float* alpha, const float* occ, const float* grad_out,
+                                           float* grad_alpha, float* grad_occ, int64_t M, int L, int64_t HW,
+                                           int64_t occ_div, void* workspace, int64_t workspace_bytes,
+                                           waldo_stream_t stream) {
+  return occ_composite_bwd("waldo_occ_composite_bwd_det", alpha, occ, grad_out, grad_alpha, grad_occ, M, L, HW, occ_div,
+                           workspace, workspace_bytes, stream, true);
 }

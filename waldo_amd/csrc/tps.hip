@@ -314,50 +314,29 @@ static TpsGradGeom tps_grad_geom(int64_t B, int64_t HW, int K3, bool det = false
   return o;
 }
 
-extern "C" int waldo_tps_grid_bwd(const float* basis_t, const float* grad_grid,
-                                  float* grad_mapping, int64_t B, int64_t HW, int K3,
-                                  waldo_stream_t stream) {
-  if (B < 0 || HW < 1 || K3 < 3 || (B + kGradNB - 1) / kGradNB > 65535) {
-    set_error("waldo_tps_grid_bwd: bad shape B=%lld HW=%lld K3=%d", (long long)B, (long long)HW,
-              K3);
-    return WALDO_EINVAL;
-  }
-  if (B == 0) return WALDO_OK;
-  if (!basis_t || !grad_grid || !grad_mapping) {
-    set_error("waldo_tps_grid_bwd: null pointer");
-    return WALDO_EINVAL;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  fill_words(grad_mapping, 0u, sizeof(float) * B * K3 * 2, st);
-  const TpsGradGeom g = tps_grad_geom(B, HW, K3);
-  hipLaunchKernelGGL(tps_grid_bwd_kernel<false>, g.grid, dim3(kBlock), 0, st, basis_t, grad_grid,
-                     grad_mapping, B, HW, K3, g.chunks, g.kper);
-  return launch_status("waldo_tps_grid_bwd");
-}
-
 // ---- deterministic mode: grad_mapping OVERWRITTEN; slab form.  K3 <= 136 (the LDS table of the workgroup's partials)
 extern "C" int64_t waldo_tps_grid_bwd_det_workspace_bytes(int64_t B, int64_t HW, int K3) {
   if (B < 0 || HW < 1 || K3 < 3 || K3 > kGradMaxK || (B + kGradNB - 1) / kGradNB > 65535) return 0;
   return round256(B * (int64_t)tps_grad_geom(B, HW, K3, true).grid.x * K3 * 2 * 4);
 }
 
-extern "C" int waldo_tps_grid_bwd_det(const float* basis_t, const float* grad_grid, float* grad_mapping, int64_t B,
-                                      int64_t HW, int K3, void* workspace, int64_t workspace_bytes,
-                                      waldo_stream_t stream) {
-  const char* fn = "waldo_tps_grid_bwd_det";
+// det: the *_det entry point -- the workgroups store their partial tables to a slab in the workspace and a reduction
+// overwrites grad_mapping, where the atomic form adds them to a zero-filled grad_mapping
+static int tps_grid_bwd(const char* fn, const float* basis_t, const float* grad_grid, float* grad_mapping, int64_t B,
+                        int64_t HW, int K3, void* workspace, int64_t workspace_bytes, waldo_stream_t stream, bool det) {
   if (B < 0 || HW < 1 || K3 < 3 || (B + kGradNB - 1) / kGradNB > 65535) {
     set_error("%s: bad shape B=%lld HW=%lld K3=%d", fn, (long long)B, (long long)HW, K3);
     return WALDO_EINVAL;
   }
-  if (K3 > kGradMaxK) {
-    set_error("%s: K3=%d: the deterministic sum needs the workgroup's table of partials (K3 <= %d)", fn, K3, kGradMaxK);
-    return WALDO_EINVAL;
-  }
-  const int64_t need = waldo_tps_grid_bwd_det_workspace_bytes(B, HW, K3);
-  if (B > 0 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
-              (long long)need);
-    return WALDO_EINVAL;
+  if (det) {
+    if (K3 > kGradMaxK) {
+      set_error("%s: K3=%d: the deterministic sum needs the workgroup's table of partials (K3 <= %d)", fn, K3, kGradMaxK);
+      return WALDO_EINVAL;
+    }
+    if (B > 0) {
+      const int rc = check_workspace(fn, workspace, workspace_bytes, waldo_tps_grid_bwd_det_workspace_bytes(B, HW, K3));
+      if (rc) return rc;
+    }
   }
   if (B == 0) return WALDO_OK;
   if (!basis_t || !grad_grid || !grad_mapping) {
@@ -365,10 +344,29 @@ extern "C" int waldo_tps_grid_bwd_det(const float* basis_t, const float* grad_gr
     return WALDO_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
-  const TpsGradGeom g = tps_grad_geom(B, HW, K3, true);
-  float* slab = reinterpret_cast<float*>(workspace);
-  hipLaunchKernelGGL(tps_grid_bwd_kernel<true>, g.grid, dim3(kBlock), 0, st, basis_t, grad_grid, slab, B, HW, K3,
-                     g.chunks, g.kper);
-  slab_reduce(slab, grad_mapping, B, (int)g.grid.x, K3 * 2, SlabPlain{B * (int64_t)g.grid.x, B, B}, st);
+  const TpsGradGeom g = tps_grad_geom(B, HW, K3, det);
+  if (!det) {
+    fill_words(grad_mapping, 0u, sizeof(float) * B * K3 * 2, st);
+    hipLaunchKernelGGL(tps_grid_bwd_kernel<false>, g.grid, dim3(kBlock), 0, st, basis_t, grad_grid, grad_mapping, B, HW,
+                       K3, g.chunks, g.kper);
+  } else {
+    float* slab = reinterpret_cast<float*>(workspace);
+    hipLaunchKernelGGL(tps_grid_bwd_kernel<true>, g.grid, dim3(kBlock), 0, st, basis_t, grad_grid, slab, B, HW, K3,
+                       g.chunks, g.kper);
+    slab_reduce(slab, grad_mapping, B, (int)g.grid.x, K3 * 2, SlabPlain{B * (int64_t)g.grid.x, B, B}, st);
+  }
   return launch_status(fn);
+}
+
+extern "C" int waldo_tps_grid_bwd(const float* basis_t, const float* grad_grid,
+                                  float* grad_mapping, int64_t B, int64_t HW, int K3,
+                                  waldo_stream_t stream) {
+  return tps_grid_bwd("waldo_tps_grid_bwd", basis_t, grad_grid, grad_mapping, B, HW, K3, nullptr, 0, stream, false);
+}
+
+extern "C" int waldo_tps_grid_bwd_det(const float* basis_t, const float* grad_grid, float* grad_mapping, int64_t B,
+                                      int64_t HW, int K3, void* workspace, int64_t workspace_bytes,
+                                      waldo_stream_t stream) {
+  return tps_grid_bwd("waldo_tps_grid_bwd_det", basis_t, grad_grid, grad_mapping, B, HW, K3, workspace, workspace_bytes,
+                      stream, true);
 }

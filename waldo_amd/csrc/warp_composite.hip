@@ -1,7 +1,7 @@
 // Fused WIF hot path -- C-ABI entry points and dispatch over the compiled (LP, K3P) variants.
 // Kernels: warp_composite_kernels.hip.h; one translation unit per padded layer count and layer element type
 // (warp_composite_lp*.hip, warp_composite_inst.hip.h) so that the variants compile in parallel.
-#include "waldo_common.hip.h"
+#include "det_common.hip.h"
 
 namespace waldo {
 
@@ -122,8 +122,11 @@ int warp_composite_pts_fwd(const char* fn, const T* layers, const float* basis_t
   return launch_status(fn);
 }
 
-// slab of the deterministic grad_occ: one L x L row per (frame, 16 x 16 tile, wave) of K1
-int64_t occ_slab_bytes(int64_t F, int L, int H, int W) { return round256(F * bwd2_layout(F, L, H, W).ntiles16 * 4 * L * L * 4); }
+// workspace of the deterministic backward: the two-kernel backward's own (a multiple of 256 bytes), then the slab of
+// grad_occ: one L x L row per (frame, 16 x 16 tile, wave) of K1
+Carved<2> det_workspace(int64_t F, int L, int H, int W, int K3) {
+  return carve(bwd_workspace_bytes(F, L, H, W, K3), F * bwd2_layout(F, L, H, W).ntiles16 * 4 * L * L * 4);
+}
 
 // det: the *_det entry points -- two-kernel backward only, its workspace followed by the grad_occ slab; grad_mapping
 // and grad_occ are overwritten
@@ -144,12 +147,9 @@ int warp_composite_bwd(const char* fn, const T* layers, const float* basis_t, co
       return WALDO_EINVAL;
     }
     if (F == 0) return WALDO_OK;
-    const int64_t need = bwd_workspace_bytes(F, L, H, W, K3), total = need + occ_slab_bytes(F, L, H, W);
-    if (workspace == nullptr || workspace_bytes < total) {
-      set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)(workspace == nullptr ? 0 : workspace_bytes),
-                (long long)total);
-      return WALDO_EINVAL;
-    }
+    const Carved<2> lo = det_workspace(F, L, H, W, K3);
+    rc = check_workspace(fn, workspace, workspace_bytes, lo.total());
+    if (rc) return rc;
     if (!layers || !basis_t || !mapping || !occ || !grad_rgb || !grad_layers) {
       set_error("%s: null pointer", fn);
       return WALDO_EINVAL;
@@ -157,7 +157,7 @@ int warp_composite_bwd(const char* fn, const T* layers, const float* basis_t, co
     hipStream_t st = (hipStream_t)stream;
     // (the reduction of the control-point partials adds to grad_mapping)
     if (grad_mapping != nullptr) fill_words(grad_mapping, 0u, sizeof(float) * (size_t)F * L * K3 * 2, st);
-    float* slab = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + need);
+    float* slab = lo.at<float>(workspace, 1);
     with_padded_layers(L, [&](auto lp) {
       constexpr int LP = decltype(lp)::value;
       if constexpr (LP <= kBwd2MaxLayers)
@@ -180,18 +180,10 @@ int warp_composite_bwd(const char* fn, const T* layers, const float* basis_t, co
   }
   hipStream_t st = (hipStream_t)stream;
   const int64_t need = debug_option(WALDO_DEBUG_BWD_GENERIC) ? 0 : bwd_workspace_bytes(F, L, H, W, K3);
-  if (!kF32 && (workspace == nullptr || workspace_bytes < need)) {
-    set_error("%s: workspace of %lld bytes given, %lld needed (a 16-bit layer stack has no generic backward)", fn,
-              (long long)(workspace == nullptr ? 0 : workspace_bytes), (long long)need);
-    return WALDO_EINVAL;
-  }
-  if (workspace != nullptr && (need == 0 || workspace_bytes < need)) {
-    if (need != 0) {
-      set_error("%s: workspace of %lld bytes given, %lld needed", fn, (long long)workspace_bytes, (long long)need);
-      return WALDO_EINVAL;
-    }
-    workspace = nullptr;  // shape served by the generic kernel, which needs none
-  }
+  if (!kF32) rc = check_workspace(fn, workspace, workspace_bytes, need, " (a 16-bit layer stack has no generic backward)");
+  else if (workspace != nullptr && need != 0) rc = check_workspace(fn, workspace, workspace_bytes, need);
+  if (rc) return rc;
+  if (need == 0) workspace = nullptr;  // shape served by the generic kernel, which needs none
   with_padded_layers(L, [&](auto lp) {
     constexpr int LP = decltype(lp)::value;
     if constexpr (kF32 || LP <= kBwd2MaxLayers)
@@ -273,8 +265,7 @@ extern "C" int waldo_warp_composite_bwd_dt(const void* layers, const float* basi
 // are OVERWRITTEN.  0: no deterministic kernel for the shape (the generic backward would serve it)
 extern "C" int64_t waldo_warp_composite_bwd_det_workspace_bytes(int64_t F, int L, int H, int W, int K3) {
   if (F < 0 || L < 1 || H < 1 || W < 1) return 0;
-  const int64_t need = bwd_workspace_bytes(F, L, H, W, K3);
-  return need == 0 ? 0 : need + occ_slab_bytes(F, L, H, W);
+  return bwd_workspace_bytes(F, L, H, W, K3) == 0 ? 0 : det_workspace(F, L, H, W, K3).total();
 }
 
 extern "C" int waldo_warp_composite_bwd_det(const void* layers, const float* basis_t, const float* mapping,
