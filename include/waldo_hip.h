@@ -1016,6 +1016,27 @@ int waldo_plane_norm_gelu_bwd(const float* x, int64_t xs_n, int64_t xs_c, const 
                               float* grad_x, float* sums, void* workspace, int64_t workspace_bytes, int64_t N, int C,
                               int H, int W, waldo_stream_t stream);
 
+/* The same with the tensor-sized buffers of element type `dtype` (enum waldo_dtype): a UNet under autocast.  Forward:
+ * x, skip and out; backward: x, grad_out and grad_x -- as void*, their strides in ELEMENTS.  gamma, beta, mean, rstd,
+ * sums and the workspace stay fp32, and so do every register and every sum: a 16-bit value is widened on load (exact),
+ * the arithmetic is the fp32 entry point's, a result is rounded to nearest-even on the store (the bits of
+ * `fp32_result.to(dtype)`; a NaN stays a NaN), and out[n, C + cs] is still the bits of skip[n, cs].  The regimes count
+ * values: waldo_plane_norm_limits and waldo_plane_norm_workspace_bytes hold for every dtype.  16-byte loads and stores
+ * -- 8 consecutive 16-bit values per lane -- when every typed pointer is 16-byte aligned and H W and the strides are
+ * multiples of 8, element accesses otherwise; the in-lane sums then run over other elements than the fp32 layout's, in
+ * an order that is just as fixed: the same bits from run to run, not the fp32 entry point's rounded.
+ * WALDO_DTYPE_F32: exactly the fp32 entry point.  An unknown code: WALDO_EINVAL ("unknown dtype") before any pointer
+ * is looked at.  "not aligned": a 16-bit buffer off a 2-byte boundary, any other off a 4-byte one (an odd-H W plane
+ * reached through a channel slice is 2- but not 4-byte aligned, and is accepted).  Every other check as above. */
+int waldo_plane_norm_gelu_fwd_dt(const void* x, int64_t xs_n, int64_t xs_c, const float* gamma, const float* beta,
+                                 float eps, const void* skip, int64_t ss_n, int64_t ss_c, void* out, int64_t os_n,
+                                 float* mean, float* rstd, void* workspace, int64_t workspace_bytes, int64_t N, int C,
+                                 int Cs, int H, int W, int dtype, waldo_stream_t stream);
+int waldo_plane_norm_gelu_bwd_dt(const void* x, int64_t xs_n, int64_t xs_c, const float* gamma, const float* beta,
+                                 const float* mean, const float* rstd, const void* grad_out, int64_t gs_n,
+                                 int64_t gs_c, void* grad_x, float* sums, void* workspace, int64_t workspace_bytes,
+                                 int64_t N, int C, int H, int W, int dtype, waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

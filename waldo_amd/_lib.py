@@ -132,6 +132,11 @@ SIGNATURES = {
                                   _i64, _int, _int, _int, _int, _stream],
     "waldo_plane_norm_gelu_bwd": [_c_f, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _c_f, _c_f, _c_f, _i64, _i64,
                                   _int, _int, _int, _stream],
+    # the same with 16-bit tensor-sized buffers: a WALDO_DTYPE_* code before the stream
+    "waldo_plane_norm_gelu_fwd_dt": [_c_f, _i64, _i64, _c_f, _c_f, _flt, _c_f, _i64, _i64, _c_f, _i64, _c_f, _c_f, _c_f, _i64,
+                                     _i64, _int, _int, _int, _int, _int, _stream],
+    "waldo_plane_norm_gelu_bwd_dt": [_c_f, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _c_f, _c_f, _c_f, _i64, _i64,
+                                     _int, _int, _int, _int, _stream],
 }
 # workspace size of each *_det entry point (0: no deterministic kernel for the shape)
 DET_QUERIES = {

@@ -1982,24 +1982,37 @@ def _plane_norm_workspace(x):
     if h * w <= _plane_norm_chunk:
         return None, 0
     words = n * c * (-(-h * w // _plane_norm_chunk)) * 2
-    return x.new_empty(words), words * 4
+    return torch.empty(words, dtype=torch.float32, device=x.device), words * 4
+
+
+_PLANE_NORM_16BIT = (torch.bfloat16, torch.float16)
 
 
 class _PlaneNormGelu(torch.autograd.Function):
+    """x, skip and the output (backward: x, grad_out, grad_x) of ONE element type -- fp32, or bf16 / fp16 through the
+    ``_dt`` entry points; weight, bias, the statistics and the workspace fp32 whatever it is."""
+
     @staticmethod
     def forward(ctx, x, weight, bias, skip, eps):
-        _lib.check_cuda(x, weight, bias, skip)
+        _lib.check_cuda(x, skip, half=True)
+        _lib.check_cuda(weight, bias)
         n, c, h, w = x.shape
         x, weight, bias = _dense_planes(x), _c(weight), _c(bias)
         cs = ss_n = ss_c = 0
         if skip is not None:
+            if skip.dtype != x.dtype:
+                raise _lib.WaldoHipError(f"plane_norm_gelu: x is {x.dtype} and skip is {skip.dtype}")
             skip = _dense_planes(skip)
             cs, ss_n, ss_c = skip.shape[1], skip.stride(0), skip.stride(1)
         out = x.new_empty(n, c + cs, h, w)
-        stats = x.new_empty(2, n * c)  # mean, rstd
+        stats = torch.empty(2, n * c, dtype=torch.float32, device=x.device)  # mean, rstd
         ws, nbytes = _plane_norm_workspace(x)
-        _lib.launch("waldo_plane_norm_gelu_fwd", x.device, x, x.stride(0), x.stride(1), weight, bias, float(eps), skip,
-                    ss_n, ss_c, out, (c + cs) * h * w, stats, stats.data_ptr() + 4 * n * c, ws, nbytes, n, c, cs, h, w)
+        args = (x, x.stride(0), x.stride(1), weight, bias, float(eps), skip, ss_n, ss_c, out, (c + cs) * h * w, stats,
+                stats.data_ptr() + 4 * n * c, ws, nbytes, n, c, cs, h, w)
+        if x.dtype == torch.float32:
+            _lib.launch("waldo_plane_norm_gelu_fwd", x.device, *args)
+        else:
+            _lib.launch("waldo_plane_norm_gelu_fwd_dt", x.device, *args, _DTYPE_CODE[x.dtype])
         ctx.save_for_backward(x, weight, bias, stats)
         ctx.has_skip = skip is not None
         return out
@@ -2010,16 +2023,19 @@ class _PlaneNormGelu(torch.autograd.Function):
         x, weight, bias, stats = ctx.saved_tensors
         n, c, h, w = x.shape
         gx = gw = gb = gs = None
-        if grad_out.dtype != torch.float32:
-            grad_out = grad_out.float()
+        if grad_out.dtype != x.dtype:
+            grad_out = grad_out.to(x.dtype)
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             grad_out = _dense_planes(grad_out)  # (its first C channels are read through the strides: no copy)
             gx = x.new_empty(n, c, h, w)
-            sums = x.new_empty(n, c, 2)
+            sums = torch.empty(n, c, 2, dtype=torch.float32, device=x.device)
             ws, nbytes = _plane_norm_workspace(x)
-            _lib.launch("waldo_plane_norm_gelu_bwd", x.device, x, x.stride(0), x.stride(1), weight, bias, stats,
-                        stats.data_ptr() + 4 * n * c, grad_out, grad_out.stride(0), grad_out.stride(1), gx, sums, ws,
-                        nbytes, n, c, h, w)
+            args = (x, x.stride(0), x.stride(1), weight, bias, stats, stats.data_ptr() + 4 * n * c, grad_out,
+                    grad_out.stride(0), grad_out.stride(1), gx, sums, ws, nbytes, n, c, h, w)
+            if x.dtype == torch.float32:
+                _lib.launch("waldo_plane_norm_gelu_bwd", x.device, *args)
+            else:
+                _lib.launch("waldo_plane_norm_gelu_bwd_dt", x.device, *args, _DTYPE_CODE[x.dtype])
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
                 # (over n: a framework reduction with a fixed order, no atomics)
                 gb, gw = (sums[0] if n == 1 else sums.sum(dim=0)).unbind(1)
@@ -2028,14 +2044,28 @@ class _PlaneNormGelu(torch.autograd.Function):
         return gx, gw, gb, gs, None
 
 
-def plane_norm_gelu(x, weight, bias, skip=None, eps=1e-5):
+def plane_norm_gelu(x, weight, bias, skip=None, eps=1e-5, out_dtype=None):
     """``cat([gelu(group_norm(x, C, weight, bias, eps)), skip], dim=1)`` -- one UNet level's work between two
     convolutions (include/waldo_hip.h "Plane norm") as one op: x (N, C, H, W), weight / bias (C), skip (N, Cs, H, W) or
     None -> (N, C + Cs, H, W).  Differentiable in x, weight, bias and skip; keeps x and two floats per plane for the
-    backward, which is free of atomics (the same bits from run to run in either deterministic mode).  fp32; under
-    autocast the inputs are cast to fp32, as ``group_norm``'s are.  Tensors on the CPU take the same arithmetic in
-    framework ops (``plane_norm_gelu_framework``), as do, under autograd, the planes of
-    ``PLANE_NORM_GRAD_FRAMEWORK_HW`` (``_NO_SKIP``)."""
+    backward, which is free of atomics (the same bits from run to run in either deterministic mode).  Tensors on the
+    CPU take the same arithmetic in framework ops (``plane_norm_gelu_framework``), as do, under autograd, the planes of
+    ``PLANE_NORM_GRAD_FRAMEWORK_HW`` (``_NO_SKIP``).
+
+    ``out_dtype=None``: fp32; under autocast the inputs are cast to fp32, as ``group_norm``'s are, and the result is
+    fp32.  A bf16 / fp16 ``x`` on the GPU outside autocast runs as ``out_dtype=x.dtype``.
+
+    ``out_dtype=torch.bfloat16 | torch.float16`` (a UNet under autocast: ``modules.UNet.act_dtype``): x, skip and the
+    result are STORED in that type, with or without autocast around the call (it is disabled inside; the casts carry
+    the gradients).  The kernel widens on load, keeps fp32 statistics, registers and sums, and rounds once to
+    nearest-even on the store -- the values the next convolution under autocast would round the fp32 result to; the
+    skip slice is ``skip``'s bits.  ``x`` and ``skip`` of another type are cast to ``out_dtype`` first: the statistics
+    are then those of the ROUNDED values, which is what a convolution under autocast hands over.  ``weight`` and
+    ``bias`` are used in fp32.  ``grad_x`` and ``grad_skip`` come back in the 16-bit type, ``grad_weight`` and
+    ``grad_bias`` in fp32; the backward keeps the 16-bit x: half the bytes.  The CPU route and the gated planes compute
+    ``plane_norm_gelu_framework`` on fp32 copies and cast the result.  Any other ``out_dtype``: ValueError."""
+    if out_dtype is not None and out_dtype not in _PLANE_NORM_16BIT:
+        raise ValueError(f"plane_norm_gelu: out_dtype must be None, torch.bfloat16 or torch.float16, got {out_dtype!r}")
     if x.dim() != 4:
         raise ValueError(f"plane_norm_gelu: x must be (N, C, H, W), got {tuple(x.shape)}")
     n, c, h, w = x.shape
@@ -2043,11 +2073,23 @@ def plane_norm_gelu(x, weight, bias, skip=None, eps=1e-5):
         raise ValueError(f"plane_norm_gelu: weight and bias must be ({c},), got {tuple(weight.shape)}, {tuple(bias.shape)}")
     if skip is not None and (skip.dim() != 4 or skip.shape[0] != n or tuple(skip.shape[2:]) != (h, w)):
         raise ValueError(f"plane_norm_gelu: skip must be ({n}, Cs, {h}, {w}), got {tuple(skip.shape)}")
-    if not x.is_cuda or x.numel() == 0:
-        return plane_norm_gelu_framework(x, weight, bias, skip, eps)
-    gate = PLANE_NORM_GRAD_FRAMEWORK_HW_NO_SKIP if skip is None else PLANE_NORM_GRAD_FRAMEWORK_HW
-    if gate and any(lo <= h * w <= hi for lo, hi in gate) and torch.is_grad_enabled() \
-            and (x.requires_grad or weight.requires_grad or bias.requires_grad or (skip is not None and skip.requires_grad)):
+    kernel = x.is_cuda and x.numel() != 0
+    if kernel:
+        gate = PLANE_NORM_GRAD_FRAMEWORK_HW_NO_SKIP if skip is None else PLANE_NORM_GRAD_FRAMEWORK_HW
+        kernel = not (gate and any(lo <= h * w <= hi for lo, hi in gate) and torch.is_grad_enabled() and
+                      (x.requires_grad or weight.requires_grad or bias.requires_grad
+                       or (skip is not None and skip.requires_grad)))
+    if out_dtype is None and x.is_cuda and x.dtype in _PLANE_NORM_16BIT and not torch.is_autocast_enabled("cuda"):
+        out_dtype = x.dtype
+    if out_dtype is not None:
+        with torch.autocast(x.device.type, enabled=False):
+            x, weight, bias = x.to(out_dtype), weight.float(), bias.float()
+            skip = None if skip is None else skip.to(out_dtype)
+            if kernel:
+                return _PlaneNormGelu.apply(x, weight, bias, skip, eps)
+            return plane_norm_gelu_framework(x.float(), weight, bias, None if skip is None else skip.float(),
+                                             eps).to(out_dtype)
+    if not kernel:
         return plane_norm_gelu_framework(x, weight, bias, skip, eps)
     if torch.is_autocast_enabled("cuda"):  # fp32 inside, as group_norm: the casts carry the gradients back
         with torch.autocast("cuda", enabled=False):

@@ -5,7 +5,8 @@ The same constructor signature, forward semantics and parameter names (``to_emb.
 checkpoint loads with ``strict=True``.  The convolutions stay the framework's (MIOpen); everything between them -- the
 per-plane normalisation (``ln2d`` = GroupNorm with one group per channel), the GELU and the concatenation with the
 skip -- is one hand-written kernel per level, ``WF.plane_norm_gelu``.  ``fused = False`` runs the spelled-out
-framework ops instead (A/B runs: tools_dev/ab_unet.py)."""
+framework ops instead (A/B runs: tools_dev/ab_unet.py).  ``act_dtype = torch.bfloat16 | torch.float16`` runs the
+network under autocast with its activations stored in 16 bits, the kernel included."""
 import torch
 import torch.nn as nn
 
@@ -61,6 +62,7 @@ class UNet(nn.Module):
         super().__init__()  # (scale_hd and upmode: accepted and unused, as in the reference)
         self.depth = depth
         self.fused = True  # False: GroupNorm, GELU and cat as framework ops
+        self.act_dtype = None
         base = embed_dim // (2 ** (depth - 1))
         self.to_emb = _same_size_conv(num_channels_in, base)
         self.from_emb = _same_size_conv(2 * base, num_channels_out)
@@ -73,12 +75,27 @@ class UNet(nn.Module):
         if zero_init:
             self.from_emb.weight.data.zero_()
 
+    @property
+    def act_dtype(self):
+        """None: the caller's precision.  torch.bfloat16 / torch.float16: ``forward`` runs inside
+        ``torch.autocast(x.device.type, dtype=act_dtype)`` -- fp32 master weights, 16-bit convolutions -- every fused
+        level stores its activations in that type (``WF.plane_norm_gelu(..., out_dtype=act_dtype)``: no fp32 copy of
+        a level crosses memory), and the output is of that type.  With ``fused = False`` the same region is the
+        framework's autocast route (GroupNorm in fp32, rounded by the next convolution)."""
+        return self._act_dtype
+
+    @act_dtype.setter
+    def act_dtype(self, dtype):
+        if dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError(f"UNet: act_dtype must be None, torch.bfloat16 or torch.float16, got {dtype!r}")
+        self._act_dtype = dtype
+
     def _level(self, layer, x, skip=None):
         """conv -> norm -> GELU (-> cat with ``skip``) of one level."""
         y = layer[0](x)
         norm = layer[1].norm
         if self.fused and isinstance(norm, nn.GroupNorm) and norm.num_groups == norm.num_channels:
-            return WF.plane_norm_gelu(y, norm.weight, norm.bias, skip, norm.eps)
+            return WF.plane_norm_gelu(y, norm.weight, norm.bias, skip, norm.eps, out_dtype=self._act_dtype)
         y = layer[2](layer[1](y))
         return y if skip is None else torch.cat([y, skip], dim=1)
 
@@ -86,6 +103,12 @@ class UNet(nn.Module):
         if x.dim() != 4 or x.shape[-2] % (1 << self.depth) or x.shape[-1] % (1 << self.depth):
             raise ValueError(f"UNet: H and W must be multiples of 2**depth = {1 << self.depth} (the skips of the "
                              f"{self.depth} stride-2 levels would not line up), got {tuple(x.shape)}")
+        if self._act_dtype is None:
+            return self._forward(x)
+        with torch.autocast(x.device.type, dtype=self._act_dtype):
+            return self._forward(x)
+
+    def _forward(self, x):
         ys = [self.to_emb(x)]
         for i in range(self.depth):
             ys.append(self._level(self.conv_layers[i], ys[-1]))

@@ -71,12 +71,17 @@ class WIF(nn.Module):
                     upmode=opt.ii_upmode)
 
     @classmethod
-    def with_unet(cls, opt):
+    def with_unet(cls, opt, act_dtype=None):
         """``WIF`` with the reference's own network built from ``opt`` as its constructor does (wif.py:18-28: the channel
         counts from num_lyt, num_obj, use_disocc, ii_score, ii_ab, ctx_len; the rest from ii_embed_dim,
         norm_layer_patch, ii_depth, ii_upmode, load_dim / dim / ii_ft_hd).  The reference WIF's ``state_dict()`` -- only
-        ``unet.*`` keys -- loads into it with ``strict=True``."""
-        return cls(opt, unet=UNet(**cls.unet_arguments(opt)))
+        ``unet.*`` keys -- loads into it with ``strict=True``.  ``act_dtype`` (torch.bfloat16 / torch.float16): the
+        network's ``act_dtype`` -- it runs under autocast with 16-bit activations and hands a 16-bit output to the
+        16-bit fusion kernel; a 16-bit ``vid`` (``decode_output(..., raw_dtype=...)``) goes straight in.  The fused
+        frames stay fp32."""
+        unet = UNet(**cls.unet_arguments(opt))
+        unet.act_dtype = act_dtype
+        return cls(opt, unet=unet)
 
     def get_last_layer(self):
         return self.unet.from_emb.weight

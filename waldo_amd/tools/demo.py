@@ -710,7 +710,7 @@ RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
         device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None, render=None, palette=None,
-        wif_ckpt=None, ii_depth=4, ii_embed_dim=512):
+        wif_ckpt=None, ii_depth=4, ii_embed_dim=512, unet_dtype=None):
     """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
     ``WF.PackedClip``) and predict() reads it as such -- the same results.  ``eval``: also score ``rec_vid`` and
     ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``.  ``out_bytes``
@@ -718,7 +718,11 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
     ``render`` ("trunc" / "round"), ``palette`` (3 * num_lyt integers): predict()'s renders of the decomposition; the
     layout pictures, the flow picture of the last context and ``ctx_obj_lyt`` are written as ``.gif`` + ``_last.png``.
     ``wif_ckpt``: a reference ``ii`` state dict (``load_wif_checkpoint``) run through ``WIF.with_unet`` at ``ii_depth`` /
-    ``ii_embed_dim`` in place of the stand-in network."""
+    ``ii_embed_dim`` in place of the stand-in network; ``unet_dtype`` (torch.bfloat16 / torch.float16): with 16-bit
+    activations (``UNet.act_dtype``) -- with the same ``raw_dtype`` the chain from ``raw_output`` to the fusion kernel is
+    16-bit throughout, no fp32 copy of ``raw_output`` or of a level's activations is made."""
+    if unet_dtype is not None and wif_ckpt is None:
+        raise ValueError("demo.run: unet_dtype needs wif_ckpt (the stand-in network has no activations to store)")
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt, ctx_len=ctx_len, ii_depth=ii_depth, ii_embed_dim=ii_embed_dim)
     size = (dim, int(dim * aspect_ratio))
     clip = wio.load_clip(clip_dir, size, num_lyt, max_frames=frames, packed=packed)
@@ -729,7 +733,7 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
         vid, lyt = clip["vid"].unsqueeze(0).to(dev), clip["lyt"].unsqueeze(0).to(dev)
     warper = Warper(opt).to(dev)
     if wif_ckpt is not None:
-        wif = load_wif_checkpoint(WIF.with_unet(opt), wif_ckpt).to(dev).eval()
+        wif = load_wif_checkpoint(WIF.with_unet(opt, act_dtype=unet_dtype), wif_ckpt).to(dev).eval()
     else:
         wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     net = synthetic_network_outputs(opt, 1, vid.shape[1], ctx_len, seed=seed, device=dev)
@@ -827,6 +831,9 @@ def main():
     ap.add_argument("--wif-ckpt", default=None, metavar="FILE",
                     help="a reference `ii` checkpoint (state dict): run the reference's UNet (WIF.with_unet) in place of "
                          "the stand-in network")
+    ap.add_argument("--unet-dtype", choices=sorted(RAW_DTYPES), default="fp32",
+                    help="with --wif-ckpt: the element type of the UNet's activations (bf16 / fp16: under autocast, the "
+                         "norm + GELU kernel included; with the same --raw-dtype nothing in between is fp32)")
     ap.add_argument("--ii-depth", type=int, default=4, help="with --wif-ckpt: the checkpoint's --s_ii_depth")
     ap.add_argument("--ii-embed-dim", type=int, default=512, help="with --wif-ckpt: the checkpoint's --s_ii_embed_dim")
     args = ap.parse_args()
@@ -834,7 +841,7 @@ def main():
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
               eval=args.eval, out_bytes=args.out_bytes, render=args.render, palette=palette, wif_ckpt=args.wif_ckpt,
-              ii_depth=args.ii_depth, ii_embed_dim=args.ii_embed_dim)
+              ii_depth=args.ii_depth, ii_embed_dim=args.ii_embed_dim, unet_dtype=RAW_DTYPES[args.unet_dtype])
     scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "

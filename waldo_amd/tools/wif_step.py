@@ -15,7 +15,7 @@ The networks outside the path are stand-ins: seeded decoder logits / pose head o
 distributions, and a 1 x 1 convolution (40 -> 5 channels, the UNet's widths at ``ii_score`` + ``ii_ab``, wif.py:19-23)
 in the UNet's place so that ``waldo_wif_fuse_bwd`` receives and produces real gradients.  ``bench.py --config WIF``
 times it.  ``WifStep(..., unet="reference")`` puts the real network there (``WIF.with_unet`` at the recipe's widths:
-``ii_depth 6``, ``ii_embed_dim 512``).
+``ii_depth 6``, ``ii_embed_dim 512``); ``act_dtype`` runs it with 16-bit activations (``UNet.act_dtype``).
 """
 import torch
 import torch.nn as nn
@@ -40,15 +40,17 @@ class WifStep:
 
     frames, ctx_len = 5, 4
 
-    def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in"):
+    def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in", act_dtype=None):
         if unet not in ("stand-in", "reference"):
             raise ValueError(f"WifStep: unet must be 'stand-in' or 'reference', got {unet!r}")
+        if act_dtype is not None and unet != "reference":
+            raise ValueError("WifStep: act_dtype needs unet='reference' (the stand-in has no activations to store)")
         self.opt = o = wif_opt()
         self.clips, self.device = clips, device
         self.warper = Warper(o).to(device)
         torch.manual_seed(seed)
         if unet == "reference":
-            self.wif = WIF.with_unet(o).to(device)
+            self.wif = WIF.with_unet(o, act_dtype=act_dtype).to(device)
             self.unet = self.wif.unet
         else:
             self.unet = nn.Conv2d(3 + o.num_lyt + o.num_obj + 1, 5, 1).to(device)
