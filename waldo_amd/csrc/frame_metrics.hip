@@ -3,10 +3,20 @@
 //
 // One pass kernel per scale: a workgroup owns a 32 x 64 pixel tile of one (frame, channel) and the SSIM outputs at the
 // same positions (an output's 11 x 11 window starts at its pixel).  It stages the tile and its 10-pixel apron of both
-// operands in LDS as fp32 values in [0, 1], runs the separable 11-tap correlation of x, y, x^2 + y^2 and xy (rows into
-// LDS, then columns in registers), and writes one partial sum of lum * cs and of cs (fp64) -- and, at scale 0, of the
-// squared error over its pixels (PSNR).  With MS-SSIM the pass also writes the 2 x 2 average of its pixels (the next
-// scale, symmetric padding at an odd end) into the caller's scratch: each scale's source is read from HBM once.
+// operands in LDS as fp32 values in [0, 1], runs the separable 11-tap correlation (rows into LDS, then columns in
+// registers), and writes one partial sum of lum * cs and of cs (fp64) -- and, at scale 0, of the squared error over its
+// pixels (PSNR).  With MS-SSIM the pass also writes the 2 x 2 average of its pixels (the next scale, symmetric padding
+// at an odd end) into the caller's scratch: each scale's source is read from HBM once.
+//
+// The window statistics are TF's _ssim_helper on SHIFTED operands.  TF forms the variance term as E[x^2 + y^2] -
+// (mx^2 + my^2), a difference of two sums of about 2 mu^2: in fp32 a bright, nearly flat window (mu^2 2000 times the
+// variance + c2) loses the bits the term needs, 4e-5 on the frame's SSIM.  Variance and covariance do not change when
+// a constant is subtracted from an operand, so the workgroup subtracts from each operand the mean of its staged
+// in-frame values (cx, cy), filters x' = x - cx, y' = y - cy, x'^2 + y'^2 and x'y', and takes
+//   cs  = (2 E[x'y'] - 2 dx dy + c2) / (E[x'^2 + y'^2] - (dx^2 + dy^2) + c2),   dx = E[x'], dy = E[y'],
+//   lum = (2 mx my + c1) / (mx^2 + my^2 + c1),   mx = dx + cx, my = dy + cy
+// -- TF's operation order otherwise, commutative in (x, y), and cs = lum = 1 exactly for equal operands.  PSNR and the
+// pooled next scale use the staged values as they are.
 // The combine kernel sums the partials of a frame in a fixed order in fp64: no atomics, the same bits on every call.
 #include "packed_clip.hip.h"
 #include "quantize.hip.h"
@@ -18,7 +28,9 @@ namespace {
 constexpr int kTaps = 11;
 constexpr int kMetTileH = 32, kMetTileW = 64;                   // owned pixels = SSIM outputs of a workgroup
 constexpr int kStageH = kMetTileH + kTaps - 1;               // 42 staged rows
-constexpr int kStageW = kMetTileW + kTaps - 1;               // 74 staged columns
+constexpr int kStageW = kMetTileW + kTaps - 1;               // 74 staged columns that feed an output
+constexpr int kStagePitch = (kStageW + 3) / 4 * 4;           // 76 staged: rows of whole float4s
+constexpr int kRowQuads = kMetTileW / 4;                     // a row thread filters 4 adjacent outputs
 constexpr int kRowsPerThread = kMetTileH / (kBlock / kMetTileW);  // 8 output rows per thread (4 waves x 8 rows)
 constexpr int kScales = 5;
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;  // (k1 max_val)^2, (k2 max_val)^2
@@ -78,7 +90,8 @@ __device__ __forceinline__ void fill_table(float* tab, const Operand& o, const f
 }
 
 // fixed-order sum over the 64 lanes of a wave (every lane gets it)
-__device__ __forceinline__ double wave_sum(double v) {
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
   return v;
 }
@@ -86,9 +99,10 @@ __device__ __forceinline__ double wave_sum(double v) {
 }  // namespace
 
 __global__ __launch_bounds__(kBlock) void frame_metrics_pass_kernel(PassArgs P, int scale0) {
-  __shared__ float sx[kStageH][kStageW], sy[kStageH][kStageW];
-  __shared__ float hq[4][kStageH][kMetTileW];  // row-filtered x, y, x^2 + y^2, xy
+  __shared__ __attribute__((aligned(16))) float sx[kStageH][kStagePitch], sy[kStageH][kStagePitch];
+  __shared__ __attribute__((aligned(16))) float hq[4][kStageH][kMetTileW];  // row-filtered x', y', x'^2 + y'^2, x'y'
   __shared__ float tab_a[kRgbTable], tab_b[kRgbTable];
+  __shared__ float stage_sum[2][kBlock / 64];
   __shared__ double red[3][kBlock / 64];
 
   const unsigned fc = blockIdx.x / (unsigned)P.tiles;  // frame * 3 + channel
@@ -103,49 +117,79 @@ __global__ __launch_bounds__(kBlock) void frame_metrics_pass_kernel(PassArgs P, 
     fill_table(tab_b, P.b, P.rgb_table, P.lo, P.range, P.quant);
     __syncthreads();
   }
-  // stage: pixels outside the frame are 0 (they feed no VALID output)
-  for (int i = threadIdx.x; i < kStageH * kStageW; i += kBlock) {
-    const int r = i / kStageW, q = i - r * kStageW;
+  // stage: pixels outside the frame are 0 (they feed no VALID output); columns 74 and 75 only fill the last float4.
+  // On the way: the sum of the in-frame values of each operand in the 74 columns (the shift), and at scale 0 the
+  // squared error over the owned pixels (PSNR)
+  double se = 0.0;
+  float sum_a = 0.0f, sum_b = 0.0f;
+  for (int i = threadIdx.x; i < kStageH * kStagePitch; i += kBlock) {
+    const int r = i / kStagePitch, q = i - r * kStagePitch;
     const int y = y0 + r, x = x0 + q;
     float va = 0.0f, vb = 0.0f;
     if (y < H && x < W) {
       va = load_unit(P.a, tab_a, bi, ti, c, y, x, P.lo, P.range, P.quant);
       vb = load_unit(P.b, tab_b, bi, ti, c, y, x, P.lo, P.range, P.quant);
+      if (q < kStageW) {
+        sum_a += va;
+        sum_b += vb;
+      }
+      if (scale0 && r < kMetTileH && q < kMetTileW) {
+        const float d = va - vb;
+        se += (double)(d * d);
+      }
     }
     sx[r][q] = va;
     sy[r][q] = vb;
   }
+  sum_a = wave_sum(sum_a);
+  sum_b = wave_sum(sum_b);
+  if ((threadIdx.x & 63) == 0) {
+    stage_sum[0][threadIdx.x / 64] = sum_a;
+    stage_sum[1][threadIdx.x / 64] = sum_b;
+  }
   __syncthreads();
+  // the shift of each operand: the mean of its staged in-frame values, the same bits in every thread
+  const float staged = (float)((min(H - y0, kStageH)) * (min(W - x0, kStageW)));
+  const float cx = ((stage_sum[0][0] + stage_sum[0][1]) + (stage_sum[0][2] + stage_sum[0][3])) / staged;
+  const float cy = ((stage_sum[1][0] + stage_sum[1][1]) + (stage_sum[1][2] + stage_sum[1][3])) / staged;
 
-  // rows: the 11-tap correlation along x of the four quantities, for every staged row
-  for (int i = threadIdx.x; i < kStageH * kMetTileW; i += kBlock) {
-    const int r = i / kMetTileW, q = i - r * kMetTileW;
-    float ex = 0.0f, ey = 0.0f, ess = 0.0f, exy = 0.0f;
+  // rows: the 11-tap correlation along x of the four quantities, for every staged row; a thread filters 4 adjacent
+  // outputs from the 14 staged values under their windows (16 read, as float4s)
+  for (int i = threadIdx.x; i < kStageH * kRowQuads; i += kBlock) {
+    const int r = i / kRowQuads, q = (i - r * kRowQuads) * 4;
+    float xs[16], ys[16], ss[16], xy[16];
 #pragma unroll
-    for (int j = 0; j < kTaps; ++j) {
-      const float xv = sx[r][q + j], yv = sy[r][q + j], g = P.win.g[j];
-      ex += g * xv;
-      ey += g * yv;
-      ess += g * (xv * xv + yv * yv);
-      exy += g * (xv * yv);
+    for (int v = 0; v < 4; ++v) {
+      const float4 a = *reinterpret_cast<const float4*>(&sx[r][q + 4 * v]);
+      const float4 b = *reinterpret_cast<const float4*>(&sy[r][q + 4 * v]);
+      xs[4 * v] = a.x - cx, xs[4 * v + 1] = a.y - cx, xs[4 * v + 2] = a.z - cx, xs[4 * v + 3] = a.w - cx;
+      ys[4 * v] = b.x - cy, ys[4 * v + 1] = b.y - cy, ys[4 * v + 2] = b.z - cy, ys[4 * v + 3] = b.w - cy;
     }
-    hq[0][r][q] = ex;
-    hq[1][r][q] = ey;
-    hq[2][r][q] = ess;
-    hq[3][r][q] = exy;
+#pragma unroll
+    for (int k = 0; k < 4 + kTaps - 1; ++k) {
+      ss[k] = xs[k] * xs[k] + ys[k] * ys[k];
+      xy[k] = xs[k] * ys[k];
+    }
+    float e[4][4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      float ex = 0.0f, ey = 0.0f, ess = 0.0f, exy = 0.0f;
+#pragma unroll
+      for (int j = 0; j < kTaps; ++j) {
+        const float g = P.win.g[j];
+        ex += g * xs[o + j];
+        ey += g * ys[o + j];
+        ess += g * ss[o + j];
+        exy += g * xy[o + j];
+      }
+      e[0][o] = ex, e[1][o] = ey, e[2][o] = ess, e[3][o] = exy;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      *reinterpret_cast<float4*>(&hq[k][r][q]) = make_float4(e[k][0], e[k][1], e[k][2], e[k][3]);
   }
 
-  // PSNR: squared error over the owned pixels (scale 0), and the next scale's 2 x 2 averages of them
-  double se = 0.0;
-  if (scale0) {
-    for (int i = threadIdx.x; i < kMetTileH * kMetTileW; i += kBlock) {
-      const int r = i / kMetTileW, q = i - r * kMetTileW;
-      if (y0 + r < H && x0 + q < W) {
-        const float d = sx[r][q] - sy[r][q];
-        se += (double)(d * d);
-      }
-    }
-  }
+  // the next scale's 2 x 2 averages of the owned pixels
   if (P.pool_a) {
     constexpr int PH = kMetTileH / 2, PW = kMetTileW / 2;
     const int64_t plane = (int64_t)P.Hn * P.Wn, fbase = ((int64_t)f * 3 + c) * plane;
@@ -181,10 +225,11 @@ __global__ __launch_bounds__(kBlock) void frame_metrics_pass_kernel(PassArgs P, 
       for (int j = 0; j < kTaps; ++j)
 #pragma unroll
         for (int k = 0; k < 4; ++k) e[k] += P.win.g[j] * h[k][o + j];
-      // TF's _ssim_helper, in its operation order
+      // TF's _ssim_helper in its operation order, on the shifted operands; the means get the shift back
+      const float mx = e[0] + cx, my = e[1] + cy;
+      const float lum = (mx * my * 2.0f + kC1) / (mx * mx + my * my + kC1);
       const float num0 = e[0] * e[1] * 2.0f;
       const float den0 = e[0] * e[0] + e[1] * e[1];
-      const float lum = (num0 + kC1) / (den0 + kC1);
       const float num1 = e[3] * 2.0f;
       const float cs = (num1 - num0 + kC2) / (e[2] - den0 + kC2);
       if (y0 + rg + o < Hv) {
