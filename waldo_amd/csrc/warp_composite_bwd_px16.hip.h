@@ -313,7 +313,9 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
       const int item = min(item_l, n - 1);
       const int r = (int)(((float)item + 0.5f) * rcp);
       const int xh = item - __mul24(r, bw2);
-      stage_load(stg[l], src, HW, (unsigned)(ox + __mul24(r, W) + 2 * xh));
+      // (layer 0's alpha plane is skipped by the parked instances, L <= 8, where it was measured: -0.7 % of the C3
+      // backward; above, the register-resident instances spill and gain nothing from it -- L = 12: no faster)
+      stage_load(stg[l], src, HW, (unsigned)(ox + __mul24(r, W) + 2 * xh), l != 0 || !kPark);
     };
 #pragma unroll
     for (int l = 0; l < kAhead; ++l) issue(l);
@@ -352,7 +354,10 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
           const Taps tg = finish_taps(tc, H, W);
           const TL* base = layers + ((int64_t)f * L + l) * 4 * HW;
 #pragma unroll
-          for (int c = 0; c < 4; ++c) sv[c] = tap_sample_d(base + c * HW, tg, sx[c], sy[c], delta);
+          for (int c = 0; c < 4; ++c) {
+            if (kPark && l == 0 && c == 3) sv[c] = sx[c] = sy[c] = 0.0f;  // the background's alpha plane is not read
+            else sv[c] = tap_sample_d(base + c * HW, tg, sx[c], sy[c], delta);
+          }
         } else {
           PairBlock pb;
           float fx, fy, shift = 0.0f;
@@ -525,8 +530,9 @@ __global__ __launch_bounds__(kBlock, (GOCC ? 2 : Px16Cfg<LP>::kWavesPerSimd)) vo
           vyr = dyr[l];
           vya = dya[l];
         }
-        ggx[l] = fmaf(gsa, vxa, ap[l] * vxr) * (0.5f * (float)W);
-        ggy[l] = fmaf(gsa, vya, ap[l] * vyr) * (0.5f * (float)H);
+        // (layer 0: a_0 is the constant 1, so gsa == 0 and the alpha term is no instruction at all)
+        ggx[l] = (kPark && l == 0 ? ap[l] * vxr : fmaf(gsa, vxa, ap[l] * vxr)) * (0.5f * (float)W);
+        ggy[l] = (kPark && l == 0 ? ap[l] * vyr : fmaf(gsa, vya, ap[l] * vyr)) * (0.5f * (float)H);
         // |tap contribution| to a colour plane <= |a'_l| sum_c |g_c| < 2^(e - 126), e the biased
         // exponent of that product; to the alpha plane <= |g_alpha| likewise: bilinear weights are
         // <= 1.  Only the exponents go into the table, one packed 16-bit max-reduction per layer;

@@ -162,15 +162,18 @@ __device__ __forceinline__ f32x2_t widen2(uint32_t w) {
 }
 
 // the item whose first texel is `tex` (row-major index inside the plane; even) of the four planes at src, src + HW, ..
+// alpha == false (layer 0, in the callers' unrolled loops a compile-time fact): reduce_comp replaces the background's
+// alpha by 1 (lvd.py:105), so nothing that leaves the kernels depends on its alpha plane -- that plane is not loaded,
+// the staged texels carry 0 in its place (finite: zero-weight taps may read any word of the image).
 template <typename T>
 __device__ __forceinline__ void stage_load(typename StageOf<T>::type& r, const T* __restrict__ src, int64_t HW,
-                                           unsigned tex) {
+                                           unsigned tex, bool alpha) {
   if constexpr (std::is_same_v<T, float>) {
     const unsigned off = tex * 4u;  // bytes; HW * 4 < 2^32 (launcher)
     r.c0 = ld8(src, off);
     r.c1 = ld8(src + HW, off);
     r.c2 = ld8(src + 2 * HW, off);
-    r.c3 = ld8(src + 3 * HW, off);
+    r.c3 = alpha ? ld8(src + 3 * HW, off) : (f32x2_t){0.0f, 0.0f};
   } else {
     auto ld4 = [](const T* base, unsigned byte_off) {
       return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + byte_off);
@@ -179,7 +182,7 @@ __device__ __forceinline__ void stage_load(typename StageOf<T>::type& r, const T
     r.c0 = ld4(src, off);
     r.c1 = ld4(src + HW, off);
     r.c2 = ld4(src + 2 * HW, off);
-    r.c3 = ld4(src + 3 * HW, off);
+    r.c3 = alpha ? ld4(src + 3 * HW, off) : 0u;  // (two zeros of either 16-bit type)
   }
 }
 
@@ -511,7 +514,7 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
       const int item = min(item_l, n - 1);
       const int r = (int)(((float)item + 0.5f) * rcp);
       const int xh = item - __mul24(r, bw2);
-      stage_load(stg[l], src, HW, (unsigned)(ox + __mul24(r, W) + 2 * xh));
+      stage_load(stg[l], src, HW, (unsigned)(ox + __mul24(r, W) + 2 * xh), l != 0);
     };
     WALDO_PRIO_ON(WALDO_FWD_PRIO_MASK, 2);
 #pragma unroll
@@ -565,7 +568,7 @@ __global__ __launch_bounds__(NW * kWave, (NW == 8 ? 1 : 1) * (LP <= 8 ? WALDO_FW
           const Taps t = make_taps_px(gx[l], gy[l], H, W);
           const TL* base = layers + ((int64_t)f * L + l) * 4 * HW;
 #pragma unroll
-          for (int c = 0; c < 4; ++c) s[l][c] = tap_sample(base + c * HW, t, delta);
+          for (int c = 0; c < 4; ++c) s[l][c] = (l == 0 && c == 3) ? 0.0f : tap_sample(base + c * HW, t, delta);
         }
       }
     }

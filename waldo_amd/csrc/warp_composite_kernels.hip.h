@@ -400,11 +400,18 @@ static inline TileGeom tile_geom(int H, int W, int rows) {
   return g;
 }
 
+// Tile form of the staged forward, 5 .. 8 fp32 layers (the instances that are built): 16 x 32 tiles once they still
+// make 2048 workgroups, enough to fill the chip several times over (chunk_frames()'s own bar).  Measured (HISTORY
+// Appendix B, profiles/r04_ab_fwd_tile16x32.txt, profiles/c3_trim_ab.json): at 112 frames of 8 layers, 256 x 512,
+// 16 x 32 is 2 - 2.5 % faster, at 72 frames of 256 x 832 4 %; at 12 layers, 512 x 1024 it is 3 % slower, so twelve
+// layers keep 16 x 16, as do the one-launch `pts` forward (short launches) and the 16-bit stacks (not measured).
+static inline bool fwd_wide_tiles(int nchunks, int H, int W) {
+  const int64_t nt = (int64_t)((W + 2 * kLdsTile - 1) / (2 * kLdsTile)) * ((H + kLdsTile - 1) / kLdsTile);
+  return nchunks * nt >= 2048;
+}
+
 // inv_kernel / src_pts != nullptr (K3 == 19, staged shapes only: checked by the C-ABI entry point):
 // the mapping is computed inside the forward kernel and `mapping` is not read
-#ifndef WALDO_FWD_NW
-#define WALDO_FWD_NW 4
-#endif
 // T: element type of the layer stack.  A 16-bit stack is served by the staged kernel alone (the C-ABI entry point
 // has checked that the shape is one it serves: waldo_warp_composite_pts_supported).
 template <int LP, int K3P, bool EXK, typename T>
@@ -423,24 +430,32 @@ static void launch_fwd(const T* layers, const float* basis_t, const float* mappi
   if constexpr (EXK) {
     // LDS-staged sampling needs 16-byte-aligned rows and a 2x2 block inside the layer
     if (!kF32 || (!debug_option(WALDO_DEBUG_FWD_PLAIN) && staged_eligible(H, W))) {
-      // WALDO_FWD_NW: wavefronts per workgroup of the staged forward, 4 (16 x 16 tiles) or 8 (16 x 32; up to 12 layers)
-      constexpr int NW = (WALDO_FWD_NW == 8 && LP <= 12) ? 8 : 4;
-      constexpr int TW = kLdsTile * NW / 4;
-      const int ntx16 = (W + TW - 1) / TW, nt16 = ntx16 * ((H + kLdsTile - 1) / kLdsTile);
-      dim3 grid16((unsigned)xcd_grid_banded(nchunks, nbands, nt16, 1));
-      auto go = [&](auto exl, auto fold) {
+      // wavefronts per workgroup of the staged forward: 4 (16 x 16 tiles) or 8 (16 x 32: less halo per pixel in the
+      // footprint box, half as many workgroups); both forms give the plain forward's bits
+      auto go = [&](auto exl, auto fold, auto nw) {
         constexpr bool EXL = decltype(exl)::value, FOLD = decltype(fold)::value;
+        constexpr int NW = decltype(nw)::value, TW = kLdsTile * NW / 4;
+        const int ntx16 = (W + TW - 1) / TW, nt16 = ntx16 * ((H + kLdsTile - 1) / kLdsTile);
+        dim3 grid16((unsigned)xcd_grid_banded(nchunks, nbands, nt16, 1));
         hipLaunchKernelGGL((warp_composite_fwd_lds_kernel<LP, EXL, FOLD, NW, T>), grid16, dim3(NW * kWave), 0, st, layers,
                            basis_t, mapping, inv_kernel, src_pts, occ, rgb, alpha, F, L, H, W, fpb, ntx16, nt16,
                            nchunks, nbands, delta);
       };
       using Y = std::true_type;
       using N = std::false_type;
+      using NW4 = std::integral_constant<int, 4>;
       if (src_pts != nullptr) {
-        if (L == LP) go(Y{}, Y{}); else go(N{}, Y{});
-      } else {
-        if (L == LP) go(Y{}, N{}); else go(N{}, N{});
+        if (L == LP) go(Y{}, Y{}, NW4{}); else go(N{}, Y{}, NW4{});
+        return;
       }
+      if constexpr (kF32 && LP == 8) {
+        if (fwd_wide_tiles(nchunks, H, W)) {
+          using NW8 = std::integral_constant<int, 8>;
+          if (L == LP) go(Y{}, N{}, NW8{}); else go(N{}, N{}, NW8{});
+          return;
+        }
+      }
+      if (L == LP) go(Y{}, N{}, NW4{}); else go(N{}, N{}, NW4{});
       return;
     }
   }
