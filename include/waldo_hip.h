@@ -1037,6 +1037,37 @@ int waldo_plane_norm_gelu_bwd_dt(const void* x, int64_t xs_n, int64_t xs_c, cons
                                  int64_t gs_c, void* grad_x, float* sums, void* workspace, int64_t workspace_bytes,
                                  int64_t N, int C, int H, int W, int dtype, waldo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Token attention: the attention of the LVD transformer blocks (the reference's models/modules/transform.py:109-117
+ * FullAttention and :175-185 ObjAttention: matmul -> scale -> softmax -> matmul, with the permutes of qkv / kv, the
+ * cat of the two key sets and the transpose in front of proj) in one call, forward only.
+ *
+ * waldo_token_attention_fwd: for every b < B, h < H, i < Nq, over the keys j of segment 1 (Nk1 of them) FOLLOWED BY
+ *   those of segment 2 (Nk2 of them; Nk2 == 0: k2, v2 and their strides are ignored and may be NULL / 0):
+ *     out[b, i, h, :] = sum_j softmax_j(scale * q[b, i, h, :] . k[b, j, h, :]) v[b, j, h, :]
+ *   Every operand is a VIEW, never copied: a pointer, a batch stride (x_b) and a token stride (x_n) in floats; heads
+ *   are D floats apart and the D values of a (token, head) row are consecutive -- so q, k, v may be the three slices
+ *   of one (B, N, 3 H D) qkv projection and k, v the two slices of a (B, N, 2 H D) kv projection.  out is
+ *   (B, Nq, H D) contiguous, the layout the output projection takes.  D is 16, 32 or 64.
+ *   fp32 throughout: both products on the exact-fp32 matrix instruction (k-ordered fma chains), the softmax online
+ *   (a running maximum and sum per row; the keys past the end of a tile are masked with -inf, a row always has a
+ *   live key).  NO SCORE MATRIX in memory, no workspace, no allocation, no synchronisation, NO ATOMICS: the same bits
+ *   from run to run; the caller's stream; capturable in a graph.
+ *   waldo_token_attention_limits(out, n): writes the first n of {query rows per workgroup, keys per tile, the head
+ *   dimensions served (ascending)} and returns how many values there are.
+ *
+ * B == 0 or Nq == 0: WALDO_OK without a launch.  WALDO_EINVAL with a message before any launch: "bad shape" (B, Nq,
+ * Nk2 < 0; H, Nk1 < 1), "bad head dimension", "bad scale" (not finite), "too large", "negative stride", "bad token
+ * stride" (no multiple of 4 floats: rows are read in 16-byte pieces, and a view with a non-unit inner stride has no
+ * description here), "bad batch stride" (no multiple of 4 floats), "null pointer", "not aligned" (a pointer off a
+ * 16-byte boundary).
+ * ------------------------------------------------------------------------------------- */
+int waldo_token_attention_limits(int* out, int n);
+int waldo_token_attention_fwd(const float* q, int64_t qs_b, int64_t qs_n, const float* k1, int64_t k1s_b, int64_t k1s_n,
+                              const float* v1, int64_t v1s_b, int64_t v1s_n, const float* k2, int64_t k2s_b,
+                              int64_t k2s_n, const float* v2, int64_t v2s_b, int64_t v2s_n, float* out, float scale,
+                              int64_t B, int H, int D, int Nq, int Nk1, int Nk2, waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

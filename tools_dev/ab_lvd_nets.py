@@ -1,0 +1,194 @@
+"""A/B of the fused token attention (WF.token_attention, csrc/token_attention.hip) against the two framework routes -- the
+reference's sequence of ops (WF.token_attention_framework) and ``F.scaled_dot_product_attention`` on the same views --
+at the LVD recipe's shapes (scripts/cityscapes/train_lvd.sh: 512 wide, 8 heads, D = 64) on one MI355X, and of the whole
+``nets.LVD`` with ``fused`` True against False.  Writes profiles/lvd_nets.json.
+
+    python tools_dev/ab_lvd_nets.py [--out profiles/lvd_nets.json] [--sections op,lvd] [--rounds 20] [--warmup 5]
+
+Sections:
+  op   the op alone, forward without autograd, fp32: the PoseEstimator's self-attention (56 and 112 sequences of
+       128 + 256 + 128 = 512 tokens, q / k / v the slices of one packed qkv projection) and the LayerEstimator's
+       two-segment attention (4 and 8 clips, 384 queries against 384 + 4 * 128 = 896 keys, the slices of two packed kv
+       projections).  ``sdpa`` gets the ``cat`` of the two key / value sets that it needs and the transpose + reshape to
+       the (B, N, H D) layout the other two routes return;
+  lvd  the whole network without autograd at the recipe's widths for 4 clips of 14 frames: encode_input,
+       estimate_layer (4 context frames), estimate_pose, estimate_alpha_grid_occ -- ``fused`` True against False of the
+       SAME module.
+Method: device time between events; the routes ALTERNATE inside one process (one call of each per round), --rounds
+rounds after --warmup of each; median, minimum and quartiles per route.  ``spread`` is the largest of the routes'
+interquartile ranges over their medians; ``kernel_wins`` says median(kernel) * (1 + spread) < median(each other route).
+Peak memory is ``max_memory_allocated`` above what was allocated before the call (the inputs), one call each.  A run
+without a GPU fails."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from waldo_amd import functional as WF  # noqa: E402
+
+HEADS, D = 8, 64
+# (name, sequences, queries, keys of the first segment, keys of the second or None)
+OP_SHAPES = (("pose_56", 56, 512, 512, None), ("pose_112", 112, 512, 512, None),
+             ("layer_4", 4, 384, 384, 512), ("layer_8", 8, 384, 384, 512))
+
+
+def alternate(routes, warmup, rounds):
+    """{name: stats} of callables timed alternately: one call of each per round."""
+    for _ in range(warmup):
+        for fn in routes.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in routes}
+    for _ in range(rounds):
+        for k, fn in routes.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    out = {}
+    for k, v in ms.items():
+        q1, med, q3 = (float(x) for x in np.percentile(v, [25, 50, 75]))
+        out[k] = dict(median_ms=med, min_ms=float(np.min(v)), q1_ms=q1, q3_ms=q3, rounds=len(v))
+    out["spread"] = max((s["q3_ms"] - s["q1_ms"]) / s["median_ms"] for s in out.values())
+    return out
+
+
+def peak_above_inputs(fn):
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    keep = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - before
+    del keep
+    return int(peak)
+
+
+def op_operands(seqs, nq, nk1, nk2, device, seed=0):
+    """The views the modules hand to the op: logits of standard deviation 2."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    mk = lambda n, parts: torch.randn(seqs, n, parts, HEADS, D, generator=g, device=device) * 1.4
+    if nk2 is None:
+        return (*mk(nq, 3).unbind(2), None, None)
+    return (mk(nq, 1)[:, :, 0], *mk(nk1, 2).unbind(2), *mk(nk2, 2).unbind(2))
+
+
+def sdpa_route(q, k, v, k2=None, v2=None):
+    if k2 is not None:
+        k, v = torch.cat([k, k2], dim=1), torch.cat([v, v2], dim=1)
+    out = F.scaled_dot_product_attention(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3))
+    return out.transpose(1, 2).reshape(q.shape[0], q.shape[1], -1)
+
+
+def kernel_route(q, k, v, k2=None, v2=None):
+    assert WF._token_attention_served(q, k, v, k2, v2) is not None
+    return WF.token_attention(q, k, v, k2, v2)
+
+
+def op_routes(ops):
+    return {"kernel": lambda: kernel_route(*ops), "framework": lambda: WF.token_attention_framework(*ops),
+            "sdpa": lambda: sdpa_route(*ops)}
+
+
+def op_flops(seqs, nq, nk):
+    return 4.0 * seqs * HEADS * nq * nk * D   # two products, a multiply and an add each
+
+
+def section_op(device, warmup, rounds):
+    res = {}
+    for name, seqs, nq, nk1, nk2 in OP_SHAPES:
+        ops = op_operands(seqs, nq, nk1, nk2, device)
+        with torch.no_grad():
+            routes = op_routes(ops)
+            ref = routes["framework"]()
+            err = {k: float((fn() - ref).abs().max()) for k, fn in routes.items() if k != "framework"}
+            del ref
+            st = alternate(routes, warmup, rounds)
+            for k, fn in routes.items():
+                st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+        others = [st[k]["median_ms"] for k in ("framework", "sdpa")]
+        st["kernel_over_framework"] = st["kernel"]["median_ms"] / st["framework"]["median_ms"]
+        st["kernel_over_sdpa"] = st["kernel"]["median_ms"] / st["sdpa"]["median_ms"]
+        st["kernel_wins"] = bool(st["kernel"]["median_ms"] * (1 + st["spread"]) < min(others))
+        st["kernel_tflops"] = op_flops(seqs, nq, nk1 + (nk2 or 0)) / (st["kernel"]["median_ms"] * 1e-3) / 1e12
+        st["max_abs_difference_from_framework"] = err
+        st["shape"] = dict(sequences=seqs, heads=HEADS, head_dim=D, queries=nq, keys=[nk1] + ([nk2] if nk2 else []))
+        res[name] = st
+        print(name, json.dumps({k: (round(v["median_ms"], 4), v["peak_bytes_above_inputs"] >> 20) for k, v in st.items()
+                                if isinstance(v, dict) and "median_ms" in v}), "spread", round(st["spread"], 3),
+              "wins", st["kernel_wins"], flush=True)
+    return res
+
+
+def lvd_forward(net, inp, ctx_len):
+    x = net(input=inp, mode="encode_input")
+    x_obj, x_bg, cls = net(x=x[:, :ctx_len], mode="estimate_layer")
+    obj_pose, bg_pose, occ_score = net(x=x, x_obj=x_obj, x_bg=x_bg, mode="estimate_pose")[:3]
+    return net(x_obj=x_obj, obj_pose=obj_pose, bg_pose=bg_pose, occ_score=occ_score, mode="estimate_alpha_grid_occ")
+
+
+def section_lvd(device, warmup, rounds, clips=4, frames=14, opt=None):
+    from waldo_amd.nets import LVD
+    from waldo_amd.tools.lvd_step import recipe_net_opt
+    opt = opt or recipe_net_opt()
+    torch.manual_seed(0)
+    net = LVD(opt).to(device).eval()
+    g = torch.Generator(device=device).manual_seed(1)
+    h, w = opt.dim, int(opt.dim * opt.aspect_ratio)
+    inp = torch.randn(clips, frames, opt.num_lyt + 2, h, w, generator=g, device=device)
+
+    def route(fused):
+        def fn():
+            net.fused = fused
+            return lvd_forward(net, inp, opt.ctx_len)
+        return fn
+
+    with torch.no_grad():
+        routes = {"fused": route(True), "framework": route(False)}
+        st = alternate(routes, warmup, rounds)
+        for k, fn in routes.items():
+            st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+    st["fused_over_framework"] = st["fused"]["median_ms"] / st["framework"]["median_ms"]
+    st["fused_wins"] = bool(st["fused"]["median_ms"] * (1 + st["spread"]) < st["framework"]["median_ms"])
+    st["shape"] = dict(clips=clips, frames=frames, embed_dim=opt.embed_dim, heads=opt.num_heads, raster=[h, w],
+                       num_obj=opt.num_obj, depths=[opt.oe_depth, opt.pe_depth])
+    print("lvd", json.dumps({k: round(v["median_ms"], 3) for k, v in st.items() if isinstance(v, dict) and "median_ms" in v}),
+          "spread", round(st["spread"], 3), flush=True)
+    return st
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lvd_nets.json"))
+    ap.add_argument("--sections", default="op,lvd")
+    ap.add_argument("--rounds", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("ab_lvd_nets: no GPU (a measurement does not fall back)")
+    device = torch.device("cuda:0")
+    doc = {}
+    if os.path.exists(args.out):
+        with open(args.out) as fh:
+            doc = json.load(fh)
+    doc.update(device=torch.cuda.get_device_name(0), torch=torch.__version__, limits=WF.token_attention_limits(),
+               method=dict(rounds=args.rounds, warmup=args.warmup, timing="device events, routes alternating"))
+    for sec in args.sections.split(","):
+        doc[sec] = {"op": section_op, "lvd": section_lvd}[sec](device, args.warmup, args.rounds)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(doc, fh, indent=1, sort_keys=True)
+    print(args.out)
+
+
+if __name__ == "__main__":
+    main()

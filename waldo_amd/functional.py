@@ -2096,3 +2096,134 @@ def plane_norm_gelu(x, weight, bias, skip=None, eps=1e-5, out_dtype=None):
             return _PlaneNormGelu.apply(x.float(), weight.float(), bias.float(), None if skip is None else skip.float(),
                                         eps)
     return _PlaneNormGelu.apply(x, weight, bias, skip, eps)
+
+
+# --------------------------------------------------------------------------------------
+# token attention: softmax(scale q k^T) v over one or two key / value segments (the LVD transformer blocks)
+# --------------------------------------------------------------------------------------
+_token_attention_limits = None
+
+
+def token_attention_limits():
+    """``{"q_tile", "k_tile", "head_dims"}`` of the kernel (``waldo_token_attention_limits``): query rows per
+    workgroup, keys per LDS tile, the head dimensions it serves."""
+    global _token_attention_limits
+    if _token_attention_limits is None:
+        buf = (ctypes.c_int * 16)()
+        n = _lib.load().waldo_token_attention_limits(buf, 16)
+        vals = [int(buf[i]) for i in range(n)]
+        _token_attention_limits = {"q_tile": vals[0], "k_tile": vals[1], "head_dims": tuple(vals[2:])}
+    return dict(_token_attention_limits)
+
+
+def _token_attention_check(q, k, v, k2, v2):
+    if q.dim() != 4:
+        raise ValueError(f"token_attention: q must be (B, Nq, H, D), got {tuple(q.shape)}")
+    b, _, h, d = q.shape
+    if k.dim() != 4 or k.shape[0] != b or tuple(k.shape[2:]) != (h, d) or k.shape[1] < 1 or v.shape != k.shape:
+        raise ValueError(f"token_attention: k and v must be ({b}, Nk >= 1, {h}, {d}), got {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    if (k2 is None) != (v2 is None):
+        raise ValueError("token_attention: k2 and v2 come together")
+    if k2 is not None and (k2.dim() != 4 or k2.shape[0] != b or tuple(k2.shape[2:]) != (h, d) or v2.shape != k2.shape):
+        raise ValueError(f"token_attention: k2 and v2 must be ({b}, Nk2, {h}, {d}), got {tuple(k2.shape)}, "
+                         f"{tuple(v2.shape)}")
+
+
+def token_attention_framework(q, k, v, k2=None, v2=None, scale=None):
+    """``token_attention`` spelled out in framework ops, as the reference runs it (models/modules/transform.py:109-117
+    for one segment, :175-185 for two): matmul, scale, ``cat`` of the two score blocks, softmax, ``cat`` of the values,
+    matmul, transpose, reshape.  The CPU route of ``token_attention``, the ``fused = False`` route of the transformer
+    blocks and what the backward of the kernel route differentiates."""
+    _token_attention_check(q, k, v, k2, v2)
+    b, nq, h, d = q.shape
+    scale = d ** -0.5 if scale is None else scale
+    qh, vh = q.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3)
+    attn = (qh @ k.permute(0, 2, 3, 1)) * scale
+    if k2 is not None:
+        attn = torch.cat([attn, (qh @ k2.permute(0, 2, 3, 1)) * scale], dim=-1)
+        vh = torch.cat([vh, v2.permute(0, 2, 1, 3)], dim=2)
+    attn = attn.softmax(dim=-1)
+    return (attn @ vh).transpose(1, 2).reshape(b, nq, h * d)
+
+
+def _token_view_strides(t):
+    """(batch stride, token stride) of a (B, N, H, D) view whose (token, head) rows are D consecutive floats D apart
+    and start on 16-byte boundaries -- what ``waldo_token_attention_fwd`` reads in place -- else None.  (The stride of
+    an axis of one element is free.)"""
+    b, n, h, d = t.shape
+    if (d > 1 and t.stride(3) != 1) or (h > 1 and t.stride(2) != d) or t.data_ptr() % 16:
+        return None
+    sb, sn = (t.stride(0) if b > 1 else 0), (t.stride(1) if n > 1 else 0)
+    if sb % 4 or sn % 4 or sb < 0 or sn < 0:
+        return None
+    return sb, sn
+
+
+def _token_attention_served(q, k, v, k2, v2):
+    """The strides of the operands if the kernel serves them as they lie, else None."""
+    ts = [t for t in (q, k, v, k2, v2) if t is not None]
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.device == q.device for t in ts):
+        return None
+    if q.shape[3] not in token_attention_limits()["head_dims"] or q.numel() == 0:
+        return None
+    if k2 is not None and k2.shape[1] == 0:
+        return None
+    if torch.is_autocast_enabled("cuda"):
+        return None
+    strides = [_token_view_strides(t) for t in ts]
+    return None if any(s is None for s in strides) else strides
+
+
+class _TokenAttention(torch.autograd.Function):
+    """Forward: the kernel on the views as they lie.  Backward: the framework sequence recomputed from the saved views
+    under ``enable_grad`` and differentiated -- the forward keeps no score tensor."""
+
+    @staticmethod
+    def forward(ctx, scale, strides, q, k, v, k2, v2):
+        b, nq, h, d = q.shape
+        out = torch.empty(b, nq, h * d, dtype=torch.float32, device=q.device)
+        flat = []
+        for t, s in zip((q, k, v), strides):
+            flat += [t, s[0], s[1]]
+        if k2 is not None:
+            flat += [k2, strides[3][0], strides[3][1], v2, strides[4][0], strides[4][1]]
+        else:
+            flat += [None, 0, 0, None, 0, 0]
+        _lib.launch("waldo_token_attention_fwd", q.device, *flat, out, float(scale), b, h, d, nq, k.shape[1],
+                    0 if k2 is None else k2.shape[1])
+        ctx.scale = scale
+        ctx.two = k2 is not None
+        ctx.save_for_backward(*((q, k, v, k2, v2) if ctx.two else (q, k, v)))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        need = ctx.needs_input_grad[2:2 + len(ctx.saved_tensors)]
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_(n) for t, n in zip(ctx.saved_tensors, need)]
+            out = token_attention_framework(*leaves, scale=ctx.scale)
+            wanted = [t for t, n in zip(leaves, need) if n]
+            grads = iter(torch.autograd.grad(out, wanted, grad_out)) if wanted else iter(())
+        res = [next(grads) if n else None for n in need]
+        return (None, None, *res, *([None] * (5 - len(res))))
+
+
+def token_attention(q, k, v, k2=None, v2=None, scale=None):
+    """``softmax(scale q k^T) v`` per head over the keys of (k, v) followed by those of (k2, v2): q (B, Nq, H, D) and
+    k / v (B, Nk, H, D), k2 / v2 (B, Nk2, H, D) or None -> (B, Nq, H D), the layout the output projection takes.
+    ``scale``: ``D ** -0.5`` when None.  The operands are VIEWS and are not copied: the slices of a packed ``qkv`` or
+    ``kv`` projection as they lie (``qkv.view(B, N, 3, H, D)[:, :, i]``).
+
+    fp32 tensors on the GPU with D in ``token_attention_limits()["head_dims"]``, a unit inner stride, heads D apart
+    and rows on 16-byte boundaries run ``waldo_token_attention_fwd`` (include/waldo_hip.h "Token attention"): no score
+    tensor, no atomics -- the same bits from run to run in either deterministic mode.  Its backward recomputes
+    ``token_attention_framework`` from the saved views and differentiates that.  Everything else -- CPU tensors,
+    another D, another dtype (16-bit inputs, autocast), another layout -- IS ``token_attention_framework``."""
+    _token_attention_check(q, k, v, k2, v2)
+    scale = q.shape[3] ** -0.5 if scale is None else float(scale)
+    strides = _token_attention_served(q, k, v, k2, v2)
+    if strides is None:
+        return token_attention_framework(q, k, v, k2, v2, scale)
+    return _TokenAttention.apply(scale, strides, q, k, v, k2, v2)

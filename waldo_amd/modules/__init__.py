@@ -1,2 +1,3 @@
 from .warp import TPSWarp, InverseWarp, kernel_distance  # noqa: F401
-from .conv import UNet  # noqa: F401
+from .conv import UNet, ConvPatchProj  # noqa: F401
+from .transform import Block, MultiBlocks  # noqa: F401

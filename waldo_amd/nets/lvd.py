@@ -17,6 +17,9 @@ No CPU path: tensors must live on the GPU.
 The occlusion products never materialise the reference's (L, L, h, w) broadcast, so the
 ``fast`` / ``restrict_to_ctx`` memory switches of the reference only change WHAT is returned
 (``alpha_unflt`` is None when ``load_dim > 0``, as in the reference), not how it is computed.
+
+The networks in front of the path -- ``ImageEncoder``, ``LayerEstimator``, ``PoseEstimator``, ``ImageDecoder`` and the
+``LVD`` module that holds them with the ``Warper`` -- follow at the end of the file.
 """
 import torch
 import torch.nn as nn
@@ -749,3 +752,452 @@ def _raw_dtype(raw_dtype):
     if raw_dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise ValueError(f"raw_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {raw_dtype}")
     return raw_dtype
+
+
+# ---------------------------------------------------------------------- the networks in front of the Warper
+# Drop-ins for the reference's ImageEncoder, ImageDecoder, PoseEstimator, LayerEstimator and LVD (models/nets/lvd.py:
+# 11-460, 873-950): the same constructors (from ``opt``), forward semantics, parameter AND buffer names, so that a
+# reference ``pe`` checkpoint loads with ``strict=True``.  Linear, LayerNorm and the convolutions are the framework's;
+# the attention of the transformer blocks is ``WF.token_attention`` (csrc/token_attention.hip), the conv -> norm -> GELU
+# triples of the patch projections ``WF.plane_norm_gelu``, and what follows the networks is the warp path above.
+# ``fused = False`` on any of them: framework ops only, which also run on the CPU (up to the Warper, which has no CPU
+# form).
+def lvd_net_opt(**over):
+    """The reference's defaults (tools/options.py) for every field its models/nets/lvd.py reads; ``over`` overrides.
+    (``dim``, ``aspect_ratio`` and ``load_dim`` are the base options' defaults; ``num_lyt`` is set per dataset there:
+    20 is Cityscapes'.)"""
+    import types
+    d = dict(
+        # rasters and tokens
+        dim=512, aspect_ratio=1.0, load_dim=0, scale_factor=1, patch_size=8, latent_shape=[4, 8], obj_shape=[4, 4],
+        embed_dim=512, num_heads=8, norm_layer="ln", norm_layer_patch="ln2d", dropout=0, use_hr=False, hr_ratio=1,
+        num_obj=1, num_lyt=20, input_rgb=True, input_lyt=False, input_flow=False, ctx_len=10,
+        # layer estimator
+        oe_depth=8, oe_num_timesteps=5, decompose_embed_oe=False, pred_cls=False,
+        # pose estimator and object decoder
+        pe_depth=8, pe_pts_mode="prior", pe_estimator_init_mode="zero", pe_decoder_init_mode="",
+        pe_decoder_use_prior=False, pe_repeat_border=False, pe_use_refiner=False, pe_use_post_refiner=False,
+        pe_use_edge_filter=False, pe_refiner_blend_mode_obj="", pe_refiner_blend_mode_bg="",
+        init_scale_obj=1., mul_scale_obj=1., mul_delta_obj=1., use_delta=True, rd_translate_bias=False,
+        translate_bias_mul=1, circle_translate_bias=False, circle_translate_radius=0.25,
+        bound_rest=False, soft_bound_rest=False, min_scale_bound=-0.5, max_scale_bound=0.5, max_translate_bound=0.5,
+        norm_scale=False, tgt_scale=1, bound_scale=False, min_scale=0, max_scale=2,
+        has_bg=False, fix_bg=False, fix_bg1=False, bg_mul=1., occ_mode="", use_last_pose_decoder=False,
+        pad_obj_alpha=0, pad_bg_alpha=0, freeze_obj=False, remove_obj=False,
+        # warp path
+        time_dropout=False, num_perm_grid=1, normalize_alpha=False, use_lyt_filtering=False, use_lyt_opacity=False,
+        weight_cls=False, min_cls=0.001, include_self=False, no_filter=False, allow_ghost=False, use_disocc=False,
+        restrict_to_ctx=False)
+    unknown = set(over) - set(d)
+    if unknown:
+        raise TypeError(f"lvd_net_opt: unknown fields {sorted(unknown)}")
+    d.update(over)
+    return types.SimpleNamespace(**d)
+
+
+def get_num_channels(dtype, num_lyt):
+    """Channels of an image whose content ``dtype`` spells: A(lpha) 1, L(ayout) num_lyt, M 1, S 2, RGB 3, F(low) 2."""
+    return (("A" in dtype) + num_lyt * ("L" in dtype) + ("M" in dtype) + 2 * ("S" in dtype) + 3 * ("RGB" in dtype)
+            + 2 * ("F" in dtype))
+
+
+def get_circle(shape, p=1.):
+    """(1, H, W) bool: the pixels closer than p min(H, W) / 2 to (H / 2, W / 2) (lvd.py:202-209)."""
+    h, w = shape
+    x = (torch.arange(w).view(1, -1).expand(h, -1) - w / 2).abs()
+    y = (torch.arange(h).view(-1, 1).expand(-1, w) - h / 2).abs()
+    return ((x ** 2 + y ** 2).sqrt() < p * min(h, w) / 2).unsqueeze(0)
+
+
+def _set_fused(module, value):
+    """``fused`` of a network: passed on to every sub-module that has the switch."""
+    for m in module.modules():
+        if m is not module and hasattr(m, "fused"):
+            m.fused = bool(value)
+
+
+class _Net(nn.Module):
+    """A network with the ``fused`` switch: True (default) the hand-written kernels where they exist, False framework
+    ops only.  Setting it sets every sub-module's."""
+
+    def __init__(self):
+        super().__init__()
+        self._fused = True
+
+    @property
+    def fused(self):
+        return self._fused
+
+    @fused.setter
+    def fused(self, value):
+        self._fused = bool(value)
+        _set_fused(self, value)
+
+
+class ImageEncoder(_Net):
+    def __init__(self, opt, dtype="RGB"):
+        from ..modules.conv import ConvPatchProj, init_weights
+        super().__init__()
+        self.scale_factor = opt.load_dim / opt.dim if opt.load_dim > 0 else opt.scale_factor
+        self.from_img = ConvPatchProj(opt.patch_size, opt.embed_dim, opt.norm_layer_patch,
+                                      get_num_channels(dtype, opt.num_lyt), from_patch=True, hr_ratio=opt.hr_ratio,
+                                      use_hr=opt.use_hr)
+        self.apply(init_weights)
+
+    def forward(self, vid, return_list=False):
+        """vid (..., C, H, W) -> tokens (..., L, embed) (``return_list``: the pyramid of the flattened batch)."""
+        lead = vid.shape[:-3]
+        img = scale(vid.reshape(-1, *vid.shape[-3:]), 1 / self.scale_factor)
+        x = self.from_img(img, return_list=return_list)
+        return x if return_list else x.reshape(*lead, *x.shape[1:])
+
+
+class ImageDecoder(_Net):
+    def __init__(self, opt, dtype="RGB", init_mode="", skip_channels=0, use_prior=False):
+        from ..modules.conv import ConvPatchProj, init_weights
+        from ..modules.transform import CustomNorm
+        super().__init__()
+        self.has_alpha = "A" in dtype
+        self.latent_shape = {opt.latent_shape[0] * opt.latent_shape[1]: opt.latent_shape,
+                             opt.obj_shape[0] * opt.obj_shape[1]: opt.obj_shape}
+        self.use_prior = use_prior
+        if use_prior:
+            ho, wo = opt.obj_shape[0] * opt.patch_size, opt.obj_shape[1] * opt.patch_size
+            self.register_buffer("circle", get_circle([ho, wo], p=0.75).float().view(1, 1, ho, wo))
+        self.scale_factor = opt.scale_factor
+        self.norm = CustomNorm(opt.norm_layer, opt.embed_dim)
+        self.to_img = ConvPatchProj(opt.patch_size, opt.embed_dim, opt.norm_layer_patch,
+                                    get_num_channels(dtype, opt.num_lyt), skip_channels=skip_channels, from_patch=False,
+                                    hr_ratio=opt.hr_ratio, use_hr=opt.use_hr)
+        self.apply(init_weights)
+        self.init_bias = 0
+        if init_mode in ("zero", "five"):
+            self.to_img.proj.weight.data.zero_()
+        if init_mode == "five":
+            self.init_bias = 5
+
+    def forward(self, x, x_list=None, fuse_m=None, drop_alpha=False, skip=None):
+        """x (..., L, embed) -> image (..., C, H, W); the last channel, if ``has_alpha``, through tanh."""
+        lead = x.shape[:-2]
+        x = x.reshape(-1, *x.shape[-2:])
+        if skip is not None:
+            skip = skip.reshape(-1, *skip.shape[-3:])
+        if fuse_m is not None and fuse_m.ndim == 5:
+            fuse_m = fuse_m.reshape(-1, *fuse_m.shape[2:])
+        img = self.to_img(self.norm(x), latent_shape=self.latent_shape[x.size(1)], x_list=x_list, fuse_m=fuse_m, skip=skip)
+        if self.fused and img.is_cuda and float(self.scale_factor) == int(self.scale_factor):
+            img = decoder_tail(img, circle=self.circle if self.use_prior else None, init_bias=float(self.init_bias),
+                               scale_factor=int(self.scale_factor), has_alpha=self.has_alpha, use_prior=self.use_prior,
+                               drop_alpha=drop_alpha)
+        else:
+            img = img + self.init_bias
+            if self.has_alpha:
+                alpha = img[:, -1:].tanh()
+                if self.use_prior:
+                    alpha = self.circle * 1 + (1 - self.circle) * alpha
+                img = img[:, :-1] if drop_alpha else torch.cat([img[:, :-1], alpha], dim=1)
+            img = scale(img, self.scale_factor)
+        return img.reshape(*lead, *img.shape[1:])
+
+
+def _block_args(opt, block_type, depth):
+    return dict(block_type=block_type, depth=depth, dim=opt.embed_dim, num_heads=opt.num_heads, norm_layer=opt.norm_layer,
+                spectral_norm_layer=None, noise=False, dropout=opt.dropout)
+
+
+def _points_through(pts, transform, fused):
+    """[pts, 1] @ transform: pts (B', N, P, 2) control points, transform (B', N, 3, 2) -> (B', N, P, 2)."""
+    if fused and pts.is_cuda:
+        n, p = pts.shape[1], pts.shape[2]
+        pose = torch.cat([transform.reshape(-1, n, 6), pts.reshape(-1, n, 2 * p)], dim=-1)
+        one, zero = pose.new_ones(6), pose.new_zeros(6)
+        # (the affine is already in ``transform`` and the base points in ``pts``: multiplier 1, bias 0, base 0)
+        return WF.pose_affine(pose, one, zero, pose.new_zeros(p, 2))
+    pts = torch.cat([pts, torch.ones_like(pts[..., :1])], dim=-1)
+    return pts @ transform
+
+
+class PoseEstimator(_Net):
+    """lvd.py:258-460: per frame, self-attention over [background tokens, object tokens, frame tokens]; a linear head
+    on the layer tokens gives, per token, the pose (8 values with ``pts_mode "prior"``: a control-point offset and an
+    affine that is averaged over the layer's tokens; 2 with ``"head"``: the control point itself), an optional scale
+    and an occlusion score."""
+
+    def __init__(self, opt, depth, pts_mode, init_mode="zero"):
+        import math
+        from ..modules.conv import init_weights
+        from ..modules.transform import CustomNorm, MultiBlocks
+        super().__init__()
+        self.latent_obj_size = lo = opt.obj_shape[0] * opt.obj_shape[1]
+        self.latent_size = lb = opt.latent_shape[0] * opt.latent_shape[1]
+        if pts_mode not in ("head", "prior"):
+            raise ValueError(f"PoseEstimator: pts_mode must be 'head' or 'prior', got {pts_mode!r}")
+        self.pts_mode = pts_mode
+        for name in ("bound_rest", "soft_bound_rest", "norm_scale", "tgt_scale", "has_bg", "fix_bg", "fix_bg1",
+                     "bound_scale", "min_scale", "max_scale", "use_delta", "occ_mode", "ctx_len"):
+            setattr(self, name, getattr(opt, name))
+        self.use_last = opt.use_last_pose_decoder
+        self.obj_embed = nn.Parameter(torch.randn(1, 1, lo, opt.embed_dim))
+        self.pos_embed = nn.Parameter(torch.randn(1, 1, lb, opt.embed_dim))
+        self.blocks = MultiBlocks(**_block_args(opt, "full", depth))
+
+        s, ar = opt.init_scale_obj, opt.aspect_ratio
+        if pts_mode == "head":
+            tgt = get_grid(*opt.obj_shape).view(1, 1, lo, 2).expand(-1, opt.num_obj, -1, -1)
+            bias = (tgt.reshape(1, -1, 2) * s).atanh()
+            mul = None
+            self.pose_size = 2
+        else:
+            self.register_buffer("tgt_pts", get_grid(*opt.obj_shape).view(1, 1, lo, 2))
+            row = lambda tx, ty: torch.tensor([[[[0., 0., s, 0., 0., ar * s, tx, ty]]]])
+            if opt.rd_translate_bias:
+                import numpy as np
+                m = opt.translate_bias_mul
+                bias = torch.cat([row(m * np.random.rand(), m * np.random.rand()) for _ in range(opt.num_obj)], dim=1)
+            elif opt.circle_translate_bias:
+                r = opt.circle_translate_radius
+                theta = [i * 2 * math.pi / (opt.num_obj + 1) for i in range(opt.num_obj)]
+                bias = torch.cat([row(r * math.cos(a), r * math.sin(a)) for a in theta], dim=1)
+            else:
+                bias = row(0., 0.)
+            md, ms = opt.mul_delta_obj, opt.mul_scale_obj
+            mul = torch.tensor([[[[md, md, ms, ms, ms, ms, 1., 1.]]]])
+            self.pose_size = 8
+            if opt.bound_rest:
+                lo_s, hi_s, tr = opt.min_scale_bound, opt.max_scale_bound, opt.max_translate_bound
+                self.register_buffer("min_bound", torch.tensor([[[0., 0., lo_s, 0., 0., ar * lo_s, -tr, -tr]]]))
+                self.register_buffer("max_bound", torch.tensor([[[0., 0., hi_s, 0., 0., ar * hi_s, tr, tr]]]))
+            if opt.has_bg:
+                self.register_buffer("bg_bias", torch.tensor([[[[0., 0., 1., 0., 0., 1., 0., 0.]]]]))
+                self.bg_mul = opt.bg_mul
+                self.register_buffer("tgt_pts_bg", get_grid(*opt.latent_shape).view(1, 1, lb, 2))
+        if pts_mode == "head" and opt.has_bg:
+            raise ValueError("PoseEstimator: has_bg needs pts_mode 'prior' (the background's base points)")
+        self.register_buffer("bias", bias)
+        self.register_buffer("mul", mul)
+        self.scale_size = 1 if opt.bound_scale else 0
+        self.occ_size = 1
+        self.register_buffer("occ_bias", torch.tensor([[2. * i for i in range(opt.num_obj)]]))
+        self.norm = CustomNorm(opt.norm_layer, opt.embed_dim)
+        self.head = nn.Linear(opt.embed_dim, self.pose_size + self.scale_size + self.occ_size)
+        nn.init.trunc_normal_(self.obj_embed, std=.02)
+        nn.init.trunc_normal_(self.pos_embed, std=.02)
+        self.apply(init_weights)
+        if init_mode == "zero":
+            self.head.weight.data.zero_()
+            self.head.bias.data.zero_()
+
+    def _unit_determinant(self, transform, target, eps):
+        """The affine's 2 x 2 part rescaled to |det| = target^2 (lvd.py:398-411)."""
+        lin = transform[:, :, :2]
+        det = (lin[:, :, 0, 0] * lin[:, :, 1, 1] - lin[:, :, 1, 0] * lin[:, :, 0, 1]).abs() + eps
+        lin = lin * target / torch.sqrt(det.view(-1, lin.shape[1], 1, 1) + eps)
+        return torch.cat([lin, transform[:, :, 2:]], dim=2)
+
+    def _sequence(self, x, x_obj, x_bg):
+        """Per frame, the tokens the blocks see: [background layer, object layers, frame], each with its embedding."""
+        b, t, l, c = x.shape
+        per_frame = lambda layer: layer.reshape(b, 1, -1, c).expand(-1, t, -1, -1)
+        parts = [per_frame(x_bg + self.pos_embed)] if self.has_bg else []
+        parts += [per_frame(x_obj + self.obj_embed), x + self.pos_embed]
+        return torch.cat(parts, dim=2).reshape(b * t, -1, c)
+
+    def _rest(self, pose):
+        """The penalty that keeps a layer's pose at rest, per frame: the mean square of the (tanh'ed) pose values --
+        with ``bound_rest`` only of those outside [min_bound, max_bound], with ``soft_bound_rest`` of their distance
+        to the interval."""
+        if self.bound_rest and self.soft_bound_rest:
+            cost = ((pose < self.min_bound).float() * (pose - self.min_bound) ** 2
+                    + (pose > self.max_bound).float() * (pose - self.max_bound) ** 2)
+        elif self.bound_rest:
+            cost = pose ** 2 * ((pose < self.min_bound) | (pose > self.max_bound)).float()
+        else:
+            cost = pose ** 2
+        return cost.flatten(start_dim=1).mean(-1)
+
+    def _layer_points(self, pose, base_pts, frames, rescale=(), offsets_on=True):
+        """One pose per token, (B T, N, P, 8) = [offset of the token's control point (2), affine (3 x 2)], to the
+        layer's control points (B T, N, P, 2): the affine is the MEAN over the layer's tokens -- its 2 x 2 part brought
+        to each |det| target of ``rescale`` in turn -- applied to ``base_pts`` + offsets.  Also what
+        ``use_last_pose_decoder`` hands to the future predictor: affine and offsets of the last context frame."""
+        n, p = pose.shape[1:3]
+        offsets, affine = pose[..., :2], pose[..., 2:].reshape(-1, n, p, 3, 2).mean(dim=2)
+        if not offsets_on:
+            offsets = offsets * 0
+        for target in rescale:
+            affine = self._unit_determinant(affine, target, 1e-6)
+        last = None
+        if self.use_last:
+            at = self.ctx_len - 1
+            last = torch.cat([affine.reshape(-1, frames, n, 6)[:, at], offsets.reshape(-1, frames, n, p * 2)[:, at]], dim=2)
+        return _points_through(base_pts + offsets, affine, self._fused).reshape(-1, n, p, 2), last
+
+    def _occ_score(self, occ, n, eps):
+        """A layer's occlusion score: the mean over its tokens, then ``occ_mode``."""
+        if self.occ_mode == "freeze":
+            return torch.ones(occ.shape[0], n, device=occ.device)
+        score = occ.reshape(occ.shape[0], n, -1).mean(dim=2)
+        if self.occ_mode == "normalize":
+            low, high = score.min(dim=1, keepdim=True)[0], score.max(dim=1, keepdim=True)[0]
+            score = (score - low) / (high - low + eps) * 4 * n
+        elif self.occ_mode == "bias":
+            score = score + self.occ_bias
+        return score
+
+    def forward(self, x, x_obj, x_bg, eps=1e-6):
+        """x (B, T, L, C), x_obj (B, No, Lo, C), x_bg (B, L, C) or None -> (obj_pose (B, T, No, Lo, 2), bg_pose
+        (B, T, 1, L, 2) or None, occ_score (B, T, No), rest (B, T), bg_rest (B, T) or None, last_obj, last_bg)."""
+        b, t, l, _ = x.shape
+        no, lo = x_obj.shape[1:3]
+        nbg = l if self.has_bg else 0
+        per_clip = lambda v: v.reshape(b, t, *v.shape[1:])
+        tokens = self.blocks(self._sequence(x, x_obj, x_bg))[:, :nbg + no * lo]   # the layers' tokens, background first
+        own_bg = self.has_bg and not self.fix_bg
+        out = self.head(self.norm(tokens if own_bg else tokens[:, nbg:]))
+        pose, scl, occ = out.split([self.pose_size, self.scale_size, self.occ_size], dim=2)
+        bg = pose[:, :l] if own_bg else None
+        pose, scl, occ = (v[:, -no * lo:] for v in (pose, scl, occ))
+
+        last_obj = last_bg = bg_pose = bg_rest = None
+        if self.pts_mode == "head":
+            rest = (pose ** 2).flatten(start_dim=1).mean(-1, keepdim=True)
+            obj_pose = (pose + self.bias).tanh().view(-1, no, lo, 2)
+        else:
+            pose = pose.tanh()
+            rest = self._rest(pose)
+            targets = [self.tgt_scale] if self.norm_scale else []
+            if self.bound_scale:
+                unit = ((scl.tanh() + 1) / 2).view(-1, no, lo, 1, 1).mean(dim=2)
+                targets.append(self.min_scale + unit * (self.max_scale - self.min_scale))
+            obj_pose, last_obj = self._layer_points(pose.view(-1, no, lo, 8) * self.mul + self.bias, self.tgt_pts, t,
+                                                    targets, offsets_on=self.use_delta)
+        if own_bg:
+            bg = bg.tanh()
+            bg_rest = per_clip((bg ** 2).flatten(start_dim=1).mean(-1))
+            bg_pose, last_bg = self._layer_points(bg.view(-1, 1, l, 8) + self.bg_bias, self.bg_mul * self.tgt_pts_bg, t)
+        elif self.has_bg:
+            bg_pose = self.tgt_pts_bg.expand(b * t, -1, -1, -1)
+        if self.has_bg:
+            bg_pose = per_clip(bg_pose)
+            if self.fix_bg1:   # the first frame's background stays where it is
+                bg_pose = torch.cat([self.tgt_pts_bg.unsqueeze(1).expand(b, -1, -1, -1, -1), bg_pose[:, 1:]], dim=1)
+        return (per_clip(obj_pose), bg_pose, per_clip(self._occ_score(occ, no, eps)), per_clip(rest), bg_rest, last_obj,
+                last_bg)
+
+
+class LayerEstimator(_Net):
+    """lvd.py:873-950: learned layer queries (the background's position embedding followed by one embedding per object
+    token) attend, block after block, to their own keys followed by the tokens of all context frames."""
+
+    def __init__(self, opt, depth, num_timesteps):
+        from ..modules.conv import init_weights
+        from ..modules.transform import CustomNorm, MultiBlocks
+        super().__init__()
+        self.num_obj = opt.num_obj
+        self.latent_size = lb = opt.latent_shape[0] * opt.latent_shape[1]
+        self.latent_obj_size = lo = opt.obj_shape[0] * opt.obj_shape[1]
+        self.decompose_embed = opt.decompose_embed_oe
+        self.has_bg = opt.has_bg
+        self.pred_cls = opt.pred_cls
+        embeds = []
+        if self.decompose_embed:
+            self.obj_spatial_embed = nn.Parameter(torch.randn(1, 1, lo, opt.embed_dim))
+            self.obj_num_embed = nn.Parameter(torch.randn(1, opt.num_obj, 1, opt.embed_dim))
+            embeds += [self.obj_spatial_embed, self.obj_num_embed]
+        else:
+            self.obj_embed = nn.Parameter(torch.randn(1, opt.num_obj, lo, opt.embed_dim))
+            embeds += [self.obj_embed]
+        self.time_embed = nn.Parameter(torch.randn(1, num_timesteps, 1, opt.embed_dim))
+        self.pos_embed = nn.Parameter(torch.randn(1, 1, lb, opt.embed_dim))
+        self.norm = CustomNorm(opt.norm_layer, opt.embed_dim)
+        self.blocks = MultiBlocks(**_block_args(opt, "obj", depth))
+        if opt.pred_cls:
+            self.cls_norm = CustomNorm(opt.norm_layer, opt.embed_dim)
+            self.cls_head = nn.Linear(opt.embed_dim, opt.num_lyt)
+        for e in embeds + [self.time_embed, self.pos_embed]:
+            nn.init.trunc_normal_(e, std=.02)
+        self.apply(init_weights)
+
+    def forward(self, x):
+        """x (B, T, L, C), the context frames' tokens -> (x_obj (B, No, Lo, C), x_bg (B, L, C) or None, cls (B, No, Nl)
+        or None)."""
+        b, t, l, c = x.shape
+        no, lo = self.num_obj, self.latent_obj_size
+        x = (x + self.pos_embed + self.time_embed[:, :t]).reshape(b, t, l, c)
+        obj_embed = (self.obj_spatial_embed + self.obj_num_embed) if self.decompose_embed else self.obj_embed
+        x_obj = obj_embed.expand(b, -1, -1, -1).reshape(b, no * lo, c)
+        if self.has_bg:
+            x_obj = torch.cat([self.pos_embed.expand(b, -1, -1, -1).reshape(b, l, c), x_obj], dim=1)
+        x_obj = self.blocks(x_obj, x_ctx=self.norm(x.reshape(b * t, l, c)))
+        x_bg = x_obj[:, :l].reshape(b, l, c) if self.has_bg else None
+        x_obj = x_obj[:, -no * lo:]
+        cls = None
+        if self.pred_cls:
+            cls = self.cls_head(self.cls_norm(x_obj.reshape(b, no, lo, -1).mean(2))).softmax(dim=-1)
+        return x_obj.reshape(b, no, lo, c), x_bg, cls
+
+
+class LVD(_Net):
+    """lvd.py:11-155, the modes a reconstruction runs: ``encode_input``, ``estimate_layer``, ``estimate_pose``,
+    ``estimate_alpha_grid_occ`` and ``decode_output``.  The refiners, the edge filter and ``time_dropout`` belong to
+    training variants the recipe does not use and are refused in the constructor; ``decode_layer`` is not served."""
+
+    def __init__(self, opt):
+        super().__init__()
+        for name in ("pe_use_refiner", "pe_use_post_refiner", "pe_use_edge_filter"):
+            if getattr(opt, name):
+                raise NotImplementedError(f"LVD: {name}")
+        if opt.time_dropout > 0:
+            raise NotImplementedError("LVD: time_dropout > 0")
+        for name in ("freeze_obj", "remove_obj", "use_disocc", "include_self", "restrict_to_ctx"):
+            setattr(self, name, getattr(opt, name))
+        if opt.pad_obj_alpha > 0:
+            ho = int(opt.obj_shape[0] * opt.patch_size * opt.scale_factor)
+            wo = int(opt.obj_shape[1] * opt.patch_size * opt.scale_factor)
+            po = int(opt.pad_obj_alpha * opt.scale_factor)
+            mask = torch.ones(ho, wo)
+            mask[:po], mask[:, :po], mask[-po:], mask[:, -po:] = 0, 0, 0, 0
+            self.register_buffer("obj_alpha_mask", mask.view(1, 1, 1, ho, wo))
+        else:
+            self.obj_alpha_mask = None
+        bg_alpha = torch.ones(1, 1, opt.dim, int(opt.dim * opt.aspect_ratio))
+        if opt.pad_bg_alpha > 0:
+            pb = int(opt.pad_bg_alpha * opt.scale_factor)
+            bg_alpha[:, :, :pb], bg_alpha[:, :, :, :pb], bg_alpha[:, :, -pb:], bg_alpha[:, :, :, -pb:] = -1, -1, -1, -1
+        self.register_buffer("bg_alpha", bg_alpha)
+        self.register_buffer("diag", torch.eye(opt.num_obj, opt.num_obj)[None, None, :, :])
+        dtype = ("RGB" if opt.input_rgb else "") + ("L" if opt.input_lyt else "") + ("F" if opt.input_flow else "")
+        self.encoder = ImageEncoder(opt, dtype=dtype)
+        self.layer_estimator = LayerEstimator(opt, opt.oe_depth, opt.oe_num_timesteps)
+        self.pose_estimator = PoseEstimator(opt, opt.pe_depth, opt.pe_pts_mode, init_mode=opt.pe_estimator_init_mode)
+        self.warper = Warper(opt, repeat_border=opt.pe_repeat_border)
+        self.decoder = ImageDecoder(opt, dtype="A", init_mode=opt.pe_decoder_init_mode, use_prior=opt.pe_decoder_use_prior)
+
+    def compute_occ(self, occ_score, eps=1e-6):
+        """lvd.py:59-68; one kernel on the fused route, the reference's ops otherwise."""
+        if self._fused and occ_score.is_cuda:
+            return compute_occ(occ_score, eps)
+        b, t, no = occ_score.shape
+        occ = torch.exp(-occ_score ** 2) + eps
+        occ = occ.view(b, t, no, 1) / (occ.view(b, t, no, 1) + occ.view(b, t, 1, no)) - 0.5 * self.diag
+        occ = torch.cat([torch.ones(b, t, no, 1, device=occ.device, dtype=occ.dtype), occ], dim=3)
+        return torch.cat([torch.zeros(b, t, 1, no + 1, device=occ.device, dtype=occ.dtype), occ], dim=2)
+
+    def forward(self, input=None, obj_pose=None, bg_pose=None, grid=None, x=None, x_obj=None, x_bg=None, obj_alpha=None,
+                bg_alpha=None, occ=None, occ_score=None, ctx_ts=None, pred_ts=None, cls=None, mode=""):
+        if mode == "encode_input":
+            return self.encoder(input)
+        if mode == "estimate_layer":
+            return self.layer_estimator(x)
+        if mode == "estimate_pose":
+            return self.pose_estimator(x, x_obj, x_bg)
+        if mode == "estimate_alpha_grid_occ":
+            occ, obj_alpha, bg_alpha, grid = estimate_alpha_grid_occ(
+                self.warper, self.decoder(x_obj), self.bg_alpha, obj_pose, bg_pose, occ_score,
+                obj_alpha_mask=self.obj_alpha_mask, remove_obj=self.remove_obj, freeze_obj=self.freeze_obj)
+            return occ, obj_alpha, bg_alpha, grid
+        if mode == "decode_output":
+            return decode_output(self.warper, input, grid, occ, obj_alpha, bg_alpha, cls, ctx_ts, pred_ts,
+                                 restrict_to_ctx=self.restrict_to_ctx, use_disocc=self.use_disocc)
+        raise ValueError(f"LVD.forward: mode {mode!r} (encode_input, estimate_layer, estimate_pose, "
+                         "estimate_alpha_grid_occ, decode_output)")

@@ -772,6 +772,99 @@ def load_wif_checkpoint(wif, path):
     return wif
 
 
+def load_lvd_checkpoint(lvd, path):
+    """Load a reference ``pe`` state dict (the file, or a tensor-only dict in it under "state_dict") into ``lvd``
+    (``nets.LVD`` built from the checkpoint's options), strictly; a ``module.`` prefix is stripped."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(state, dict) and "state_dict" in state:
+        state = state["state_dict"]
+    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    lvd.load_state_dict(state, strict=True)
+    return lvd
+
+
+def lvd_demo_opt(opt, **over):
+    """``nets.lvd_net_opt`` for the demo's ``opt``: the fields the two share taken from ``opt``, the networks' own
+    (widths, depths, input modalities: the checkpoint's training options) from ``over``."""
+    from ..nets.lvd import lvd_net_opt
+    known = vars(lvd_net_opt())
+    d = {k: v for k, v in vars(opt).items() if k in known}
+    d["time_dropout"] = False
+    d.update(over)
+    nopt = lvd_net_opt(**d)
+    # the encoder's token raster is the frame over scale_factor over patch_size: it has to be latent_shape
+    raster = [int(nopt.dim / nopt.scale_factor) // nopt.patch_size,
+              int(nopt.dim * nopt.aspect_ratio / nopt.scale_factor) // nopt.patch_size]
+    if raster != list(nopt.latent_shape):
+        raise ValueError(f"lvd_demo_opt: {nopt.dim} x {int(nopt.dim * nopt.aspect_ratio)} frames at scale_factor "
+                         f"{nopt.scale_factor} and patch_size {nopt.patch_size} give {raster} tokens, latent_shape is "
+                         f"{list(nopt.latent_shape)}")
+    return nopt
+
+
+def reconstruct(opt, lvd, wif, real_vid, real_lyt, real_flow, ctx_len):
+    """The reconstruction half of the reference's ``Synthesizer.predict`` (models/synthesizer.py:419-460) with the
+    decomposition coming from the networks: encode the clip, estimate the layers from the first ``ctx_len`` frames, the
+    poses of every frame, alphas / grids / occlusion, decode every frame from the context frames and fuse.  ``opt``:
+    the options ``lvd`` was built from (input_rgb / input_lyt / input_flow, last_n_ctx if present).  real_vid
+    (B, T, 3, H, W), real_lyt (B, T, Nl, H, W), real_flow (B, T, 2, H, W) or None when ``opt.input_flow`` is off.
+    Returns ``rec_vid``, ``rec_disocc``, ``inp_rec_vid`` and the decomposition (``cls``, ``obj_pose``, ``bg_pose``,
+    ``occ``, ``obj_alpha``)."""
+    with torch.no_grad():
+        parts = [real_vid] if opt.input_rgb else []
+        parts += [real_lyt] if opt.input_lyt else []
+        if opt.input_flow:
+            if real_flow is None:
+                raise ValueError("reconstruct: the networks take the flow as input (opt.input_flow) and real_flow is None")
+            parts.append(real_flow)
+        x = lvd(input=torch.cat(parts, dim=2), mode="encode_input")
+        x_obj, x_bg, cls = lvd(x=x[:, :ctx_len], mode="estimate_layer")
+        obj_pose, bg_pose, occ_score = lvd(x=x, x_obj=x_obj, x_bg=x_bg, mode="estimate_pose")[:3]
+        occ, obj_alpha, bg_alpha, grid = lvd(x_obj=x_obj, obj_pose=obj_pose, bg_pose=bg_pose, occ_score=occ_score,
+                                             mode="estimate_alpha_grid_occ")
+        b, t = x.shape[:2]
+        ctx_ts = torch.arange(ctx_len, device=x.device, dtype=torch.int64).view(1, -1, 1).expand(b, -1, t)
+        if getattr(opt, "last_n_ctx", 0) > 0:
+            ctx_ts = ctx_ts[:, -opt.last_n_ctx:]
+        pred_ts = torch.arange(t, device=x.device, dtype=torch.int64)
+        out = lvd(input=torch.cat([real_vid, real_lyt], dim=2), grid=grid, occ=occ, obj_alpha=obj_alpha, bg_alpha=bg_alpha,
+                  ctx_ts=ctx_ts.contiguous(), pred_ts=pred_ts, cls=cls, mode="decode_output")
+        rec_output, raw_output, alpha_ctx = out[0], out[5], out[6]
+        disocc = WF.disocc_test(alpha_ctx.amax(dim=3))  # synthesizer.py:447-450
+        return dict(rec_vid=rec_output[:, :, :3], rec_disocc=disocc.unsqueeze(2), inp_rec_vid=wif(raw_output), cls=cls,
+                    obj_pose=obj_pose, bg_pose=bg_pose, occ=occ, obj_alpha=obj_alpha)
+
+
+def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4,
+            device="cuda:0", lvd_over=None, wif_ckpt=None, ii_depth=4, ii_embed_dim=512):
+    """``--lvd-ckpt``: the clip through ``reconstruct`` with a reference ``pe`` checkpoint; ``rec_vid`` and
+    ``inp_rec_vid`` written by the writers ``run`` uses.  ``lvd_over``: the checkpoint's training options where they
+    differ from ``lvd_demo_opt(demo_opt(...))`` (``--lvd-opt FILE``: a JSON object)."""
+    from ..nets.lvd import LVD
+    opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt, ctx_len=ctx_len, ii_depth=ii_depth, ii_embed_dim=ii_embed_dim)
+    nopt = lvd_demo_opt(opt, **(lvd_over or {}))
+    dev = torch.device(device)
+    clip = wio.load_clip(clip_dir, (dim, int(dim * aspect_ratio)), num_lyt, max_frames=frames)
+    vid, lyt = clip["vid"].unsqueeze(0).to(dev), clip["lyt"].unsqueeze(0).to(dev)
+    flow = None
+    if nopt.input_flow:
+        if clip.get("flow") is None:
+            raise ValueError(f"run_lvd: the networks take the flow as input and {clip_dir} has no flow files next to it")
+        flow = torch.nn.functional.interpolate(clip["flow"].to(dev), size=vid.shape[-2:], mode="bilinear").unsqueeze(0)
+    lvd = load_lvd_checkpoint(LVD(nopt), lvd_ckpt).to(dev).eval()
+    if wif_ckpt is not None:
+        wif = load_wif_checkpoint(WIF.with_unet(opt), wif_ckpt).to(dev).eval()
+    else:
+        wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
+    res = reconstruct(nopt, lvd, wif, vid, lyt, flow, ctx_len)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        for key in ("rec_vid", "inp_rec_vid"):
+            wio.dump_video(res[key][0], os.path.join(out_dir, key + ".gif"))
+            wio.dump_image(res[key][0, -1], os.path.join(out_dir, key + "_last.png"))
+    return res
+
+
 EVAL_KEYS = ("rec_vid", "inp_pred_vid")
 
 
@@ -836,7 +929,27 @@ def main():
                          "norm + GELU kernel included; with the same --raw-dtype nothing in between is fp32)")
     ap.add_argument("--ii-depth", type=int, default=4, help="with --wif-ckpt: the checkpoint's --s_ii_depth")
     ap.add_argument("--ii-embed-dim", type=int, default=512, help="with --wif-ckpt: the checkpoint's --s_ii_embed_dim")
+    ap.add_argument("--lvd-ckpt", default=None, metavar="FILE",
+                    help="a reference `pe` checkpoint (state dict): decompose the clip with the LVD networks and write "
+                         "its reconstruction (rec_vid, inp_rec_vid) instead of running the seeded stand-ins")
+    ap.add_argument("--lvd-opt", default=None, metavar="FILE",
+                    help="with --lvd-ckpt: a JSON object of the checkpoint's training options (embed_dim, num_heads, "
+                         "oe_depth, pe_depth, input_lyt, ...) where they differ from the defaults")
     args = ap.parse_args()
+    if args.lvd_ckpt is not None:
+        over = None
+        if args.lvd_opt is not None:
+            import json
+            with open(args.lvd_opt) as fh:
+                over = json.load(fh)
+        res = run_lvd(args.clip, args.lvd_ckpt, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
+                      ctx_len=args.ctx_len, lvd_over=over, wif_ckpt=args.wif_ckpt, ii_depth=args.ii_depth,
+                      ii_embed_dim=args.ii_embed_dim)
+        for k, v in res.items():
+            if v is not None:
+                print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "
+                      f"finite={bool(torch.isfinite(v).all())}")
+        return
     palette = read_palette_file(args.palette) if args.palette is not None else None
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,

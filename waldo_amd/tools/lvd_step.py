@@ -13,6 +13,10 @@ outputs, occlusion scores, class logits).  ``bench.py --config LVD`` times it.
 ``objective="recipe"`` with the recipe's own four terms (``--s_vid_object_extractor_losses "ent_flt_edge" "l1_flow"
 "cell_dis" "reg_mov"``, train_lvd.sh:15) on a seeded real flow: the moving-object target is built on the device at
 every call, as the reference builds it at every step (``waldo_amd.supervision``).
+
+``nets="reference"`` feeds the step from a seeded ``nets.LVD`` at the recipe's widths -- encoder, layer estimator, pose
+estimator and object decoder in front of the same warp path (synthesizer.py:815-823) -- instead of from leaves: the
+gradients then land in the networks' parameters.  ``nets="stand-in"`` (the default) is the step described above.
 """
 import types
 
@@ -20,7 +24,7 @@ import torch
 
 from .. import functional as WF
 from .. import supervision
-from ..nets import Warper, decode_output, estimate_alpha_grid_occ, flp
+from ..nets import LVD, Warper, decode_output, estimate_alpha_grid_occ, flp
 from ..nets.lvd import decoder_tail
 from .utils import get_grid
 
@@ -41,6 +45,20 @@ RECIPE_TARGET = dict(fg_idx=[0, 4, 5, 6, 7, 8, 12, 13, 14, 15, 16, 17, 18, 19], 
                      use_dominant_flow_other=True)
 RECIPE_WEIGHTS = {"cell_dis": 10.0, "l1_flow": 1000.0, "reg_mov": 10.0, "ent_flt_edge": 1.0}
 OBJECTIVES = ("stand-in", "recipe")
+NETS = ("stand-in", "reference")
+
+
+def recipe_net_opt(**over):
+    """``nets.lvd_net_opt`` at scripts/cityscapes/train_lvd.sh: what ``lvd_opt`` holds for the warp path plus the
+    networks' widths and switches (512 wide, 8 heads, two blocks each, layout + flow input)."""
+    from ..nets.lvd import lvd_net_opt
+    d = dict(vars(lvd_opt()), time_dropout=False, embed_dim=512, num_heads=8, oe_depth=2, pe_depth=2, oe_num_timesteps=5,
+             num_lyt=LvdStep.num_lyt, input_rgb=False, input_lyt=True, input_flow=True, ctx_len=4, bound_rest=True,
+             soft_bound_rest=True, pe_decoder_init_mode="five", pe_estimator_init_mode="", has_bg=True, pad_obj_alpha=3,
+             pad_bg_alpha=3, init_scale_obj=0.25, mul_scale_obj=0.25, mul_delta_obj=0.2, circle_translate_bias=True,
+             circle_translate_radius=0.2, pred_cls=True, bg_mul=1.2)
+    d.update(over)
+    return lvd_net_opt(**d)
 
 
 class LvdStep:
@@ -49,10 +67,14 @@ class LvdStep:
 
     frames, num_lyt = 5, 20
 
-    def __init__(self, clips, device, seed=0, objective="stand-in"):
+    def __init__(self, clips, device, seed=0, objective="stand-in", nets="stand-in"):
         if objective not in OBJECTIVES:
             raise ValueError(f"LvdStep: objective must be one of {OBJECTIVES}, got {objective!r}")
+        if nets not in NETS:
+            raise ValueError(f"LvdStep: nets must be one of {NETS}, got {nets!r}")
         self.objective = objective
+        self.nets = nets
+        self.net = None
         self.opt = o = lvd_opt()
         self.clips = b = clips
         t, no, nl = self.frames, o.num_obj, self.num_lyt
@@ -81,11 +103,34 @@ class LvdStep:
         self.real_flow = (0.05 * torch.randn(b, t, 2, h, w, generator=g, device=device)) if objective == "recipe" else None
         self.leaves = [self.raw, self.pose_o, self.pose_b, self.score, self.cls_logit]
         self.shape = (b, t, no, lo, lb, ho)
+        if nets == "reference":
+            # (built last, from a generator state of its own: everything above keeps the stand-in step's values)
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(seed)
+                self.net = LVD(recipe_net_opt()).to(device)
+            if self.real_flow is None:
+                self.real_flow = 0.05 * torch.randn(b, t, 2, h, w, generator=g, device=device)
+            self.leaves = list(self.net.parameters())
+
+    def _network_step(self):
+        """The forward of synthesizer.py:810-841 through the networks; returns decode_output's tuple and obj_pose."""
+        net, ctx_len = self.net, self.net.pose_estimator.ctx_len
+        x = net(input=torch.cat([self.inp[:, :, 3:], self.real_flow], dim=2), mode="encode_input")
+        x_obj, x_bg, cls = net(x=x[:, :ctx_len], mode="estimate_layer")
+        obj_pose, bg_pose, occ_score = net(x=x, x_obj=x_obj, x_bg=x_bg, mode="estimate_pose")[:3]
+        occ, oa, ba, grid = net(x_obj=x_obj, obj_pose=obj_pose, bg_pose=bg_pose, occ_score=occ_score,
+                                mode="estimate_alpha_grid_occ")
+        out = net(input=self.inp, grid=grid, occ=occ, obj_alpha=oa, bg_alpha=ba, ctx_ts=self.ctx_ts, pred_ts=self.pred_ts,
+                  cls=cls, mode="decode_output")
+        return out, obj_pose
 
     def __call__(self):
         b, t, no, lo, lb, ho = self.shape
         for x in self.leaves:
             x.grad = None
+        if self.net is not None:
+            out, obj_pose = self._network_step()
+            return self._close(out, obj_pose)
         obj_alpha = decoder_tail(self.raw, init_bias=5.0).view(b, no, 1, ho, ho)
         obj_pose = flp.obj_pose_to_points(torch.tanh(self.pose_o), self.base_o, self.mul6, self.bias_o, 0.2)
         bg_pose = flp.bg_pose_to_points(torch.tanh(self.pose_b), self.base_b, self.bias_b, 1.2)
@@ -94,6 +139,10 @@ class LvdStep:
                                                     self.score)
         out = decode_output(self.warper, self.inp, grid, occ, oa, ba, self.cls_logit.softmax(-1), self.ctx_ts,
                             self.pred_ts, restrict_to_ctx=False)
+        return self._close(out, obj_pose)
+
+    def _close(self, out, obj_pose):
+        b, t, no, lo, lb, ho = self.shape
         if self.objective == "recipe":
             real_lyt = self.inp[:, :, 3:]
             target = supervision.moving_object_target(self.real_flow, real_lyt, **RECIPE_TARGET)
