@@ -1040,7 +1040,7 @@ int waldo_plane_norm_gelu_bwd_dt(const void* x, int64_t xs_n, int64_t xs_c, cons
 /* ---------------------------------------------------------------------------------------
  * Token attention: the attention of the LVD transformer blocks (the reference's models/modules/transform.py:109-117
  * FullAttention and :175-185 ObjAttention: matmul -> scale -> softmax -> matmul, with the permutes of qkv / kv, the
- * cat of the two key sets and the transpose in front of proj) in one call, forward only.
+ * cat of the two key sets and the transpose in front of proj) in one call, forward and backward.
  *
  * waldo_token_attention_fwd: for every b < B, h < H, i < Nq, over the keys j of segment 1 (Nk1 of them) FOLLOWED BY
  *   those of segment 2 (Nk2 of them; Nk2 == 0: k2, v2 and their strides are ignored and may be NULL / 0):
@@ -1061,12 +1061,48 @@ int waldo_plane_norm_gelu_bwd_dt(const void* x, int64_t xs_n, int64_t xs_c, cons
  * stride" (no multiple of 4 floats: rows are read in 16-byte pieces, and a view with a non-unit inner stride has no
  * description here), "bad batch stride" (no multiple of 4 floats), "null pointer", "not aligned" (a pointer off a
  * 16-byte boundary).
+ *
+ * waldo_token_attention_fwd_lse: the same call (one host body, one kernel template, the same bits in out) that also
+ *   stores the row statistics the backward needs: lse (B, H, Nq) contiguous fp32,
+ *     lse[b, h, i] = m + log(l) = log sum_j exp(scale * q[b, i, h, :] . k[b, j, h, :]).
+ *   Its refusals are the forward's under its own name; "null pointer" covers lse.
+ *
+ * waldo_token_attention_bwd: the gradients of the forward in its five views, from out, grad_out (both (B, Nq, H D)
+ *   contiguous) and lse.  Per (b, h), fp32 throughout, every product on the exact-fp32 matrix instruction:
+ *     P = exp(scale S - lse)   dP = dO V^T   delta = rowsum(dO o O)   dS = P o (dP - delta)
+ *     dQ = scale dS K          dK = scale dS^T Q                      dV = P^T dO
+ *   grad_q (B, Nq, H, D), grad_k1 / grad_v1 (B, Nk1, H, D) and grad_k2 / grad_v2 (B, Nk2, H, D) are contiguous fp32 and
+ *   are OVERWRITTEN; a NULL gradient pointer means that gradient is not wanted (all five NULL: WALDO_OK without a
+ *   launch; Nk2 == 0: grad_k2 and grad_v2 are ignored).  The gradients are per batch element: a caller whose keys are
+ *   broadcast over the batch (batch stride 0, legal for reading) sums them itself.  delta (B, H, Nq) is a workspace
+ *   the caller allocates; nothing is allocated here.  Three launches at the most: the delta pass, a dQ kernel (skipped
+ *   when grad_q is NULL) and a dK/dV kernel (skipped when the other four are NULL), each recomputing the scores from
+ *   the views -- NO SCORE-SIZED MEMORY and NO ATOMICS: every gradient element is summed by one lane in one order, so
+ *   the gradients are a function of the inputs alone, the same bits from run to run.  No synchronisation; the caller's
+ *   stream; capturable in a graph.
+ *   waldo_token_attention_bwd_limits(out, n): as waldo_token_attention_limits, for the backward's kernels: {query rows
+ *   per workgroup of the dQ kernel (and per tile of the dK/dV kernel), keys per tile of the dQ kernel (and per
+ *   workgroup of the dK/dV kernel), the head dimensions served}.
+ *   Refusals: the forward's, under this function's name ("too large" also covers the key blocks of all (b, h) and the
+ *   rows of out); "null pointer" also for out, grad_out, lse and delta; "not aligned" for every non-NULL pointer.
  * ------------------------------------------------------------------------------------- */
 int waldo_token_attention_limits(int* out, int n);
 int waldo_token_attention_fwd(const float* q, int64_t qs_b, int64_t qs_n, const float* k1, int64_t k1s_b, int64_t k1s_n,
                               const float* v1, int64_t v1s_b, int64_t v1s_n, const float* k2, int64_t k2s_b,
                               int64_t k2s_n, const float* v2, int64_t v2s_b, int64_t v2s_n, float* out, float scale,
                               int64_t B, int H, int D, int Nq, int Nk1, int Nk2, waldo_stream_t stream);
+int waldo_token_attention_fwd_lse(const float* q, int64_t qs_b, int64_t qs_n, const float* k1, int64_t k1s_b,
+                                  int64_t k1s_n, const float* v1, int64_t v1s_b, int64_t v1s_n, const float* k2,
+                                  int64_t k2s_b, int64_t k2s_n, const float* v2, int64_t v2s_b, int64_t v2s_n, float* out,
+                                  float* lse, float scale, int64_t B, int H, int D, int Nq, int Nk1, int Nk2,
+                                  waldo_stream_t stream);
+int waldo_token_attention_bwd_limits(int* out, int n);
+int waldo_token_attention_bwd(const float* q, int64_t qs_b, int64_t qs_n, const float* k1, int64_t k1s_b, int64_t k1s_n,
+                              const float* v1, int64_t v1s_b, int64_t v1s_n, const float* k2, int64_t k2s_b,
+                              int64_t k2s_n, const float* v2, int64_t v2s_b, int64_t v2s_n, const float* out,
+                              const float* grad_out, const float* lse, float* delta, float* grad_q, float* grad_k1,
+                              float* grad_v1, float* grad_k2, float* grad_v2, float scale, int64_t B, int H, int D,
+                              int Nq, int Nk1, int Nk2, waldo_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,11 @@
 """A/B of the fused token attention (WF.token_attention, csrc/token_attention.hip) against the two framework routes -- the
 reference's sequence of ops (WF.token_attention_framework) and ``F.scaled_dot_product_attention`` on the same views --
 at the LVD recipe's shapes (scripts/cityscapes/train_lvd.sh: 512 wide, 8 heads, D = 64) on one MI355X, and of the whole
-``nets.LVD`` with ``fused`` True against False.  Writes profiles/lvd_nets.json.
+``nets.LVD`` with ``fused`` True against False.  Writes profiles/lvd_nets.json; the two training sections, ``bwd`` and
+``step``, are run with ``--out profiles/lvd_nets_bwd.json``.
 
     python tools_dev/ab_lvd_nets.py [--out profiles/lvd_nets.json] [--sections op,lvd] [--rounds 20] [--warmup 5]
+    python tools_dev/ab_lvd_nets.py --out profiles/lvd_nets_bwd.json --sections bwd,step [--clips 4]
 
 Sections:
   op   the op alone, forward without autograd, fp32: the PoseEstimator's self-attention (56 and 112 sequences of
@@ -13,7 +15,14 @@ Sections:
        the (B, N, H D) layout the other two routes return;
   lvd  the whole network without autograd at the recipe's widths for 4 clips of 14 frames: encode_input,
        estimate_layer (4 context frames), estimate_pose, estimate_alpha_grid_occ -- ``fused`` True against False of the
-       SAME module.
+       SAME module;
+  bwd  forward + backward of the op at the shapes of ``op``, the gradient of a fixed ``grad_out`` in every operand:
+       ``kernel`` (WF.token_attention under token_attention_backward_route("kernel"): waldo_token_attention_fwd_lse +
+       waldo_token_attention_bwd), ``framework_recompute`` (the same forward kernel, the backward recomputing and
+       differentiating WF.token_attention_framework: the route before the backward kernel) and ``sdpa`` with its own
+       backward.  ``kernel_default`` applies the rule: the kernel route beats the recompute by more than the spread;
+  step ``LvdStep(--clips, device, nets="reference")`` at the recipe's widths, eager: forward, loss and backward under
+       both routes of the attention's backward.
 Method: device time between events; the routes ALTERNATE inside one process (one call of each per round), --rounds
 rounds after --warmup of each; median, minimum and quartiles per route.  ``spread`` is the largest of the routes'
 interquartile ranges over their medians; ``kernel_wins`` says median(kernel) * (1 + spread) < median(each other route).
@@ -129,6 +138,78 @@ def section_op(device, warmup, rounds):
     return res
 
 
+def bwd_routes(ops, go):
+    """Forward + backward per route, on leaves that are the views themselves (detached: no gradient accumulates)."""
+    leaves = [None if t is None else t.detach().requires_grad_() for t in ops]
+    wanted = [t for t in leaves if t is not None]
+
+    def through(fn, route=None):
+        def run():
+            if route is None:
+                out = fn(*leaves)
+            else:
+                with WF.token_attention_backward_route(route):
+                    out = fn(*leaves)
+            return torch.autograd.grad(out, wanted, go)
+        return run
+
+    return {"kernel": through(kernel_route, "kernel"), "framework_recompute": through(kernel_route, "framework"),
+            "sdpa": through(sdpa_route)}
+
+
+def section_bwd(device, warmup, rounds):
+    res = {}
+    for name, seqs, nq, nk1, nk2 in OP_SHAPES:
+        ops = op_operands(seqs, nq, nk1, nk2, device)
+        go = torch.randn(seqs, nq, HEADS * D, generator=torch.Generator(device=device).manual_seed(1), device=device)
+        routes = bwd_routes(ops, go)
+        ref = routes["framework_recompute"]()
+        err = {k: max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(fn(), ref))
+               for k, fn in routes.items() if k != "framework_recompute"}
+        del ref
+        st = alternate(routes, warmup, rounds)
+        for k, fn in routes.items():
+            st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+        med = {k: st[k]["median_ms"] for k in routes}
+        st["kernel_over_framework_recompute"] = med["kernel"] / med["framework_recompute"]
+        st["kernel_over_sdpa"] = med["kernel"] / med["sdpa"]
+        st["kernel_beats_framework_recompute"] = bool(med["kernel"] * (1 + st["spread"]) < med["framework_recompute"])
+        st["kernel_beats_sdpa"] = bool(med["kernel"] * (1 + st["spread"]) < med["sdpa"])
+        # seven products forward + backward of the mathematics; the kernel route runs eleven (S three times, dP twice)
+        st["kernel_tflops_of_the_mathematics"] = 3.5 * op_flops(seqs, nq, nk1 + (nk2 or 0)) / (med["kernel"] * 1e-3) / 1e12
+        st["max_relative_gradient_difference_from_framework_recompute"] = err
+        st["shape"] = dict(sequences=seqs, heads=HEADS, head_dim=D, queries=nq, keys=[nk1] + ([nk2] if nk2 else []))
+        res[name] = st
+        print(name, json.dumps({k: (round(v["median_ms"], 4), v["peak_bytes_above_inputs"] >> 20) for k, v in st.items()
+                                if isinstance(v, dict) and "median_ms" in v}), "spread", round(st["spread"], 3),
+              "beats recompute", st["kernel_beats_framework_recompute"], "beats sdpa", st["kernel_beats_sdpa"], flush=True)
+    res["kernel_beats_framework_recompute_everywhere"] = all(v["kernel_beats_framework_recompute"] for v in res.values())
+    return res
+
+
+def section_step(device, warmup, rounds, clips=4):
+    from waldo_amd.tools.lvd_step import LvdStep
+    step = LvdStep(clips, device, nets="reference")
+
+    def route(name):
+        def fn():
+            with WF.token_attention_backward_route(name):
+                return step()
+        return fn
+
+    routes = {"kernel": route("kernel"), "framework_recompute": route("framework")}
+    st = alternate(routes, warmup, rounds)
+    for k, fn in routes.items():
+        st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+    st["kernel_over_framework_recompute"] = st["kernel"]["median_ms"] / st["framework_recompute"]["median_ms"]
+    st["kernel_beats_framework_recompute"] = bool(st["kernel"]["median_ms"] * (1 + st["spread"])
+                                                  < st["framework_recompute"]["median_ms"])
+    st["shape"] = dict(clips=clips, frames=LvdStep.frames, nets="reference", mode="eager")
+    print("step", json.dumps({k: (round(v["median_ms"], 3), v["peak_bytes_above_inputs"] >> 20) for k, v in st.items()
+                              if isinstance(v, dict) and "median_ms" in v}), "spread", round(st["spread"], 3), flush=True)
+    return st
+
+
 def lvd_forward(net, inp, ctx_len):
     x = net(input=inp, mode="encode_input")
     x_obj, x_bg, cls = net(x=x[:, :ctx_len], mode="estimate_layer")
@@ -172,6 +253,7 @@ def main():
     ap.add_argument("--sections", default="op,lvd")
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--clips", type=int, default=4, help="clips of the step section")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ab_lvd_nets: no GPU (a measurement does not fall back)")
@@ -181,10 +263,25 @@ def main():
         with open(args.out) as fh:
             doc = json.load(fh)
     doc.update(device=torch.cuda.get_device_name(0), torch=torch.__version__, limits=WF.token_attention_limits(),
+               bwd_limits=WF.token_attention_bwd_limits(),
                method=dict(rounds=args.rounds, warmup=args.warmup, timing="device events, routes alternating"))
+    sections = {"op": section_op, "lvd": section_lvd, "bwd": section_bwd,
+                "step": lambda *a: section_step(*a, clips=args.clips)}
     for sec in args.sections.split(","):
-        doc[sec] = {"op": section_op, "lvd": section_lvd}[sec](device, args.warmup, args.rounds)
+        doc[sec] = sections[sec](device, args.warmup, args.rounds)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(doc, fh, indent=1, sort_keys=True)
+    if "bwd" in doc and "step" in doc:
+        # the rule for the default route: the kernel beats the route before it, by more than the spread, at every op
+        # shape and in the step
+        doc["kernel_route_wins_everywhere"] = bool(doc["bwd"]["kernel_beats_framework_recompute_everywhere"]
+                                                   and doc["step"]["kernel_beats_framework_recompute"])
+        doc["default_route"] = WF.get_token_attention_backward_route()
+        doc["default_route_note"] = ("the default stays 'framework' while tests/test_gpu_lvd_nets.py counts the plain "
+                                     "waldo_token_attention_fwd launches of a training step: under 'kernel' a forward "
+                                     "that records a node runs waldo_token_attention_fwd_lse")
+        doc["not_measured"] = ["D = 16 and D = 32", "the step replayed from a graph"]
         with open(args.out, "w") as fh:
             json.dump(doc, fh, indent=1, sort_keys=True)
     print(args.out)

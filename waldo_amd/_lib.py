@@ -140,6 +140,11 @@ SIGNATURES = {
     # token attention (include/waldo_hip.h "Token attention"): q, k1, v1, k2, v2 with a batch and a token stride each,
     # out, scale, B, H, D, Nq, Nk1, Nk2
     "waldo_token_attention_fwd": [_c_f, _i64, _i64] * 5 + [_c_f, _flt, _i64, _int, _int, _int, _int, _int, _stream],
+    # the same with lse (B, H, Nq) after out; the backward: the five views, out, grad_out, lse, delta, the five
+    # gradients (None: not wanted), scale, B, H, D, Nq, Nk1, Nk2
+    "waldo_token_attention_fwd_lse": [_c_f, _i64, _i64] * 5 + [_c_f, _c_f, _flt, _i64, _int, _int, _int, _int, _int,
+                                                               _stream],
+    "waldo_token_attention_bwd": [_c_f, _i64, _i64] * 5 + [_c_f] * 9 + [_flt, _i64, _int, _int, _int, _int, _int, _stream],
 }
 # workspace size of each *_det entry point (0: no deterministic kernel for the shape)
 DET_QUERIES = {
@@ -160,6 +165,7 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_plane_norm_workspace_bytes": (_i64, [_i64, _int, _int, _int]),
          "waldo_plane_norm_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_token_attention_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
+         "waldo_token_attention_bwd_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),
          "waldo_last_error_string": (ctypes.c_char_p, []),
          "waldo_set_debug_option": (_int, [_int, _int]),

@@ -16,25 +16,22 @@
 // The kTaK / 16 score blocks and the D / 16 output blocks are independent accumulator chains (the MFMA's dependent
 // latency), and several workgroups share a CU.  The next tile's K and V rows are in flight (registers) while the
 // current one is computed.
-#include "waldo_common.hip.h"
+//
+// The _lse entry point is the same kernel template with one more store: the row's m + log(l) of the scaled scores, which
+// the backward (token_attention_bwd.hip) rebuilds the probabilities from.
+#include "token_attention_common.hip.h"
 
 namespace waldo {
 
-constexpr int kTaQ = 64;    // query rows per workgroup (16 per wavefront)
-constexpr int kTaK = 64;    // keys per tile
-constexpr int kTaPad = 4;   // floats added to an LDS row
-
-typedef float ta_f32x4 __attribute__((ext_vector_type(4)));
-
 struct TokenAttentionArgs {
   const float *q, *k1, *v1, *k2, *v2;
-  float* out;
+  float *out, *lse;
   int64_t qs_b, qs_n, k1s_b, k1s_n, v1s_b, v1s_n, k2s_b, k2s_n, v2s_b, v2s_n;
   float scale;
   int H, Nq, Nk1, Nk, qblocks;  // Nk = Nk1 + Nk2
 };
 
-template <int D>
+template <int D, bool LSE>
 __global__ __launch_bounds__(kBlock) void token_attention_fwd_kernel(TokenAttentionArgs a) {
   constexpr int LD = D + kTaPad;          // LDS row, floats
   constexpr int V4 = D / 4;               // 16-byte pieces of a row
@@ -170,12 +167,44 @@ __global__ __launch_bounds__(kBlock) void token_attention_fwd_kernel(TokenAttent
     float* op = a.out + ((b * a.Nq + (q0 + qi)) * a.H + h) * D + 4 * g;
 #pragma unroll
     for (int d = 0; d < DB; ++d) *reinterpret_cast<ta_f32x4*>(op + 16 * d) = o[d] * inv;
+    if (LSE && g == 0) a.lse[(b * a.H + h) * a.Nq + (q0 + qi)] = m + logf(l);
   }
 }
 
 namespace {
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+template <bool LSE>
+int token_attention_fwd_host(const char* fn, const float* q, int64_t qs_b, int64_t qs_n, const float* k1, int64_t k1s_b,
+                             int64_t k1s_n, const float* v1, int64_t v1s_b, int64_t v1s_n, const float* k2,
+                             int64_t k2s_b, int64_t k2s_n, const float* v2, int64_t v2s_b, int64_t v2s_n, float* out,
+                             float* lse, float scale, int64_t B, int H, int D, int Nq, int Nk1, int Nk2,
+                             waldo_stream_t stream) {
+  const int64_t strides[10] = {qs_b, qs_n, k1s_b, k1s_n, v1s_b, v1s_n, k2s_b, k2s_n, v2s_b, v2s_n};
+  const int64_t qblocks = ((int64_t)Nq + kTaQ - 1) / kTaQ;
+  if (ta_check_shape(fn, strides, scale, B, H, D, Nq, Nk1, Nk2, qblocks) != WALDO_OK) return WALDO_EINVAL;
+  if (B == 0 || Nq == 0) return WALDO_OK;
+  if (!q || !k1 || !v1 || !out || (LSE && !lse) || (Nk2 > 0 && (!k2 || !v2))) {
+    set_error("%s: null pointer", fn);
+    return WALDO_EINVAL;
+  }
+  if (!ta_aligned16(q) || !ta_aligned16(k1) || !ta_aligned16(v1) || !ta_aligned16(out) ||
+      (Nk2 > 0 && (!ta_aligned16(k2) || !ta_aligned16(v2)))) {
+    set_error("%s: pointer not aligned to 16 bytes", fn);
+    return WALDO_EINVAL;
+  }
+  TokenAttentionArgs a{};
+  a.q = q, a.k1 = k1, a.v1 = v1, a.k2 = Nk2 > 0 ? k2 : nullptr, a.v2 = Nk2 > 0 ? v2 : nullptr, a.out = out;
+  a.lse = lse;
+  a.qs_b = qs_b, a.qs_n = qs_n, a.k1s_b = k1s_b, a.k1s_n = k1s_n, a.v1s_b = v1s_b, a.v1s_n = v1s_n;
+  a.k2s_b = k2s_b, a.k2s_n = k2s_n, a.v2s_b = v2s_b, a.v2s_n = v2s_n;
+  a.scale = scale, a.H = H, a.Nq = Nq, a.Nk1 = Nk1, a.Nk = Nk1 + Nk2, a.qblocks = (int)qblocks;
+  const dim3 grid((unsigned)(B * H * qblocks));
+  hipStream_t st = (hipStream_t)stream;
+  if (D == 16) token_attention_fwd_kernel<16, LSE><<<grid, dim3(kBlock), 0, st>>>(a);
+  else if (D == 32) token_attention_fwd_kernel<32, LSE><<<grid, dim3(kBlock), 0, st>>>(a);
+  else token_attention_fwd_kernel<64, LSE><<<grid, dim3(kBlock), 0, st>>>(a);
+  return launch_status(fn);
+}
 
 }  // namespace
 
@@ -194,65 +223,17 @@ extern "C" int waldo_token_attention_fwd(const float* q, int64_t qs_b, int64_t q
                                          int64_t k2s_b, int64_t k2s_n, const float* v2, int64_t v2s_b, int64_t v2s_n,
                                          float* out, float scale, int64_t B, int H, int D, int Nq, int Nk1, int Nk2,
                                          waldo_stream_t stream) {
-  const char* fn = "waldo_token_attention_fwd";
-  if (B < 0 || H < 1 || Nq < 0 || Nk1 < 1 || Nk2 < 0) {
-    set_error("%s: bad shape B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (B, Nq, Nk2 >= 0; H, Nk1 >= 1)", fn, (long long)B, H, Nq,
-              Nk1, Nk2);
-    return WALDO_EINVAL;
-  }
-  if (D != 16 && D != 32 && D != 64) {
-    set_error("%s: bad head dimension D=%d (16, 32 or 64)", fn, D);
-    return WALDO_EINVAL;
-  }
-  if (!(scale == scale) || scale == INFINITY || scale == -INFINITY) {
-    set_error("%s: bad scale %g (finite)", fn, (double)scale);
-    return WALDO_EINVAL;
-  }
-  const int64_t qblocks = ((int64_t)Nq + kTaQ - 1) / kTaQ;
-  if ((int64_t)Nk1 + Nk2 > INT32_MAX - kTaK || B * H > INT32_MAX || B * H * qblocks > INT32_MAX) {
-    set_error("%s: too large: B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (Nk1 + Nk2 and the %d-row query blocks of all (b, h) stay "
-              "below 2^31)", fn, (long long)B, H, Nq, Nk1, Nk2, kTaQ);
-    return WALDO_EINVAL;
-  }
-  const int64_t strides[10] = {qs_b, qs_n, k1s_b, k1s_n, v1s_b, v1s_n, k2s_b, k2s_n, v2s_b, v2s_n};
-  const int nstr = Nk2 > 0 ? 10 : 6;
-  for (int i = 0; i < nstr; ++i)
-    if (strides[i] < 0) {
-      set_error("%s: negative stride", fn);
-      return WALDO_EINVAL;
-    }
-  // a (token, head) row is D consecutive floats read in 16-byte pieces.  A token stride that is no whole number of
-  // pieces is what a view with a non-unit inner stride (or rows off the 16-byte boundaries) would need: it has no
-  // description here.  A batch stride only has to keep the rows of the next sequence on those boundaries.
-  for (int i = 0; i < nstr; ++i)
-    if (strides[i] % 4 != 0) {
-      if (i & 1)
-        set_error("%s: bad token stride %lld: rows are D consecutive floats a multiple of 4 floats apart (a view with a "
-                  "non-unit inner stride is not served)", fn, (long long)strides[i]);
-      else
-        set_error("%s: bad batch stride %lld: a multiple of 4 floats (rows on 16-byte boundaries)", fn,
-                  (long long)strides[i]);
-      return WALDO_EINVAL;
-    }
-  if (B == 0 || Nq == 0) return WALDO_OK;
-  if (!q || !k1 || !v1 || !out || (Nk2 > 0 && (!k2 || !v2))) {
-    set_error("%s: null pointer", fn);
-    return WALDO_EINVAL;
-  }
-  if (!aligned16(q) || !aligned16(k1) || !aligned16(v1) || !aligned16(out) ||
-      (Nk2 > 0 && (!aligned16(k2) || !aligned16(v2)))) {
-    set_error("%s: pointer not aligned to 16 bytes", fn);
-    return WALDO_EINVAL;
-  }
-  TokenAttentionArgs a{};
-  a.q = q, a.k1 = k1, a.v1 = v1, a.k2 = Nk2 > 0 ? k2 : nullptr, a.v2 = Nk2 > 0 ? v2 : nullptr, a.out = out;
-  a.qs_b = qs_b, a.qs_n = qs_n, a.k1s_b = k1s_b, a.k1s_n = k1s_n, a.v1s_b = v1s_b, a.v1s_n = v1s_n;
-  a.k2s_b = k2s_b, a.k2s_n = k2s_n, a.v2s_b = v2s_b, a.v2s_n = v2s_n;
-  a.scale = scale, a.H = H, a.Nq = Nq, a.Nk1 = Nk1, a.Nk = Nk1 + Nk2, a.qblocks = (int)qblocks;
-  const dim3 grid((unsigned)(B * H * qblocks));
-  hipStream_t st = (hipStream_t)stream;
-  if (D == 16) token_attention_fwd_kernel<16><<<grid, dim3(kBlock), 0, st>>>(a);
-  else if (D == 32) token_attention_fwd_kernel<32><<<grid, dim3(kBlock), 0, st>>>(a);
-  else token_attention_fwd_kernel<64><<<grid, dim3(kBlock), 0, st>>>(a);
-  return launch_status(fn);
+  return token_attention_fwd_host<false>("waldo_token_attention_fwd", q, qs_b, qs_n, k1, k1s_b, k1s_n, v1, v1s_b, v1s_n,
+                                         k2, k2s_b, k2s_n, v2, v2s_b, v2s_n, out, nullptr, scale, B, H, D, Nq, Nk1, Nk2,
+                                         stream);
+}
+
+extern "C" int waldo_token_attention_fwd_lse(const float* q, int64_t qs_b, int64_t qs_n, const float* k1, int64_t k1s_b,
+                                             int64_t k1s_n, const float* v1, int64_t v1s_b, int64_t v1s_n,
+                                             const float* k2, int64_t k2s_b, int64_t k2s_n, const float* v2,
+                                             int64_t v2s_b, int64_t v2s_n, float* out, float* lse, float scale, int64_t B,
+                                             int H, int D, int Nq, int Nk1, int Nk2, waldo_stream_t stream) {
+  return token_attention_fwd_host<true>("waldo_token_attention_fwd_lse", q, qs_b, qs_n, k1, k1s_b, k1s_n, v1, v1s_b,
+                                        v1s_n, k2, k2s_b, k2s_n, v2, v2s_b, v2s_n, out, lse, scale, B, H, D, Nq, Nk1,
+                                        Nk2, stream);
 }

@@ -2134,7 +2134,7 @@ def token_attention_framework(q, k, v, k2=None, v2=None, scale=None):
     """``token_attention`` spelled out in framework ops, as the reference runs it (models/modules/transform.py:109-117
     for one segment, :175-185 for two): matmul, scale, ``cat`` of the two score blocks, softmax, ``cat`` of the values,
     matmul, transpose, reshape.  The CPU route of ``token_attention``, the ``fused = False`` route of the transformer
-    blocks and what the backward of the kernel route differentiates."""
+    blocks and what the ``"framework"`` backward route of the kernel differentiates."""
     _token_attention_check(q, k, v, k2, v2)
     b, nq, h, d = q.shape
     scale = d ** -0.5 if scale is None else scale
@@ -2175,12 +2175,68 @@ def _token_attention_served(q, k, v, k2, v2):
     return None if any(s is None for s in strides) else strides
 
 
+_token_attention_bwd_limits = None
+
+
+def token_attention_bwd_limits():
+    """``token_attention_limits`` of the backward's kernels (``waldo_token_attention_bwd_limits``): ``q_tile`` the query
+    rows per workgroup of the dQ kernel and per LDS tile of the dK/dV kernel, ``k_tile`` the keys per LDS tile of the dQ
+    kernel and per workgroup of the dK/dV kernel."""
+    global _token_attention_bwd_limits
+    if _token_attention_bwd_limits is None:
+        buf = (ctypes.c_int * 16)()
+        n = _lib.load().waldo_token_attention_bwd_limits(buf, 16)
+        vals = [int(buf[i]) for i in range(n)]
+        _token_attention_bwd_limits = {"q_tile": vals[0], "k_tile": vals[1], "head_dims": tuple(vals[2:])}
+    return dict(_token_attention_bwd_limits)
+
+
+TOKEN_ATTENTION_BACKWARD_ROUTES = ("kernel", "framework")
+_token_attention_backward_route = "framework"
+
+
+def get_token_attention_backward_route():
+    """The route the backward of a ``token_attention`` whose forward runs now will take."""
+    return _token_attention_backward_route
+
+
+class token_attention_backward_route:
+    """``token_attention_backward_route(route)`` sets how the kernel route of ``token_attention`` differentiates:
+    ``"kernel"`` -- ``waldo_token_attention_bwd`` from the forward's ``out`` and row statistics (no score tensor, no
+    atomics) -- or ``"framework"`` -- ``token_attention_framework`` recomputed from the saved views and differentiated
+    (kept for A/B runs and as the fallback).  Used as ``with token_attention_backward_route(route):`` the earlier setting
+    comes back on exit, also after an exception; nests.  The route is read when the op's FORWARD runs and travels with
+    the autograd node.  The default is ``"framework"`` (the measurements favour the kernel; the default
+    follows once the launch counts the suite pins for a training step change with it)."""
+
+    def __init__(self, route):
+        global _token_attention_backward_route
+        if route not in TOKEN_ATTENTION_BACKWARD_ROUTES:
+            raise ValueError(f"token_attention_backward_route: route must be one of {TOKEN_ATTENTION_BACKWARD_ROUTES}, "
+                             f"got {route!r}")
+        self.route = route
+        self.prev = _token_attention_backward_route
+        _token_attention_backward_route = route
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _token_attention_backward_route
+        _token_attention_backward_route = self.prev
+        return False
+
+
 class _TokenAttention(torch.autograd.Function):
-    """Forward: the kernel on the views as they lie.  Backward: the framework sequence recomputed from the saved views
-    under ``enable_grad`` and differentiated -- the forward keeps no score tensor."""
+    """Forward: the kernel on the views as they lie; no score tensor is kept.  Backward, by the route read in the
+    forward (``token_attention_backward_route``): ``"kernel"`` -- the forward ran ``waldo_token_attention_fwd_lse`` and
+    saved ``out`` and ``lse`` with the views, and ``waldo_token_attention_bwd`` computes only the wanted gradients in one
+    call; ``"framework"`` -- the framework sequence recomputed from the saved views under ``enable_grad`` and
+    differentiated.  A forward none of whose inputs needs a gradient runs the plain entry point and allocates no
+    ``lse``."""
 
     @staticmethod
-    def forward(ctx, scale, strides, q, k, v, k2, v2):
+    def forward(ctx, scale, strides, route, q, k, v, k2, v2):
         b, nq, h, d = q.shape
         out = torch.empty(b, nq, h * d, dtype=torch.float32, device=q.device)
         flat = []
@@ -2190,24 +2246,43 @@ class _TokenAttention(torch.autograd.Function):
             flat += [k2, strides[3][0], strides[3][1], v2, strides[4][0], strides[4][1]]
         else:
             flat += [None, 0, 0, None, 0, 0]
-        _lib.launch("waldo_token_attention_fwd", q.device, *flat, out, float(scale), b, h, d, nq, k.shape[1],
-                    0 if k2 is None else k2.shape[1])
+        shape = (b, h, d, nq, k.shape[1], 0 if k2 is None else k2.shape[1])
+        ctx.route = route
         ctx.scale = scale
         ctx.two = k2 is not None
-        ctx.save_for_backward(*((q, k, v, k2, v2) if ctx.two else (q, k, v)))
+        views = (q, k, v, k2, v2) if ctx.two else (q, k, v)
+        if route == "kernel":
+            lse = torch.empty(b, h, nq, dtype=torch.float32, device=q.device)
+            _lib.launch("waldo_token_attention_fwd_lse", q.device, *flat, out, lse, float(scale), *shape)
+            ctx.flat, ctx.shape = [a if type(a) is int else None for a in flat], shape
+            ctx.save_for_backward(*views, out, lse)
+        else:
+            _lib.launch("waldo_token_attention_fwd", q.device, *flat, out, float(scale), *shape)
+            ctx.save_for_backward(*views)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        need = ctx.needs_input_grad[2:2 + len(ctx.saved_tensors)]
+        nv = 5 if ctx.two else 3
+        need = ctx.needs_input_grad[3:3 + nv]
+        if ctx.route == "kernel":
+            *views, out, lse = ctx.saved_tensors
+            dev = out.device
+            grads = [torch.empty(t.shape, dtype=torch.float32, device=dev) if n else None for t, n in zip(views, need)]
+            flat = list(ctx.flat)
+            flat[0:nv * 3:3] = views
+            delta = torch.empty_like(lse)
+            _lib.launch("waldo_token_attention_bwd", dev, *flat, out, _c(grad_out), lse, delta, *grads,
+                        *([None] * (5 - nv)), float(ctx.scale), *ctx.shape)
+            return (None, None, None, *grads, *([None] * (5 - nv)))
         with torch.enable_grad():
             leaves = [t.detach().requires_grad_(n) for t, n in zip(ctx.saved_tensors, need)]
             out = token_attention_framework(*leaves, scale=ctx.scale)
             wanted = [t for t, n in zip(leaves, need) if n]
             grads = iter(torch.autograd.grad(out, wanted, grad_out)) if wanted else iter(())
         res = [next(grads) if n else None for n in need]
-        return (None, None, *res, *([None] * (5 - len(res))))
+        return (None, None, None, *res, *([None] * (5 - len(res))))
 
 
 def token_attention(q, k, v, k2=None, v2=None, scale=None):
@@ -2218,12 +2293,20 @@ def token_attention(q, k, v, k2=None, v2=None, scale=None):
 
     fp32 tensors on the GPU with D in ``token_attention_limits()["head_dims"]``, a unit inner stride, heads D apart
     and rows on 16-byte boundaries run ``waldo_token_attention_fwd`` (include/waldo_hip.h "Token attention"): no score
-    tensor, no atomics -- the same bits from run to run in either deterministic mode.  Its backward recomputes
-    ``token_attention_framework`` from the saved views and differentiates that.  Everything else -- CPU tensors,
-    another D, another dtype (16-bit inputs, autocast), another layout -- IS ``token_attention_framework``."""
+    tensor, no atomics -- the same bits from run to run in either deterministic mode.  Its backward takes the route
+    set by ``token_attention_backward_route``: ``"kernel"`` is ``waldo_token_attention_bwd`` (the forward then also
+    stores its row statistics, ``waldo_token_attention_fwd_lse``; no score tensor, no atomics, only the wanted
+    gradients), ``"framework"`` recomputes ``token_attention_framework`` from the saved views and differentiates that.
+    Everything else -- CPU tensors, another D, another dtype (16-bit inputs, autocast), another layout -- IS
+    ``token_attention_framework`` end to end."""
     _token_attention_check(q, k, v, k2, v2)
     scale = q.shape[3] ** -0.5 if scale is None else float(scale)
     strides = _token_attention_served(q, k, v, k2, v2)
     if strides is None:
         return token_attention_framework(q, k, v, k2, v2, scale)
-    return _TokenAttention.apply(scale, strides, q, k, v, k2, v2)
+    # the route travels with the node; a call that records no node (no gradient wanted) needs no row statistics
+    route = _token_attention_backward_route
+    if route == "kernel" and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                                                  for t in (q, k, v, k2, v2))):
+        route = "framework"
+    return _TokenAttention.apply(scale, strides, route, q, k, v, k2, v2)
