@@ -5,7 +5,7 @@ shapes sit on the kernel's tile edges (``WF.token_attention_limits()``); every c
 import pytest
 import torch
 
-from parity import close
+from parity import TOL, close
 
 pytestmark = pytest.mark.gpu
 
@@ -37,12 +37,69 @@ def operands(dev, b, h, nq, nk1, nk2, d, seed=0, amp=1.4):
     return q, k, v, mk(nk2, amp), mk(nk2, 1.0)
 
 
-def check(ops, what, scale=None):
-    out = kernel(*ops, scale=scale)
+def check(ops, what, scale=None, fn=None):
+    """``fn``: the candidate, the kernel unless a restatement is judged by the same yardstick
+    (test_token_attention_sensitivity_cpu.py)."""
+    out = (fn or kernel)(*ops, scale=scale)
     r32, r64 = refs(*ops, scale=scale)
     assert out.shape == r32.shape and out.is_contiguous()
     close(out, r32, exact=r64, what=what)
     return out
+
+
+# The operand recipes of the families that test_token_attention_sensitivity_cpu.py replays on a tile-by-tile
+# restatement with planted faults: plain lists, one list for both sides.
+def tile_edge_cases(qt, kt, d):
+    """(b, h, nq, nk1, nk2, d, seed): every combination of Nq in {1, QT-1, QT, QT+1}, Nk1 in {1, KT-1, KT, KT+1,
+    2 KT+3} and Nk2 in {absent, 1, KT+1}."""
+    grid = [(nq, nk1, nk2) for nq in (1, qt - 1, qt, qt + 1) for nk1 in (1, kt - 1, kt, kt + 1, 2 * kt + 3)
+            for nk2 in (None, 1, kt + 1)]
+    return [(1, 2, nq, nk1, nk2, d, i + 1) for i, (nq, nk1, nk2) in enumerate(grid)]
+
+
+SCALE_FACTORS = (0.0, -1.0, 0.37, 2.5)   # of D ** -0.5: uniform weights, a negative scale, a smaller and a larger one
+
+
+def scale_cases(qt, kt):
+    """((b, h, nq, nk1, nk2, d, seed), scale): a query tail, a key tail and a seam inside the last tile, at scales
+    away from the default."""
+    return [((1, 2, qt + 1, kt + 1, 9, d, 5), f * d ** -0.5) for d in (16, 32, 64) for f in SCALE_FACTORS]
+
+
+LARGE_SCORE_CASES = (False, True)   # low_rows of large_score_operands
+
+
+def large_score_operands(dev, kt, low_rows=False):
+    """Scores from below -60 to above +60; the running maximum of every row rises in the first tile (a planted 40), in
+    the second segment (45), in the last tile (58) and once more at the very last key (60): every tile rescales.
+    ``low_rows``: component 1 then moves EVERY score of the first and of the last query row down by 160, so that their
+    row statistic lse is near -100 and exp(-lse) beyond fp32 -- the softmax of those rows is what it was."""
+    b, h, nq, nk1, nk2, d = 2, 2, 70, kt + 7, 2 * kt + 5, 64
+    q, k, v, k2, v2 = operands(dev, b, h, nq, nk1, nk2, d, seed=17)            # logits of std ~ 2
+    q[..., 0], k[..., 0], k2[..., 0] = 8.0, 0.0, 0.0                           # component 0 carries the planted scores
+    plant = lambda score: score / (d ** -0.5 * 8.0)
+    k[:, 0, :, 0] = plant(-60.0)
+    k[:, 5, :, 0] = plant(40.0)
+    k2[:, 3, :, 0] = plant(45.0)
+    k2[:, nk2 - 9, :, 0] = plant(58.0)      # in the last tile
+    k2[:, nk2 - 1, :, 0] = plant(60.0)      # the last key of all
+    scores = torch.einsum("bihd,bjhd->bhij", q.double(), torch.cat([k, k2], 1).double()) * d ** -0.5
+    assert scores.max() > 60 and scores.min() < -60 and scores[..., nk1 + 3].min() > 35
+    assert (scores.argmax(-1) >= nk1 + nk2 - 9).all()
+    if low_rows:
+        q[..., 1], k[..., 1], k2[..., 1] = 0.0, 1.0, 1.0
+        q[:, 0, :, 1] = q[:, nq - 1, :, 1] = -160.0 / d ** -0.5
+        scores = torch.einsum("bihd,bjhd->bhij", q.double(), torch.cat([k, k2], 1).double()) * d ** -0.5
+        lse = torch.logsumexp(scores, -1)
+        assert lse[..., 0].max() < -95 and lse[..., nq - 1].max() < -95 and lse[..., 1:nq - 1].min() > 50
+    return q, k, v, k2, v2
+
+
+def scale_moves_the_output(ops, scale):
+    """From the reference alone: the fp32 framework output at ``scale`` is more than 100 TOL from the one at the
+    default scale, so a kernel that ignored the argument cannot pass."""
+    moved = (refs(*ops, scale=scale)[0] - refs(*ops)[0]).abs().max().item()
+    assert moved > 100 * TOL, moved
 
 
 @pytest.mark.parametrize("d", [16, 32, 64])
@@ -51,13 +108,19 @@ def test_tile_edges(dev, d):
     key tails, a seam inside a tile, a seam on a tile boundary, a second segment that is all of the last tile."""
     lim = WF().token_attention_limits()
     assert d in lim["head_dims"]
-    qt, kt = lim["q_tile"], lim["k_tile"]
-    seed = 0
-    for nq in (1, qt - 1, qt, qt + 1):
-        for nk1 in (1, kt - 1, kt, kt + 1, 2 * kt + 3):
-            for nk2 in (None, 1, kt + 1):
-                seed += 1
-                check(operands(dev, 1, 2, nq, nk1, nk2, d, seed), f"D={d} Nq={nq} Nk1={nk1} Nk2={nk2}")
+    for b, h, nq, nk1, nk2, d, seed in tile_edge_cases(lim["q_tile"], lim["k_tile"], d):
+        check(operands(dev, b, h, nq, nk1, nk2, d, seed), f"D={d} Nq={nq} Nk1={nk1} Nk2={nk2}")
+
+
+@pytest.mark.parametrize("d", [16, 32, 64])
+@pytest.mark.parametrize("f", SCALE_FACTORS)
+def test_a_scale_that_is_not_the_default(dev, d, f):
+    """f = 0 pins uniform weights, f = -1 that nothing assumes a positive scale."""
+    lim = WF().token_attention_limits()
+    (shape, scale), = [c for c in scale_cases(lim["q_tile"], lim["k_tile"]) if c[0][5] == d and c[1] == f * d ** -0.5]
+    ops = operands(dev, *shape[:6], seed=shape[6])
+    scale_moves_the_output(ops, scale)
+    check(ops, f"D={d} scale={f} D^-1/2", scale=scale)
 
 
 def test_many_heads_and_query_blocks(dev):
@@ -107,22 +170,15 @@ def test_what_the_kernel_does_not_serve_takes_the_framework_route(dev):
 
 
 def test_large_scores_and_the_online_rescale(dev):
-    """Scores from below -60 to above +60; the running maximum of every row rises in the first tile (a planted 40), in
-    the second segment (45), in the last tile (58) and once more at the very last key (60): every tile rescales."""
+    """The operands of large_score_operands: scores from below -60 to above +60, the row maximum rising in every
+    tile."""
     kt = WF().token_attention_limits()["k_tile"]
-    b, h, nq, nk1, nk2, d = 2, 2, 70, kt + 7, 2 * kt + 5, 64
-    q, k, v, k2, v2 = operands(dev, b, h, nq, nk1, nk2, d, seed=17)            # logits of std ~ 2
-    q[..., 0], k[..., 0], k2[..., 0] = 8.0, 0.0, 0.0                           # component 0 carries the planted scores
-    plant = lambda score: score / (d ** -0.5 * 8.0)
-    k[:, 0, :, 0] = plant(-60.0)
-    k[:, 5, :, 0] = plant(40.0)
-    k2[:, 3, :, 0] = plant(45.0)
-    k2[:, nk2 - 9, :, 0] = plant(58.0)      # in the last tile
-    k2[:, nk2 - 1, :, 0] = plant(60.0)      # the last key of all
-    scores = torch.einsum("bihd,bjhd->bhij", q.double(), torch.cat([k, k2], 1).double()) * d ** -0.5
-    assert scores.max() > 60 and scores.min() < -60 and scores[..., nk1 + 3].min() > 35
-    assert (scores.argmax(-1) >= nk1 + nk2 - 9).all()
-    check((q, k, v, k2, v2), "scores up to +-60")
+    check(large_score_operands(dev, kt), "scores up to +-60")
+
+
+def test_large_scores_with_two_rows_far_below_zero(dev):
+    kt = WF().token_attention_limits()["k_tile"]
+    check(large_score_operands(dev, kt, low_rows=True), "scores up to +-60, two rows 160 lower")
 
 
 def test_equal_scores_give_the_mean_and_a_far_ahead_key_gives_its_row(dev):

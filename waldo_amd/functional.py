@@ -2273,7 +2273,11 @@ class _TokenAttention(torch.autograd.Function):
             flat = list(ctx.flat)
             flat[0:nv * 3:3] = views
             delta = torch.empty_like(lse)
-            _lib.launch("waldo_token_attention_bwd", dev, *flat, out, _c(grad_out), lse, delta, *grads,
+            # the kernel reads grad_out as dense rows in 16-byte pieces; autograd also hands over strided gradients and
+            # contiguous views off that boundary (the gradient of a ``cat``): one copy then, an ordinary op in a graph
+            if not grad_out.is_contiguous() or grad_out.data_ptr() % 16:
+                grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+            _lib.launch("waldo_token_attention_bwd", dev, *flat, out, grad_out, lse, delta, *grads,
                         *([None] * (5 - nv)), float(ctx.scale), *ctx.shape)
             return (None, None, None, *grads, *([None] * (5 - nv)))
         with torch.enable_grad():
