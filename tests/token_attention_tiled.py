@@ -1,5 +1,5 @@
-"""What the token attention kernels compute (waldo_amd/csrc/token_attention.hip, token_attention_bwd.hip), restated in
-plain torch, with one named FAULT at a time: the candidates that test_token_attention_sensitivity_cpu.py hands to the
+"""What the token attention kernels compute (waldo_amd/csrc/token_attention.hip, token_attention_bwd.hip and the tile
+pipeline they share, token_attention_common.hip.h), restated in plain torch, with one named FAULT at a time: the candidates that test_token_attention_sensitivity_cpu.py hands to the
 yardsticks of the GPU tests.  Forward: the online softmax over key tiles of ``k_tile`` across the concatenated segments
 with the running (m, l), lse = m + log l.  Backward: the kernels' formulas from out and lse -- delta = rowsum(dO o O),
 P = exp(scale S - lse), dS = P o (dP - delta), dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO -- with delta and dP

@@ -6,6 +6,11 @@ at the LVD recipe's shapes (scripts/cityscapes/train_lvd.sh: 512 wide, 8 heads, 
 
     python tools_dev/ab_lvd_nets.py [--out profiles/lvd_nets.json] [--sections op,lvd] [--rounds 20] [--warmup 5]
     python tools_dev/ab_lvd_nets.py --out profiles/lvd_nets_bwd.json --sections bwd,step [--clips 4]
+    python tools_dev/ab_lvd_nets.py --out FILE --sections op,bwd --head-dim 16 --lib tools_dev/_variants/NAME.so
+
+--lib binds another build of the library (``_lib.use_library``: tools_dev/build_variant.py makes one) for an A/B of two
+builds in two processes; --head-dim D runs ``op`` and ``bwd`` at another head dimension with the same token counts and
+512 / D heads (the width stays 512; the default 64 is the recipe's).
 
 Sections:
   op   the op alone, forward without autograd, fp32: the PoseEstimator's self-attention (56 and 112 sequences of
@@ -42,7 +47,8 @@ sys.path.insert(0, ROOT)
 
 from waldo_amd import functional as WF  # noqa: E402
 
-HEADS, D = 8, 64
+WIDTH = 512
+HEADS, D = 8, 64   # main() sets them from --head-dim
 # (name, sequences, queries, keys of the first segment, keys of the second or None)
 OP_SHAPES = (("pose_56", 56, 512, 512, None), ("pose_112", 112, 512, 512, None),
              ("layer_4", 4, 384, 384, 512), ("layer_8", 8, 384, 384, 512))
@@ -254,7 +260,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--clips", type=int, default=4, help="clips of the step section")
+    ap.add_argument("--lib", help="another build of the library to bind instead of the product's")
+    ap.add_argument("--head-dim", type=int, default=64, choices=(16, 32, 64), help="D of the op and bwd sections")
     args = ap.parse_args()
+    global HEADS, D
+    HEADS, D = WIDTH // args.head_dim, args.head_dim
+    if args.lib:
+        from waldo_amd import _lib
+        _lib.use_library(args.lib)
     if not torch.cuda.is_available():
         raise SystemExit("ab_lvd_nets: no GPU (a measurement does not fall back)")
     device = torch.device("cuda:0")
@@ -263,6 +276,7 @@ def main():
         with open(args.out) as fh:
             doc = json.load(fh)
     doc.update(device=torch.cuda.get_device_name(0), torch=torch.__version__, limits=WF.token_attention_limits(),
+               library=args.lib or "product", head_dim=D,
                bwd_limits=WF.token_attention_bwd_limits(),
                method=dict(rounds=args.rounds, warmup=args.warmup, timing="device events, routes alternating"))
     sections = {"op": section_op, "lvd": section_lvd, "bwd": section_bwd,

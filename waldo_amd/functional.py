@@ -2101,19 +2101,23 @@ def plane_norm_gelu(x, weight, bias, skip=None, eps=1e-5, out_dtype=None):
 # --------------------------------------------------------------------------------------
 # token attention: softmax(scale q k^T) v over one or two key / value segments (the LVD transformer blocks)
 # --------------------------------------------------------------------------------------
-_token_attention_limits = None
+_token_attention_limits_read = {}
+
+
+def _token_attention_limits_of(symbol):
+    """``{"q_tile", "k_tile", "head_dims"}`` as the library's ``symbol`` reports them (read once per symbol)."""
+    if symbol not in _token_attention_limits_read:
+        buf = (ctypes.c_int * 16)()
+        n = getattr(_lib.load(), symbol)(buf, 16)
+        vals = [int(buf[i]) for i in range(n)]
+        _token_attention_limits_read[symbol] = {"q_tile": vals[0], "k_tile": vals[1], "head_dims": tuple(vals[2:])}
+    return dict(_token_attention_limits_read[symbol])
 
 
 def token_attention_limits():
     """``{"q_tile", "k_tile", "head_dims"}`` of the kernel (``waldo_token_attention_limits``): query rows per
     workgroup, keys per LDS tile, the head dimensions it serves."""
-    global _token_attention_limits
-    if _token_attention_limits is None:
-        buf = (ctypes.c_int * 16)()
-        n = _lib.load().waldo_token_attention_limits(buf, 16)
-        vals = [int(buf[i]) for i in range(n)]
-        _token_attention_limits = {"q_tile": vals[0], "k_tile": vals[1], "head_dims": tuple(vals[2:])}
-    return dict(_token_attention_limits)
+    return _token_attention_limits_of("waldo_token_attention_limits")
 
 
 def _token_attention_check(q, k, v, k2, v2):
@@ -2175,20 +2179,11 @@ def _token_attention_served(q, k, v, k2, v2):
     return None if any(s is None for s in strides) else strides
 
 
-_token_attention_bwd_limits = None
-
-
 def token_attention_bwd_limits():
     """``token_attention_limits`` of the backward's kernels (``waldo_token_attention_bwd_limits``): ``q_tile`` the query
     rows per workgroup of the dQ kernel and per LDS tile of the dK/dV kernel, ``k_tile`` the keys per LDS tile of the dQ
     kernel and per workgroup of the dK/dV kernel."""
-    global _token_attention_bwd_limits
-    if _token_attention_bwd_limits is None:
-        buf = (ctypes.c_int * 16)()
-        n = _lib.load().waldo_token_attention_bwd_limits(buf, 16)
-        vals = [int(buf[i]) for i in range(n)]
-        _token_attention_bwd_limits = {"q_tile": vals[0], "k_tile": vals[1], "head_dims": tuple(vals[2:])}
-    return dict(_token_attention_bwd_limits)
+    return _token_attention_limits_of("waldo_token_attention_bwd_limits")
 
 
 TOKEN_ATTENTION_BACKWARD_ROUTES = ("kernel", "framework")
