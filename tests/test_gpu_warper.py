@@ -1122,6 +1122,44 @@ def test_frame_warp_fuse_staged_boxes_same_bits(dev, tc, include_self, hw, amp_p
     assert torch.equal(raw, raw_g), (raw - raw_g).abs().max().item()
 
 
+@pytest.mark.parametrize("raw_dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("tc,include_self", [(4, False), (3, True), (1, False)])
+@pytest.mark.parametrize("hw", [(8, 36), (37, 100)])
+@pytest.mark.parametrize("amp_px", [3.0, 40.0])
+def test_frame_warp_fuse_raw_staged_boxes_same_bits(dev, raw_dtype, tc, include_self, hw, amp_px):
+    """The raw path of the two forward kernels on the same data (aligned frames: frame_warp_fuse_lds_kernel; the same
+    values one float into a buffer: frame_warp_fuse_kernel), bit for bit in `out` and in the WHOLE of `raw`, the alpha
+    slots neither kernel writes included: the staged kernel's lane-pair stores of a 16-bit `raw` (4 x 64 tiles, two
+    pixels per 4-byte store, the tile's last PAIR duplicated past the edge) against the gather kernel's store per pixel,
+    and the two kernels' reads of the score plane.  Both rasters have ragged tiles in either tile shape and
+    Wd % 4 == 0, the second an odd height; 3 px flows give boxes that fit, 40 px over 16-pixel cells some that do not."""
+    from waldo_amd import functional as WF
+    hd, wd = hw
+    b, t, c, nl = 2, 5, 6, 3
+    tp = t if include_self else 3
+    tcx = tc + (1 if include_self else 0)
+    g = torch.Generator(device=dev).manual_seed(hd + tc)
+    buf = torch.randn(b * t * c * hd * wd + 1, generator=g, device=dev)
+    inp_off = buf[1:].view(b, t, c, hd, wd)
+    inp = inp_off.clone()                                       # 16-byte aligned copy of the same values
+    assert inp.data_ptr() % 16 == 0 and inp_off.data_ptr() % 16 == 4
+    fl = (amp_px * 2 / wd) * torch.randn(b * tc * tp, 2, max(hd // 16, 1), max(wd // 16, 1), generator=g, device=dev)
+    flow = torch.nn.functional.interpolate(fl, size=(hd, wd), mode="bilinear").view(b, tc, tp, 2, hd, wd).contiguous()
+    flow[0, 0, 0, :, : hd // 2] += 2.5                          # a block of samples outside the frame
+    raw0 = (torch.rand(b, tp, tcx, c + nl, hd, wd, generator=g, device=dev) * 2 - 1).to(raw_dtype)
+    score = torch.rand(b, tc, tp, hd, wd, generator=g, device=dev) * nl + 0.05
+    ctx_ts = torch.randint(0, t, (b, tc, tp), generator=g, device=dev)
+    res = []
+    for frames in (inp, inp_off):
+        slots = WF.RawSlots(raw0.clone(), score, c, include_self)
+        out, _ = WF.frame_warp_fuse_raw(frames, flow, slots, ctx_ts)
+        res.append((out, slots.raw))
+    (out, raw), (out_g, raw_g) = res
+    assert raw.dtype == raw_dtype and torch.equal(raw[:, :, :tc, c:], raw0[:, :, :tc, c:])
+    assert torch.equal(out, out_g), (out - out_g).abs().max().item()
+    assert torch.equal(raw, raw_g), (raw.float() - raw_g.float()).abs().max().item()
+
+
 @pytest.mark.parametrize("include_self", [False, True])
 @pytest.mark.parametrize("shape", [(2, 3, 2, 2, 7, 5, 4, 16, 32, 2, True), (1, 4, 4, 3, 23, 12, 8, 32, 4, 4, False),
                                    (1, 2, 5, 1, 4, 3, 8, 16, 1, 1, True)])

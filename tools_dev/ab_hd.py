@@ -2,7 +2,11 @@
 across library builds on one box, interleaved, at the C5 recipe's size (512 x 1024, L = 12, 23 input channels,
 4 context frames).  Calls the C ABI through ctypes directly.
 
-    python tools_dev/ab_hd.py [--clips 2 --tp 10 --rounds 3] lib1.so lib2.so ..."""
+    python tools_dev/ab_hd.py [--clips 2 --tp 10 --rounds 3] [--tc 4] [--misalign] lib1.so lib2.so ...
+
+--tc: the context frames of frame_warp_fuse (1, 2, 4: an instance of their own each; 8 takes the gather kernel's <8>, use
+--clips 1).  --misalign: the frames are a view one float into a larger buffer, so frame_warp_fuse takes the gather kernel
+(frame_warp_fuse_kernel) at the same size where 16-byte aligned frames take the LDS kernel."""
 import argparse
 import ctypes
 import os
@@ -23,21 +27,24 @@ ap.add_argument('--scale', type=int, default=4)
 ap.add_argument('--layers', type=int, default=12)
 ap.add_argument('--amp', type=float, default=0.02, help='flow amplitude in grid units (0.02 = 10 px at 1024)')
 ap.add_argument('--coarse', type=int, default=32, help='the flow is smooth over this many pixels')
+ap.add_argument('--tc', type=int, default=4, choices=(1, 2, 4, 8), help='context frames')
+ap.add_argument('--misalign', action='store_true', help='frames one float into a buffer: the gather kernel')
 ap.add_argument('libs', nargs='+')
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 g = torch.Generator(device=dev).manual_seed(0)
-b, t, tc, tp, nl, ncls = a.clips, 14, 4, a.tp, a.layers, 20
+b, t, tc, tp, nl, ncls = a.clips, 14, a.tc, a.tp, a.layers, 20
 c = 3 + ncls
 h, w, s = a.dim, 2 * a.dim, a.scale
 hd, wd = h * s, w * s
-inp = torch.randn(b, t, c, hd, wd, generator=g, device=dev)
+inp = torch.randn(b * t * c * hd * wd + 1, generator=g, device=dev)[1 if a.misalign else 0:][:b * t * c * hd * wd].view(b, t, c, hd, wd)
+assert inp.data_ptr() % 16 == (4 if a.misalign else 0)
 # smooth flows of a few pixels (grid units), like the composited TPS flows of the chain
 lo = a.amp * torch.randn(b * tc * tp, 2, hd // a.coarse, wd // a.coarse, generator=g, device=dev)
 flow = torch.nn.functional.interpolate(lo, size=(hd, wd), mode='bilinear').view(b, tc, tp, 2, hd, wd).contiguous()
 alpha = torch.rand(b, tc, tp, nl, hd, wd, generator=g, device=dev) * 2 - 1
 ctx_ts = torch.arange(tc, device=dev).view(1, tc, 1).expand(b, tc, tp).contiguous()
-pred_ts = torch.arange(tc, tc + tp, device=dev)
+pred_ts = torch.arange(tc, tc + tp, device=dev).clamp(max=t - 1)
 out = torch.empty(b, tp, c + 1, hd, wd, device=dev)
 raw = torch.empty(b, tp, tc, c + nl, hd, wd, device=dev)
 # flow_ctx_warp inputs
@@ -65,13 +72,13 @@ for path in a.libs:
 
 
 def fwf(lib):
-    assert lib.waldo_frame_warp_fuse_fwd(ptr(inp), ptr(flow), ptr(alpha), ptr(ctx_ts), ptr(out), ptr(raw), b, t, tc, tp,
-                                         c, nl, hd, wd, 0, 1e-6, st) == 0
+    assert lib.waldo_frame_warp_fuse_fwd(ptr(inp), ptr(flow), ptr(alpha), ptr(ctx_ts), ptr(out), ptr(raw), None, b, t, tc,
+                                         tp, c, nl, hd, wd, 0, 1e-6, st) == 0
 
 
 def fcw(lib):
     assert lib.waldo_flow_ctx_warp_fwd(ptr(flow_lr), None, ptr(a01), ptr(ctx_ts), ptr(pred_ts), ptr(occ), ptr(oflow),
-                                       ptr(oactx), ptr(odis), None, b, t, tc, tc, tp, nl, h, w, s, st) == 0
+                                       ptr(oactx), ptr(odis), None, None, None, b, t, tc, tc, tp, nl, h, w, s, st) == 0
 
 
 def timeit(fn, n):

@@ -3,7 +3,7 @@ clip packed (functional.PackedClip: RGB bytes + class id, one word per pixel), e
 same seeds, interleaved rounds.  The two inputs hold the same data (the fp32 clip is the packed one's unpack()), and the
 first step of every raw dtype checks that both give the same outputs bit for bit.  One JSON line per variant.
 
-    python tools_dev/ab_packed_clip.py [--steps 5] [--warmup 2] [--rounds 2] [--only packed-bf16]
+    python tools_dev/ab_packed_clip.py [--steps 5] [--warmup 2] [--rounds 2] [--only packed-bf16] [--lib OTHER.so]
 
 (--only: one variant and nothing else -- for rocprofv3 runs, `rocprofv3 --kernel-trace --stats ... -- python
 tools_dev/ab_packed_clip.py --only packed-bf16 --steps 2 --warmup 1`, and `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` in runs
@@ -46,7 +46,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--only", choices=sorted(VARIANTS), default=None)
+    ap.add_argument("--lib", default=None, help="another build of the library (tools_dev/build_variant.py)")
     args = ap.parse_args()
+    if args.lib:
+        _lib.use_library(args.lib)
     dev = torch.device("cuda:0")
     pipe = Pipeline("C5", 4, dev, seed=0)
     opt, ctx_len = pipe.opt, pipe.ctx_len
@@ -86,7 +89,7 @@ def main():
             step(n)
             torch.cuda.synchronize()
         entry = {k: round(v[1] * v[0], 3) for k, v in kt.summary().items() if any(e in k for e in ENTRIES)}
-        line = {"variant": "pipeline_C5", "clip": "packed" if VARIANTS[n][0] else "fp32",
+        line = {"variant": "pipeline_C5", "lib": os.path.basename(_lib.LIB_PATH), "clip": "packed" if VARIANTS[n][0] else "fp32",
                 "raw_dtype": n.split("-")[1], "ms_per_step": round(min(res[n]), 3),
                 "ms_rounds": [round(x, 3) for x in res[n]], "entry_ms_per_step": entry,
                 "clip_bytes": packed.data.numel() if VARIANTS[n][0] else 4 * b * t * (3 + opt.num_lyt) * hd * wd}

@@ -556,6 +556,10 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? ((R == 2 && !std::is_
 // the normalised weights as (B,Tc,Tp,.,Hd,Wd) tensors; here the taps and scores of the Tc contexts
 // of a pixel stay in registers and every input channel is sampled, written to `raw` and fused
 // into `out` in one pass.
+// Two kernels run it -- frame_warp_fuse_kernel reads each context's taps as pair gathers, frame_warp_fuse_lds_kernel
+// stages each context's footprint box in LDS -- and everything a pixel does with its taps is written ONCE, in the fwf_*
+// pieces below: the same taps, weights and arithmetic, so the same bits.  A kernel keeps its pixel decode and edge
+// policy, where its taps come from (byte offsets in the plane, or in the box) and its channel loop.
 
 #ifndef WALDO_FWF_TILE_COLS
 #define WALDO_FWF_TILE_COLS 32  // workgroup tile = 8 rows x 32 columns (HdTile); measured below
@@ -576,177 +580,252 @@ __device__ __forceinline__ void fwf_put(T* at, bool odd, float v) {
   else store_px16<true>(at, v);
 }
 
+// The kernels' arguments as the shared pieces read them (Tc, include_self: constants in the LDS kernel's FULL instances).
+// RT: the element type of `raw` (16-bit: the raw path only -- `alpha` is then NULL).
+// IN: the element type of `input` -- float, or uint32_t for a packed clip (the raw path only; packed_clip.hip.h): the four
+// tap words of a context are loaded ONCE and every channel is expanded from them (C = 3 + Nl channels).
+// (include_self stays the entry point's int: as a bool the 16-bit instances took 1-2 VGPRs more -- gather <8> 168 -> 169,
+// LDS <2> 64 -> 66, packed gather <4> 80 -> 82 -- and each of those lost a wave per SIMD)
+template <typename RT, typename IN>
+struct FwfArgs {
+  const IN* input;
+  const float *flow, *alpha, *score;
+  const int64_t* ctx_ts;
+  float* out;
+  RT* raw;
+  int* status;
+  int T, Tc, Tp, C, L, Hd, Wd;
+  int include_self;
+  float eps;
+  int64_t HWd;
+  __device__ __forceinline__ int tcx() const { return Tc + (include_self ? 1 : 0); }
+  static constexpr bool kPacked = std::is_same<IN, uint32_t>::value;
+};
+
+// A pixel of (b, tp) and its contexts, in registers.  The arrays are indexed by compile-time constants only (unrolled
+// loops): a run-time index would put them in scratch.  Branch-free over the padded context count TCP: a padding context
+// repeats context Tc - 1 and is never stored or summed.
+template <int TCP, typename RT, typename IN>
+struct FwfPixel {
+  int b, tp;
+  int64_t p, pr;  // the pixel in its plane; where this thread's stores to `raw` go (PAIR: its lane pair's first pixel)
+  bool odd;       // (PAIR) the pair's second pixel
+  // per context (fwf_context): corner re-assignment, corner weights, score, source frame
+  int shift[TCP];
+  float w00[TCP], w01[TCP], w10[TCP], w11[TCP], sc[TCP];
+  const IN* frame[TCP];
+  float ssum = 0.0f;
+  bool shifted = false;
+  // the fusion weights and the pixel's planes (fwf_weights)
+  float wt[TCP], wself;
+  const IN* self;
+  RT* rbase;  // context tc: + tc * (C + L) * HWd
+  float* obase;
+  bool any_shift;  // wave-uniform
+};
+
+// The two taps of a row are ONE 8-byte load at the pair origin xb = clamp(x0, 0, Wd - 2) (inside the row;
+// 4-byte aligned: gfx950 takes unaligned dwordx2 loads): half the gather instructions of four single
+// taps.  Within one texel of the left / right border the pair sits one column off the footprint
+// (shift = x0 - xb = -1 / +1) and its elements are re-assigned to the corners (fwf_assign); the corner outside the
+// frame carries weight 0 as before.
+//
+// Context tc of the pixel: taps and weights, the checked source frame, the score -- read from `score` (the alphas
+// already sit in `raw`, waldo_flow_ctx_warp_raw_fwd wrote them there, and their sum came with them: one plane per
+// context instead of L read and L copied) or summed from `alpha` while the alphas are copied into `raw`.
+// origin(cy0, xb, cy1) -- the clamped rows y0 and y0 + 1 and the pair origin: what a kernel makes of them (byte
+// offsets in the plane, the tile's box) is its own, and it does so HERE, before the frame index and the score are
+// read (handed back to the caller and used after the call, the 16-bit gather <8> went from 168 to 172 VGPRs, two waves).
+template <int TCP, typename RT, typename IN, typename F>
+__device__ __forceinline__ void fwf_context(FwfPixel<TCP, RT, IN>& px, int tc, const FwfArgs<RT, IN>& a, float gx0,
+                                            float gy0, F origin) {
+  const int tcc = min(tc, a.Tc - 1);
+  const bool real = tc < a.Tc;
+  const int64_t m = ((int64_t)px.b * a.Tc + tcc) * a.Tp + px.tp;
+  const float* fl = a.flow + m * 2 * a.HWd + px.p;
+  const Taps t = make_taps(gx0 + fl[0], gy0 + fl[a.HWd], a.Hd, a.Wd);
+  const int xb = min(max(t.x0, 0), a.Wd - 2);
+  const int cy0 = min(max(t.y0, 0), a.Hd - 1), cy1 = min(max(t.y0 + 1, 0), a.Hd - 1);
+  origin(cy0, xb, cy1);
+  px.shift[tc] = t.x0 - xb;
+  px.shifted |= px.shift[tc] != 0;
+  px.w00[tc] = t.w00, px.w01[tc] = t.w01, px.w10[tc] = t.w10, px.w11[tc] = t.w11;
+  // (read through the vector path the frame index lands in VGPRs: it is wave-uniform, say so)
+  const int ts = __builtin_amdgcn_readfirstlane(checked_frame(a.ctx_ts, m, a.T, a.status, kStatusCtx));
+  px.frame[tc] = a.input + ((int64_t)px.b * a.T + ts) * (FwfArgs<RT, IN>::kPacked ? 1 : a.C) * a.HWd;
+  float s = 0.0f;
+  if (a.score != nullptr) {
+    s = a.score[m * a.HWd + px.p];
+  } else if constexpr (std::is_same<RT, float>::value) {
+    const float* al = a.alpha + m * a.L * a.HWd + px.p;
+    float* rw = a.raw + ((((int64_t)px.b * a.Tp + px.tp) * a.tcx() + tcc) * (a.C + a.L) + a.C) * a.HWd + px.p;
+    for (int l = 0; l < a.L; ++l) {
+      const float av = al[(int64_t)l * a.HWd];
+      s += (av + 1.0f) / 2.0f;
+      if (real) fwf_store(rw + (int64_t)l * a.HWd, av);
+    }
+  }
+  px.sc[tc] = s;
+  px.ssum += real ? fabsf(s + a.eps) : 0.0f;
+}
+
+// `include_self`: ones into the alpha slots of context Tc, and its score 1 into the sum
+template <bool PAIR, int TCP, typename RT, typename IN>
+__device__ __forceinline__ void fwf_self_alpha(FwfPixel<TCP, RT, IN>& px, const FwfArgs<RT, IN>& a) {
+  if (a.include_self) {
+    RT* rw = a.raw + ((((int64_t)px.b * a.Tp + px.tp) * a.tcx() + a.Tc) * (a.C + a.L) + a.C) * a.HWd + px.pr;
+    for (int l = 0; l < a.L; ++l) fwf_put<PAIR>(rw + (int64_t)l * a.HWd, px.odd, 1.0f);
+    px.ssum += fabsf(1.0f + a.eps);
+  }
+}
+
+// the normalised weights of the contexts and of the unwarped frame, and the pixel's planes of input, raw and out
+template <int TCP, typename RT, typename IN>
+__device__ __forceinline__ void fwf_weights(FwfPixel<TCP, RT, IN>& px, const FwfArgs<RT, IN>& a) {
+  const float den = fmaxf(px.ssum, 1e-12f);
+  px.wself = (1.0f + a.eps) / den;
+#pragma unroll
+  for (int tc = 0; tc < TCP; ++tc) px.wt[tc] = (tc < a.Tc) ? (px.sc[tc] + a.eps) / den : 0.0f;
+  px.self = a.input + ((int64_t)px.b * a.T + min(px.tp, a.T - 1)) * (FwfArgs<RT, IN>::kPacked ? 1 : a.C) * a.HWd + px.p;
+  px.rbase = a.raw + ((int64_t)px.b * a.Tp + px.tp) * a.tcx() * (a.C + a.L) * a.HWd + px.pr;
+  px.obase = a.out + ((int64_t)px.b * a.Tp + px.tp) * (a.C + 1) * a.HWd + px.p;
+  px.any_shift = __ballot(px.shifted) != 0ull;
+}
+
+// corners of the footprint from the pair elements (fwf_context); interior wavefronts (shift == 0 in every lane, for every
+// context) skip the re-assignment
+template <int TCP, typename RT, typename IN, typename V>
+__device__ __forceinline__ void fwf_assign(const FwfPixel<TCP, RT, IN>& px, V (&v)[TCP][4]) {  // (float or uint32_t elements)
+  if (px.any_shift) {
+#pragma unroll
+    for (int tc = 0; tc < TCP; ++tc) {
+      const V a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
+      v[tc][0] = px.shift[tc] > 0 ? a1 : a0;
+      v[tc][1] = px.shift[tc] < 0 ? a0 : a1;
+      v[tc][2] = px.shift[tc] > 0 ? b1 : b0;
+      v[tc][3] = px.shift[tc] < 0 ? b0 : b1;
+    }
+  }
+}
+
+// channel c of `raw` and `out` from the corner values of every context and the unwarped frame's (include_self).
+// FULL: Tc == TCP and no `include_self` -- every store is then unconditional (frame_warp_fuse_lds_kernel).
+template <bool PAIR, bool FULL, int TCP, typename RT, typename IN>
+__device__ __forceinline__ void fwf_fuse(const FwfPixel<TCP, RT, IN>& px, const FwfArgs<RT, IN>& a, int c,
+                                         const float (&tv)[TCP][4], float vself) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int tc = 0; tc < TCP; ++tc) {
+    const float v = fmaf(tv[tc][3], px.w11[tc], fmaf(tv[tc][2], px.w10[tc], fmaf(tv[tc][1], px.w01[tc], tv[tc][0] * px.w00[tc])));
+    if (FULL || tc < a.Tc) fwf_put<PAIR>(px.rbase + ((int64_t)tc * (a.C + a.L) + c) * a.HWd, px.odd, v);
+    acc += v * px.wt[tc];
+  }
+  if (a.include_self) {
+    fwf_put<PAIR>(px.rbase + ((int64_t)a.Tc * (a.C + a.L) + c) * a.HWd, px.odd, vself);
+    acc += vself * px.wself;
+  }
+  fwf_store(px.obase + (int64_t)c * a.HWd, acc);
+}
+
+// a packed clip: every channel of a tap is in its word -- C channels expanded from the tap words tw of all contexts,
+// no loads (`table`: the RGB table, in memory or in LDS)
+template <bool PAIR, bool FULL, int TCP, typename RT>
+__device__ __forceinline__ void fwf_packed_channels(const FwfPixel<TCP, RT, uint32_t>& px, const FwfArgs<RT, uint32_t>& a,
+                                                    const float* table, uint32_t (&tw)[TCP][4]) {
+  fwf_assign(px, tw);
+  const uint32_t pself = a.include_self ? px.self[0] : 0u;  // (the unwarped frame's word)
+  for (int c = 0; c < a.C; ++c) {
+    float tv[TCP][4];
+#pragma unroll
+    for (int tc = 0; tc < TCP; ++tc)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) tv[tc][k] = packed_channel(table, tw[tc][k], c);
+    fwf_fuse<PAIR, FULL>(px, a, c, tv, a.include_self ? packed_channel(table, pself, c) : 0.0f);
+  }
+}
+
+// the score channel of `out`
+template <int TCP, typename RT, typename IN>
+__device__ __forceinline__ void fwf_score_channel(const FwfPixel<TCP, RT, IN>& px, const FwfArgs<RT, IN>& a) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int tc = 0; tc < TCP; ++tc) acc += (px.sc[tc] * 2.0f - 1.0f) * px.wt[tc];
+  if (a.include_self) acc += px.wself;  // (1 * 2 - 1) * w
+  px.obase[(int64_t)a.C * a.HWd] = acc;
+}
+
+// The gather kernel: every shape the LDS kernel below does not take (frame_warp_fuse_launch).
 // Tile shape (tools_dev/ab_hd.py --amp, C5 size, ms at flow amplitudes of 10 / 25 / 50 / 150 px over 32-pixel
 // cells): 4 x 64 (a wavefront = one 64-pixel row segment, as the other kernels of this file) 3.86 / 4.89 / 6.53
 // / 14.4; 8 x 32 (a wavefront = two rows of 32) 3.64 / 4.11 / 4.89 / 11.3; 16 x 16: 4.56 / 4.93 / 5.55 / 10.7.
 // Under a sheared flow the footprint of a long row segment crosses many image rows and every 8-byte pair
 // pulls a line of its own; the squarer wavefront keeps the footprint compact, and at 32 columns the stores
 // are still whole 128-byte lines.
-// RT: the element type of `raw` (16-bit: the raw path only -- `alpha` is then NULL -- one 2-byte store per pixel).
-// IN: the element type of `input` -- float, or uint32_t for a packed clip (the raw path only; packed_clip.hip.h): the four
-// tap words of a context are loaded ONCE and every channel is expanded from them (C = 3 + Nl channels, `rgb_table` the
-// RGB table; NULL for an fp32 input).  The taps, weights and the per-channel arithmetic (fwf_fuse) are the same code.
+// (`rgb_table`: a packed clip's RGB table; NULL for an fp32 input.  A 16-bit `raw`: one 2-byte store per pixel.)
 template <int TCP, typename RT = float, typename IN = float>
 __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
     const IN* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
     const float* __restrict__ score, const int64_t* __restrict__ ctx_ts, float* __restrict__ out,
     RT* __restrict__ raw, int* __restrict__ status, int T, int Tc, int Tp, int C, int L, int Hd, int Wd, int include_self,
     float eps, int units, int tiles, int nbands, const float* __restrict__ rgb_table) {
-  constexpr bool kPacked = std::is_same<IN, uint32_t>::value;
+  constexpr bool kPacked = FwfArgs<RT, IN>::kPacked;
   const int64_t HWd = (int64_t)Hd * Wd;
+  const FwfArgs<RT, IN> a = {input, flow, alpha, score, ctx_ts, out, raw, status, T, Tc, Tp, C, L, Hd, Wd, include_self,
+                             eps, HWd};
   int n, x, y;  // n = (b, tp); the Tp predicted frames of a clip innermost in an XCD's tile walk
   if (!HdTile<WALDO_FWF_TILE_COLS>::pixel_grouped(units / Tp, Tp, Hd, Wd, tiles, nbands, n, x, y) || x >= Wd || y >= Hd) return;
-  const int b = n / Tp, tp = n % Tp;
-  const int64_t p = (int64_t)y * Wd + x;
+  FwfPixel<TCP, RT, IN> px;
+  px.b = n / Tp, px.tp = n % Tp;
+  px.p = px.pr = (int64_t)y * Wd + x;
+  px.odd = false;
   float gx0, gy0;
   identity_grid(x, y, Wd, Hd, gx0, gy0);
 
-  // taps, score and source frame of every context of this pixel, in registers (branch-free over the
-  // padded context count: a padding context repeats context Tc-1 and is never stored or summed)
-  const int Tcx = Tc + (include_self ? 1 : 0);
-  // The two taps of a row are ONE 8-byte load at the pair origin xb = clamp(x0, 0, Wd - 2) (inside the row;
-  // 4-byte aligned: gfx950 takes unaligned dwordx2 loads): half the gather instructions of four single
-  // taps.  Within one texel of the left / right border the pair sits one column off the footprint
-  // (shift = x0 - xb = -1 / +1) and its elements are re-assigned to the corners; the corner outside the
-  // frame carries weight 0 as before.  Interior wavefronts (shift == 0 in every lane, for every context)
-  // skip the re-assignment.
-  uint32_t ob0[TCP], ob1[TCP];
-  int shift[TCP];
-  float w00[TCP], w01[TCP], w10[TCP], w11[TCP], sc[TCP];
-  const IN* frame[TCP];
-  float ssum = 0.0f;
-  bool shifted = false;
+  uint32_t ob0[TCP], ob1[TCP];  // byte offsets of the two pair origins in a plane
 #pragma unroll
   for (int tc = 0; tc < TCP; ++tc) {
-    const int tcc = min(tc, Tc - 1);
-    const bool real = tc < Tc;
-    const int64_t m = ((int64_t)b * Tc + tcc) * Tp + tp;
-    const float* fl = flow + m * 2 * HWd + p;
-    const Taps t = make_taps(gx0 + fl[0], gy0 + fl[HWd], Hd, Wd);
-    {
-      const int xb = min(max(t.x0, 0), Wd - 2);
-      const int cy0 = min(max(t.y0, 0), Hd - 1), cy1 = min(max(t.y0 + 1, 0), Hd - 1);
+    fwf_context(px, tc, a, gx0, gy0, [&](int cy0, int xb, int cy1) {
       ob0[tc] = (uint32_t)(__mul24(cy0, Wd) + xb) * 4u;
       ob1[tc] = (uint32_t)(__mul24(cy1, Wd) + xb) * 4u;
-      shift[tc] = t.x0 - xb;
-      shifted |= shift[tc] != 0;
-    }
-    w00[tc] = t.w00;
-    w01[tc] = t.w01;
-    w10[tc] = t.w10;
-    w11[tc] = t.w11;
-    const int ts = __builtin_amdgcn_readfirstlane(checked_frame(ctx_ts, m, T, status, kStatusCtx));  // wave-uniform
-    frame[tc] = input + ((int64_t)b * T + ts) * (kPacked ? 1 : C) * HWd;
-    float s = 0.0f;
-    if (score != nullptr) {
-      // the alphas already sit in `raw` (waldo_flow_ctx_warp_raw_fwd wrote them there) and their sum came with
-      // them: one plane per context instead of L read and L copied
-      s = score[m * HWd + p];
-    } else if constexpr (std::is_same<RT, float>::value) {
-      const float* al = alpha + m * L * HWd + p;
-      float* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + tcc) * (C + L) + C) * HWd + p;
-      for (int l = 0; l < L; ++l) {
-        const float av = al[(int64_t)l * HWd];
-        s += (av + 1.0f) / 2.0f;
-        if (real) fwf_store(rw + (int64_t)l * HWd, av);
-      }
-    }
-    sc[tc] = s;
-    ssum += real ? fabsf(s + eps) : 0.0f;
+    });
   }
-  if (include_self) {
-    RT* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + p;
-    for (int l = 0; l < L; ++l) fwf_put<false>(rw + (int64_t)l * HWd, false, 1.0f);
-    ssum += fabsf(1.0f + eps);
-  }
-  const float den = fmaxf(ssum, 1e-12f);
-  const float wself = (1.0f + eps) / den;
-  float wt[TCP];
-#pragma unroll
-  for (int tc = 0; tc < TCP; ++tc) wt[tc] = (tc < Tc) ? (sc[tc] + eps) / den : 0.0f;
-  const IN* self = input + ((int64_t)b * T + min(tp, T - 1)) * (kPacked ? 1 : C) * HWd + p;
-  RT* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + p;  // context tc: + tc * (C+L) * HWd
-  float* obase = out + ((int64_t)b * Tp + tp) * (C + 1) * HWd + p;
-  // Channel loop, software-pipelined by hand: the sixteen tap loads of channel c + 1 are issued BEFORE the
-  // stores of channel c.  Vector-memory operations retire in issue order (loads, stores: one counter), so
-  // with the stores first every channel's taps would wait for the previous channel's stores to reach
-  // memory -- gathers and stores then take turns instead of overlapping (timing ablations at the C5 size:
-  // 4.5 ms as written that way, 3.3 without the raw stores, 3.3 without the gathers, 1.7 without both).
-  const bool any_shift = __ballot(shifted) != 0ull;  // wave-uniform
+  fwf_self_alpha<false>(px, a);
+  fwf_weights(px, a);
   typedef IN in2_fw __attribute__((ext_vector_type(2)));  // (two taps of a row: one 8-byte load)
   auto load_taps = [&](int c, IN (&v)[TCP][4]) {
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
-      const IN* plane = frame[tc] + (int64_t)c * HWd;
+      const IN* plane = px.frame[tc] + (int64_t)c * HWd;
       const in2_fw top = *reinterpret_cast<const in2_fw*>(reinterpret_cast<const char*>(plane) + ob0[tc]);
       const in2_fw bot = *reinterpret_cast<const in2_fw*>(reinterpret_cast<const char*>(plane) + ob1[tc]);
-      v[tc][0] = top[0];
-      v[tc][1] = top[1];
-      v[tc][2] = bot[0];
-      v[tc][3] = bot[1];
+      v[tc][0] = top[0], v[tc][1] = top[1], v[tc][2] = bot[0], v[tc][3] = bot[1];
     }
-  };
-  // corners of the footprint from the pair elements (see above); a no-op for interior wavefronts
-  auto assign = [&](auto& v) {  // (float or uint32_t elements)
-    if (any_shift) {
-#pragma unroll
-      for (int tc = 0; tc < TCP; ++tc) {
-        const auto a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
-        v[tc][0] = shift[tc] > 0 ? a1 : a0;
-        v[tc][1] = shift[tc] < 0 ? a0 : a1;
-        v[tc][2] = shift[tc] > 0 ? b1 : b0;
-        v[tc][3] = shift[tc] < 0 ? b0 : b1;
-      }
-    }
-  };
-  // channel c of the output from the corner values of every context and the unwarped frame's (include_self)
-  auto fuse = [&](int c, const float (&tv)[TCP][4], float vself) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int tc = 0; tc < TCP; ++tc) {
-      const float v = fmaf(tv[tc][3], w11[tc], fmaf(tv[tc][2], w10[tc], fmaf(tv[tc][1], w01[tc], tv[tc][0] * w00[tc])));
-      if (tc < Tc) fwf_put<false>(rbase + ((int64_t)tc * (C + L) + c) * HWd, false, v);
-      acc += v * wt[tc];
-    }
-    if (include_self) {
-      fwf_put<false>(rbase + ((int64_t)Tc * (C + L) + c) * HWd, false, vself);
-      acc += vself * wself;
-    }
-    fwf_store(obase + (int64_t)c * HWd, acc);
   };
   if constexpr (kPacked) {
-    // every channel of a tap is in its word: the taps of all contexts once, then C channels from registers
+    // the taps of all contexts once, then C channels from registers
     uint32_t tw[TCP][4];
     load_taps(0, tw);
-    assign(tw);
-    const uint32_t pself = include_self ? self[0] : 0u;  // (the unwarped frame's word)
-    for (int c = 0; c < C; ++c) {
-      float tv[TCP][4];
-#pragma unroll
-      for (int tc = 0; tc < TCP; ++tc)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) tv[tc][k] = packed_channel(rgb_table, tw[tc][k], c);
-      fuse(c, tv, include_self ? packed_channel(rgb_table, pself, c) : 0.0f);
-    }
+    fwf_packed_channels<false, false>(px, a, rgb_table, tw);
   } else {
+    // Channel loop, software-pipelined by hand: the sixteen tap loads of channel c + 1 are issued BEFORE the
+    // stores of channel c.  Vector-memory operations retire in issue order (loads, stores: one counter), so
+    // with the stores first every channel's taps would wait for the previous channel's stores to reach
+    // memory -- gathers and stores then take turns instead of overlapping (timing ablations at the C5 size:
+    // 4.5 ms as written that way, 3.3 without the raw stores, 3.3 without the gathers, 1.7 without both).
     float tv[TCP][4];
     load_taps(0, tv);
     for (int c = 0; c < C; ++c) {
       float nv[TCP][4];
       load_taps(min(c + 1, C - 1), nv);  // the last trip re-reads its own channel: no branch around the loads
-      assign(tv);
-      fuse(c, tv, include_self ? self[(int64_t)c * HWd] : 0.0f);
+      fwf_assign(px, tv);
+      fwf_fuse<false, false>(px, a, c, tv, include_self ? px.self[(int64_t)c * HWd] : 0.0f);
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc)
 #pragma unroll
         for (int k = 0; k < 4; ++k) tv[tc][k] = nv[tc][k];
     }
   }
-  float acc = 0.0f;  // the score channel
-#pragma unroll
-  for (int tc = 0; tc < TCP; ++tc) acc += (sc[tc] * 2.0f - 1.0f) * wt[tc];
-  if (include_self) acc += wself;  // (1 * 2 - 1) * w
-  obase[(int64_t)C * HWd] = acc;
+  fwf_score_channel(px, a);
 }
 
 // The same pass with the contexts' FOOTPRINTS STAGED IN LDS.  Timing-only ablations of the kernel above at the Cityscapes
@@ -761,7 +840,7 @@ __global__ __launch_bounds__(kBlock) void frame_warp_fuse_kernel(
 // ONE 16-byte load per thread (columns from a multiple of four: needs Wd % 4 == 0), parks it in a 4 KB LDS image and
 // reads the taps from there -- four coalesced loads per thread and channel instead of eight gathers, every line
 // requested once per tile.  Channel c + 1's loads are in flight while channel c is sampled and stored; two LDS-only
-// barriers per channel (no vmcnt wait: the stores keep draining).  Same taps, weights and arithmetic: same bits.
+// barriers per channel (no vmcnt wait: the stores keep draining).
 constexpr int kFwfCap = 1024;  // texels of one context's staged box = one float4 per thread
 // FULL: Tc == TCP and no `include_self` -- every vector-memory operation of the channel loop is then unconditional,
 // and the wait for channel c + 1's box can leave channel c's stores in flight (with a store behind a branch the
@@ -775,22 +854,22 @@ constexpr int kFwfCap = 1024;  // texels of one context's staged box = one float
 // (8 x 32 tiles with the same lane pairs write half lines: 8.66 against 7.33 ms per C5 step, profiles/r07_raw_dtype_*)
 template <typename RT>
 constexpr int fwf_kcols() { return std::is_same<RT, float>::value ? 32 : 64; }
-// IN = uint32_t: a packed clip (the raw path only, `rgb_table` its RGB table; packed_clip.hip.h).  A context's box holds
-// ONE word per pixel for all C = 3 + Nl channels: it is staged once, its taps are read from LDS once, and the channel
-// loop expands them with the same corner assignment and per-channel arithmetic (fuse_store) -- no loads, no barriers.
+// IN = uint32_t: a packed clip (`rgb_table` its RGB table).  A context's box holds ONE word per pixel for all
+// C = 3 + Nl channels: it is staged once, its taps are read from LDS once, and fwf_packed_channels expands them -- no
+// loads, no barriers.
 template <int TCP, bool FULL, typename RT = float, typename IN = float>
 __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_lds_kernel(
     const IN* __restrict__ input, const float* __restrict__ flow, const float* __restrict__ alpha,
     const float* __restrict__ score, const int64_t* __restrict__ ctx_ts, float* __restrict__ out,
     RT* __restrict__ raw, int* __restrict__ status, int T, int Tc_, int Tp, int C, int L, int Hd, int Wd, int include_self_,
     float eps, int units, int tiles, int nbands, const float* __restrict__ rgb_table) {
-  constexpr bool kPacked = std::is_same<IN, uint32_t>::value;
   typedef float f32x2_fw __attribute__((ext_vector_type(2)));
   typedef short s16x2 __attribute__((ext_vector_type(2)));
   static_assert(kBlock * 4 == kFwfCap, "one float4 of the box per thread");
-  const int Tc = FULL ? TCP : Tc_;
-  const bool include_self = FULL ? false : include_self_ != 0;
+  constexpr bool kPacked = FwfArgs<RT, IN>::kPacked;
   const int64_t HWd = (int64_t)Hd * Wd;
+  const FwfArgs<RT, IN> a = {input, flow, alpha, score, ctx_ts, out, raw, status, T, FULL ? TCP : Tc_, Tp, C, L, Hd, Wd,
+                             FULL ? 0 : include_self_, eps, HWd};
   int n, x, y;  // n = (b, tp)
   constexpr bool kF32 = std::is_same<RT, float>::value;
   if (!HdTile<fwf_kcols<RT>()>::pixel_grouped(units / Tp, Tp, Hd, Wd, tiles, nbands, n, x, y)) return;  // (uniform)
@@ -801,10 +880,11 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   if constexpr (kF32) x = min(x, Wd - 1);
   else x = min(x, Wd - 2 + (x & 1));
   y = min(y, Hd - 1);
-  const int b = n / Tp, tp = n % Tp;
-  const int64_t p = (int64_t)y * Wd + x;
-  const bool odd = (x & 1) != 0;
-  const int64_t pr = kF32 ? p : p - (odd ? 1 : 0);  // where this thread's stores to `raw` go (16-bit: its pair's)
+  FwfPixel<TCP, RT, IN> px;
+  px.b = n / Tp, px.tp = n % Tp;
+  px.p = (int64_t)y * Wd + x;
+  px.odd = (x & 1) != 0;
+  px.pr = kF32 ? px.p : px.p - (px.odd ? 1 : 0);
   const int t = (int)threadIdx.x, lane = t & (kWave - 1), wave = t >> 6;
   float gx0, gy0;
   identity_grid(x, y, Wd, Hd, gx0, gy0);
@@ -813,65 +893,28 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   __shared__ __attribute__((aligned(16))) float img[TCP][kFwfCap];
   __shared__ int wbox[kBlock / kWave][TCP][2];
 
-  const int Tcx = Tc + (include_self ? 1 : 0);
   uint32_t ob0[TCP], ob1[TCP];  // byte offsets of the two pair origins: in the context's LDS image, or in the plane
-  int shift[TCP];
-  float w00[TCP], w01[TCP], w10[TCP], w11[TCP], sc[TCP];
-  int cyx0[TCP], cy1v[TCP];  // (clamped row y0, pair origin xb) packed; clamped row y1
-  const IN* frame[TCP];
-  float ssum = 0.0f;
-  bool shifted = false;
+  int cyx0[TCP], cy1v[TCP];     // (clamped row y0, pair origin xb) packed; clamped row y1
 #pragma unroll
   for (int tc = 0; tc < TCP; ++tc) {
-    const int tcc = min(tc, Tc - 1);  // (a padding context repeats context Tc - 1 and is never stored or summed)
-    const bool real = tc < Tc;
-    const int64_t m = ((int64_t)b * Tc + tcc) * Tp + tp;
-    const float* fl = flow + m * 2 * HWd + p;
-    const Taps tp4 = make_taps(gx0 + fl[0], gy0 + fl[HWd], Hd, Wd);
-    const int xb = min(max(tp4.x0, 0), Wd - 2);
-    const int cy0 = min(max(tp4.y0, 0), Hd - 1), cy1 = min(max(tp4.y0 + 1, 0), Hd - 1);
-    cyx0[tc] = (cy0 << 16) | xb;
-    cy1v[tc] = cy1;
-    shift[tc] = tp4.x0 - xb;
-    shifted |= shift[tc] != 0;
-    w00[tc] = tp4.w00;
-    w01[tc] = tp4.w01;
-    w10[tc] = tp4.w10;
-    w11[tc] = tp4.w11;
-    // the box of this wavefront: (row, column) pairs packed 16 + 16 bits (Hd, Wd < 32768), six exchange steps
-    s16x2 lo = {(short)cy0, (short)xb}, hi = {(short)cy1, (short)(xb + 1)};
+    fwf_context(px, tc, a, gx0, gy0, [&](int cy0, int xb, int cy1) {
+      cyx0[tc] = (cy0 << 16) | xb;
+      cy1v[tc] = cy1;
+      // the box of this wavefront: (row, column) pairs packed 16 + 16 bits (Hd, Wd < 32768), six exchange steps
+      s16x2 lo = {(short)cy0, (short)xb}, hi = {(short)cy1, (short)(xb + 1)};
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const int olo = __shfl_xor(__builtin_bit_cast(int, lo), d, kWave), ohi = __shfl_xor(__builtin_bit_cast(int, hi), d, kWave);
-      lo = __builtin_elementwise_min(lo, __builtin_bit_cast(s16x2, olo));
-      hi = __builtin_elementwise_max(hi, __builtin_bit_cast(s16x2, ohi));
-    }
-    if (lane == 0) {
-      wbox[wave][tc][0] = __builtin_bit_cast(int, lo);
-      wbox[wave][tc][1] = __builtin_bit_cast(int, hi);
-    }
-    const int ts = __builtin_amdgcn_readfirstlane(checked_frame(ctx_ts, m, T, status, kStatusCtx));  // wave-uniform
-    frame[tc] = input + ((int64_t)b * T + ts) * (kPacked ? 1 : C) * HWd;
-    float sv = 0.0f;
-    if (score != nullptr) {
-      sv = score[m * HWd + p];
-    } else if constexpr (kF32) {
-      const float* al = alpha + m * L * HWd + p;
-      float* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + tcc) * (C + L) + C) * HWd + p;
-      for (int l = 0; l < L; ++l) {
-        const float av = al[(int64_t)l * HWd];
-        sv += (av + 1.0f) / 2.0f;
-        if (real) fwf_store(rw + (int64_t)l * HWd, av);
+      for (int d = 32; d >= 1; d >>= 1) {
+        const int olo = __shfl_xor(__builtin_bit_cast(int, lo), d, kWave), ohi = __shfl_xor(__builtin_bit_cast(int, hi), d, kWave);
+        lo = __builtin_elementwise_min(lo, __builtin_bit_cast(s16x2, olo));
+        hi = __builtin_elementwise_max(hi, __builtin_bit_cast(s16x2, ohi));
       }
-    }
-    sc[tc] = sv;
-    ssum += real ? fabsf(sv + eps) : 0.0f;
+      if (lane == 0) {
+        wbox[wave][tc][0] = __builtin_bit_cast(int, lo);
+        wbox[wave][tc][1] = __builtin_bit_cast(int, hi);
+      }
+    });
   }
-  if (include_self) {
-    RT* rw = raw + ((((int64_t)b * Tp + tp) * Tcx + Tc) * (C + L) + C) * HWd + pr;
-    for (int l = 0; l < L; ++l) fwf_put<true>(rw + (int64_t)l * HWd, odd, 1.0f);
-    ssum += fabsf(1.0f + eps);
-  }
+  fwf_self_alpha<true>(px, a);
   // (packed) the RGB table in LDS, one entry per thread (read after the barriers below)
   __shared__ float stab[kPacked ? kRgbTable : 1];
   if constexpr (kPacked) {
@@ -905,42 +948,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     ob0[tc] = (uint32_t)(__mul24(cy0 - ylo, pitch) + (xb - xlo)) * 4u;
     ob1[tc] = (uint32_t)(__mul24(cy1v[tc] - ylo, pitch) + (xb - xlo)) * 4u;
   }
-  const float den = fmaxf(ssum, 1e-12f);
-  const float wself = (1.0f + eps) / den;
-  float wt[TCP];
-#pragma unroll
-  for (int tc = 0; tc < TCP; ++tc) wt[tc] = (tc < Tc) ? (sc[tc] + eps) / den : 0.0f;
-  const IN* self = input + ((int64_t)b * T + min(tp, T - 1)) * (kPacked ? 1 : C) * HWd + p;
-  RT* rbase = raw + ((int64_t)b * Tp + tp) * Tcx * (C + L) * HWd + pr;  // context tc: + tc * (C+L) * HWd
-  float* obase = out + ((int64_t)b * Tp + tp) * (C + 1) * HWd + p;
-  const bool any_shift = __ballot(shifted) != 0ull;  // wave-uniform
-  // corners of the footprint from the pair elements (see the kernel above); a no-op for interior wavefronts
-  auto assign = [&](auto& v) {  // (float or uint32_t elements)
-    if (any_shift) {
-#pragma unroll
-      for (int tc = 0; tc < TCP; ++tc) {
-        const auto a0 = v[tc][0], a1 = v[tc][1], b0 = v[tc][2], b1 = v[tc][3];
-        v[tc][0] = shift[tc] > 0 ? a1 : a0;
-        v[tc][1] = shift[tc] < 0 ? a0 : a1;
-        v[tc][2] = shift[tc] > 0 ? b1 : b0;
-        v[tc][3] = shift[tc] < 0 ? b0 : b1;
-      }
-    }
-  };
-  auto fuse_store = [&](int c, const float (&v4)[TCP][4], float vself) {
-    float acc = 0.0f;
-#pragma unroll
-    for (int tc = 0; tc < TCP; ++tc) {
-      const float v = fmaf(v4[tc][3], w11[tc], fmaf(v4[tc][2], w10[tc], fmaf(v4[tc][1], w01[tc], v4[tc][0] * w00[tc])));
-      if (FULL || tc < Tc) fwf_put<true>(rbase + ((int64_t)tc * (C + L) + c) * HWd, odd, v);
-      acc += v * wt[tc];
-    }
-    if (include_self) {
-      fwf_put<true>(rbase + ((int64_t)Tc * (C + L) + c) * HWd, odd, vself);
-      acc += vself * wself;
-    }
-    fwf_store(obase + (int64_t)c * HWd, acc);
-  };
+  fwf_weights(px, a);
   // The channel loop for a compile-time set of staged contexts (bit tc of MASK): a staged context's taps come from
   // its LDS image (one float4 of its box per thread and channel, loaded a channel ahead), the others' straight from
   // memory as two 8-byte pairs, also a channel ahead.  Round 4 had two loops -- every context staged, or the WHOLE
@@ -962,16 +970,13 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
     auto issue = [&](int c) {  // channel c: this thread's float4 of every staged box, the pairs of the others
 #pragma unroll
       for (int tc = 0; tc < TCP; ++tc) {
-        const auto* plane = frame[tc] + (int64_t)c * HWd;
+        const auto* plane = px.frame[tc] + (int64_t)c * HWd;
         if ((MASK >> tc) & 1u) {
           box4[tc] = *reinterpret_cast<const f32x4*>(plane + goff[tc]);
         } else {
           const f32x2_fw top = *reinterpret_cast<const f32x2_fw*>(reinterpret_cast<const char*>(plane) + ob0[tc]);
           const f32x2_fw bot = *reinterpret_cast<const f32x2_fw*>(reinterpret_cast<const char*>(plane) + ob1[tc]);
-          nv[tc][0] = top[0];
-          nv[tc][1] = top[1];
-          nv[tc][2] = bot[0];
-          nv[tc][3] = bot[1];
+          nv[tc][0] = top[0], nv[tc][1] = top[1], nv[tc][2] = bot[0], nv[tc][3] = bot[1];
         }
       }
     };
@@ -1008,8 +1013,8 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
           for (int k = 0; k < 4; ++k) tv[tc][k] = gv[tc][k];
         }
       }
-      assign(tv);
-      fuse_store(c, tv, include_self ? self[(int64_t)c * HWd] : 0.0f);
+      fwf_assign(px, tv);
+      fwf_fuse<true, FULL>(px, a, c, tv, a.include_self ? px.self[(int64_t)c * HWd] : 0.0f);
       if (kAny) lds_barrier();  // every thread has read channel c's taps
       park();  // (waits for the boxes of channel c + 1, not for channel c's stores)
       take();
@@ -1026,17 +1031,14 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
 #pragma unroll
     for (int tc = 0; tc < TCP; ++tc) {
       if ((stage_mask >> tc) & 1u) {  // (uniform)
-        const u32x4_fw q = *reinterpret_cast<const u32x4_fw*>(frame[tc] + goff[tc]);
+        const u32x4_fw q = *reinterpret_cast<const u32x4_fw*>(px.frame[tc] + goff[tc]);
         if ((mine >> tc) & 1u) *reinterpret_cast<u32x4_fw*>(&img[tc][4 * t]) = q;
       } else {
         const int cy0 = cyx0[tc] >> 16, xb = cyx0[tc] & 0xffff;
-        const char* fr = reinterpret_cast<const char*>(frame[tc]);
+        const char* fr = reinterpret_cast<const char*>(px.frame[tc]);
         const u32x2_fw top = *reinterpret_cast<const u32x2_fw*>(fr + (uint32_t)(__mul24(cy0, Wd) + xb) * 4u);
         const u32x2_fw bot = *reinterpret_cast<const u32x2_fw*>(fr + (uint32_t)(__mul24(cy1v[tc], Wd) + xb) * 4u);
-        tw[tc][0] = top[0];
-        tw[tc][1] = top[1];
-        tw[tc][2] = bot[0];
-        tw[tc][3] = bot[1];
+        tw[tc][0] = top[0], tw[tc][1] = top[1], tw[tc][2] = bot[0], tw[tc][3] = bot[1];
       }
     }
     lds_barrier();
@@ -1049,16 +1051,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
         tw[tc][2] = *reinterpret_cast<const uint32_t*>(im + ob1[tc]);
         tw[tc][3] = *reinterpret_cast<const uint32_t*>(im + ob1[tc] + 4);
       }
-    assign(tw);
-    const uint32_t pself = include_self ? self[0] : 0u;  // (the unwarped frame's word)
-    for (int c = 0; c < C; ++c) {
-      float tv[TCP][4];
-#pragma unroll
-      for (int tc = 0; tc < TCP; ++tc)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) tv[tc][k] = packed_channel(stab, tw[tc][k], c);
-      fuse_store(c, tv, include_self ? packed_channel(stab, pself, c) : 0.0f);
-    }
+    fwf_packed_channels<true, FULL>(px, a, stab, tw);
   } else if (FULL && TCP == 4) {
     switch (stage_mask & 15u) {
 #define WALDO_FWF_CASE(M) case M: channel_loop(std::integral_constant<unsigned, M>{}); break;
@@ -1072,11 +1065,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FWF_LDS_WAVES) void frame_warp_fuse_l
   } else {
     channel_loop(std::integral_constant<unsigned, 0u>{});
   }
-  float acc = 0.0f;  // the score channel
-#pragma unroll
-  for (int tc = 0; tc < TCP; ++tc) acc += (sc[tc] * 2.0f - 1.0f) * wt[tc];
-  if (include_self) acc += wself;  // (1 * 2 - 1) * w
-  obase[(int64_t)C * HWd] = acc;
+  fwf_score_channel(px, a);
 }
 
 static int check_flow_ctx(const char* fn, int64_t N, int L, int H, int W, int scale) {
@@ -1203,6 +1192,25 @@ int flow_ctx_warp_raw(const char* fn, const float* flow_lr, const float* isobj_l
                               score, disocc, alpha_max, layer_bits, status, B, T, Tw, Tc, Tp, L, H, W, scale, stream);
 }
 
+// The launch geometry of frame_warp_fuse for tiles of COLS columns; false: too large for one launch.
+// Every unit's tiles in 8 bands, one per XCD: the whole chip walks the (b, tp) units IN ORDER instead of eight
+// units side by side, so the Tp units of a clip, which gather from the same Tc context frames, follow each other
+// closely (the frames of one clip, 193 MB at the Cityscapes recipe, are what the 256 MiB Infinity Cache can hold).
+// A/B on one box: 10.94 -> 10.59 ms per C5 pipeline step (-3 %).
+template <int COLS>
+static bool fwf_grid(const char* fn, int B, int Tp, int Hd, int Wd, HdGeom& geom, dim3& grid) {
+  const int64_t units = (int64_t)B * Tp;
+  geom = HdTile<COLS>::geom(units, Hd, Wd);
+  geom.nbands = WALDO_FWF_BANDS;
+  const int64_t blocks = xcd_grid_banded(B, geom.nbands, geom.tiles, Tp);  // (equal to hd_grid(units, geom): 8 bands, both 8 B Tp ceil(tiles / 8))
+  if (blocks > 2147483647) {
+    set_error("%s: problem too large for one launch", fn);
+    return false;
+  }
+  grid = dim3((unsigned)blocks);
+  return true;
+}
+
 // IN = uint32_t: a packed clip of C = 3 + Nl channels, rgb_table its RGB table (the raw path only); NULL for fp32
 template <typename RT, typename IN = float>
 int frame_warp_fuse_launch(const char* fn, const IN* input, const float* flow, const float* alpha, const float* score,
@@ -1221,32 +1229,20 @@ int frame_warp_fuse_launch(const char* fn, const IN* input, const float* flow, c
     return WALDO_EINVAL;
   }
   const int64_t units = (int64_t)B * Tp;
-  HdGeom geom = HdTile<WALDO_FWF_TILE_COLS>::geom(units, Hd, Wd);
-  // Every unit's tiles in 8 bands, one per XCD: the whole chip walks the (b, tp) units IN ORDER instead of eight
-  // units side by side, so the Tp units of a clip, which gather from the same Tc context frames, follow each other
-  // closely (the frames of one clip, 193 MB at the Cityscapes recipe, are what the 256 MiB Infinity Cache can hold).
-  // A/B on one box: 10.94 -> 10.59 ms per C5 pipeline step (-3 %).
-  geom.nbands = WALDO_FWF_BANDS;
-  if (hd_grid(units, geom) > 2147483647 || xcd_grid_banded(B, geom.nbands, geom.tiles, Tp) > 2147483647) {
-    set_error("%s: problem too large for one launch", fn);
-    return WALDO_EINVAL;
-  }
+  HdGeom geom;
+  dim3 grid;
+  if (!fwf_grid<WALDO_FWF_TILE_COLS>(fn, B, Tp, Hd, Wd, geom, grid)) return WALDO_EINVAL;
   if (units == 0) return WALDO_OK;
   if (!input || !flow || (!alpha && !score) || !ctx_ts || !out || !raw) {
     set_error("%s: null pointer", fn);
     return WALDO_EINVAL;
   }
-  const dim3 grid((unsigned)xcd_grid_banded(B, geom.nbands, geom.tiles, Tp));
 #if WALDO_FWF_TILE_COLS == 32
   // (16-byte loads of the boxes: rows that start on a multiple of four texels from a 16-byte aligned base)
   if (Wd % 4 == 0 && (reinterpret_cast<uintptr_t>(input) & 15) == 0 && Tc <= 4) {
-    HdGeom lgeom = HdTile<fwf_kcols<RT>()>::geom(units, Hd, Wd);  // (16-bit `raw`: 4 x 64 tiles)
-    lgeom.nbands = WALDO_FWF_BANDS;
-    if (xcd_grid_banded(B, lgeom.nbands, lgeom.tiles, Tp) > 2147483647) {
-      set_error("%s: problem too large for one launch", fn);
-      return WALDO_EINVAL;
-    }
-    const dim3 lgrid((unsigned)xcd_grid_banded(B, lgeom.nbands, lgeom.tiles, Tp));
+    HdGeom lgeom;  // (16-bit `raw`: 4 x 64 tiles)
+    dim3 lgrid;
+    if (!fwf_grid<fwf_kcols<RT>()>(fn, B, Tp, Hd, Wd, lgeom, lgrid)) return WALDO_EINVAL;
     // (the context count is a template parameter: a padding context repeats the last real one -- its taps, its box, its
     // loads -- so one context compiled for four did four contexts' work: the LVD recipe's "prev" mode, 114 us per call)
     auto launch = [&](auto tcp, auto full) {
