@@ -704,6 +704,36 @@ def test_flow_ctx_alpha_backward_takes_both_output_gradients(dev, nl, s, ncls):
         close(got[2], want[2], 1e-5, rel=True, what=f"{name}: grad_occ (float atomics)")
 
 
+@pytest.mark.parametrize("nl", [5, 17])
+def test_flow_ctx_alpha_backward_is_occ_composite_backward(dev, nl):
+    """The composite's backward is the same arithmetic in the same order in flow_ctx_alpha_bwd (csrc/flow_ctx_bwd.hip:
+    composite_bwd, the order read from LDS) and in occ_composite_bwd (the order through the scalar cache).  At scale 1, without
+    a layout filter and with Tw = T, flow_ctx_alpha IS occ_composite (the upsampling is the plane itself, the filter
+    weight 1): the same incoming gradient gives the same bits of d / d alpha, and under deterministic() of d / d occ
+    (in the default mode grad_occ is summed with float atomics).  9 x 40: two tiles, the second partly live; L = 5
+    pads to the <8> instance, L = 17 is the instance that spills."""
+    from waldo_amd import functional as WF
+    b, t, h, w = 1, 2, 9, 40
+    g = torch.Generator(device=dev).manual_seed(90 + nl)
+    alpha = torch.rand(b * t, nl, h, w, generator=g, device=dev)
+    inp = torch.randn(b, t, 3, h, w, generator=g, device=dev)
+    occ = torch.rand(b, t, nl, nl, generator=g, device=dev) * 0.5
+    go = torch.randn(b * t, nl, h, w, generator=g, device=dev)
+
+    def grads(op):
+        leaves = [alpha.clone().requires_grad_(), occ.clone().requires_grad_()]
+        (op(*leaves) * go).sum().backward()
+        return [x.grad for x in leaves]
+
+    for det in (False, True):
+        with WF.deterministic(det):
+            fused = grads(lambda a, o: WF.flow_ctx_alpha(a, inp, None, o, t, 3, 1)[0])
+            plain = grads(lambda a, o: WF.occ_composite(a, o.view(b * t, nl, nl)))
+        assert torch.equal(fused[0], plain[0]), f"deterministic={det}: grad_alpha"
+        if det:
+            assert torch.equal(fused[1], plain[1]), "deterministic: grad_occ"
+
+
 @pytest.mark.parametrize("over,ctx_only,include_self", [
     (dict(num_obj=3, dim=16, load_dim=0), False, True),                       # the LVD recipe's shape: x1, ctx "prev"
     (dict(num_obj=16, obj_shape=[2, 2], dim=8, load_dim=32), True, False),   # L = 17, x4, ghost mask

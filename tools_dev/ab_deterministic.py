@@ -11,6 +11,7 @@ Per variant: ms per step, the entry points' event time per step, the determinist
 step's peak device memory.  One JSON line per variant, also written to OUT/r11_deterministic_<config>_<mode>.json.
 
     python tools_dev/ab_deterministic.py [--steps 20] [--warmup 5] [--config LVD LVD_graph HD C3] [--out profiles]
+                                         [--lib OTHER/libwaldo_hip.so]
 """
 import argparse
 import json
@@ -134,7 +135,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", nargs="+", default=list(BUILD), choices=list(BUILD))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--lib", help="another build of libwaldo_hip.so (the whole run uses it)")
     args = ap.parse_args()
+    if args.lib:
+        _lib.use_library(args.lib)
     dev = torch.device("cuda:0")
     os.makedirs(args.out, exist_ok=True)
     for config in args.config:

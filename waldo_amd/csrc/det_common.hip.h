@@ -34,6 +34,48 @@ constexpr int kSlabLanes = 32, kSlabGroups = kBlock / kSlabLanes;
 // theirs from the whole problem's size, which would make the slab (and the workspace query) shrink where a size grows.
 constexpr int kDetTilesPerBlock = 4;
 
+// A workgroup's partial table of N entries in LDS, one row per wave, over `__shared__ float s[4][N]`
+// of the kernel: every wave zeroes and adds into ITS OWN row (wave_transpose_reduce leaves one lane per entry: plain
+// read-modify-write, no atomics, no barrier), and after a barrier the four rows are summed in a fixed order and leave
+// the workgroup -- as ONE float atomic per entry into the table's home row of `dest`, or (DET) as a plain store into
+// the workgroup's row of the slab `dest`.  occ_composite_bwd_kernel's table; the two flow_ctx backward kernels
+// (flow_ctx_bwd.hip) keep the same steps written out (through this type their largest
+// instances spill more).
+template <int N>
+struct WaveTable {
+  static_assert(kBlock == 4 * kWave, "four waves, four rows");
+  float (*rows)[N];
+  __device__ __forceinline__ void zero(int wave, int lane) const {
+    for (int e = lane; e < N; e += kWave) rows[wave][e] = 0.0f;
+  }
+  __device__ __forceinline__ float* row(int wave) const { return rows[wave]; }
+  // E: entries of a row of dest; index(e, at): whether entry e of the table goes anywhere (not padding), and where inside
+  // that row
+  template <bool DET, typename Index>
+  __device__ __forceinline__ void flush(float* __restrict__ dest, int E, int64_t home_row, Index&& index) const {
+    for (int e = threadIdx.x; e < N; e += kBlock) {
+      int at;
+      if (index(e, at)) {
+        const float sum = (rows[0][e] + rows[1][e]) + (rows[2][e] + rows[3][e]);
+        float* out = dest + (DET ? (int64_t)blockIdx.x : home_row) * E;
+        if constexpr (DET) out[at] = sum;
+        else atomicAdd(out + at, sum);
+      }
+    }
+  }
+};
+
+// index() of an L x L matrix kept as an LP x LP table: entry i * LP + j -> i * L + j
+template <int LP>
+struct PaddedSquare {
+  int L;
+  __device__ __forceinline__ bool operator()(int e, int& at) const {
+    const int i = e / LP, j = e % LP;
+    at = i * L + j;
+    return i < L && j < L;
+  }
+};
+
 // rows d * nparts .. (d + 1) * nparts - 1 (those below `rows`); destination (d / dq) * dstride + d % dq
 struct SlabPlain {
   int64_t rows, dq, dstride;

@@ -40,6 +40,9 @@ __device__ __forceinline__ float sgnf(float x) { return (x > 0.0f ? 1.0f : 0.0f)
 // gv[j] = d loss / d v_j.  The occ gradients go, reduced over the wave, into the wave's LDS row.
 // occm: the order in LDS (OccLds; column j is a row of the transposed copy).  A padding layer has a == 0:
 // its factor is exactly 1 and its occ gradient exactly 0, no guard needed; its ga is never stored.
+// (occ_composite_bwd_kernel computes the same column in the same order from scalar loads -- the same bits,
+// tests/test_gpu_warper.py::test_flow_ctx_alpha_backward_is_occ_composite_backward -- and stays a text of its own: as
+// one body with the fetch as a parameter that kernel took 22 more registers at <17> and ran 3 to 7 % longer.)
 template <int LP>
 __device__ __forceinline__ void composite_bwd(const float (&a)[LP], const float (&gv)[LP],
                                               const float* occm, int L, float (&ga)[LP],
@@ -47,7 +50,7 @@ __device__ __forceinline__ void composite_bwd(const float (&a)[LP], const float 
 #pragma unroll
   for (int l = 0; l < LP; ++l) ga[l] = 0.0f;
 #pragma unroll
-  for (int j = 0; j < LP; ++j) {
+  for (int j = 0; j < LP; ++j)
     if (j < L) {  // wave-uniform
       float tf[LP], ex[LP];
       float pre = 1.0f;
@@ -91,7 +94,6 @@ __device__ __forceinline__ void composite_bwd(const float (&a)[LP], const float 
         if (i < L) acc_row[i * LP + j] += red;  // one lane per entry
       }
     }
-  }
 }
 
 // d loss / d a01 from the gradients of the two outputs of the forward, a01 and alpha_out = 2 a01 - 1: what the caller
@@ -125,7 +127,6 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_ALPHA_WAVES) void flow_ctx_alpha_
   const int64_t HWd = (int64_t)Hd * Wd, HW = (int64_t)H * W;
   const int n = blockIdx.x / groups;  // (b, t) with t < Tw
   const int b = n / Tw, t = n % Tw;
-  const int t0 = (blockIdx.x % groups) * tiles_per_block, t1 = min(tiles, t0 + tiles_per_block);
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const int No = L - 1;
   __shared__ __attribute__((aligned(16))) float sdist[(LP - 1) * kMaxCls];
@@ -140,18 +141,14 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_ALPHA_WAVES) void flow_ctx_alpha_
   for (int e = lane; e < (LP - 1) * kMaxCls; e += kWave) acc_d[wave][e] = 0.0f;
   __syncthreads();
 
-  for (int tile = t0; tile < t1; ++tile) {
-    // the LDS tables do not change while the workgroup walks its tiles, and the compiler knows: it would hoist
-    // all their reads out of this loop, into ~600 registers it does not have.  An offset it cannot see through:
-    int fresh = 0;
-    asm volatile("" : "+v"(fresh));
-    const float* occm_t = occm + fresh;
-    const float* sdist_t = sdist + fresh;
-    const int64_t p = (int64_t)tile * kBlock + threadIdx.x;
-    const bool live = p < HWd;
-    const int64_t pc = live ? p : HWd - 1;
-    const int y = (int)(pc / Wd), x = (int)(pc - (int64_t)y * Wd);
-    const UpTaps ut = up_taps(y, x, 1.0f / (float)scale, H, W);
+  for (BwdTileWalk w(tiles, tiles_per_block, groups); w.more();) {
+    const BwdTile q = w.next(HWd);
+    int y, x;
+    const UpTaps ut = bwd_tile_taps(q, H, W, scale, y, x);
+    const float* occm_t = occm + q.fresh;
+    const float* sdist_t = sdist + q.fresh;
+    const int64_t p = q.p, pc = q.pc;
+    const bool live = q.live;
     // (the upsampled rough alpha is not kept across the composite: it is one load to have again)
     float f[LP], a[LP], gv[LP], ga[LP];
 #pragma unroll
@@ -162,20 +159,7 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_ALPHA_WAVES) void flow_ctx_alpha_
     float pr[NCP];
     if (filt) {
       const float* lg = input + (((int64_t)b * T + t) * C + chan_off) * HWd + pc;
-      float m = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < NCP; ++c) {
-        pr[c] = (c < Nl) ? lg[(int64_t)min(c, Nl - 1) * HWd] : -INFINITY;
-        m = fmaxf(m, pr[c]);
-      }
-      float den = 0.0f;
-#pragma unroll
-      for (int c = 0; c < NCP; ++c) {
-        pr[c] = (c < Nl) ? expf(pr[c] - m) : 0.0f;
-        den += pr[c];
-      }
-#pragma unroll
-      for (int c = 0; c < NCP; ++c) pr[c] = pr[c] / den;
+      (void)lyt_softmax<NCP>(pr, Nl, [&](int c) { return lg[(int64_t)min(c, Nl - 1) * HWd]; });
 #pragma unroll
       for (int l = 1; l < LP; ++l) f[l] = 1.0f - dist_l1(sdist_t + (l - 1) * kMaxCls, pr, Nl) / 2.0f;
     }
@@ -252,28 +236,26 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bw
   const int Hd = H * scale, Wd = W * scale;
   const int64_t HWd = (int64_t)Hd * Wd, HW = (int64_t)H * W;
   const int m = blockIdx.x / groups;  // (b, tc, tp)
-  const int tp = m % Tp, b = m / (Tc * Tp);
-  const int t0 = (blockIdx.x % groups) * tiles_per_block, t1 = min(tiles, t0 + tiles_per_block);
+  const int tp = m % Tp;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   __shared__ float acc_o[4][LP * LP];
   __shared__ __attribute__((aligned(16))) float occm[OccLds<LP>::kFloats];
   for (int e = lane; e < LP * LP; e += kWave) acc_o[wave][e] = 0.0f;
+  const CtxUnit unit = ctx_unit(ctx_ts, m, Tw, Tc, Tp);
   // (wave-uniform; through the vector path they land in VGPRs and so does every plane address)
-  const int ts = __builtin_amdgcn_readfirstlane((int)min(max(ctx_ts[m], (int64_t)0), (int64_t)(Tw - 1)));
+  const int b = unit.b, ts = __builtin_amdgcn_readfirstlane(unit.ts);
   const int tpred = __builtin_amdgcn_readfirstlane((int)min(max(pred_ts[tp], (int64_t)0), (int64_t)(T - 1)));
   occ_stage<LP>(occm, occ + ((int64_t)b * T + tpred) * L * L, L);
   __syncthreads();
   const float hw = 0.5f * (float)Wd, hh = 0.5f * (float)Hd;
 
-  for (int tile = t0; tile < t1; ++tile) {
-    int fresh = 0;  // (see flow_ctx_alpha_bwd_kernel: keeps the reads of the order inside the loop)
-    asm volatile("" : "+v"(fresh));
-    const float* occm_t = occm + fresh;
-    const int64_t p = (int64_t)tile * kBlock + threadIdx.x;
-    const bool live = p < HWd;
-    const int64_t pc = live ? p : HWd - 1;
-    const int y = (int)(pc / Wd), x = (int)(pc - (int64_t)y * Wd);
-    const UpTaps ut = up_taps(y, x, 1.0f / (float)scale, H, W);
+  for (BwdTileWalk w(tiles, tiles_per_block, groups); w.more();) {
+    const BwdTile q = w.next(HWd);
+    int y, x;
+    const UpTaps ut = bwd_tile_taps(q, H, W, scale, y, x);
+    const float* occm_t = occm + q.fresh;
+    const int64_t p = q.p, pc = q.pc;
+    const bool live = q.live;
     float gx0, gy0;
     identity_grid(x, y, Wd, Hd, gx0, gy0);
     const float gfx = (g_flow != nullptr && live) ? g_flow[((int64_t)m * 2) * HWd + pc] : 0.0f;
@@ -309,7 +291,6 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bw
     }
     composite_bwd<LP>(a, gv, occm_t, L, ga, g_occ != nullptr ? acc_o[wave] : nullptr, lane);
     const float gd = (g_dis != nullptr && live) ? g_dis[(int64_t)m * HWd + pc] : 0.0f;
-    typedef float f32x2_w __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int j = 0; j < LP; j += 4) {
       // v_j (the composited alphas) of four layers, as the forward kernel takes them (same bits) ...
@@ -351,14 +332,10 @@ __global__ __launch_bounds__(kBlock, WALDO_FCB_WARP_WAVES) void flow_ctx_warp_bw
             const float gsg = live ? gs * ghost : 0.0f;
             if (gsg != 0.0f) {
               float* gp = g_a01 + (((int64_t)b * Tw + ts) * L + l) * HWd;
-              // the lerp form's weights: (1-fx)(1-fy) v00 ... with the validity of each corner
-              const float wx0 = 1.0f - t.fx, wy0 = 1.0f - t.fy;
-              const float w00 = wx0 * wy0 * (t.vx0 * t.vy0), w01 = t.fx * wy0 * (t.vx1 * t.vy0);
-              const float w10 = wx0 * t.fy * (t.vx0 * t.vy1), w11 = t.fx * t.fy * (t.vx1 * t.vy1);
-              if (w00 != 0.0f) atomicAdd(gp + (t.o00 >> 2), gsg * w00);
-              if (w01 != 0.0f) atomicAdd(gp + (t.o01 >> 2), gsg * w01);
-              if (w10 != 0.0f) atomicAdd(gp + (t.o10 >> 2), gsg * w10);
-              if (w11 != 0.0f) atomicAdd(gp + (t.o11 >> 2), gsg * w11);
+              const SplatWeights s = splat_weights(t);
+#pragma unroll
+              for (int c = 0; c < 4; ++c)
+                if (s.w[c] != 0.0f) atomicAdd(gp + (s.o[c] >> 2), gsg * s.w[c]);
             }
           }
         }
@@ -392,13 +369,12 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_warp_det_max_kernel(const flo
                                                                        int Tp, int L, int64_t HWd, int chunks) {
   const int64_t plane = blockIdx.x / chunks, m = plane / L;
   const int l = (int)(plane % L);
-  const int64_t b = m / ((int64_t)Tc * Tp);
-  const int ts = (int)min(max(ctx_ts[m], (int64_t)0), (int64_t)(Tw - 1));
+  const CtxUnit unit = ctx_unit(ctx_ts, (int)m, Tw, Tc, Tp);
   const int64_t i0 = (int64_t)(blockIdx.x % chunks) * kFcwMaxChunk, i1 = min(HWd, i0 + kFcwMaxChunk);
   const float* v = vals + plane * HWd;
   unsigned bits = 0u;
   for (int64_t i = i0 + threadIdx.x; i < i1; i += kBlock) bits = max(bits, abs_bits(v[i]));
-  plane_max_update(plane_max + (b * Tw + ts) * L + l, bits);
+  plane_max_update(plane_max + ((int64_t)unit.b * Tw + unit.ts) * L + l, bits);
 }
 
 __global__ __launch_bounds__(kBlock) void flow_ctx_warp_det_splat_kernel(
@@ -410,32 +386,27 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_warp_det_splat_kernel(
   const int64_t m = blockIdx.x / tiles;
   const int64_t p = (int64_t)(blockIdx.x % tiles) * kBlock + threadIdx.x;
   if (p >= HWd) return;
-  const int64_t b = m / ((int64_t)Tc * Tp);
-  const int ts = (int)min(max(ctx_ts[m], (int64_t)0), (int64_t)(Tw - 1));
+  const CtxUnit unit = ctx_unit(ctx_ts, (int)m, Tw, Tc, Tp);
   const int y = (int)(p / Wd), x = (int)(p - (int64_t)y * Wd);
   const UpTaps ut = up_taps(y, x, 1.0f / (float)scale, H, W);
   float gx0, gy0;
   identity_grid(x, y, Wd, Hd, gx0, gy0);
   for (int l = 0; l < L; ++l) {
-    const int64_t plane = (b * Tw + ts) * L + l;
+    const int64_t plane = ((int64_t)unit.b * Tw + unit.ts) * L + l;
     const unsigned mb = plane_max[plane];        // (uniform)
     if (mb == 0u || mb >= kInfBits) continue;    // nothing to add / the plane comes back NaN
     const float gsg = vals[(m * L + l) * HWd + p];
     if (gsg == 0.0f) continue;
     const int k = splat_shift(mb, clog);
-    // the sample position and the weights as flow_ctx_warp_bwd_kernel takes them
+    // the sample position as flow_ctx_warp_bwd_kernel takes it
     const float* fl = flow_lr + ((m * L + l) * 2) * HW;
     const float fxl = up_sample(fl, ut), fyl = up_sample(fl + HW, ut);
-    const Taps t = make_taps(gx0 + fxl, gy0 + fyl, Hd, Wd);
-    const float wx0 = 1.0f - t.fx, wy0 = 1.0f - t.fy;
-    const float wq[4] = {wx0 * wy0 * (t.vx0 * t.vy0), t.fx * wy0 * (t.vx1 * t.vy0), wx0 * t.fy * (t.vx0 * t.vy1),
-                         t.fx * t.fy * (t.vx1 * t.vy1)};
-    const uint32_t key[4] = {t.o00, t.o01, t.o10, t.o11};
+    const SplatWeights s = splat_weights(make_taps(gx0 + fxl, gy0 + fyl, Hd, Wd));
     unsigned long long* ap = acc + plane * HWd;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const unsigned long long term = splat_term(gsg * wq[q], k);
-      if (term != 0ull) atomicAdd(ap + (key[q] >> 2), term);
+      const unsigned long long term = splat_term(gsg * s.w[q], k);
+      if (term != 0ull) atomicAdd(ap + (s.o[q] >> 2), term);
     }
   }
 }
@@ -669,13 +640,11 @@ static int flow_ctx_alpha_bwd(const char* fn, const float* alpha_lr, const float
   }
   // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
   with_padded_layers(L, [&](auto lp) {
-    auto launch = [&](auto ncp) {
+    with_padded_classes(dist != nullptr, Nl, [&](auto ncp) {
       hipLaunchKernelGGL((flow_ctx_alpha_bwd_kernel<decltype(lp)::value, decltype(ncp)::value, det>),
                          dim3((unsigned)(N * groups)), dim3(kBlock), 0, st, alpha_lr, input, dist, occ, grad_a01,
                          grad_alpha_out, gup, table_d, table_o, T, Tw, L, Nl, C, chan_off, H, W, scale, tiles, tpb, groups);
-    };
-    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
-    else launch(std::integral_constant<int, kMaxCls>{});
+    });
   });
   if constexpr (det) {
     if (table_o != nullptr) {

@@ -67,6 +67,34 @@ constexpr int kMaxCls = 32;
 // the backward -- a 32-value transpose-reduce per object, for 20 classes.
 constexpr int kFewCls = 20;
 
+// (host) the padded class count of a launch: f(std::integral_constant<int, NCP>); no filter counts as few classes
+template <typename F>
+void with_padded_classes(bool filt, int Nl, F&& f) {
+  if (!filt || Nl <= kFewCls) f(std::integral_constant<int, kFewCls>{});
+  else f(std::integral_constant<int, kMaxCls>{});
+}
+
+// softmax over the Nl layout logits of a pixel, held in registers: pr[c] = softmax_c(logit(c)), 0 from class Nl on.
+// Returns the denominator (>= 1 and finite unless a logit is not).
+template <int NCP, typename Logit>
+__device__ __forceinline__ float lyt_softmax(float (&pr)[NCP], int Nl, Logit&& logit) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < NCP; ++c) {
+    pr[c] = (c < Nl) ? logit(c) : -INFINITY;
+    m = fmaxf(m, pr[c]);
+  }
+  float den = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NCP; ++c) {
+    pr[c] = (c < Nl) ? expf(pr[c] - m) : 0.0f;
+    den += pr[c];
+  }
+#pragma unroll
+  for (int c = 0; c < NCP; ++c) pr[c] = pr[c] / den;
+  return den;
+}
+
 // ---------------------------------------------------------------------------------------
 // The order (occlusion matrix) of one frame in LDS, padded to LP x LP: by rows ([i][j], row stride kRow)
 // and transposed ([j][i]).  A padding row / column repeats the last real one -- its layer's alpha is 0, so
@@ -140,6 +168,73 @@ template <int LP, bool T>
 __device__ __forceinline__ f32x4_o occ_quad(const float* occm, int r, int c0) {
   constexpr int R = OccLds<LP>::kRow;
   return *reinterpret_cast<const f32x4_o*>(occm + (T ? LP * R : 0) + r * R + c0);
+}
+
+// two columns of the order's product on the packed-fp32 pipe (v_pk_fma_f32)
+typedef float f32x2_w __attribute__((ext_vector_type(2)));
+
+// The tile walk of a backward pixel kernel: workgroup blockIdx.x % groups of its unit takes tiles_per_block tiles of
+// kBlock pixels of the unit's HW.
+struct BwdTile {
+  int64_t p, pc;  // this thread's pixel, and the same clamped into the raster (loads)
+  bool live;      // p is inside the raster (the last tile may be partly live)
+  int fresh;      // 0: see below
+};
+
+// for (BwdTileWalk w(tiles, tiles_per_block, groups); w.more();) { const BwdTile q = w.next(HW); ... }
+// (the loop stays in the kernel: with the tile's work handed over as a callable the register allocation of the
+// flow_ctx backward kernels changed, and the <17> instances spilled a quarter more)
+struct BwdTileWalk {
+  int tile, t1;
+  __device__ __forceinline__ BwdTileWalk(int tiles, int tiles_per_block, int groups) {
+    tile = (int)(blockIdx.x % groups) * tiles_per_block;
+    t1 = min(tiles, tile + tiles_per_block);
+  }
+  __device__ __forceinline__ bool more() const { return tile < t1; }
+  // FRESH false: a kernel that reads no LDS table inside the loop (occ_composite_bwd_kernel) and does not use q.fresh
+  template <bool FRESH = true>
+  __device__ __forceinline__ BwdTile next(int64_t HW) {
+    BwdTile q;
+    // the LDS tables (the order, the class distributions) do not change while the workgroup walks its tiles, and the
+    // compiler knows: it would hoist all their reads out of this loop, into ~600 registers it does not have.  An
+    // offset it cannot see through, for the kernels to add to their tables' addresses:
+    q.fresh = 0;
+    if constexpr (FRESH) asm volatile("" : "+v"(q.fresh));
+    q.p = (int64_t)tile * kBlock + threadIdx.x;
+    q.live = q.p < HW;
+    q.pc = q.live ? q.p : HW - 1;
+    ++tile;
+    return q;
+  }
+};
+
+// (y, x) of the tile's clamped pixel on the x `scale` raster of an H x W plane, and its upsampling taps
+__device__ __forceinline__ UpTaps bwd_tile_taps(const BwdTile& q, int H, int W, int scale, int& y, int& x) {
+  const int Wd = W * scale;
+  y = (int)(q.pc / Wd);
+  x = (int)(q.pc - (int64_t)y * Wd);
+  return up_taps(y, x, 1.0f / (float)scale, H, W);
+}
+
+// (b, ts) of unit m = (b, tc, tp) of flow_ctx_warp: the batch element, and the context frame clamped into the window
+struct CtxUnit {
+  int b, ts;
+};
+__device__ __forceinline__ CtxUnit ctx_unit(const int64_t* __restrict__ ctx_ts, int m, int Tw, int Tc, int Tp) {
+  return {m / (Tc * Tp), (int)min(max(ctx_ts[m], (int64_t)0), (int64_t)(Tw - 1))};
+}
+
+// the bilinear splat of a value sampled through `t` (the transpose of tap_sample's lerp form): the weights
+// (1-fx)(1-fy) ... with the validity of each corner, and the corners' byte offsets
+struct SplatWeights {
+  float w[4];
+  uint32_t o[4];
+};
+__device__ __forceinline__ SplatWeights splat_weights(const Taps& t) {
+  const float wx0 = 1.0f - t.fx, wy0 = 1.0f - t.fy;
+  return {{wx0 * wy0 * (t.vx0 * t.vy0), t.fx * wy0 * (t.vx1 * t.vy0), wx0 * t.fy * (t.vx0 * t.vy1),
+           t.fx * t.fy * (t.vx1 * t.vy1)},
+          {t.o00, t.o01, t.o10, t.o11}};
 }
 
 

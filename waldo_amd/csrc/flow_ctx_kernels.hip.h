@@ -78,30 +78,29 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
   if (dist != nullptr) {
     // softmax over the Nl layout logits of this pixel (held in registers)
     float pr[NCP];
-    float m = -INFINITY;
+    float den;
     if constexpr (std::is_same<IN, uint32_t>::value) {
       const uint32_t w = input[((int64_t)b * T + t) * HWd + p];
-#pragma unroll
-      for (int c = 0; c < NCP; ++c) {
-        pr[c] = (c < Nl) ? packed_lyt(w, c) : -INFINITY;
-        m = fmaxf(m, pr[c]);
-      }
+      den = lyt_softmax<NCP>(pr, Nl, [&](int c) { return packed_lyt(w, c); });
     } else {
+      // lyt_softmax written out: through the template this branch's instances were allocated anew and
+      // waldo_flow_ctx_alpha_fwd took 0.37 ms for 0.33 at the C5 recipe (the packed branch: 0.30 either way)
       const float* lg = input + (((int64_t)b * T + t) * C + chan_off) * HWd + p;
+      float m = -INFINITY;
 #pragma unroll
       for (int c = 0; c < NCP; ++c) {
         pr[c] = (c < Nl) ? lg[(int64_t)min(c, Nl - 1) * HWd] : -INFINITY;
         m = fmaxf(m, pr[c]);
       }
-    }
-    float den = 0.0f;
+      den = 0.0f;
 #pragma unroll
-    for (int c = 0; c < NCP; ++c) {
-      pr[c] = (c < Nl) ? expf(pr[c] - m) : 0.0f;
-      den += pr[c];
-    }
+      for (int c = 0; c < NCP; ++c) {
+        pr[c] = (c < Nl) ? expf(pr[c] - m) : 0.0f;
+        den += pr[c];
+      }
 #pragma unroll
-    for (int c = 0; c < NCP; ++c) pr[c] = pr[c] / den;
+      for (int c = 0; c < NCP; ++c) pr[c] = pr[c] / den;
+    }
     // (non-finite logits make every filter weight NaN, and 0 * NaN is NaN: no short cuts then)
     if (__ballot(!(den >= 1.0f && den <= 3.0e38f)) != 0ull) active = LP >= 32 ? 0xffffffffu : (1u << LP) - 1u;
 #pragma unroll
@@ -112,7 +111,6 @@ __global__ __launch_bounds__(kBlock) void flow_ctx_alpha_kernel(
 
   // padding layers carry alpha 0 (factor exactly 1); branch-free so that the arrays stay in registers.
   // Four columns of the order per step (OccLds), two and two on the packed-fp32 pipe.
-  typedef float f32x2_w __attribute__((ext_vector_type(2)));
   unsigned nz = 0;  // (layer_bits) bit l: a01 of layer l is non-zero (or NaN) in some pixel of this wavefront's row segment
 #pragma unroll
   for (int j = 0; j < LP; j += 4) {
@@ -217,7 +215,6 @@ __global__ __launch_bounds__(kBlock, (R > 1 && LP <= 12) ? ((R == 2 && !std::is_
     int Tp, int L, int H, int W, int scale, int units, int tiles, int nbands) {
   using G = FcwLds<LP, R>;
   constexpr bool kF32 = std::is_same<AT, float>::value;
-  typedef float f32x2_w __attribute__((ext_vector_type(2)));
   const int Hd = H * scale, Wd = W * scale;
   const int64_t HWd = (int64_t)Hd * Wd, HW = (int64_t)H * W;
   int m, x, y_first;  // m = (b, tc, tp)
@@ -1105,15 +1102,13 @@ int flow_ctx_alpha_launch(const char* fn, const float* alpha_lr, const IN* input
   }
   const HdGeom geom = hd_geom(N, H * scale, W * scale);
   with_padded_layers(L, [&](auto lp) {
-    auto launch = [&](auto ncp) {
+    // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
+    with_padded_classes(dist != nullptr, Nl, [&](auto ncp) {
       hipLaunchKernelGGL((flow_ctx_alpha_kernel<decltype(lp)::value, decltype(ncp)::value, IN>),
                          dim3((unsigned)hd_grid(N, geom)), dim3(kBlock), 0, (hipStream_t)stream, alpha_lr, input, dist,
                          occ, a01, alpha_out, layer_bits, T, Tw, L, Nl, C, chan_off, H, W, scale, (int)N, geom.tiles,
                          geom.nbands);
-    };
-    // (the class probabilities of a pixel live in registers: compiled for up to kFewCls classes and for kMaxCls)
-    if (dist == nullptr || Nl <= kFewCls) launch(std::integral_constant<int, kFewCls>{});
-    else launch(std::integral_constant<int, kMaxCls>{});
+    });
   });
   return launch_status(fn);
 }

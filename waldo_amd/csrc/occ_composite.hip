@@ -4,6 +4,7 @@
 // (L, L, h, w) tensor per map; here every thread keeps its L alphas in registers, occ is
 // wave-uniform (scalar cache), and nothing of size L*L*h*w exists.
 #include "det_common.hip.h"
+#include "flow_ctx_common.hip.h"
 
 namespace waldo {
 
@@ -32,10 +33,10 @@ __global__ __launch_bounds__(kBlock) void occ_composite_fwd_kernel(
 }
 
 // Backward.  grad_alpha is per pixel; grad_occ[m_occ][i][j] is a sum over ALL pixels of all maps that
-// share the matrix.  A workgroup walks `tiles_per_block` pixel tiles of one map: per tile and column
-// j every wave reduces its 64 pixels (wave_transpose_reduce: lane bitrev(i) ends up with row i) and
-// adds the result to ITS OWN row of an LDS table -- no atomics, no barrier; at the end the four rows
-// are summed in a fixed order and leave the workgroup as ONE float atomic per matrix entry (the
+// share the matrix.  A workgroup walks `tiles_per_block` pixel tiles of one map (BwdTileWalk): per tile and
+// column j every wave reduces its 64 pixels (wave_transpose_reduce: lane bitrev(i) ends up with row i) and
+// adds the result to ITS OWN row of an LDS table (WaveTable) -- no atomics, no barrier; at the end
+// the four rows are summed in a fixed order and leave the workgroup as ONE float atomic per matrix entry (the
 // first version issued one per wave, tile and entry: thousands of waves on a few hundred addresses,
 // 0.37 ms for 22 MB at the LVD recipe -- the pattern measured 14x below the streaming atomic rate).
 // DET (deterministic mode): grad_occ is a slab of one L x L row per workgroup, stored, not added (det_common.hip.h).
@@ -46,18 +47,14 @@ __global__ __launch_bounds__(kBlock) void occ_composite_bwd_kernel(
     float* __restrict__ grad_occ, int L, int64_t HW, int tiles, int tiles_per_block, int groups,
     int64_t occ_div) {
   const int64_t m = blockIdx.x / groups;
-  const int t0 = (int)(blockIdx.x % groups) * tiles_per_block;
-  const int t1 = min(tiles, t0 + tiles_per_block);
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
   const float* oc = occ + (m / occ_div) * L * L;
-  __shared__ float acc[4][LP * LP];
-  if (grad_occ != nullptr)
-    for (int e = lane; e < LP * LP; e += kWave) acc[wave][e] = 0.0f;  // wave-private row
-  for (int tile = t0; tile < t1; ++tile) {
-    const int64_t p = (int64_t)tile * kBlock + threadIdx.x;
-    const bool live = p < HW;
-    const int64_t pc = live ? p : HW - 1;
-    const float* ap = alpha + m * L * HW + pc;
+  __shared__ float acc_s[4][LP * LP];
+  const WaveTable<LP * LP> acc{acc_s};
+  if (grad_occ != nullptr) acc.zero(wave, lane);
+  for (BwdTileWalk w(tiles, tiles_per_block, groups); w.more();) {
+    const BwdTile q = w.next<false>(HW);
+    const float* ap = alpha + m * L * HW + q.pc;
     float a[LP], ga[LP];
 #pragma unroll
     for (int l = 0; l < LP; ++l) {
@@ -81,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void occ_composite_bwd_kernel(
           ex[i] *= suf;
           suf *= tf[i];
         }
-        const float go = live ? grad_out[(m * L + j) * HW + pc] : 0.0f;
+        const float go = q.live ? grad_out[(m * L + j) * HW + q.pc] : 0.0f;
         ga[j] = fmaf(go, pre, ga[j]);
         const float gaj = go * a[j];
         float gocc[LP];
@@ -97,27 +94,19 @@ __global__ __launch_bounds__(kBlock) void occ_composite_bwd_kernel(
         if (grad_occ != nullptr) {
           const float red = wave_transpose_reduce<LP>(gocc, lane);
           const int i = bitrev6(lane);
-          if (i < L) acc[wave][i * LP + j] += red;  // one lane per entry: plain read-modify-write
+          if (i < L) acc.row(wave)[i * LP + j] += red;  // one lane per entry: plain read-modify-write
         }
       }
     }
-    if (live) {
+    if (q.live) {
 #pragma unroll
       for (int l = 0; l < LP; ++l)
-        if (l < L) grad_alpha[(m * L + l) * HW + p] = ga[l];
+        if (l < L) grad_alpha[(m * L + l) * HW + q.p] = ga[l];
     }
   }
   if (grad_occ != nullptr) {
     __syncthreads();
-    for (int e = threadIdx.x; e < LP * LP; e += kBlock) {
-      const int i = e / LP, j = e % LP;
-      if (i < L && j < L) {
-        if constexpr (DET)
-          grad_occ[(int64_t)blockIdx.x * L * L + i * L + j] = (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]);
-        else
-          atomicAdd(grad_occ + (m / occ_div) * L * L + i * L + j, (acc[0][e] + acc[1][e]) + (acc[2][e] + acc[3][e]));
-      }
-    }
+    acc.template flush<DET>(grad_occ, L * L, m / occ_div, PaddedSquare<LP>{L});
   }
 }
 
