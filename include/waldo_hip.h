@@ -1104,6 +1104,63 @@ int waldo_token_attention_bwd(const float* q, int64_t qs_b, int64_t qs_n, const 
                               float* grad_v1, float* grad_k2, float* grad_v2, float scale, int64_t B, int H, int D,
                               int Nq, int Nk1, int Nk2, waldo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Token attention over clips: the attention of the future layer predictor's blocks (the reference's
+ * models/modules/transform.py FullAttention / CrossAttention with ctx_mask: from_ctx -> attention over all T N keys
+ * under a -inf mask -> to_ctx), as what those masks say: within a clip the selected query rows attend to the selected
+ * key rows and nothing else survives.  The rows stay PACKED -- the selected frames' tokens of all clips one after the
+ * other -- and a clip is a segment of them.  The kernels are the section above's (one template, the same tile
+ * pipeline and arithmetic); only where a workgroup finds its rows differs.
+ *
+ * waldo_token_attention_clips_fwd: q is (Rq, H, D) and k, v are (Rk, H, D), VIEWS as above with a token stride in
+ *   floats and no batch axis; q_off and k_off are int32 tables of B + 1 entries IN DEVICE MEMORY: clip b's queries are
+ *   the rows [q_off[b], q_off[b + 1]) and its keys the rows [k_off[b], k_off[b + 1]).  For every clip b, h < H and
+ *   query row i of the clip, over the clip's key rows j:
+ *     out[i, h, :] = sum_j softmax_j(scale * q[i, h, :] . k[j, h, :]) v[j, h, :]
+ *   out is (Rq, H D) contiguous.  max_q_len and max_k_len are the caller's upper bounds on a clip's rows; the grid is
+ *   B x H x ceil(max_q_len / 64) and a workgroup whose block starts at or past its clip's last query returns at once;
+ *   the key loop runs to the clip's own length.  A clip longer than its bound is served up to the bound only.
+ *   The host never reads the tables: NO SYNCHRONISATION, no allocation, NO ATOMICS, the same bits from run to run, the
+ *   caller's stream, capturable in a graph.  The kernels clamp every table entry into [0, Rq] / [0, Rk] and take a
+ *   clip whose end lies before its start as empty, so that NO TABLE CONTENT makes them address a row outside the
+ *   operands; rows that belong to no clip are not written.
+ *   A clip without queries writes nothing.  A clip with queries and no keys gets NaN in exactly its rows of out (the
+ *   softmax of a row whose keys are all masked) and -inf in lse.
+ *   The tile sizes and head dimensions are waldo_token_attention_limits's.
+ *
+ * B == 0 or Rq == 0: WALDO_OK without a launch.  WALDO_EINVAL with a message before any launch: "bad shape" (B, Rq,
+ * Rk < 0; H < 1), "bad clip bound" (max_q_len or max_k_len < 0), "bad head dimension", "bad scale", "too large",
+ * "negative stride", "bad token stride", "null pointer" (a view, out, a table), "not aligned" (a view or out off a
+ * 16-byte boundary).
+ *
+ * waldo_token_attention_clips_fwd_lse: the same call that also stores lse (H, Rq) contiguous fp32, the row's
+ *   log sum_j exp(scale * q . k_j); "null pointer" covers lse.
+ *
+ * waldo_token_attention_clips_bwd: the gradients in the three views, from out, grad_out (both (Rq, H D) contiguous)
+ *   and lse, by the section above's formulas and structure: a delta pass (delta (H, Rq): the caller's workspace), a dQ
+ *   kernel and a dK/dV kernel whose workgroup owns a key block of ONE clip and walks that clip's query tiles (grid
+ *   B x H x ceil(max_k_len / 64)).  grad_q (Rq, H, D) and grad_k / grad_v (Rk, H, D) are contiguous fp32 and are
+ *   OVERWRITTEN in the rows that belong to a clip; a NULL gradient pointer means that gradient is not wanted (all
+ *   three NULL: WALDO_OK without a launch).  The keys of a clip without queries get exact zeros; the queries of a clip
+ *   without keys get zeros, and no other clip's gradients see that clip's NaN rows.  NO SCORE-SIZED MEMORY, no atomics,
+ *   no synchronisation; the same bits from run to run; capturable in a graph.
+ *   Refusals: the forward's, under this function's name ("too large" also covers the key blocks and the rows of out);
+ *   "null pointer" also for out, grad_out, lse and delta; "not aligned" for every non-NULL pointer but the tables.
+ * ------------------------------------------------------------------------------------- */
+int waldo_token_attention_clips_fwd(const float* q, int64_t qs_n, const float* k, int64_t ks_n, const float* v,
+                                    int64_t vs_n, const int* q_off, const int* k_off, float* out, float scale, int64_t B,
+                                    int H, int D, int64_t Rq, int64_t Rk, int max_q_len, int max_k_len,
+                                    waldo_stream_t stream);
+int waldo_token_attention_clips_fwd_lse(const float* q, int64_t qs_n, const float* k, int64_t ks_n, const float* v,
+                                        int64_t vs_n, const int* q_off, const int* k_off, float* out, float* lse,
+                                        float scale, int64_t B, int H, int D, int64_t Rq, int64_t Rk, int max_q_len,
+                                        int max_k_len, waldo_stream_t stream);
+int waldo_token_attention_clips_bwd(const float* q, int64_t qs_n, const float* k, int64_t ks_n, const float* v,
+                                    int64_t vs_n, const int* q_off, const int* k_off, const float* out,
+                                    const float* grad_out, const float* lse, float* delta, float* grad_q, float* grad_k,
+                                    float* grad_v, float scale, int64_t B, int H, int D, int64_t Rq, int64_t Rk,
+                                    int max_q_len, int max_k_len, waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

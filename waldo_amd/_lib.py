@@ -145,6 +145,15 @@ SIGNATURES = {
     "waldo_token_attention_fwd_lse": [_c_f, _i64, _i64] * 5 + [_c_f, _c_f, _flt, _i64, _int, _int, _int, _int, _int,
                                                                _stream],
     "waldo_token_attention_bwd": [_c_f, _i64, _i64] * 5 + [_c_f] * 9 + [_flt, _i64, _int, _int, _int, _int, _int, _stream],
+    # token attention over clips (include/waldo_hip.h "Token attention over clips"): q, k, v with a token stride each,
+    # the two offset tables, out (, lse), scale, B, H, D, Rq, Rk, max_q_len, max_k_len; the backward: ..., the tables,
+    # out, grad_out, lse, delta, the three gradients (None: not wanted), scale, ...
+    "waldo_token_attention_clips_fwd": [_c_f, _i64] * 3 + [_c_f] * 3 + [_flt, _i64, _int, _int, _i64, _i64, _int, _int,
+                                                                        _stream],
+    "waldo_token_attention_clips_fwd_lse": [_c_f, _i64] * 3 + [_c_f] * 4 + [_flt, _i64, _int, _int, _i64, _i64, _int, _int,
+                                                                            _stream],
+    "waldo_token_attention_clips_bwd": [_c_f, _i64] * 3 + [_c_f] * 9 + [_flt, _i64, _int, _int, _i64, _i64, _int, _int,
+                                                                        _stream],
 }
 # workspace size of each *_det entry point (0: no deterministic kernel for the shape)
 DET_QUERIES = {

@@ -22,6 +22,9 @@
 //
 // The _lse entry point is the same kernel template with one more store: the row's m + log(l) of the scaled scores, which
 // the backward (token_attention_bwd.hip) rebuilds the probabilities from.
+//
+// The waldo_token_attention_clips_* entry points (include/waldo_hip.h "Token attention over clips") run the same
+// template with CLIPS: b is a clip of PACKED rows whose first row and length come from offset tables in device memory.
 #include "token_attention_common.hip.h"
 
 namespace waldo {
@@ -31,19 +34,31 @@ struct TokenAttentionArgs {
   float *out, *lse;
   float scale;
   int H, Nq, Nk1, Nk, qblocks;  // Nk = Nk1 + Nk2
+  TaClips clips;                // CLIPS: the lengths are the clip's own, Nq / Nk1 / Nk are not read
 };
 
-template <int D, bool LSE>
+// CLIPS: b is a clip of packed rows (TaClips).  Its lengths come from the tables, a workgroup whose block starts at or
+// past the clip's last query leaves before the first barrier (workgroup-uniform), out is (Rq, H D) and lse (H, Rq).  A
+// clip without keys has no tile: o = 0 and l = 0 give its rows 0 * inf = NaN, the softmax of a row with every key
+// masked.  Everything between is the dense kernel, which is the instantiation without a table read.
+template <int D, bool LSE, bool CLIPS>
 __global__ __launch_bounds__(kBlock) void token_attention_fwd_kernel(TokenAttentionArgs a) {
   constexpr int LD = TaTile<D>::LD, PER = TaTile<D>::PER, JB = TaTile<D>::JB, DB = TaTile<D>::DB;
   __shared__ __attribute__((aligned(16))) float sk[kTaK * LD];
   __shared__ __attribute__((aligned(16))) float sv[kTaK * LD];
 
   const TaCoord c = ta_coord(a.qblocks, a.H);
+  const TaSegment qs = CLIPS ? ta_segment(a.clips.q_off, c.b, a.clips.Rq) : TaSegment{0, a.Nq};
+  const TaSegment ks = CLIPS ? ta_segment(a.clips.k_off, c.b, a.clips.Rk) : TaSegment{0, a.Nk};
+  const int Nq = qs.len, Nk = ks.len, Nk1 = CLIPS ? Nk : a.Nk1;
+  if (CLIPS && c.block * kTaQ >= Nq) return;
+  const int64_t qb = CLIPS ? (int64_t)qs.first : c.b, kb = CLIPS ? (int64_t)ks.first : c.b;
+  const int64_t orow = CLIPS ? (int64_t)qs.first : c.b * Nq;                                        // first row of out
+  const int64_t lrow = CLIPS ? (int64_t)c.h * a.clips.Rq + qs.first : (c.b * a.H + c.h) * Nq;      // ... and of lse
   const int q0 = c.block * kTaQ + c.wave * 16;
-  const bool wave_live = q0 < a.Nq;  // wave-uniform: a wave past the last row only helps to stage
-  const int qrow = min(q0 + c.row, a.Nq - 1);
-  const TaViews at = ta_views_at(a.v, c.b, c.h * D);
+  const bool wave_live = q0 < Nq;  // wave-uniform: a wave past the last row only helps to stage
+  const int qrow = min(q0 + c.row, Nq - 1);
+  const TaViews at = ta_views_at(a.v, qb, kb, c.h * D);
 
   ta_f32x4 qf[DB];  // Q[q][16 t + 4 g + c]
   ta_load_row<D>(at.q.p + (int64_t)qrow * at.q.sn + 4 * c.g, true, qf);
@@ -55,13 +70,13 @@ __global__ __launch_bounds__(kBlock) void token_attention_fwd_kernel(TokenAttent
   ta_zero(o);
   float m = -INFINITY, l = 0.0f;  // the row's running maximum; THIS LANE's part of its running sum
 
-  const int tiles = (a.Nk + kTaK - 1) / kTaK;
-  ta_fetch_kv<D>(at, 0, a.Nk1, a.Nk, kreg, vreg);
+  const int tiles = (Nk + kTaK - 1) / kTaK;
+  if (!CLIPS || tiles > 0) ta_fetch_kv<D>(at, 0, Nk1, Nk, kreg, vreg);  // (a clip without keys has no row 0 to read)
   for (int tile = 0; tile < tiles; ++tile) {
     __syncthreads();  // the previous tile has been read by every wave
     ta_stage<D>(sk, sv, kreg, vreg);
     __syncthreads();
-    if (tile + 1 < tiles) ta_fetch_kv<D>(at, tile + 1, a.Nk1, a.Nk, kreg, vreg);
+    if (tile + 1 < tiles) ta_fetch_kv<D>(at, tile + 1, Nk1, Nk, kreg, vreg);
     if (!wave_live) continue;
 
     // S^T = K Q^T: lane (q, g) gets the keys 16 j + 4 g + r
@@ -77,7 +92,7 @@ __global__ __launch_bounds__(kBlock) void token_attention_fwd_kernel(TokenAttent
     for (int j = 0; j < JB; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float x = key0 + 16 * j + r < a.Nk ? s[j][r] * a.scale : -INFINITY;
+        const float x = key0 + 16 * j + r < Nk ? s[j][r] * a.scale : -INFINITY;
         s[j][r] = x;
         tmax = fmaxf(tmax, x);
       }
@@ -109,12 +124,12 @@ __global__ __launch_bounds__(kBlock) void token_attention_fwd_kernel(TokenAttent
   if (!wave_live) return;
   l += __shfl_xor(l, 16);
   l += __shfl_xor(l, 32);
-  if (q0 + c.row < a.Nq) {
+  if (q0 + c.row < Nq) {
     const float inv = 1.0f / l;
-    float* op = a.out + ((c.b * a.Nq + (q0 + c.row)) * a.H + c.h) * D + 4 * c.g;
+    float* op = a.out + ((orow + (q0 + c.row)) * a.H + c.h) * D + 4 * c.g;
 #pragma unroll
     for (int d = 0; d < DB; ++d) *reinterpret_cast<ta_f32x4*>(op + 16 * d) = o[d] * inv;
-    if (LSE && c.g == 0) a.lse[(c.b * a.H + c.h) * a.Nq + (q0 + c.row)] = m + logf(l);
+    if (LSE && c.g == 0) a.lse[lrow + (q0 + c.row)] = m + logf(l);
   }
 }
 
@@ -132,7 +147,30 @@ int token_attention_fwd_host(const char* fn, TaViews v, float* out, float* lse, 
   a.scale = scale, a.H = H, a.Nq = Nq, a.Nk1 = Nk1, a.Nk = Nk1 + Nk2, a.qblocks = (int)qblocks;
   const dim3 grid((unsigned)(B * H * qblocks));
   ta_for_head_dim(D, [&](auto d) {
-    token_attention_fwd_kernel<decltype(d)::value, LSE><<<grid, dim3(kBlock), 0, (hipStream_t)stream>>>(a);
+    token_attention_fwd_kernel<decltype(d)::value, LSE, false><<<grid, dim3(kBlock), 0, (hipStream_t)stream>>>(a);
+  });
+  return launch_status(fn);
+}
+
+// The per-clip forward: the grid is sized by the caller's bound on a clip's queries, nothing here reads the tables.
+template <bool LSE>
+int token_attention_clips_fwd_host(const char* fn, TaViews v, const int* q_off, const int* k_off, float* out, float* lse,
+                                   float scale, int64_t B, int H, int D, int64_t Rq, int64_t Rk, int max_q_len,
+                                   int max_k_len, waldo_stream_t stream) {
+  const int64_t qblocks = ((int64_t)(max_q_len > 0 ? max_q_len : 0) + kTaQ - 1) / kTaQ;
+  if (ta_clips_check_shape(fn, v, scale, B, H, D, Rq, Rk, max_q_len, max_k_len, qblocks) != WALDO_OK)
+    return WALDO_EINVAL;
+  if (B == 0 || Rq == 0) return WALDO_OK;
+  if (ta_check_pointers(fn, v, 0, out && (!LSE || lse) && q_off && k_off, {out}) != WALDO_OK) return WALDO_EINVAL;
+  if (qblocks == 0) return WALDO_OK;  // no clip has a query
+  ta_clips_rows_as_batch(v);
+  TokenAttentionArgs a{};
+  a.v = v, a.out = out, a.lse = lse;
+  a.scale = scale, a.H = H, a.qblocks = (int)qblocks;
+  a.clips = {q_off, k_off, (int)Rq, (int)Rk};
+  const dim3 grid((unsigned)(B * H * qblocks));
+  ta_for_head_dim(D, [&](auto d) {
+    token_attention_fwd_kernel<decltype(d)::value, LSE, true><<<grid, dim3(kBlock), 0, (hipStream_t)stream>>>(a);
   });
   return launch_status(fn);
 }
@@ -163,4 +201,23 @@ extern "C" int waldo_token_attention_fwd_lse(const float* q, int64_t qs_b, int64
   return token_attention_fwd_host<true>(
       "waldo_token_attention_fwd_lse", {{q, qs_b, qs_n}, {k1, k1s_b, k1s_n}, {v1, v1s_b, v1s_n}, {k2, k2s_b, k2s_n},
                                         {v2, v2s_b, v2s_n}}, out, lse, scale, B, H, D, Nq, Nk1, Nk2, stream);
+}
+
+extern "C" int waldo_token_attention_clips_fwd(const float* q, int64_t qs_n, const float* k, int64_t ks_n, const float* v,
+                                               int64_t vs_n, const int* q_off, const int* k_off, float* out, float scale,
+                                               int64_t B, int H, int D, int64_t Rq, int64_t Rk, int max_q_len,
+                                               int max_k_len, waldo_stream_t stream) {
+  return token_attention_clips_fwd_host<false>("waldo_token_attention_clips_fwd",
+                                               ta_clips_views(q, qs_n, k, ks_n, v, vs_n), q_off, k_off, out, nullptr,
+                                               scale, B, H, D, Rq, Rk, max_q_len, max_k_len, stream);
+}
+
+extern "C" int waldo_token_attention_clips_fwd_lse(const float* q, int64_t qs_n, const float* k, int64_t ks_n,
+                                                   const float* v, int64_t vs_n, const int* q_off, const int* k_off,
+                                                   float* out, float* lse, float scale, int64_t B, int H, int D,
+                                                   int64_t Rq, int64_t Rk, int max_q_len, int max_k_len,
+                                                   waldo_stream_t stream) {
+  return token_attention_clips_fwd_host<true>("waldo_token_attention_clips_fwd_lse",
+                                              ta_clips_views(q, qs_n, k, ks_n, v, vs_n), q_off, k_off, out, lse, scale,
+                                              B, H, D, Rq, Rk, max_q_len, max_k_len, stream);
 }

@@ -31,13 +31,19 @@ struct TokenAttentionBwdArgs {
   int64_t rows;  // B Nq H: the (token, head) rows of out
   float scale;
   int H, Nq, Nk1, Nk, blocks;  // Nk = Nk1 + Nk2; blocks: the kernel's row blocks per (b, h)
+  TaClips clips;               // CLIPS: the lengths are the clip's own, Nq / Nk1 / Nk are not read
 };
+
+// CLIPS, in all three kernels (the forward's, token_attention.hip): b is a clip of packed rows, out / grad_out / grad_q
+// are (Rq, H D), grad_k / grad_v (Rk, H D) and lse / delta (H, Rq).  A workgroup whose block starts at or past its
+// clip's last row leaves before the first barrier; the dK/dV workgroup of a clip without queries walks no tile and
+// stores the zeros it started from.
 
 // delta[b, h, i] = sum_d grad_out[b, i, h, d] out[b, i, h, d]: one lane per row, ONE fma chain in the order in which the
 // matrix instruction sums dP = dO . V in the two kernels below (d = 16 t + 4 g + c: t, then c, then the instruction's
 // k index g).  Where a row has one key, P = 1 and O = V: delta and dP are then the same chain and dS = P (dP - delta)
 // is exactly 0, as it is in exact arithmetic -- two different orders would leave a rounding residue in dQ and dK.
-template <int D>
+template <int D, bool CLIPS>
 __global__ __launch_bounds__(kBlock) void token_attention_delta_kernel(TokenAttentionBwdArgs a) {
   constexpr int DB = D / 16;
   const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -57,28 +63,39 @@ __global__ __launch_bounds__(kBlock) void token_attention_delta_kernel(TokenAtte
   }
   const int h = (int)(row % a.H);
   const int64_t bi = row / a.H;
+  if (CLIPS) {
+    a.delta[(int64_t)h * a.clips.Rq + bi] = s;
+    return;
+  }
   const int64_t b = bi / a.Nq, i = bi % a.Nq;
   a.delta[(b * a.H + h) * a.Nq + i] = s;
 }
 
-template <int D>
+template <int D, bool CLIPS>
 __global__ __launch_bounds__(kBlock) void token_attention_bwd_dq_kernel(TokenAttentionBwdArgs a) {
   constexpr int LD = TaTile<D>::LD, PER = TaTile<D>::PER, JB = TaTile<D>::JB, DB = TaTile<D>::DB;
   __shared__ __attribute__((aligned(16))) float sk[kTaK * LD];
   __shared__ __attribute__((aligned(16))) float sv[kTaK * LD];
 
   const TaCoord c = ta_coord(a.blocks, a.H);
+  const TaSegment qs = CLIPS ? ta_segment(a.clips.q_off, c.b, a.clips.Rq) : TaSegment{0, a.Nq};
+  const TaSegment ks = CLIPS ? ta_segment(a.clips.k_off, c.b, a.clips.Rk) : TaSegment{0, a.Nk};
+  const int Nq = qs.len, Nk = ks.len, Nk1 = CLIPS ? Nk : a.Nk1;
+  if (CLIPS && c.block * kTaQ >= Nq) return;
+  const int64_t qb = CLIPS ? (int64_t)qs.first : c.b, kb = CLIPS ? (int64_t)ks.first : c.b;
+  const int64_t orow = CLIPS ? (int64_t)qs.first : c.b * Nq;                                    // first row of grad_out
+  const int64_t lrow = CLIPS ? (int64_t)c.h * a.clips.Rq + qs.first : (c.b * a.H + c.h) * Nq;  // ... of lse and delta
   const int q0 = c.block * kTaQ + c.wave * 16;
-  const bool wave_live = q0 < a.Nq;  // wave-uniform: a wave past the last row only helps to stage
-  const int qrow = min(q0 + c.row, a.Nq - 1);
-  const TaViews at = ta_views_at(a.v, c.b, c.h * D);
+  const bool wave_live = q0 < Nq;  // wave-uniform: a wave past the last row only helps to stage
+  const int qrow = min(q0 + c.row, Nq - 1);
+  const TaViews at = ta_views_at(a.v, qb, kb, c.h * D);
 
   // Q[q][16 t + 4 g + c] and dO[q][16 t + 4 g + c]; the row's lse and delta
   ta_f32x4 qf[DB], gf[DB];
   ta_load_row<D>(at.q.p + (int64_t)qrow * at.q.sn + 4 * c.g, true, qf);
-  ta_load_row<D>(a.grad_out + ((c.b * a.Nq + qrow) * a.H + c.h) * D + 4 * c.g, true, gf);
-  const float lse = a.lse[(c.b * a.H + c.h) * a.Nq + qrow];
-  const float delta = a.delta[(c.b * a.H + c.h) * a.Nq + qrow];
+  ta_load_row<D>(a.grad_out + ((orow + qrow) * a.H + c.h) * D + 4 * c.g, true, gf);
+  const float lse = a.lse[lrow + qrow];
+  const float delta = a.delta[lrow + qrow];
   const float* krows = sk + c.row * LD + 4 * c.g;   // K[16 j + q][16 t + 4 g + c], and V at
   const float* vrows = sv + c.row * LD + 4 * c.g;   //   the same place
   const float* kcols = sk + 4 * c.g * LD + c.row;   // K[16 j + 4 g + r][16 d + q]
@@ -87,13 +104,13 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dq_kernel(TokenAtt
   ta_f32x4 dq[DB];
   ta_zero(dq);
 
-  const int tiles = (a.Nk + kTaK - 1) / kTaK;
-  ta_fetch_kv<D>(at, 0, a.Nk1, a.Nk, kreg, vreg);
+  const int tiles = (Nk + kTaK - 1) / kTaK;
+  if (!CLIPS || tiles > 0) ta_fetch_kv<D>(at, 0, Nk1, Nk, kreg, vreg);  // (a clip without keys has no row 0 to read)
   for (int tile = 0; tile < tiles; ++tile) {
     __syncthreads();  // the previous tile has been read by every wave
     ta_stage<D>(sk, sv, kreg, vreg);
     __syncthreads();
-    if (tile + 1 < tiles) ta_fetch_kv<D>(at, tile + 1, a.Nk1, a.Nk, kreg, vreg);
+    if (tile + 1 < tiles) ta_fetch_kv<D>(at, tile + 1, Nk1, Nk, kreg, vreg);
     if (!wave_live) continue;
 
     // S^T = K Q^T and dP^T = V dO^T: lane (q, g) gets the keys 16 j + 4 g + r
@@ -111,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dq_kernel(TokenAtt
     for (int j = 0; j < JB; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = key0 + 16 * j + r < a.Nk ? __expf(s[j][r] * a.scale - lse) : 0.0f;
+        const float p = key0 + 16 * j + r < Nk ? __expf(s[j][r] * a.scale - lse) : 0.0f;
         s[j][r] = p * (dp[j][r] - delta);
       }
 
@@ -122,8 +139,8 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dq_kernel(TokenAtt
       for (int r = 0; r < 4; ++r) ta_cols_step<D>(kcols + (16 * j + r) * LD, s[j][r], dq);
   }
   if (!wave_live) return;
-  if (q0 + c.row < a.Nq) {
-    float* op = a.grad_q + ((c.b * a.Nq + (q0 + c.row)) * a.H + c.h) * D + 4 * c.g;
+  if (q0 + c.row < Nq) {
+    float* op = a.grad_q + ((orow + (q0 + c.row)) * a.H + c.h) * D + 4 * c.g;
 #pragma unroll
     for (int d = 0; d < DB; ++d) *reinterpret_cast<ta_f32x4*>(op + 16 * d) = dq[d] * a.scale;
   }
@@ -153,7 +170,7 @@ __device__ __forceinline__ void ta_fetch_qg(const float* qp0, int64_t qs_n, cons
   dreg = live ? dx : 0.0f;
 }
 
-template <int D>
+template <int D, bool CLIPS>
 __global__ __launch_bounds__(kBlock) void token_attention_bwd_dkv_kernel(TokenAttentionBwdArgs a) {
   constexpr int LD = TaTile<D>::LD, PER = TaTile<D>::PER, JB = TaTile<D>::JB, DB = TaTile<D>::DB;
   static_assert(kTaQ <= kBlock, "one thread per row statistic of a tile");
@@ -163,27 +180,33 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dkv_kernel(TokenAt
   __shared__ __attribute__((aligned(16))) float sdelta[kTaQ];
 
   const TaCoord c = ta_coord(a.blocks, a.H);
+  const TaSegment qs = CLIPS ? ta_segment(a.clips.q_off, c.b, a.clips.Rq) : TaSegment{0, a.Nq};
+  const TaSegment ks = CLIPS ? ta_segment(a.clips.k_off, c.b, a.clips.Rk) : TaSegment{0, a.Nk};
+  const int Nq = qs.len, Nk = ks.len, Nk1 = CLIPS ? Nk : a.Nk1;
+  if (CLIPS && c.block * kTaK >= Nk) return;
+  const int64_t qb = CLIPS ? (int64_t)qs.first : c.b, kb = CLIPS ? (int64_t)ks.first : c.b;
+  const int64_t lrow = CLIPS ? (int64_t)c.h * a.clips.Rq + qs.first : (c.b * a.H + c.h) * Nq;  // first of lse and delta
   const int tid = threadIdx.x;
   const int k0 = c.block * kTaK + c.wave * 16;
-  const bool wave_live = k0 < a.Nk;  // wave-uniform: a wave past the last key only helps to stage
+  const bool wave_live = k0 < Nk;  // wave-uniform: a wave past the last key only helps to stage
   const int key = k0 + c.row;
-  const bool key_live = key < a.Nk, second = key_live && key >= a.Nk1;
-  const int64_t kidx = second ? key - a.Nk1 : (key_live ? key : 0);
+  const bool key_live = key < Nk, second = key_live && key >= Nk1;
+  const int64_t kidx = second ? key - Nk1 : (key_live ? key : 0);
 
   // K[key][16 t + 4 g + c] and V[key][16 t + 4 g + c], from the key's segment; zeros past the last key
   ta_f32x4 kf[DB], vf[DB];
   {
     const TaView k1 = a.v.k1, v1 = a.v.v1, k2 = a.v.k2, v2 = a.v.v2;
-    const float* kp = (second ? k2.p + c.b * k2.sb + kidx * k2.sn : k1.p + c.b * k1.sb + kidx * k1.sn) + c.h * D + 4 * c.g;
-    const float* vp = (second ? v2.p + c.b * v2.sb + kidx * v2.sn : v1.p + c.b * v1.sb + kidx * v1.sn) + c.h * D + 4 * c.g;
+    const float* kp = (second ? k2.p + kb * k2.sb + kidx * k2.sn : k1.p + kb * k1.sb + kidx * k1.sn) + c.h * D + 4 * c.g;
+    const float* vp = (second ? v2.p + kb * v2.sb + kidx * v2.sn : v1.p + kb * v1.sb + kidx * v1.sn) + c.h * D + 4 * c.g;
     ta_load_row<D>(kp, key_live, kf);
     ta_load_row<D>(vp, key_live, vf);
   }
 
-  const float* qp0 = a.v.q.p + c.b * a.v.q.sb + c.h * D;
-  const float* gp0 = a.grad_out + (c.b * a.Nq * a.H + c.h) * D;
-  const float* lsep = a.lse + (c.b * a.H + c.h) * a.Nq;
-  const float* deltap = a.delta + (c.b * a.H + c.h) * a.Nq;
+  const float* qp0 = a.v.q.p + qb * a.v.q.sb + c.h * D;
+  const float* gp0 = a.grad_out + ((CLIPS ? (int64_t)qs.first * a.H : c.b * Nq * a.H) + c.h) * D;
+  const float* lsep = a.lse + lrow;
+  const float* deltap = a.delta + lrow;
   const float* qrows = sq + c.row * LD + 4 * c.g;   // Q[16 j + key][16 t + 4 g + c], and dO at
   const float* grows = sg + c.row * LD + 4 * c.g;   //   the same place
   const float* qcols = sq + 4 * c.g * LD + c.row;   // Q[16 j + 4 g + r][16 d + key], and dO at
@@ -195,15 +218,16 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dkv_kernel(TokenAt
   ta_f32x4 dk[DB], dv[DB];
   ta_zero(dk), ta_zero(dv);
 
-  const int tiles = (a.Nq + kTaQ - 1) / kTaQ;
-  ta_fetch_qg<D>(qp0, a.v.q.sn, gp0, (int64_t)a.H * D, lsep, deltap, 0, a.Nq, qreg, greg, lreg, dreg);
+  const int tiles = (Nq + kTaQ - 1) / kTaQ;
+  if (!CLIPS || tiles > 0)  // (a clip without queries has no row 0 to read)
+    ta_fetch_qg<D>(qp0, a.v.q.sn, gp0, (int64_t)a.H * D, lsep, deltap, 0, Nq, qreg, greg, lreg, dreg);
   for (int tile = 0; tile < tiles; ++tile) {
     __syncthreads();  // the previous tile has been read by every wave
     ta_stage<D>(sq, sg, qreg, greg);
     if (tid < kTaQ) slse[tid] = lreg, sdelta[tid] = dreg;
     __syncthreads();
     if (tile + 1 < tiles)
-      ta_fetch_qg<D>(qp0, a.v.q.sn, gp0, (int64_t)a.H * D, lsep, deltap, tile + 1, a.Nq, qreg, greg, lreg, dreg);
+      ta_fetch_qg<D>(qp0, a.v.q.sn, gp0, (int64_t)a.H * D, lsep, deltap, tile + 1, Nq, qreg, greg, lreg, dreg);
     if (!wave_live) continue;
 
     // S = Q K^T and dP = dO V^T: lane (key, g) gets the queries 16 j + 4 g + r
@@ -223,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dkv_kernel(TokenAt
       const ta_f32x4 d4 = *reinterpret_cast<const ta_f32x4*>(sdelta + 16 * j + 4 * c.g);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = query0 + 16 * j + r < a.Nq ? __expf(s[j][r] * a.scale - l4[r]) : 0.0f;
+        const float p = query0 + 16 * j + r < Nq ? __expf(s[j][r] * a.scale - l4[r]) : 0.0f;
         s[j][r] = p * (dp[j][r] - d4[r]);
         dp[j][r] = p;
       }
@@ -240,8 +264,8 @@ __global__ __launch_bounds__(kBlock) void token_attention_bwd_dkv_kernel(TokenAt
   }
   if (!wave_live || !key_live) return;
   // the key's gradients go to its segment: (B, Nk1, H, D) or (B, Nk2, H, D), either of which may not be wanted
-  const int64_t nseg = second ? a.Nk - a.Nk1 : a.Nk1;
-  const int64_t at = ((c.b * nseg + kidx) * a.H + c.h) * D + 4 * c.g;
+  const int64_t nseg = second ? Nk - Nk1 : Nk1;
+  const int64_t at = (((CLIPS ? (int64_t)ks.first : c.b * nseg) + kidx) * a.H + c.h) * D + 4 * c.g;
   float* gk = second ? a.grad_k2 : a.grad_k1;
   float* gv = second ? a.grad_v2 : a.grad_v1;
   if (gk) {
@@ -294,14 +318,61 @@ extern "C" int waldo_token_attention_bwd(const float* q, int64_t qs_b, int64_t q
   const dim3 block(kBlock);
   ta_for_head_dim(D, [&](auto d) {
     constexpr int kD = decltype(d)::value;
-    token_attention_delta_kernel<kD><<<dim3((unsigned)((rows + kBlock - 1) / kBlock)), block, 0, st>>>(a);
+    token_attention_delta_kernel<kD, false><<<dim3((unsigned)((rows + kBlock - 1) / kBlock)), block, 0, st>>>(a);
     if (grad_q) {
       a.blocks = (int)qblocks;
-      token_attention_bwd_dq_kernel<kD><<<dim3((unsigned)(B * H * qblocks)), block, 0, st>>>(a);
+      token_attention_bwd_dq_kernel<kD, false><<<dim3((unsigned)(B * H * qblocks)), block, 0, st>>>(a);
     }
     if (grad_k1 || grad_v1 || grad_k2 || grad_v2) {
       a.blocks = (int)kblocks;
-      token_attention_bwd_dkv_kernel<kD><<<dim3((unsigned)(B * H * kblocks)), block, 0, st>>>(a);
+      token_attention_bwd_dkv_kernel<kD, false><<<dim3((unsigned)(B * H * kblocks)), block, 0, st>>>(a);
+    }
+  });
+  return launch_status(fn);
+}
+
+extern "C" int waldo_token_attention_clips_bwd(const float* q, int64_t qs_n, const float* k, int64_t ks_n, const float* v,
+                                               int64_t vs_n, const int* q_off, const int* k_off, const float* out,
+                                               const float* grad_out, const float* lse, float* delta, float* grad_q,
+                                               float* grad_k, float* grad_v, float scale, int64_t B, int H, int D,
+                                               int64_t Rq, int64_t Rk, int max_q_len, int max_k_len,
+                                               waldo_stream_t stream) {
+  const char* fn = "waldo_token_attention_clips_bwd";
+  TaViews vw = ta_clips_views(q, qs_n, k, ks_n, v, vs_n);
+  const int64_t qblocks = ((int64_t)(max_q_len > 0 ? max_q_len : 0) + kTaQ - 1) / kTaQ;
+  const int64_t kblocks = ((int64_t)(max_k_len > 0 ? max_k_len : 0) + kTaK - 1) / kTaK;
+  if (ta_clips_check_shape(fn, vw, scale, B, H, D, Rq, Rk, max_q_len, max_k_len,
+                           qblocks > kblocks ? qblocks : kblocks) != WALDO_OK)
+    return WALDO_EINVAL;
+  // the delta pass: a thread per (row, head) of out in blocks of kBlock
+  const int64_t rows = Rq * H;
+  if ((rows + kBlock - 1) / kBlock > INT32_MAX) {
+    set_error("%s: too large: H=%d Rq=%lld (the rows of out stay below 2^31 blocks of %d)", fn, H, (long long)Rq, kBlock);
+    return WALDO_EINVAL;
+  }
+  if (B == 0 || Rq == 0) return WALDO_OK;
+  if (!grad_q && !grad_k && !grad_v) return WALDO_OK;
+  if (ta_check_pointers(fn, vw, 0, out && grad_out && lse && delta && q_off && k_off,
+                        {out, grad_out, lse, delta, grad_q, grad_k, grad_v}) != WALDO_OK)
+    return WALDO_EINVAL;
+  ta_clips_rows_as_batch(vw);
+  TokenAttentionBwdArgs a{};
+  a.v = vw, a.out = out, a.grad_out = grad_out, a.lse = lse, a.delta = delta;
+  a.grad_q = grad_q, a.grad_k1 = grad_k, a.grad_v1 = grad_v;
+  a.rows = rows, a.scale = scale, a.H = H;
+  a.clips = {q_off, k_off, (int)Rq, (int)Rk};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 block(kBlock);
+  ta_for_head_dim(D, [&](auto d) {
+    constexpr int kD = decltype(d)::value;
+    token_attention_delta_kernel<kD, true><<<dim3((unsigned)((rows + kBlock - 1) / kBlock)), block, 0, st>>>(a);
+    if (grad_q && qblocks > 0) {
+      a.blocks = (int)qblocks;
+      token_attention_bwd_dq_kernel<kD, true><<<dim3((unsigned)(B * H * qblocks)), block, 0, st>>>(a);
+    }
+    if ((grad_k || grad_v) && kblocks > 0) {
+      a.blocks = (int)kblocks;
+      token_attention_bwd_dkv_kernel<kD, true><<<dim3((unsigned)(B * H * kblocks)), block, 0, st>>>(a);
     }
   });
   return launch_status(fn);

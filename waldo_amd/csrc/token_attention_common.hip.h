@@ -4,7 +4,8 @@
 // coordinates, the fetch of the next tile into registers, the stage step into LDS, and one step of each of the two
 // products on v_mfma_f32_16x16x4_f32.  The helpers are force-inlined templates on D that take the register arrays by
 // reference and index them with compile-time constants only; a kernel is the sequence of these calls plus what is
-// its own (the online softmax, the dS formula, the stores).
+// its own (the online softmax, the dS formula, the stores).  The per-clip entry points (waldo_token_attention_clips_*)
+// are the same kernels instantiated with CLIPS: what differs is where a workgroup finds its rows (TaClips, ta_segment).
 #pragma once
 #include <initializer_list>
 #include <type_traits>
@@ -30,19 +31,23 @@ struct TaViews {
   TaView q, k1, v1, k2, v2;
 };
 
+// The per-clip form (waldo_token_attention_clips_*): the operands are PACKED rows, (R, H, D) with no batch axis, and
+// clip b's rows are [off[b], off[b + 1]) of a B + 1 entry table in device memory.  The kernels are the dense ones with
+// another first step: where a dense workgroup takes its sequence from b and the lengths from the arguments, a clips
+// workgroup reads its two table entries, clamped into [0, R] (ta_segment), and the host hands every view over with its
+// token stride in the batch stride's place -- so "batch element" i of a view is its row i, and the views are moved to
+// a clip's first row by the expression that moves them to a sequence.
+struct TaClips {
+  const int *q_off, *k_off;
+  int Rq, Rk;  // the rows of q and of k / v: no table entry addresses a row past them
+};
+
 // ---------------------------------------------------------------- host
 
 inline bool ta_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// The refusals every entry point of the section shares, in the forward's order and words, up to the strides; `blocks`
-// is the larger of the row blocks per (b, h) that the entry point's launches make.  WALDO_OK: go on.
-inline int ta_check_shape(const char* fn, const TaViews& v, float scale, int64_t B, int H, int D, int Nq, int Nk1,
-                          int Nk2, int64_t blocks) {
-  if (B < 0 || H < 1 || Nq < 0 || Nk1 < 1 || Nk2 < 0) {
-    set_error("%s: bad shape B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (B, Nq, Nk2 >= 0; H, Nk1 >= 1)", fn, (long long)B, H, Nq,
-              Nk1, Nk2);
-    return WALDO_EINVAL;
-  }
+// The head dimension's and the scale's refusals, and the strides' (n of them: batch, token, batch, token, ...).
+inline int ta_check_head_scale(const char* fn, int D, float scale) {
   if (D != 16 && D != 32 && D != 64) {
     set_error("%s: bad head dimension D=%d (16, 32 or 64)", fn, D);
     return WALDO_EINVAL;
@@ -51,13 +56,10 @@ inline int ta_check_shape(const char* fn, const TaViews& v, float scale, int64_t
     set_error("%s: bad scale %g (finite)", fn, (double)scale);
     return WALDO_EINVAL;
   }
-  if ((int64_t)Nk1 + Nk2 > INT32_MAX - kTaK || B * H > INT32_MAX || B * H * blocks > INT32_MAX) {
-    set_error("%s: too large: B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (Nk1 + Nk2 and the %d-row query blocks of all (b, h) stay "
-              "below 2^31)", fn, (long long)B, H, Nq, Nk1, Nk2, kTaQ);
-    return WALDO_EINVAL;
-  }
-  const int64_t strides[10] = {v.q.sb, v.q.sn, v.k1.sb, v.k1.sn, v.v1.sb, v.v1.sn, v.k2.sb, v.k2.sn, v.v2.sb, v.v2.sn};
-  const int nstr = Nk2 > 0 ? 10 : 6;
+  return WALDO_OK;
+}
+
+inline int ta_check_strides(const char* fn, const int64_t* strides, int nstr) {
   for (int i = 0; i < nstr; ++i)
     if (strides[i] < 0) {
       set_error("%s: negative stride", fn);
@@ -78,6 +80,58 @@ inline int ta_check_shape(const char* fn, const TaViews& v, float scale, int64_t
     }
   return WALDO_OK;
 }
+
+// The refusals every entry point of the section shares, in the forward's order and words, up to the strides; `blocks`
+// is the larger of the row blocks per (b, h) that the entry point's launches make.  WALDO_OK: go on.
+inline int ta_check_shape(const char* fn, const TaViews& v, float scale, int64_t B, int H, int D, int Nq, int Nk1,
+                          int Nk2, int64_t blocks) {
+  if (B < 0 || H < 1 || Nq < 0 || Nk1 < 1 || Nk2 < 0) {
+    set_error("%s: bad shape B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (B, Nq, Nk2 >= 0; H, Nk1 >= 1)", fn, (long long)B, H, Nq,
+              Nk1, Nk2);
+    return WALDO_EINVAL;
+  }
+  if (ta_check_head_scale(fn, D, scale) != WALDO_OK) return WALDO_EINVAL;
+  if ((int64_t)Nk1 + Nk2 > INT32_MAX - kTaK || B * H > INT32_MAX || B * H * blocks > INT32_MAX) {
+    set_error("%s: too large: B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (Nk1 + Nk2 and the %d-row query blocks of all (b, h) stay "
+              "below 2^31)", fn, (long long)B, H, Nq, Nk1, Nk2, kTaQ);
+    return WALDO_EINVAL;
+  }
+  const int64_t strides[10] = {v.q.sb, v.q.sn, v.k1.sb, v.k1.sn, v.v1.sb, v.v1.sn, v.k2.sb, v.k2.sn, v.v2.sb, v.v2.sn};
+  return ta_check_strides(fn, strides, Nk2 > 0 ? 10 : 6);
+}
+
+// The same for the per-clip entry points, whose views come with a token stride alone (batch stride 0 here; see
+// ta_clips_views): `blocks` is the larger of the row blocks per (clip, h) that the launches make, from the caller's
+// bounds max_q_len / max_k_len on a clip's rows.
+inline int ta_clips_check_shape(const char* fn, const TaViews& v, float scale, int64_t B, int H, int D, int64_t Rq,
+                                int64_t Rk, int max_q_len, int max_k_len, int64_t blocks) {
+  if (B < 0 || H < 1 || Rq < 0 || Rk < 0) {
+    set_error("%s: bad shape B=%lld H=%d Rq=%lld Rk=%lld (B, Rq, Rk >= 0; H >= 1)", fn, (long long)B, H, (long long)Rq,
+              (long long)Rk);
+    return WALDO_EINVAL;
+  }
+  if (max_q_len < 0 || max_k_len < 0) {
+    set_error("%s: bad clip bound max_q_len=%d max_k_len=%d (>= 0: no clip has more rows)", fn, max_q_len, max_k_len);
+    return WALDO_EINVAL;
+  }
+  if (ta_check_head_scale(fn, D, scale) != WALDO_OK) return WALDO_EINVAL;
+  if (Rq > INT32_MAX - kTaQ || Rk > INT32_MAX - kTaK || max_q_len > INT32_MAX - kTaQ || max_k_len > INT32_MAX - kTaK ||
+      B * H > INT32_MAX || B * H * blocks > INT32_MAX) {
+    set_error("%s: too large: B=%lld H=%d Rq=%lld Rk=%lld max_q_len=%d max_k_len=%d (the rows and the %d-row blocks of "
+              "all (clip, h) stay below 2^31)", fn, (long long)B, H, (long long)Rq, (long long)Rk, max_q_len, max_k_len,
+              kTaQ);
+    return WALDO_EINVAL;
+  }
+  const int64_t strides[6] = {v.q.sb, v.q.sn, v.k1.sb, v.k1.sn, v.v1.sb, v.v1.sn};
+  return ta_check_strides(fn, strides, 6);
+}
+
+// The three packed views of a per-clip entry point, for the checks: no second segment, batch stride 0.
+inline TaViews ta_clips_views(const float* q, int64_t qs_n, const float* k, int64_t ks_n, const float* v, int64_t vs_n) {
+  return {{q, 0, qs_n}, {k, 0, ks_n}, {v, 0, vs_n}, {nullptr, 0, 0}, {nullptr, 0, 0}};
+}
+// ... and for the kernels, after the checks: a view's row index in the batch index's place (TaClips).
+inline void ta_clips_rows_as_batch(TaViews& v) { v.q.sb = v.q.sn, v.k1.sb = v.k1.sn, v.v1.sb = v.v1.sn; }
 
 // The pointer refusals, after the shape's: drops the second segment's views where Nk2 == 0, then refuses a null view
 // (or `rest_present` false: one of the entry point's other required pointers is null) and a view or a pointer of `rest`
@@ -150,9 +204,21 @@ __device__ __forceinline__ TaCoord ta_coord(int blocks, int H) {
 __device__ __forceinline__ TaView ta_view_at(const TaView& v, int64_t b, int hd) {
   return {v.p ? v.p + b * v.sb + hd : nullptr, v.sb, v.sn};
 }
-__device__ __forceinline__ TaViews ta_views_at(const TaViews& v, int64_t b, int hd) {
-  return {ta_view_at(v.q, b, hd), ta_view_at(v.k1, b, hd), ta_view_at(v.v1, b, hd), ta_view_at(v.k2, b, hd),
-          ta_view_at(v.v2, b, hd)};
+// (qb for the queries' view and kb for the keys' and values': the sequence b of both, or a clip's two first rows)
+__device__ __forceinline__ TaViews ta_views_at(const TaViews& v, int64_t qb, int64_t kb, int hd) {
+  return {ta_view_at(v.q, qb, hd), ta_view_at(v.k1, kb, hd), ta_view_at(v.v1, kb, hd), ta_view_at(v.k2, kb, hd),
+          ta_view_at(v.v2, kb, hd)};
+}
+
+// Clip b's rows of a packed operand of R rows: [first, first + len), whatever the table holds -- both entries are
+// clamped into [0, R] and an end before its start is an empty clip, so first + len <= R and no row past the operand is
+// ever addressed.  A kernel reads a row of a segment only where len >= 1.
+struct TaSegment {
+  int first, len;
+};
+__device__ __forceinline__ TaSegment ta_segment(const int* off, int64_t b, int R) {
+  const int lo = min(max(off[b], 0), R), hi = min(max(off[b + 1], 0), R);
+  return {lo, max(hi - lo, 0)};
 }
 
 // 16 bytes through a clamped row: the load is unconditional, a dead row gives zeros (its scores are masked, and 0 * x

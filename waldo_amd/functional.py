@@ -2309,3 +2309,153 @@ def token_attention(q, k, v, k2=None, v2=None, scale=None):
                                                                   for t in (q, k, v, k2, v2))):
         route = "framework"
     return _TokenAttention.apply(scale, strides, route, q, k, v, k2, v2)
+
+
+# --------------------------------------------------------------------------------------
+# token attention over clips: per-clip segments of packed rows (the future layer predictor's blocks under ctx_mask)
+# --------------------------------------------------------------------------------------
+def clip_offsets(ctx_mask, tokens_per_frame):
+    """The offset table of a boolean (B, T) frame mask whose selected frames carry ``tokens_per_frame`` packed rows each:
+    int32 (B + 1,), clip b's rows are ``[off[b], off[b + 1])``.  A ``cumsum`` on the mask's device; no host read."""
+    if ctx_mask.dim() != 2:
+        raise ValueError(f"clip_offsets: ctx_mask must be (B, T), got {tuple(ctx_mask.shape)}")
+    off = torch.zeros(ctx_mask.shape[0] + 1, dtype=torch.int32, device=ctx_mask.device)
+    off[1:] = torch.cumsum(ctx_mask.sum(dim=1, dtype=torch.int32) * int(tokens_per_frame), dim=0)
+    return off
+
+
+def _token_attention_clips_check(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len):
+    if q.dim() != 3:
+        raise ValueError(f"token_attention_clips: q must be (Rq, H, D), got {tuple(q.shape)}")
+    _, h, d = q.shape
+    if k.dim() != 3 or tuple(k.shape[1:]) != (h, d) or v.shape != k.shape:
+        raise ValueError(f"token_attention_clips: k and v must be (Rk, {h}, {d}), got {tuple(k.shape)}, "
+                         f"{tuple(v.shape)}")
+    for name, off in (("q_offsets", q_offsets), ("k_offsets", k_offsets)):
+        if off.dim() != 1 or off.numel() < 1 or off.dtype != torch.int32 or off.device != q.device:
+            raise ValueError(f"token_attention_clips: {name} must be int32 (B + 1,) on {q.device}, got {off.dtype} "
+                             f"{tuple(off.shape)} on {off.device}")
+    if q_offsets.shape != k_offsets.shape:
+        raise ValueError(f"token_attention_clips: q_offsets and k_offsets must have B + 1 entries each, got "
+                         f"{tuple(q_offsets.shape)}, {tuple(k_offsets.shape)}")
+    if int(max_q_len) < 0 or int(max_k_len) < 0:
+        raise ValueError(f"token_attention_clips: max_q_len and max_k_len must be >= 0, got {max_q_len}, {max_k_len}")
+
+
+def _clip_of_rows(offsets, rows):
+    """The clip of each of ``rows`` packed rows: the number of clip ends at or before the row (no host read)."""
+    return torch.bucketize(torch.arange(rows, device=offsets.device, dtype=torch.int32), offsets[1:], right=True)
+
+
+def token_attention_clips_framework(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, scale=None):
+    """``token_attention_clips`` in framework ops: the scores of all Rq x Rk rows under a block mask (the clip of the
+    query is not the clip of the key -> -inf), softmax, the values.  The clip of a row comes from ``bucketize`` on the
+    offsets, so nothing is read on the host.  A query row whose clip has no key is a softmax over -inf alone: NaN, as
+    in the reference.  The CPU route of ``token_attention_clips``, the ``fused = False`` route of the future layer
+    predictor's blocks, the fallback for operands the kernel does not serve and what its ``"framework"`` backward
+    route differentiates.  ``max_q_len`` / ``max_k_len`` only size the kernel's grid and are not used here."""
+    _token_attention_clips_check(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len)
+    rq, h, d = q.shape
+    scale = d ** -0.5 if scale is None else scale
+    attn = (q.permute(1, 0, 2) @ k.permute(1, 2, 0)) * scale
+    other = _clip_of_rows(q_offsets, rq)[:, None] != _clip_of_rows(k_offsets, k.shape[0])[None, :]
+    attn = attn.masked_fill(other, float("-inf")).softmax(dim=-1)
+    return (attn @ v.permute(1, 0, 2)).transpose(0, 1).reshape(rq, h * d)
+
+
+def _packed_view_stride(t):
+    """The token stride of a (R, H, D) view whose (row, head) rows are D consecutive floats D apart and start on 16-byte
+    boundaries -- what ``waldo_token_attention_clips_fwd`` reads in place -- else None."""
+    r, h, d = t.shape
+    if (d > 1 and t.stride(2) != 1) or (h > 1 and t.stride(1) != d) or t.data_ptr() % 16:
+        return None
+    sn = t.stride(0) if r > 1 else 0
+    return None if sn % 4 or sn < 0 else sn
+
+
+def _token_attention_clips_served(q, k, v, q_offsets, k_offsets):
+    """The token strides of the operands if the kernel serves them as they lie, else None."""
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.device == q.device for t in (q, k, v)):
+        return None
+    if q.shape[2] not in token_attention_limits()["head_dims"] or q.numel() == 0 or k.numel() == 0:
+        return None
+    if not (q_offsets.is_contiguous() and k_offsets.is_contiguous()) or torch.is_autocast_enabled("cuda"):
+        return None
+    strides = [_packed_view_stride(t) for t in (q, k, v)]
+    return None if any(s is None for s in strides) else strides
+
+
+class _TokenAttentionClips(torch.autograd.Function):
+    """``_TokenAttention`` for per-clip segments: the kernel on the packed views as they lie; the backward by the route
+    read in the forward -- ``"kernel"``: ``waldo_token_attention_clips_bwd`` from the saved ``out`` and ``lse``;
+    ``"framework"``: ``token_attention_clips_framework`` recomputed from the saved views and differentiated."""
+
+    @staticmethod
+    def forward(ctx, scale, strides, route, bounds, q, k, v, q_offsets, k_offsets):
+        rq, h, d = q.shape
+        out = torch.empty(rq, h * d, dtype=torch.float32, device=q.device)
+        flat = [q, strides[0], k, strides[1], v, strides[2], q_offsets, k_offsets]
+        shape = (q_offsets.numel() - 1, h, d, rq, k.shape[0], int(bounds[0]), int(bounds[1]))
+        ctx.route, ctx.scale, ctx.strides, ctx.shape = route, scale, strides, shape
+        if route == "kernel":
+            lse = torch.empty(h, rq, dtype=torch.float32, device=q.device)
+            _lib.launch("waldo_token_attention_clips_fwd_lse", q.device, *flat, out, lse, float(scale), *shape)
+            ctx.save_for_backward(q, k, v, q_offsets, k_offsets, out, lse)
+        else:
+            _lib.launch("waldo_token_attention_clips_fwd", q.device, *flat, out, float(scale), *shape)
+            ctx.save_for_backward(q, k, v, q_offsets, k_offsets)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        need = ctx.needs_input_grad[4:7]
+        if ctx.route == "kernel":
+            q, k, v, q_offsets, k_offsets, out, lse = ctx.saved_tensors
+            # (empty: the kernel overwrites every row that belongs to a clip, and the tables of a plan cover all rows)
+            grads = [torch.empty(t.shape, dtype=torch.float32, device=out.device) if n else None
+                     for t, n in zip((q, k, v), need)]
+            delta = torch.empty_like(lse)
+            if not grad_out.is_contiguous() or grad_out.data_ptr() % 16:  # (see _TokenAttention.backward)
+                grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+            s = ctx.strides
+            _lib.launch("waldo_token_attention_clips_bwd", out.device, q, s[0], k, s[1], v, s[2], q_offsets, k_offsets,
+                        out, grad_out, lse, delta, *grads, float(ctx.scale), *ctx.shape)
+            return (None, None, None, None, *grads, None, None)
+        q, k, v, q_offsets, k_offsets = ctx.saved_tensors
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_(n) for t, n in zip((q, k, v), need)]
+            out = token_attention_clips_framework(*leaves, q_offsets, k_offsets, ctx.shape[5], ctx.shape[6],
+                                                  scale=ctx.scale)
+            wanted = [t for t, n in zip(leaves, need) if n]
+            grads = iter(torch.autograd.grad(out, wanted, grad_out)) if wanted else iter(())
+        return (None, None, None, None, *[next(grads) if n else None for n in need], None, None)
+
+
+def token_attention_clips(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, scale=None):
+    """``softmax(scale q k^T) v`` per head within each clip of PACKED rows: q (Rq, H, D) and k / v (Rk, H, D) hold the
+    rows of all clips one after the other, clip b's queries are the rows ``[q_offsets[b], q_offsets[b + 1])`` and its
+    keys the rows ``[k_offsets[b], k_offsets[b + 1])`` -> (Rq, H D).  The offsets are int32 (B + 1,) tensors on the
+    operands' device (``clip_offsets``) and must cover the rows: a row that belongs to no clip is not written.
+    ``max_q_len`` / ``max_k_len`` are host integers no clip's length exceeds (the kernel's grid; a clip longer than its
+    bound is served up to the bound only).  ``scale``: ``D ** -0.5`` when None.  The operands are VIEWS and are not
+    copied: the slices of a packed ``qkv`` / ``kv`` projection as they lie (``qkv.view(R, 3, H, D)[:, i]``).
+
+    This is the reference's attention under ``ctx_mask`` (models/modules/transform.py: ``from_ctx``, a dense -inf mask
+    over all T N keys, ``to_ctx``) without the dense tensors and without their host reads: nothing here reads the
+    offsets on the host, so a call can be captured in a graph.  A clip with queries and no keys gives NaN in its rows.
+
+    fp32 tensors on the GPU that ``waldo_token_attention_clips_fwd`` serves (as ``token_attention``: D in
+    ``token_attention_limits()["head_dims"]``, unit inner stride, heads D apart, rows on 16-byte boundaries, Rk > 0)
+    run the kernel, with the backward set by ``token_attention_backward_route``; everything else IS
+    ``token_attention_clips_framework``."""
+    _token_attention_clips_check(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len)
+    scale = q.shape[2] ** -0.5 if scale is None else float(scale)
+    strides = _token_attention_clips_served(q, k, v, q_offsets, k_offsets)
+    if strides is None:
+        return token_attention_clips_framework(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, scale)
+    route = _token_attention_backward_route
+    if route == "kernel" and not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))):
+        route = "framework"
+    return _TokenAttentionClips.apply(scale, strides, route, (int(max_q_len), int(max_k_len)), q, k, v, q_offsets,
+                                      k_offsets)

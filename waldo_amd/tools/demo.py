@@ -447,7 +447,7 @@ def predict(opt, warper, wif, real_vid, real_lyt, net, ctx_len, raw_dtype=None, 
     if not opt.no_future:
         # the pose generator (net_pg, outside the path) returns full-length pose sequences: the context
         # poses as they came in, the future ones predicted (flp.py:275-290) -- here the synthetic poses
-        # of all T frames stand for them (synthesizer.py:464-472)
+        # of all T frames stand for them (synthesizer.py:464-472); with the networks: ``predict_future``
         if alpha and alpha[0] is not None:  # (with opt.use_inpainter: what the prediction hands to net_ii.inpaint, synthesizer.py:484)
             out["pred_alpha"] = alpha[0]
         out["pred_disocc"] = dis
@@ -783,6 +783,28 @@ def load_lvd_checkpoint(lvd, path):
     return lvd
 
 
+def load_flp_checkpoint(flp, path):
+    """Load a reference ``pg`` state dict (the file, or a tensor-only dict in it under "state_dict") into ``flp``
+    (``nets.FLP`` built from the checkpoint's options), strictly; a ``module.`` prefix is stripped."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if isinstance(state, dict) and "state_dict" in state:
+        state = state["state_dict"]
+    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    flp.load_state_dict(state, strict=True)
+    return flp
+
+
+def flp_demo_opt(nopt, **over):
+    """``nets.flp_net_opt`` next to LVD networks built from ``nopt``: the fields the two share (token rasters, width,
+    heads, objects, the pose heads' constants) taken from ``nopt``, FLP's own (depths, ``pg_num_timesteps``, ``cat_z``,
+    ...: the checkpoint's training options) from ``over``."""
+    from ..nets.flp import flp_net_opt
+    known = vars(flp_net_opt())
+    d = {k: v for k, v in vars(nopt).items() if k in known}
+    d.update(over)
+    return flp_net_opt(**d)
+
+
 def lvd_demo_opt(opt, **over):
     """``nets.lvd_net_opt`` for the demo's ``opt``: the fields the two share taken from ``opt``, the networks' own
     (widths, depths, input modalities: the checkpoint's training options) from ``over``."""
@@ -835,11 +857,52 @@ def reconstruct(opt, lvd, wif, real_vid, real_lyt, real_flow, ctx_len):
                     obj_pose=obj_pose, bg_pose=bg_pose, occ=occ, obj_alpha=obj_alpha)
 
 
+def predict_future(opt, lvd, flp, wif, real_vid, real_lyt, real_flow, ctx_len):
+    """The prediction half of the reference's ``Synthesizer.predict`` (models/synthesizer.py:462-480) with the poses of
+    the frames after the first ``ctx_len`` coming from FLP: the decomposition of ``reconstruct``, FLP on the poses of
+    the whole clip under the mask "the first ``ctx_len`` frames" -- an integer-built plan, so nothing of it reads the
+    host --, alphas / grids / occlusion for the predicted poses, the future frames decoded from the context frames and
+    fused.  Arguments as ``reconstruct``; ``flp``: ``nets.FLP`` of the same widths and rasters as ``lvd``.  Returns
+    ``pred_vid`` (B, T, 3, H, W: the context frames as they are, then the predicted ones), ``fused_pred_vid``
+    (B, T - ctx_len, 3, H, W: ``wif`` on the raw output; the reference's border inpainting is ``WIF.inpaint``),
+    ``pred_disocc`` and the poses FLP returned (``obj_pose``, ``bg_pose``, ``occ_score``: all T frames)."""
+    with torch.no_grad():
+        parts = [real_vid] if opt.input_rgb else []
+        parts += [real_lyt] if opt.input_lyt else []
+        if opt.input_flow:
+            if real_flow is None:
+                raise ValueError("predict_future: the networks take the flow as input (opt.input_flow) and real_flow is "
+                                 "None")
+            parts.append(real_flow)
+        x = lvd(input=torch.cat(parts, dim=2), mode="encode_input")
+        b, t = x.shape[:2]
+        if not 0 < ctx_len < t:
+            raise ValueError(f"predict_future: 0 < ctx_len < {t} frames, got {ctx_len}")
+        x_obj, x_bg, cls = lvd(x=x[:, :ctx_len], mode="estimate_layer")
+        obj_pose, bg_pose, occ_score, _, _, last_obj, last_bg = lvd(x=x, x_obj=x_obj, x_bg=x_bg, mode="estimate_pose")
+        obj_pose, bg_pose, occ_score = flp(obj_pose, bg_pose, occ_score, x_obj, x_bg, last_obj, last_bg,
+                                           ctx_mask=flp.plan(b, t, ctx_len, x.device))
+        occ, obj_alpha, bg_alpha, grid = lvd(x_obj=x_obj, obj_pose=obj_pose, bg_pose=bg_pose, occ_score=occ_score,
+                                             mode="estimate_alpha_grid_occ")
+        pred_ts = torch.arange(ctx_len, t, device=x.device, dtype=torch.int64)
+        ctx_ts = torch.arange(ctx_len, device=x.device, dtype=torch.int64).view(1, -1, 1).expand(b, -1, t - ctx_len)
+        out = lvd(input=torch.cat([real_vid, real_lyt], dim=2), grid=grid, occ=occ, obj_alpha=obj_alpha, bg_alpha=bg_alpha,
+                  ctx_ts=ctx_ts.contiguous(), pred_ts=pred_ts, cls=cls, mode="decode_output")
+        pred_output, raw_output, alpha_ctx = out[0], out[5], out[6]
+        disocc = WF.disocc_test(alpha_ctx.amax(dim=3))  # synthesizer.py:474-477
+        return dict(pred_vid=torch.cat([real_vid[:, :ctx_len], pred_output[:, :, :3]], dim=1),
+                    fused_pred_vid=wif(raw_output), pred_disocc=disocc.unsqueeze(2), obj_pose=obj_pose, bg_pose=bg_pose,
+                    occ_score=occ_score)
+
+
 def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4,
-            device="cuda:0", lvd_over=None, wif_ckpt=None, ii_depth=4, ii_embed_dim=512):
+            device="cuda:0", lvd_over=None, wif_ckpt=None, ii_depth=4, ii_embed_dim=512, flp_ckpt=None, flp_over=None):
     """``--lvd-ckpt``: the clip through ``reconstruct`` with a reference ``pe`` checkpoint; ``rec_vid`` and
     ``inp_rec_vid`` written by the writers ``run`` uses.  ``lvd_over``: the checkpoint's training options where they
-    differ from ``lvd_demo_opt(demo_opt(...))`` (``--lvd-opt FILE``: a JSON object)."""
+    differ from ``lvd_demo_opt(demo_opt(...))`` (``--lvd-opt FILE``: a JSON object).  ``flp_ckpt`` (``--flp-ckpt``): a
+    reference ``pg`` checkpoint too -- the frames after ``ctx_len`` through ``predict_future`` as well (``pred_vid``,
+    ``fused_pred_vid``); ``flp_over``: its training options where they differ from ``flp_demo_opt`` (``--flp-opt``)."""
+    from ..nets.flp import FLP
     from ..nets.lvd import LVD
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt, ctx_len=ctx_len, ii_depth=ii_depth, ii_embed_dim=ii_embed_dim)
     nopt = lvd_demo_opt(opt, **(lvd_over or {}))
@@ -857,9 +920,15 @@ def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj
     else:
         wif = WIF(opt, unet=UniformFusionUNet()).to(dev)
     res = reconstruct(nopt, lvd, wif, vid, lyt, flow, ctx_len)
+    keys = ("rec_vid", "inp_rec_vid")
+    if flp_ckpt is not None:
+        flp = load_flp_checkpoint(FLP(flp_demo_opt(nopt, **(flp_over or {}))), flp_ckpt).to(dev).eval()
+        future = predict_future(nopt, lvd, flp, wif, vid, lyt, flow, ctx_len)
+        res.update(pred_vid=future["pred_vid"], fused_pred_vid=future["fused_pred_vid"])
+        keys += ("pred_vid", "fused_pred_vid")
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
-        for key in ("rec_vid", "inp_rec_vid"):
+        for key in keys:
             wio.dump_video(res[key][0], os.path.join(out_dir, key + ".gif"))
             wio.dump_image(res[key][0, -1], os.path.join(out_dir, key + "_last.png"))
     return res
@@ -935,16 +1004,25 @@ def main():
     ap.add_argument("--lvd-opt", default=None, metavar="FILE",
                     help="with --lvd-ckpt: a JSON object of the checkpoint's training options (embed_dim, num_heads, "
                          "oe_depth, pe_depth, input_lyt, ...) where they differ from the defaults")
+    ap.add_argument("--flp-ckpt", default=None, metavar="FILE",
+                    help="with --lvd-ckpt: a reference `pg` checkpoint (state dict): predict the frames after --ctx-len "
+                         "with the FLP networks and write them too (pred_vid, fused_pred_vid)")
+    ap.add_argument("--flp-opt", default=None, metavar="FILE",
+                    help="with --flp-ckpt: a JSON object of the checkpoint's training options (pg_enc_depth, "
+                         "pg_num_timesteps, cat_z, ...) where they differ from the defaults")
     args = ap.parse_args()
+    if args.flp_ckpt is not None and args.lvd_ckpt is None:
+        ap.error("--flp-ckpt needs --lvd-ckpt: FLP predicts the poses the LVD networks estimate")
     if args.lvd_ckpt is not None:
-        over = None
-        if args.lvd_opt is not None:
-            import json
-            with open(args.lvd_opt) as fh:
-                over = json.load(fh)
+        import json
+        over = {}
+        for name in ("lvd_opt", "flp_opt"):
+            if getattr(args, name) is not None:
+                with open(getattr(args, name)) as fh:
+                    over[name] = json.load(fh)
         res = run_lvd(args.clip, args.lvd_ckpt, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
-                      ctx_len=args.ctx_len, lvd_over=over, wif_ckpt=args.wif_ckpt, ii_depth=args.ii_depth,
-                      ii_embed_dim=args.ii_embed_dim)
+                      ctx_len=args.ctx_len, lvd_over=over.get("lvd_opt"), wif_ckpt=args.wif_ckpt, ii_depth=args.ii_depth,
+                      ii_embed_dim=args.ii_embed_dim, flp_ckpt=args.flp_ckpt, flp_over=over.get("flp_opt"))
         for k, v in res.items():
             if v is not None:
                 print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "
