@@ -1161,6 +1161,46 @@ int waldo_token_attention_clips_bwd(const float* q, int64_t qs_n, const float* k
                                     float* grad_v, float scale, int64_t B, int H, int D, int64_t Rq, int64_t Rk,
                                     int max_q_len, int max_k_len, waldo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Pose objective: the three L1 terms of the future layer predictor's training step (models/synthesizer.py:752-754),
+ *   (to_ctx(real, ~ctx_mask) - to_ctx(pred, ~ctx_mask)).abs().mean()   for obj_pose, bg_pose and occ_score,
+ * as what the mask says: the mean of |real - pred| over the frames the mask does NOT select, without the gathers and
+ * without their host reads.  Term k = 0, 1, 2 (obj, bg, occ) has a pair of dense fp32 tensors (F, E_k), F = B T frames
+ * of E_k elements, addressed FLAT: no row alignment is assumed (E_occ = No can be 3, 5, 17) and only 4-byte alignment of
+ * the pointers.  ctx_mask is F bytes in device memory; frame f is KEPT when ctx_mask[f] == 0.
+ *
+ * waldo_pose_l1_fwd: terms[k] = (sum over the kept frames f and e < E_k of |real_k[f, e] - pred_k[f, e]|)
+ *                               / (kept * E_k),   kept = the number of kept frames, counted on the device;
+ *   kept_out[0] = kept as a float (for the backward).  No kept frame: the three terms are NaN (0 / 0: the reference's
+ *   mean of an empty selection).  The values of the other frames are never part of a sum (a NaN there changes nothing).
+ *   Two launches: a partial per workgroup of 2048 elements into the workspace (the three terms in the same launch), then
+ *   one workgroup that counts the mask and adds each term's partials in a fixed order.  NO ATOMICS: the same bits from
+ *   run to run and in a graph replay.  workspace: waldo_pose_l1_workspace_bytes(F, E_obj, E_bg, E_occ) (0: bad sizes).
+ *
+ * waldo_pose_l1_bwd: ONE launch.  On a kept frame
+ *     grad_pred_k[f, e] = sgn(pred_k - real_k) * (grad_terms[k] / (kept * E_k)),   sgn(0) = 0 (exact zero);
+ *   on every other frame EXACT 0, whatever kept is (no kept frame: all-zero gradients, not NaN ones).  grad_terms[k] is
+ *   grad_obj, grad_bg, grad_occ: one float each in device memory, NULL = that term carries no gradient (zeros are
+ *   written).  grad_real_k = -grad_pred_k, written only where the pointer is not NULL (each of the three
+ *   on its own: NULL = not wanted).  Every element of every gradient tensor passed is written; nothing needs a fill.
+ *
+ * Both: caller-owned buffers, the caller's stream, no allocation, no synchronisation, no memset node; capturable in a
+ * graph.  WALDO_EINVAL with a message before any launch: "null pointer" (a pair, ctx_mask, terms, kept_out / kept,
+ * a grad_pred, the workspace), "bad shape" (F <= 0 or an E_k <= 0), "too large" (F > 2^24 or F E_k > 2^31 - 1),
+ * "workspace" (smaller than the query's answer).
+ * ------------------------------------------------------------------------------------- */
+int64_t waldo_pose_l1_workspace_bytes(int64_t F, int64_t E_obj, int64_t E_bg, int64_t E_occ);
+int waldo_pose_l1_fwd(const float* real_obj, const float* pred_obj, const float* real_bg, const float* pred_bg,
+                      const float* real_occ, const float* pred_occ, const uint8_t* ctx_mask, float* terms,
+                      float* kept_out, void* workspace, int64_t workspace_bytes, int64_t F, int64_t E_obj, int64_t E_bg,
+                      int64_t E_occ, waldo_stream_t stream);
+int waldo_pose_l1_bwd(const float* real_obj, const float* pred_obj, const float* real_bg, const float* pred_bg,
+                      const float* real_occ, const float* pred_occ, const uint8_t* ctx_mask, const float* kept,
+                      const float* grad_obj, const float* grad_bg, const float* grad_occ, float* grad_pred_obj,
+                      float* grad_pred_bg, float* grad_pred_occ, float* grad_real_obj, float* grad_real_bg,
+                      float* grad_real_occ, int64_t F, int64_t E_obj, int64_t E_bg, int64_t E_occ,
+                      waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,9 @@ SIGNATURES = {
     "waldo_mov_finish_fwd": [_c_f] * 7 + [_flt] * 4 + [_int] + [_c_f] * 4 + [_i64, _i64, _stream],
     "waldo_cell_distance_fwd": [_c_f] * 8 + [_i64, _i64, _int, _int, _int, _flt, _flt, _stream],
     "waldo_cell_distance_bwd": [_c_f] * 10 + [_i64, _i64, _int, _int, _int, _flt, _flt, _stream],
+    # pose objective (include/waldo_hip.h "Pose objective"): the three (real, pred) pairs, the mask, ...
+    "waldo_pose_l1_fwd": [_c_f] * 10 + [_i64] * 5 + [_stream],
+    "waldo_pose_l1_bwd": [_c_f] * 17 + [_i64] * 4 + [_stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],
@@ -169,6 +172,7 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_lyt_dist_workspace_bytes": (_i64, [_i64, _int, _int, _int, _int, _int]),
          "waldo_border_objects_workspace_bytes": (_i64, [_i64]),
          "waldo_cell_distance_workspace_bytes": (_i64, [_i64, _int, _i64]),
+         "waldo_pose_l1_workspace_bytes": (_i64, [_i64] * 4),
          "waldo_frame_metrics_partial_bytes": (_i64, [_int] * 5),
          "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
          "waldo_plane_norm_workspace_bytes": (_i64, [_i64, _int, _int, _int]),

@@ -11,7 +11,12 @@ models/modules/edge.py), the control-point distance terms (synthesizer.py:965-97
     terms = recipe_terms(alpha_flt, rec_flow, real_flow, real_lyt, obj_pose, (4, 4), tgt)
 
 fp32, contiguous NCHW.  The target carries no gradient; ``cell_distance`` sums without float atomics, so its value and
-gradients are the same bits from run to run in either mode of ``set_deterministic``.  No CPU fallback."""
+gradients are the same bits from run to run in either mode of ``set_deterministic``.  No CPU fallback.
+
+Below them the objective of the future layer predictor's step (synthesizer.py:752-754), the one entry here that also
+serves CPU tensors and other dtypes, in framework ops:
+
+    terms = pose_terms((real_obj_pose, real_bg_pose, real_occ_score), (pred_obj_pose, pred_bg_pose, pred_occ_score), ctx_mask)"""
 from typing import NamedTuple
 
 import torch
@@ -272,3 +277,107 @@ def recipe_terms(alpha_flt, rec_flow, real_flow, real_lyt, obj_pose, obj_shape, 
     lyt_edge_mask = (gaussian_blur(real_lyt / 10 + 1 / 2, 2.0, 3).amax(dim=2, keepdim=True) > 0.999).float()
     return {"cell_dis": cell_dis, "reg_mov": reg_mov, "ent_flt_edge": (ent * lyt_edge_mask).mean(),
             "l1_flow": (real_flow[:, 1:] - rec_flow).abs().mean()}
+
+
+# --------------------------------------------------------------------------------------
+# the pose objective of the future layer predictor's step
+# --------------------------------------------------------------------------------------
+POSE_TERMS = ("rec_obj_pose", "rec_bg_pose", "rec_occ_score")  # synthesizer.py:752-754
+
+
+def _pose_mask(fn, ctx_mask, batch, steps, device):
+    """``ctx_mask`` as a contiguous (B, T) tensor of one byte per frame on ``device``, non-zero = context frame.  A plan's
+    bytes are scattered once from its frame indices, on the device and without a host read, and kept on the plan."""
+    from .modules.transform import ClipPlan
+    from .nets.flp import FlpPlan
+    plan = ctx_mask.frames if isinstance(ctx_mask, FlpPlan) else ctx_mask  # (the ClipPlan of the mask itself)
+    if isinstance(plan, ClipPlan):
+        mask = getattr(plan, "_pose_mask", None)
+        if mask is None:
+            mask = torch.zeros(plan.batch * plan.steps, dtype=torch.uint8, device=plan.index.device)
+            mask = plan._pose_mask = mask.index_fill_(0, plan.index, 1).view(plan.batch, plan.steps)
+        what = f"the plan's mask uint8 {tuple(mask.shape)}"
+    else:
+        mask = ctx_mask
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.ndim != 2:
+            raise ValueError(f"{fn}: ctx_mask must be a boolean (B, T) tensor or a plan, got "
+                             f"{getattr(mask, 'dtype', type(mask).__name__)} {tuple(getattr(mask, 'shape', ()))}")
+        what = f"ctx_mask bool {tuple(mask.shape)}"
+    if tuple(mask.shape) != (batch, steps):
+        raise ValueError(f"{fn}: {what} does not cover the poses' ({batch}, {steps}) frames")
+    if mask.device != device:
+        raise ValueError(f"{fn}: {what} is on {mask.device}, the poses are on {device}")
+    return mask.contiguous()
+
+
+class _PoseL1(torch.autograd.Function):
+    """The three masked L1 means in one forward call and one backward launch; ``kept``, the number of kept frames, stays
+    on the device between the two."""
+
+    @staticmethod
+    def forward(ctx, mask, *pairs):
+        pairs = tuple(x.contiguous() for x in pairs)   # (real, pred) x (obj, bg, occ)
+        dev = pairs[0].device
+        f = mask.numel()
+        sizes = tuple(x.numel() // f for x in pairs[::2])
+        out = torch.empty(4, dtype=torch.float32, device=dev)  # the three terms, kept
+        nbytes = _lib.query("waldo_pose_l1_workspace_bytes", f, *sizes)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _lib.launch("waldo_pose_l1_fwd", dev, *pairs, mask, out, out[3:], ws, nbytes, f, *sizes)
+        ctx.save_for_backward(mask, out, *pairs)
+        ctx.sizes = (f, *sizes)
+        ctx.set_materialize_grads(False)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, *grads):
+        mask, out, *pairs = ctx.saved_tensors
+        grads = [None if g is None else g.contiguous() for g in grads]
+        grad_pred = [torch.empty_like(x) for x in pairs[1::2]]
+        grad_real = [torch.empty_like(x) if ctx.needs_input_grad[1 + 2 * k] else None for k, x in enumerate(pairs[::2])]
+        _lib.launch("waldo_pose_l1_bwd", mask.device, *pairs, mask, out[3:], *grads, *grad_pred, *grad_real, *ctx.sizes)
+        return (None, grad_real[0], grad_pred[0], grad_real[1], grad_pred[1], grad_real[2], grad_pred[2])
+
+
+def pose_terms(real, pred, ctx_mask, *, fused=True):
+    """The three terms of the future layer predictor's objective (models/synthesizer.py:752-754),
+    ``(to_ctx(real, ~ctx_mask) - to_ctx(pred, ~ctx_mask)).abs().mean()`` for each of ``(obj_pose, bg_pose, occ_score)``,
+    as a dict of 0-d tensors ``rec_obj_pose``, ``rec_bg_pose``, ``rec_occ_score`` -- the mean of ``|real - pred|`` over
+    the frames ``ctx_mask`` does NOT select, computed without gathers and without reading anything on the host (the
+    reference's ``to_ctx`` reads ``any()`` and the size of a boolean index, six times).  ``real`` and ``pred`` are
+    3-tuples of tensors (B, T, ...) that agree pair by pair; ``ctx_mask`` a boolean (B, T) tensor on their device, or the
+    ``FlpPlan`` / ``ClipPlan`` the network ran under.  With no frame kept the terms are NaN (the reference's mean of an
+    empty selection) and every gradient is exact 0.  CUDA fp32 inputs with ``fused``: one kernel call forward and one
+    backward (include/waldo_hip.h "Pose objective"), no float atomics -- the same bits from run to run, and of a strided
+    input and its contiguous copy; gradients reach ``pred`` and, where it asks, ``real``.  Everything else (CPU, fp64,
+    16-bit, ``fused=False``): the same masked mean in framework ops."""
+    fn = "pose_terms"
+    if len(real) != 3 or len(pred) != 3:
+        raise ValueError(f"{fn}: real and pred must be the 3-tuples (obj_pose, bg_pose, occ_score), got {len(real)} and "
+                         f"{len(pred)} entries")
+    lead, dev, dtype = tuple(real[0].shape[:2]), real[0].device, real[0].dtype
+    for name, r, p in zip(POSE_TERMS, real, pred):
+        if not torch.is_tensor(r) or not torch.is_tensor(p) or r.shape != p.shape or r.dtype != p.dtype:
+            raise ValueError(f"{fn}: the {name} pair disagrees: real {getattr(r, 'dtype', type(r).__name__)} "
+                             f"{tuple(getattr(r, 'shape', ()))}, pred {getattr(p, 'dtype', type(p).__name__)} "
+                             f"{tuple(getattr(p, 'shape', ()))}")
+        if r.ndim < 2 or tuple(r.shape[:2]) != lead or r.dtype != dtype or not r.is_floating_point():
+            raise ValueError(f"{fn}: {name} must be a floating (B, T, ...) = ({lead[0]}, {lead[1]}, ...) {dtype} tensor, "
+                             f"got {r.dtype} {tuple(r.shape)}")
+        if r.device != dev or p.device != dev:
+            raise ValueError(f"{fn}: {name} is on {r.device} / {p.device}, obj_pose is on {dev}")
+        if r.numel() == 0:
+            raise ValueError(f"{fn}: {name} {tuple(r.shape)} is empty")
+    mask = _pose_mask(fn, ctx_mask, *lead, dev)
+    if fused and dev.type == "cuda" and dtype == torch.float32:
+        pairs = [x for pair in zip(real, pred) for x in pair]
+        return dict(zip(POSE_TERMS, _PoseL1.apply(mask, *pairs)))
+    # the masked sum, by selection: a frame that is not kept gets an exact 0 gradient whatever the count is (a product
+    # with the 0 / 1 mask would hand it inf * 0 when no frame is kept)
+    keep = mask == 0
+    kept = keep.sum().to(dtype)
+    terms = {}
+    for name, r, p in zip(POSE_TERMS, real, pred):
+        k = keep.view(*lead, *([1] * (r.ndim - 2)))
+        terms[name] = torch.where(k, (r - p).abs(), 0).sum() / (kept * r[0, 0].numel())
+    return terms
