@@ -1201,6 +1201,49 @@ int waldo_pose_l1_bwd(const float* real_obj, const float* pred_obj, const float*
                       float* grad_real_occ, int64_t F, int64_t E_obj, int64_t E_bg, int64_t E_occ,
                       waldo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * LPIPS level distance: the tail of LPIPS at ONE feature level -- lpips.normalize_tensor of both maps, the squared
+ * difference, the bias-free 1 x 1 "lin" convolution to one channel and spatial_average (eval mode: the dropout in front
+ * of the lin layer is the identity).  f0, f1: dense fp32 (N, C, P), P = H W pixels of unit stride; w: (C,) fp32.
+ * Per image n:
+ *     n0[p] = sqrt(sum_c f0[c, p]^2),  m0 = n0 + eps  (eps is added AFTER the square root);   n1, m1 likewise from f1
+ *     d[p]  = sum_c w[c] * (f0[c, p] / m0[p] - f1[c, p] / m1[p])^2
+ *     out[n] = (1 / P) * sum_p d[p]
+ * evaluated in this form (not as the expanded A / m0^2 - 2 B / (m0 m1) + Cc / m1^2, which cancels where the maps are
+ * close): f1 == f0 gives out == 0 and an all-zero gradient exactly.  Only 4-byte alignment of the pointers and no
+ * alignment of P are assumed (a lane reads a dword per channel).  The image base n C P is 64-bit, offsets inside an
+ * image are 32-bit.
+ * eps is taken as it is: eps == 0 is served (lanes past the end of a ragged tile take no part in any product), and
+ * a pixel that is zero on every channel then gives NaN in out[n], as the chain's 0 / 0 does.
+ *
+ * waldo_lpips_level_fwd: two launches.  A workgroup owns a tile of 64 pixels of one image and stores one partial into the
+ *   workspace; a finishing launch adds each image's partials in a fixed order and divides by P.  NO ATOMICS: the same
+ *   bits from run to run and in a graph replay.  workspace: waldo_lpips_level_workspace_bytes(N, C, P) (0: a bad
+ *   shape; a multiple of 256 otherwise).  saved: NULL, or (N, 3, P) fp32 of waldo_lpips_level_saved_bytes(N, C, P)
+ *   bytes that receives, per pixel, what the backward needs to walk the maps once: 1 / m0 (0 where n0 == 0),
+ *   1 / m1 and q = (sum_k w[k] e[k] f0[k, p]) / (n0 m0^2) (0 where n0 == 0),  e = f0 / m0 - f1 / m1.
+ *
+ * waldo_lpips_level_bwd: ONE launch; produces grad_f0 (N, C, P) only, from `saved` of the forward on the same operands.
+ *   With g = grad_out[n] / P:
+ *     grad_f0[c, p] = 2 g (w[c] e[c] / m0 - f0[c, p] / (n0 m0^2) * sum_k w[k] e[k] f0[k, p])
+ *   and where n0[p] == 0 every channel of that pixel gets EXACT 0.  (The framework chain yields NaN there: the
+ *   backward of sqrt at 0 is 0 / 0.  In LPIPS every tapped feature sits behind a ReLU whose backward turns either value
+ *   into 0 -- an all-zero pixel is one the ReLU clipped on every channel -- so the deviation is invisible at the module.)
+ *   Every element of grad_f0 is written; nothing needs a fill.  grad_f1 is the same call with f0 and f1 exchanged (and
+ *   the `saved` of a forward with them exchanged): the distance is symmetric.
+ *
+ * Both: caller-owned buffers, the caller's stream, no allocation, no synchronisation; capturable in a graph.
+ * WALDO_EINVAL with a message before any launch: "null pointer" (f0, f1, w, out, the workspace / saved, grad_out,
+ * grad_f0), "bad shape" (N, C or P <= 0), "too large" (C P > 2^31 - 1, or N x ceil(P / 64) > 2^31 - 1 workgroups),
+ * "workspace" (smaller than the query's answer).
+ * ------------------------------------------------------------------------------------- */
+int64_t waldo_lpips_level_workspace_bytes(int64_t N, int64_t C, int64_t P);
+int64_t waldo_lpips_level_saved_bytes(int64_t N, int64_t C, int64_t P);
+int waldo_lpips_level_fwd(const float* f0, const float* f1, const float* w, float* out, float* saved, void* workspace,
+                          int64_t workspace_bytes, int64_t N, int64_t C, int64_t P, float eps, waldo_stream_t stream);
+int waldo_lpips_level_bwd(const float* f0, const float* f1, const float* w, const float* saved, const float* grad_out,
+                          float* grad_f0, int64_t N, int64_t C, int64_t P, waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

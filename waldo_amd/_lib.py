@@ -98,6 +98,10 @@ SIGNATURES = {
     # pose objective (include/waldo_hip.h "Pose objective"): the three (real, pred) pairs, the mask, ...
     "waldo_pose_l1_fwd": [_c_f] * 10 + [_i64] * 5 + [_stream],
     "waldo_pose_l1_bwd": [_c_f] * 17 + [_i64] * 4 + [_stream],
+    # LPIPS level distance (include/waldo_hip.h "LPIPS level distance"): f0, f1, w, out, saved, workspace and its size,
+    # N, C, P, eps; the backward: f0, f1, w, saved, grad_out, grad_f0, N, C, P
+    "waldo_lpips_level_fwd": [_c_f] * 6 + [_i64] * 4 + [_flt, _stream],
+    "waldo_lpips_level_bwd": [_c_f] * 6 + [_i64] * 3 + [_stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],
@@ -173,6 +177,8 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_border_objects_workspace_bytes": (_i64, [_i64]),
          "waldo_cell_distance_workspace_bytes": (_i64, [_i64, _int, _i64]),
          "waldo_pose_l1_workspace_bytes": (_i64, [_i64] * 4),
+         "waldo_lpips_level_workspace_bytes": (_i64, [_i64] * 3),
+         "waldo_lpips_level_saved_bytes": (_i64, [_i64] * 3),
          "waldo_frame_metrics_partial_bytes": (_i64, [_int] * 5),
          "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
          "waldo_plane_norm_workspace_bytes": (_i64, [_i64, _int, _int, _int]),

@@ -2459,3 +2459,93 @@ def token_attention_clips(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, s
         route = "framework"
     return _TokenAttentionClips.apply(scale, strides, route, (int(max_q_len), int(max_k_len)), q, k, v, q_offsets,
                                       k_offsets)
+
+
+def lpips_level_framework(f0, f1, w, eps=1e-10):
+    """``lpips_level`` in framework ops, as the ``lpips`` package spells it: ``normalize_tensor`` (eps added after the
+    square root), the squared difference, the bias-free 1 x 1 lin convolution, ``spatial_average``.  Any device and
+    floating dtype; differentiable in every operand."""
+    u0 = f0 / (torch.sqrt(torch.sum(f0 ** 2, dim=1, keepdim=True)) + eps)
+    u1 = f1 / (torch.sqrt(torch.sum(f1 ** 2, dim=1, keepdim=True)) + eps)
+    d = torch.nn.functional.conv2d((u0 - u1) ** 2, w.reshape(1, -1, 1, 1))
+    return d.mean([2, 3]).reshape(-1)
+
+
+def _lpips_level_call(f0, f1, w, eps, want_saved):
+    """One forward call on dense operands: (out (N,), saved or None)."""
+    n, c, h, wd = f0.shape
+    p, dev = h * wd, f0.device
+    nbytes = _lib.query("waldo_lpips_level_workspace_bytes", n, c, p)
+    if nbytes <= 0:
+        raise ValueError(f"lpips_level: unsupported shape {tuple(f0.shape)} (C H W at most 2^31 - 1)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    saved = None
+    if want_saved:
+        saved = torch.empty(_lib.query("waldo_lpips_level_saved_bytes", n, c, p) // 4, dtype=torch.float32, device=dev)
+    _lib.launch("waldo_lpips_level_fwd", dev, f0, f1, w, out, saved, ws, nbytes, n, c, p, float(eps))
+    return out, saved
+
+
+class _LpipsLevel(torch.autograd.Function):
+    """``waldo_lpips_level_fwd`` with the per-pixel values its backward needs kept only when ``f0`` asks for a gradient;
+    ``grad_f1`` is the same pair of calls with the operands exchanged (the distance is symmetric), its forward run in
+    the backward: the loss differentiates the prediction alone."""
+
+    @staticmethod
+    def forward(ctx, eps, f0, f1, w):
+        f0, f1, w = f0.contiguous(), f1.contiguous(), w.contiguous()
+        out, saved = _lpips_level_call(f0, f1, w, eps, ctx.needs_input_grad[1])
+        ctx.eps = eps
+        ctx.save_for_backward(f0, f1, w, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        f0, f1, w, saved = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        n, c, h, wd = f0.shape
+        grads = [None, None]
+        for i, (a, b) in enumerate(((f0, f1), (f1, f0))):
+            if not ctx.needs_input_grad[1 + i]:
+                continue
+            if i == 1:
+                _, saved = _lpips_level_call(a, b, w, ctx.eps, True)
+            grads[i] = torch.empty_like(a)
+            _lib.launch("waldo_lpips_level_bwd", a.device, a, b, w, saved, grad_out, grads[i], n, c, h * wd)
+        return (None, grads[0], grads[1], None)
+
+
+def _lpips_level_check(f0, f1, w):
+    for name, t in (("f0", f0), ("f1", f1)):
+        if not torch.is_tensor(t) or t.ndim != 4 or not t.is_floating_point():
+            raise ValueError(f"lpips_level: {name} must be a floating (N, C, H, W) tensor, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+    if f0.shape != f1.shape or f0.dtype != f1.dtype or f0.device != f1.device:
+        raise ValueError(f"lpips_level: f0 and f1 disagree: {f0.dtype} {tuple(f0.shape)} on {f0.device} and {f1.dtype} "
+                         f"{tuple(f1.shape)} on {f1.device}")
+    if f0.numel() == 0:
+        raise ValueError(f"lpips_level: the operands {tuple(f0.shape)} are empty")
+    if not torch.is_tensor(w) or w.numel() != f0.shape[1] or w.dtype != f0.dtype or w.device != f0.device:
+        raise ValueError(f"lpips_level: w must hold C = {f0.shape[1]} {f0.dtype} weights on {f0.device}, got "
+                         f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}"
+                         + (f" on {w.device}" if torch.is_tensor(w) else ""))
+
+
+def lpips_level(f0, f1, w, eps=1e-10):
+    """The tail of LPIPS at one feature level: ``f0``, ``f1`` (N, C, H, W) feature maps, ``w`` the lin layer's C weights
+    (any shape of C elements: ``lin.model[1].weight`` as it is) -> (N,)::
+
+        u = f / (sqrt(sum_c f^2) + eps);   out[n] = mean over pixels of sum_c w[c] (u0 - u1)^2
+
+    fp32 operands on the GPU with a ``w`` that needs no gradient run ``waldo_lpips_level_fwd`` / ``_bwd``
+    (include/waldo_hip.h "LPIPS level distance"): the two maps are read, one float per image is written; no atomics --
+    the same bits from run to run; ``f1 == f0`` gives exact zeros, value and gradient; a pixel of ``f0`` that is zero on
+    every channel gets an exact 0 gradient (the framework chain: NaN from the square root's backward, which the ReLU
+    behind every LPIPS tap turns into 0 as well).  Operands that are not contiguous are made so.  Everything else (CPU,
+    fp64, 16-bit, ``w.requires_grad``) IS ``lpips_level_framework``."""
+    _lpips_level_check(f0, f1, w)
+    if f0.is_cuda and f0.dtype == torch.float32 and not w.requires_grad:
+        return _LpipsLevel.apply(float(eps), f0, f1, w.detach().reshape(-1))
+    return lpips_level_framework(f0, f1, w, eps)

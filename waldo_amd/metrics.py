@@ -12,8 +12,13 @@ metrics"):
   scale times ``relu(ssim_4)^w_4``, averaged over the channels.  Every scale must be at least 11 x 11: H, W >= 161.
 - PSNR: ``-10 log10(mse)`` over all pixels and channels, ``+inf`` for equal frames.
 
-Not covered: LPIPS (its AlexNet / linear-layer weights are downloaded by the reference and are not shipped here), the
-reference's ``--compress`` / ``--resize`` (cv2 ``INTER_LINEAR``) and reading mp4 files.
+- LPIPS (the reference's ``lpips_tf.lpips(..., model='net-lin', net='alex')`` on frames in [0, 1] mapped to [-1, 1],
+  tools/eval/metrics.py:127): with ``lpips=`` a ``waldo_amd.nets.LPIPS`` module, through its backbone and the fused
+  level kernel (include/waldo_hip.h "LPIPS level distance").  Its pretrained weights are not shipped: the caller loads
+  them (``LPIPS.load``), and without a module the metric is refused.  Agreement with the ``lpips`` package's own
+  weights and outputs has not been verified.
+
+Not covered: the reference's ``--compress`` / ``--resize`` (cv2 ``INTER_LINEAR``) and reading mp4 files.
 """
 import numpy as np
 import torch
@@ -63,12 +68,17 @@ def _descriptor(x):
     return d, enc, (d.stride(0), d.stride(1), d.stride(2), d.stride(3))
 
 
-def check_metrics(metrics):
-    """The metric names as a tuple; ValueError for an unknown one, and for LPIPS, whose weights are not shipped."""
+def check_metrics(metrics, lpips=None):
+    """The metric names as a tuple; ValueError for an unknown one, and for ``"lpips"`` without an ``LPIPS`` module (its
+    weights are not shipped: the caller loads them)."""
     metrics = tuple(metrics)
     if not metrics:
         raise ValueError("frame_metrics: no metric asked for")
     for m in metrics:
+        if m == "lpips" and lpips is not None:
+            if not callable(lpips):
+                raise ValueError(f"frame_metrics: lpips= must be an LPIPS module, got {type(lpips).__name__}")
+            continue
         if m == "lpips":
             raise ValueError("frame_metrics: 'lpips' is not available: it needs the pretrained AlexNet and LPIPS "
                              "linear-layer weights (alexnet / net-lin), which are not shipped with this library")
@@ -77,7 +87,17 @@ def check_metrics(metrics):
     return metrics
 
 
-def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc"):
+def _unit_frames(x, lo, hi, quantize):
+    """A dense clip as the [0, 1] values the metrics see (``frame_metrics``'s ``quantize``), flattened to frames."""
+    if x.dtype == torch.uint8:
+        return x.flatten(0, 1).float() / 255.0
+    u = ((x.flatten(0, 1) - lo) / (hi - lo)).clamp(0.0, 1.0)
+    if quantize == "none":
+        return u
+    return torch.trunc(u * 255.0 + (0.5 if quantize == "round" else 0.0)) / 255.0
+
+
+def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc", lpips=None):
     """Per-frame scores of ``pred`` against ``real``: a dict metric name -> (B, T) float32 tensor on the device.
 
     Each operand is a (B, T, 3, H, W) float32 clip with values in ``span`` (any strides for B, T and C; W unit-stride,
@@ -91,10 +111,15 @@ def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc
     - ``"round"``: ``trunc(u * 255 + 0.5) / 255``, the bytes ``tools.io.dump_video`` / ``dump_image`` write;
     - ``"none"``: ``u`` itself.
 
+    ``lpips``: a ``waldo_amd.nets.LPIPS`` module on the operands' device; with it ``"lpips"`` may be asked for, and the
+    result gains ``"lpips"``: the module applied to ``2 u - 1`` of both clips' frames, ``u`` the [0, 1] values above
+    (bytes: ``x / 255``), under ``no_grad``, ``lpips.chunk`` frames at a time.  Dense operands only.
+
     Raises ``ValueError`` for shapes that differ, channels other than 3, a frame below a metric's size limit
-    (SSIM 11 x 11, MS-SSIM 161 x 161) and ``"lpips"``; ``WaldoHipError`` for operands that are not on the GPU.
+    (SSIM 11 x 11, MS-SSIM 161 x 161), ``"lpips"`` without a module or with a ``PackedClip``; ``WaldoHipError`` for
+    operands that are not on the GPU.
     Deterministic: two calls, and ``frame_metrics(a, b)`` / ``frame_metrics(b, a)``, give the same bits."""
-    metrics = check_metrics(metrics)
+    metrics = check_metrics(metrics, lpips)
     if quantize not in QUANTIZE:
         raise ValueError(f"frame_metrics: quantize must be one of {tuple(QUANTIZE)}, got {quantize!r}")
     lo, hi = (float(v) for v in span)
@@ -104,9 +129,11 @@ def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc
     if _operand_shape(real, "real") != shp:
         raise ValueError(f"frame_metrics: pred and real differ in shape: {tuple(pred.shape)} vs {tuple(real.shape)}")
     b, t, h, w = shp
+    if "lpips" in metrics and (isinstance(pred, PackedClip) or isinstance(real, PackedClip)):
+        raise ValueError("frame_metrics: 'lpips' takes dense (B, T, 3, H, W) clips, not a PackedClip: unpack_clip it")
     mask = 0
     for m in metrics:
-        mask |= _BITS[m]
+        mask |= _BITS.get(m, 0)
     if "msssim" in metrics and not (_scales_ok(h, 5) and _scales_ok(w, 5)):
         raise ValueError(f"frame_metrics: msssim needs 5 scales of at least 11x11, and {h}x{w} has "
                          f"{(h + 15) // 16}x{(w + 15) // 16} at the last: the smallest frame that works is "
@@ -120,6 +147,13 @@ def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc
     dev = pred.device
     if real.device != dev:
         raise ValueError(f"frame_metrics: pred on {dev}, real on {real.device}")
+    out = {}
+    if "lpips" in metrics:
+        with torch.no_grad():
+            d = lpips(_unit_frames(pred, lo, hi, quantize) * 2.0 - 1.0, _unit_frames(real, lo, hi, quantize) * 2.0 - 1.0)
+        out["lpips"] = d.float().view(b, t)
+        if not mask:
+            return out
     part_bytes = _lib.query("waldo_frame_metrics_partial_bytes", b, t, h, w, mask)
     scratch_bytes = _lib.query("waldo_frame_metrics_scratch_bytes", b, t, h, w, mask)
     if part_bytes < 0 or scratch_bytes < 0:
@@ -128,11 +162,11 @@ def frame_metrics(pred, real, metrics=METRICS, span=(-1.0, 1.0), quantize="trunc
     db, eb, sb = _descriptor(real)
     partials = torch.empty(max(part_bytes // 8, 1), dtype=torch.float64, device=dev)
     scratch = torch.empty(scratch_bytes // 4, dtype=torch.float32, device=dev) if scratch_bytes else None
-    out = {m: torch.empty(b, t, dtype=torch.float32, device=dev) for m in metrics}
+    out.update({m: torch.empty(b, t, dtype=torch.float32, device=dev) for m in metrics if m in _BITS})
     table = rgb_table(dev) if _ENC_PACKED in (ea, eb) else None
     _lib.launch("waldo_frame_metrics_fwd", dev, da, ea, *sa, db, eb, *sb, table, b, t, h, w, lo, hi - lo,
                 QUANTIZE[quantize], mask, partials, scratch, out.get("psnr"), out.get("ssim"), out.get("msssim"))
-    return out
+    return {m: out[m] for m in metrics}
 
 
 def summarize(scores, vid_context):

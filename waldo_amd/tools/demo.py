@@ -710,10 +710,11 @@ RAW_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --
 
 def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4, seed=0,
         device="cuda:0", raw_dtype=None, packed=False, eval=False, out_bytes=None, render=None, palette=None,
-        wif_ckpt=None, ii_depth=4, ii_embed_dim=512, unet_dtype=None):
+        wif_ckpt=None, ii_depth=4, ii_embed_dim=512, unet_dtype=None, lpips=None):
     """The demo on a clip directory.  ``packed``: the clip goes to the device packed (RGB bytes + class ids,
     ``WF.PackedClip``) and predict() reads it as such -- the same results.  ``eval``: also score ``rec_vid`` and
-    ``inp_pred_vid`` against the real frames (``evaluate_prediction``), returned under ``"metrics"``.  ``out_bytes``
+    ``inp_pred_vid`` against the real frames (``evaluate_prediction``; with ``lpips``, an ``LPIPS`` module on the device,
+    LPIPS too -- not with ``packed``), returned under ``"metrics"``.  ``out_bytes``
     ("trunc" / "round"): predict() returns its clips as uint8, and those bytes are what is written and scored.
     ``render`` ("trunc" / "round"), ``palette`` (3 * num_lyt integers): predict()'s renders of the decomposition; the
     layout pictures, the flow picture of the last context and ``ctx_obj_lyt`` are written as ``.gif`` + ``_last.png``.
@@ -757,7 +758,7 @@ def run(clip_dir, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20
             fl = res["pred_flow"][0, -1, 0]
             wio.write_flo(os.path.join(out_dir, "pred_flow_last.flo"), fl)
     if eval:
-        res["metrics"] = evaluate_prediction(res, vid)
+        res["metrics"] = evaluate_prediction(res, vid, lpips=lpips)
     return res
 
 
@@ -937,16 +938,18 @@ def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj
 EVAL_KEYS = ("rec_vid", "inp_pred_vid")
 
 
-def evaluate_prediction(res, real_vid):
-    """PSNR / SSIM / MS-SSIM of ``rec_vid`` and ``inp_pred_vid`` against the real frames at the same time indices, both
+def evaluate_prediction(res, real_vid, lpips=None):
+    """PSNR / SSIM / MS-SSIM (and, with an ``LPIPS`` module and a dense ``real_vid``, LPIPS) of ``rec_vid`` and ``inp_pred_vid`` against the real frames at the same time indices, both
     quantised to the bytes the reference dumps (its two save_vid calls: ``metrics.frame_metrics``'s "trunc").  ``real_vid``:
     the fp32 clip (B, T, 3, H, W) or the ``WF.PackedClip``.  MS-SSIM is left out below its size limit (161 x 161).
     Returns {key: {metric: (B, T) tensor}}."""
     from .. import metrics as M
     h, w = real_vid.shape[-2:]
     names = tuple(m for m in M.METRICS if m != "msssim" or min(h, w) >= M.MIN_MSSSIM_SIDE)
+    if lpips is not None:
+        names += ("lpips",)
     real = real_vid if isinstance(real_vid, WF.PackedClip) else real_vid[:, :, :3]
-    return {key: M.frame_metrics(res[key], real, metrics=names) for key in EVAL_KEYS if key in res}
+    return {key: M.frame_metrics(res[key], real, metrics=names, lpips=lpips) for key in EVAL_KEYS if key in res}
 
 
 def print_evaluation(scores, ctx_len, frame_size):
@@ -990,6 +993,8 @@ def main():
                          "colours of the object layers)")
     ap.add_argument("--eval", action="store_true",
                     help="score rec_vid and inp_pred_vid against the real frames (PSNR, SSIM, MS-SSIM from 161x161)")
+    from .evaluate import add_lpips_arguments, lpips_module
+    add_lpips_arguments(ap)  # (with --eval, and not with --packed: LPIPS takes dense clips)
     ap.add_argument("--wif-ckpt", default=None, metavar="FILE",
                     help="a reference `ii` checkpoint (state dict): run the reference's UNet (WIF.with_unet) in place of "
                          "the stand-in network")
@@ -1032,7 +1037,9 @@ def main():
     res = run(args.clip, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
               eval=args.eval, out_bytes=args.out_bytes, render=args.render, palette=palette, wif_ckpt=args.wif_ckpt,
-              ii_depth=args.ii_depth, ii_embed_dim=args.ii_embed_dim, unet_dtype=RAW_DTYPES[args.unet_dtype])
+              ii_depth=args.ii_depth, ii_embed_dim=args.ii_embed_dim, unet_dtype=RAW_DTYPES[args.unet_dtype],
+              lpips=lpips_module(args.lpips_net, args.lpips_state, args.lpips_backbone, args.lpips_lin) if args.eval
+              else None)
     scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "

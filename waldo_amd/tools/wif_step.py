@@ -15,13 +15,15 @@ The networks outside the path are stand-ins: seeded decoder logits / pose head o
 distributions, and a 1 x 1 convolution (40 -> 5 channels, the UNet's widths at ``ii_score`` + ``ii_ab``, wif.py:19-23)
 in the UNet's place so that ``waldo_wif_fuse_bwd`` receives and produces real gradients.  ``bench.py --config WIF``
 times it.  ``WifStep(..., unet="reference")`` puts the real network there (``WIF.with_unet`` at the recipe's widths:
-``ii_depth 6``, ``ii_embed_dim 512``); ``act_dtype`` runs it with 16-bit activations (``UNet.act_dtype``).
+``ii_depth 6``, ``ii_embed_dim 512``); ``act_dtype`` runs it with 16-bit activations (``UNet.act_dtype``).  ``WifStep(..., objective="recipe")`` runs the recipe's full objective,
+``--s_vid_inpainting_losses "sharp_vid" "lpips_vid"`` with both lambdas 1 (synthesizer.py:587-600): the L1 term plus
+``LPIPS("vgg")`` of the predicted frames against the real ones (``nets.lpips``; random weights unless a module is passed).
 """
 import torch
 import torch.nn as nn
 
 from .. import functional as WF
-from ..nets import WIF, Warper, decode_output, estimate_alpha_grid_occ, flp
+from ..nets import LPIPS, WIF, Warper, decode_output, estimate_alpha_grid_occ, flp
 from ..nets.lvd import decoder_tail
 from . import demo
 from .pipeline import synthetic_clip
@@ -36,11 +38,21 @@ def wif_opt(**over):
 
 class WifStep:
     """``clips`` clips of 5 frames resident on ``device``; ``__call__`` runs the no-grad decode, ``WIF.forward``, the
-    loss and its backward once and returns the loss (the stand-in network's ``.grad`` hold the gradients)."""
+    loss and its backward once and returns the loss (the stand-in network's ``.grad`` hold the gradients).
+    ``objective``: ``"sharp"``, the `sharp_vid` L1 term alone, or ``"recipe"``, `sharp_vid` + `lpips_vid` as train_wif.sh
+    trains; ``lpips``: the ``LPIPS`` module of the latter (a seeded random-weight ``LPIPS("vgg")`` when None).  After a
+    call ``terms`` holds the detached terms of the loss by the reference's names."""
 
     frames, ctx_len = 5, 4
 
-    def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in", act_dtype=None):
+    def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in", act_dtype=None, objective="sharp",
+                 lpips=None):
+        if objective not in ("sharp", "recipe"):
+            raise ValueError(f"WifStep: objective must be 'sharp' or 'recipe', got {objective!r}")
+        if lpips is not None and objective != "recipe":
+            raise ValueError("WifStep: lpips= needs objective='recipe' (the 'sharp' objective has no LPIPS term)")
+        if lpips is not None and not isinstance(lpips, LPIPS):
+            raise ValueError(f"WifStep: lpips must be an LPIPS module, got {type(lpips).__name__}")
         if unet not in ("stand-in", "reference"):
             raise ValueError(f"WifStep: unet must be 'stand-in' or 'reference', got {unet!r}")
         if act_dtype is not None and unet != "reference":
@@ -63,6 +75,11 @@ class WifStep:
         self.ctx_ts = torch.arange(tc, device=device, dtype=torch.int64).view(1, -1, 1).expand(clips, -1, t - tc).contiguous()
         self.pred_ts = torch.arange(tc, t, device=device, dtype=torch.int64)
         self.raw_output = None
+        self.objective, self.terms, self.lpips = objective, {}, None
+        if objective == "recipe":
+            if lpips is None:
+                lpips = LPIPS("vgg", generator=torch.Generator().manual_seed(seed))  # (no global generator is touched)
+            self.lpips = lpips.to(device)
 
     def decode(self):
         """The no-grad half: what ``inpaint`` computes before ``net_ii`` (synthesizer.py:517-574)."""
@@ -94,6 +111,11 @@ class WifStep:
         inp_output = self.wif(raw_output)                                   # synthesizer.py:576
         real = self.vid[:, self.ctx_len:]
         loss = (inp_output[:, :, :3] - real).abs().mean()                   # `sharp_vid` (synthesizer.py:587-590)
+        self.terms = {"sharp_vid": loss.detach()}
+        if self.objective == "recipe":                                      # `lpips_vid` (synthesizer.py:597-600)
+            lp = self.lpips(inp_output[:, :, :3].flatten(0, 1), real.flatten(0, 1)).mean()
+            self.terms["lpips_vid"] = lp.detach()
+            loss = loss + lp
         loss.backward()                                                     # synthesizer.py:631
         return loss
 
