@@ -1244,6 +1244,53 @@ int waldo_lpips_level_fwd(const float* f0, const float* f1, const float* w, floa
 int waldo_lpips_level_bwd(const float* f0, const float* f1, const float* w, const float* saved, const float* grad_out,
                           float* grad_f0, int64_t N, int64_t C, int64_t P, waldo_stream_t stream);
 
+/* -------------------------------------------------------------------------------------
+ * Clip augmentation (waldo_amd.augment; the reference's data/base_dataset.py:113-165 parameters, :330-370 transforms,
+ * :173-208 layout and flow).  A training sample from a packed clip ("Packed clip" above) in ONE launch: crop, bilinear
+ * resize, flips, colour jitter and normalisation of the frames, the resized layout logits, and the flow through its
+ * two resizes.
+ *   clip (B,T,Hd,Wd) 4-byte pixels; flow NULL or (B,T,2,Hf,Wf) fp32, normalised (read_flo's units), Hf <= Hd, Wf <= Wd;
+ *   per-clip tables in DEVICE memory (they may change between the replays of a graph that holds the launch):
+ *     box    (B,4) int32   [top, left, h_crop, w_crop] in clip pixels
+ *     flip   (B)   uint8   bit 0: left-right (the reference's v_flip), bit 1: top-bottom (its h_flip)
+ *     jitter (B,3) fp32    [brightness, saturation, hue]
+ *     order  (B,T) uint8   0..5: the six orders of (brightness, saturation, hue), lexicographic
+ *                          (0 BSH, 1 BHS, 2 SBH, 3 SHB, 4 HBS, 5 HSB); any other byte: no jitter for that frame
+ *     zoom   (B)   fp32    the flow's multiplier
+ *   out (B,T,3+Nl,Ho,Wo) fp32, the layout of the unpacked clip; flow_out NULL (with flow NULL) or (B,T,2,Ho,Wo) fp32.
+ *
+ * The kernel CLAMPS every box into the clip (the tables cannot be checked without a device read):
+ *   top <- clamp(top, 0, Hd-1), h_crop <- clamp(h_crop, 1, Hd-top); left and w_crop likewise.
+ * No value of any table moves a read outside the clip or the flow.
+ *
+ * Per output pixel (y, x) of a frame, all in fp32:
+ *   xf = Wo-1-x under the left-right flip, else x;  sx = clamp((xf + 0.5) (w_crop / Wo) - 0.5, 0, w_crop-1);
+ *   x0 = floor(sx), x1 = min(x0+1, w_crop-1), fx = sx - x0; rows likewise.  The four taps are pixels
+ *   (top + y0|y1, left + x0|x1) with weights (1-fy|fy)(1-fx|fx): F.interpolate(bilinear, align_corners=False) on the
+ *   CROPPED frame -- the taps clamp to the box, not to the image.
+ *   RGB: u = (sum of weight x byte) / 255 per channel; then the frame's jitter operations in its order:
+ *     brightness  u <- clamp(u f, 0, 1)
+ *     saturation  u <- clamp(f u + (1-f) g, 0, 1),  g = 0.299 r + 0.587 g + 0.114 b
+ *     hue         hexcone RGB -> HSV, h <- (h + hue) mod 1, HSV -> RGB (max == min: s = 0, the pixel is unchanged)
+ *   then (u - 0.5) / 0.5.  (No contrast: it needs the frame's mean, a second pass.)
+ *   Layout channel n: 5 (2 s_n - 1), s_n = the sum of the weights of the taps whose class byte is n -- the bilinear
+ *   resize of the one-hot planes, which are never written.  A class byte >= Nl adds to no channel.
+ *   Flow channel c: each of the four taps, at (Y, X) of the Hd x Wd grid, is the bilinear sample of the (Hf,Wf) flow at
+ *   ((Y + 0.5) Hf / Hd - 0.5, (X + 0.5) Wf / Wd - 0.5) clamped to the flow's edges (the reference resizes the flow to
+ *   the frame size first); the four are blended with the frame's weights, multiplied by zoom, and channel 0 is negated
+ *   under the left-right flip, channel 1 under the top-bottom flip.  Two bilinear resizes composed, no intermediate.
+ * With the full box, Ho x Wo = Hd x Wd, no flip and no jitter, `out` is waldo_unpack_clip_fwd's, bit for bit.
+ *
+ * Caller-owned buffers, the caller's stream, no allocation, no synchronisation; capturable in a graph.  B T == 0:
+ * WALDO_OK without a launch.  WALDO_EINVAL with a message before any launch: "bad shape" (B or T < 0, Nl outside
+ * [0, 32], a size outside [1, 32767]), "downsample" (Ho < Hd or Wo < Wd: with the boxes clamped into the clip the
+ * resize then never shrinks, which would need an antialiasing filter), "flow larger than the clip" (Hf > Hd or
+ * Wf > Wd), "null pointer" (anything but flow AND flow_out together), "too large" (more than 2^31 - 1 workgroups).
+ * ------------------------------------------------------------------------------------- */
+int waldo_augment_clip_fwd(const uint8_t* clip, const float* flow, const int32_t* box, const uint8_t* flip,
+                           const float* jitter, const uint8_t* order, const float* zoom, float* out, float* flow_out,
+                           int B, int T, int Nl, int Hd, int Wd, int Hf, int Wf, int Ho, int Wo, waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
