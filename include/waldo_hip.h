@@ -1291,6 +1291,66 @@ int waldo_augment_clip_fwd(const uint8_t* clip, const float* flow, const int32_t
                            const float* jitter, const uint8_t* order, const float* zoom, float* out, float* flow_out,
                            int B, int T, int Nl, int Hd, int Wd, int Hf, int Wf, int Ho, int Wo, waldo_stream_t stream);
 
+/* -------------------------------------------------------------------------------------
+ * Optimizer step (waldo_amd.optim): what ends every training step of the reference (models/synthesizer.py:1057-1072,
+ * :619-631, :765-778; the optimizer of create_optimizers, :114-143) -- the NaN test, GradScaler's unscale and update,
+ * clip_grad_norm_ and torch.optim.Adam / AdamW -- on the device, with no host read.  Multi-tensor over n_tensors
+ * (param, grad, exp_avg, exp_avg_sq) quadruples of fp32 of any sizes, in three phases on the caller's stream:
+ *
+ *   statistics  one pass over the gradients: per chunk of 4096 elements of a tensor the sum of squares and a non-finite
+ *               flag (any NaN or +-inf element) into the workspace.  The chunk geometry depends on the sizes alone.
+ *               16-byte loads where the tensor's base is 16-byte aligned, element loads for the numel % 4 tail and for a
+ *               base that is only 4-byte aligned.  NO ATOMICS: the same bits from run to run and in a graph replay.
+ *   finalize    ONE workgroup: adds the partials in index order in double, ORs the flags and isnan(*loss) (loss: NULL or
+ *               a device pointer; the reference's test), and writes `state`; updates hyper[5], the scale.
+ *   update      per element, only on a finite step (a skipped step writes NOTHING), torch.optim.Adam's single-tensor
+ *               arithmetic in its order of operations:
+ *                 adamw and wd[t] != 0:  p = p (1 - lr wd[t])                       (decoupled decay, per tensor)
+ *                 g' = g mult                                                        (mult = clip_coef / scale)
+ *                 m  = lerp(m, g', 1 - beta1)     = m + (1 - beta1)(g' - m), in torch.lerp's two forms
+ *                 v  = beta2 v + ((1 - beta2) g') g'
+ *                 p  = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+ *               amsgrad, maximize and L2-style decay are not offered.
+ *
+ * The tensors' pointers travel BY VALUE in the kernel arguments, at most K = 64 non-empty tensors per launch; a workgroup
+ * finds its tensor from the pack's chunk prefix.  There is no pointer table in device memory: new gradient addresses at
+ * every eager step need no refresh, and in a graph capture the addresses are baked into the nodes.  A step over n
+ * non-empty tensors is 2 ceil(n / K) + 1 launches; *launches (a HOST int, or NULL) receives the count.  The host arrays
+ * (params .. weight_decays; weight_decays NULL: no decay) are consumed during the call.
+ *
+ * state: WALDO_ADAM_STATE_WORDS fp32 in device memory, zeroed once by the caller, written by finalize:
+ *   [0] step (finite steps so far; +1 on a finite step)   [1] grad norm = sqrt(sum) / scale, what clip_grad_norm_ sees
+ *   [2] clip_coef = min(1, max_norm / (norm + 1e-6)) when max_norm > 0, else 1       after unscale_
+ *   [3] mult = clip_coef / scale          [4] 1 on a finite step, 0 on a skipped one
+ *   [5] bias_correction1 = 1 - beta1^step [6] sqrt(bias_correction2)   [7] lr / bias_correction1  (double, one lane)
+ *   [8] skipped steps in a row (0 after a finite step)    [9] skipped steps in all
+ *   [10] finite steps since the scale last changed (GradScaler's growth tracker)      [11..15] reserved
+ * hyper: WALDO_ADAM_HYPER_WORDS fp32 in device memory, read at every step -- a scheduler changes them between the
+ * replays of a graph without a recapture:
+ *   [0] lr  [1] beta1  [2] beta2  [3] eps  [4] max_norm (<= 0: no clipping)
+ *   [5] scale (the loss scale the gradients carry; 1 without a scaler; WRITTEN by finalize, GradScaler.update's rule:
+ *       x backoff_factor on a non-finite step, x growth_factor after growth_interval finite steps in a row)
+ *   [6] growth_factor  [7] backoff_factor  [8] growth_interval (0: the scale never grows)   [9..11] reserved
+ *
+ * waldo_adam_limits(out, n): writes the first n of {K, the chunk's elements, WALDO_ADAM_STATE_WORDS,
+ * WALDO_ADAM_HYPER_WORDS} and returns how many there are.  waldo_adam_workspace_bytes(n_tensors, numels): 8 bytes per
+ * chunk, a multiple of 256 and at least 256; 0 for bad sizes (a negative count or size, too many chunks).
+ *
+ * Caller-owned buffers, the caller's stream, no allocation, no synchronisation, no memset node; capturable in a graph.
+ * WALDO_EINVAL with a message before any launch: "null pointer" (state, hyper, the workspace, an array, a buffer of a
+ * non-empty tensor), "bad shape" (n_tensors or a size < 0; a tensor of 0 elements is allowed and skipped), "too large"
+ * (more than 2^31 - 1 chunks), "not aligned" (a pointer off a 4-byte boundary, the workspace off 8), "workspace"
+ * (smaller than the query's answer).
+ * ------------------------------------------------------------------------------------- */
+#define WALDO_ADAM_STATE_WORDS 16
+#define WALDO_ADAM_HYPER_WORDS 12
+int waldo_adam_limits(int* out, int n);
+int64_t waldo_adam_workspace_bytes(int64_t n_tensors, const int64_t* numels);
+int waldo_adam_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                    const int64_t* numels, const float* weight_decays, int64_t n_tensors, float* state, float* hyper,
+                    const float* loss, void* workspace, int64_t workspace_bytes, int adamw, int* launches,
+                    waldo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

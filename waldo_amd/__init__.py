@@ -7,6 +7,7 @@ operator modules (``modules.warp``, ``nets.lvd``, ``nets.wif``).
 from . import functional  # noqa: F401
 from . import supervision  # noqa: F401
 from . import augment  # noqa: F401
+from . import optim  # noqa: F401
 from .functional import set_deterministic, is_deterministic, deterministic  # noqa: F401
 from .functional import token_attention_backward_route  # noqa: F401
 from .modules.warp import TPSWarp, InverseWarp  # noqa: F401

@@ -105,6 +105,9 @@ SIGNATURES = {
     # clip augmentation (include/waldo_hip.h "Clip augmentation"): clip, flow, the five tables, out, flow_out, B, T, Nl,
     # Hd, Wd, Hf, Wf, Ho, Wo
     "waldo_augment_clip_fwd": [_c_f] * 9 + [_int] * 9 + [_stream],
+    # optimizer step (include/waldo_hip.h "Optimizer step"): the four HOST arrays of device pointers, the host arrays of
+    # sizes and decays, n_tensors, state, hyper, loss, workspace and its size, adamw, the host launch count
+    "waldo_adam_step": [_c_f] * 6 + [_i64] + [_c_f] * 4 + [_i64, _int, _c_f, _stream],
     "waldo_time_gather_fwd": [_c_f, _c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_time_gather_bwd": [_c_f, _c_f, _c_f, _c_f, _int, _int, _int, _int, _i64, _i64, _int, _stream],
     "waldo_downscale_frames_fwd": [_c_f, _c_f] + [_int] * 8 + [_stream],
@@ -186,6 +189,8 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_frame_metrics_scratch_bytes": (_i64, [_int] * 5),
          "waldo_plane_norm_workspace_bytes": (_i64, [_i64, _int, _int, _int]),
          "waldo_plane_norm_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
+         "waldo_adam_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
+         "waldo_adam_workspace_bytes": (_i64, [_i64, ctypes.POINTER(_i64)]),
          "waldo_token_attention_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_token_attention_bwd_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),

@@ -11,12 +11,14 @@ frames, 16 objects + background, layout + flow input):
 The recipe pins ``min_ctx_length_vid`` = ``max_ctx_length_vid`` = 4, so the mask is "the first 4 frames of every clip":
 ``FLP.plan`` builds it from integers and ``supervision.pose_terms`` takes the plan, so nothing between the clip and the
 parameter gradients reads the host, and ``graph=True`` replays the whole step from ONE HIP graph.  The clip is seeded
-and resident on the device; the optimizer, gradient clipping (``clip_value`` is 0 in the recipe) and the GradScaler are
-the caller's.
+and resident on the device.  ``optimizer=None`` stops at the gradients: the optimizer, gradient clipping (``clip_value``
+is 0 in the recipe) and the GradScaler are then the caller's.  ``optimizer="adam"`` / ``"adamw"`` / an ``optim.Adam`` ends
+the step as the reference does (synthesizer.py:765-778) with ``optimizer.step(loss)`` -- the NaN test, the clip and the
+update on the device (``waldo_amd.optim``), inside the graph when there is one.
 """
 import torch
 
-from .. import supervision
+from .. import optim, supervision
 from ..nets import FLP, LVD
 from ..nets.flp import FlpPlan
 from . import demo
@@ -54,12 +56,14 @@ class FlpStep:
     kernel or through framework ops.  ``lvd_over`` / ``flp_over``: option fields that differ from the recipe's (smaller
     networks).  ``graph``: the step is captured once, here, and ``__call__`` replays it -- ``lyt`` and ``flow`` are the
     graph's inputs (new data written into them is a new step), the returned loss, ``terms`` and the gradients its
-    outputs, overwritten by every replay."""
+    outputs, overwritten by every replay.  ``optimizer``: None, "adam", "adamw" (the reference's defaults) or an
+    ``optim.Adam`` over FLP's parameters; the step then ends in ``optimizer.step(loss)`` (in the graph too: a replay
+    trains), and ``step.optimizer`` is it."""
 
     num_lyt = 20
 
     def __init__(self, clips, device, seed=0, frames=14, ctx_len=4, objective="kernel", graph=False, lvd_over=None,
-                 flp_over=None, dim=128, aspect_ratio=2):
+                 flp_over=None, dim=128, aspect_ratio=2, optimizer=None):
         if objective not in OBJECTIVES:
             raise ValueError(f"FlpStep: objective must be one of {OBJECTIVES}, got {objective!r}")
         if not 0 < ctx_len < frames:
@@ -86,6 +90,7 @@ class FlpStep:
         for p in self.lvd.parameters():
             p.requires_grad_(False)
         self.leaves = list(self.flp.parameters())
+        self.optimizer = optim.resolve(optimizer, self.leaves, "FlpStep")
         self.plan = self.flp.plan(clips, frames, ctx_len, device)
         self.terms = None
         self.graph = self._loss = None
@@ -120,17 +125,28 @@ class FlpStep:
         loss.backward()
         # (detached: a term that kept the autograd graph alive would keep its AccumulateGrad nodes on this stream)
         self.terms = {k: v.detach() for k, v in terms.items()}
-        return loss.detach()
+        loss = loss.detach()
+        if self.optimizer is not None:
+            self.optimizer.step(loss)
+        return loss
 
     def _capture(self):
         """Two warm-up steps on a side stream, then the whole step -- producers, FLP, objective, backward -- captured in
-        one graph.  The gradients are allocated inside the capture: they are the graph's buffers."""
+        one graph.  The gradients are allocated inside the capture: they are the graph's buffers.  With an optimizer the
+        warm-up steps train, so the parameters and the optimizer's state are put back before the capture."""
+        if self.optimizer is not None:
+            kept = [p.detach().clone() for p in self.leaves], self.optimizer.snapshot()
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(2):
                 self._step()
         torch.cuda.current_stream(self.device).wait_stream(side)
+        if self.optimizer is not None:
+            with torch.no_grad():
+                for p, p0 in zip(self.leaves, kept[0]):
+                    p.copy_(p0)
+            self.optimizer.restore(kept[1])
         torch.cuda.synchronize(self.device)
         for p in self.leaves:
             p.grad = None

@@ -17,13 +17,15 @@ every call, as the reference builds it at every step (``waldo_amd.supervision``)
 ``nets="reference"`` feeds the step from a seeded ``nets.LVD`` at the recipe's widths -- encoder, layer estimator, pose
 estimator and object decoder in front of the same warp path (synthesizer.py:815-823) -- instead of from leaves: the
 gradients then land in the networks' parameters.  ``nets="stand-in"`` (the default) is the step described above.
+With ``nets="reference"``, ``optimizer="adam"`` / ``"adamw"`` / an ``optim.Adam`` ends the step as the reference does
+(synthesizer.py:1057-1072) with ``optimizer.step(loss)`` on the device (``waldo_amd.optim``); None stops at the gradients.
 """
 import types
 
 import torch
 
 from .. import functional as WF
-from .. import supervision
+from .. import optim, supervision
 from ..nets import LVD, Warper, decode_output, estimate_alpha_grid_occ, flp
 from ..nets.lvd import decoder_tail
 from .utils import get_grid
@@ -63,17 +65,22 @@ def recipe_net_opt(**over):
 
 class LvdStep:
     """``clips`` clips of 5 frames resident on ``device``; ``__call__`` runs forward, loss and backward once and
-    returns the loss (the leaves' ``.grad`` hold the gradients)."""
+    returns the loss (the leaves' ``.grad`` hold the gradients).  ``optimizer`` (with ``nets="reference"``): None, "adam",
+    "adamw" or an ``optim.Adam`` over the networks' parameters; the step then ends in ``optimizer.step(loss)``, and
+    ``step.optimizer`` is it."""
 
     frames, num_lyt = 5, 20
 
-    def __init__(self, clips, device, seed=0, objective="stand-in", nets="stand-in"):
+    def __init__(self, clips, device, seed=0, objective="stand-in", nets="stand-in", optimizer=None):
         if objective not in OBJECTIVES:
             raise ValueError(f"LvdStep: objective must be one of {OBJECTIVES}, got {objective!r}")
         if nets not in NETS:
             raise ValueError(f"LvdStep: nets must be one of {NETS}, got {nets!r}")
+        if optimizer is not None and nets != "reference":
+            raise ValueError("LvdStep: optimizer= needs nets='reference' (the stand-in step has leaves, no parameters)")
         self.objective = objective
         self.nets = nets
+        self.optimizer = None
         self.net = None
         self.opt = o = lvd_opt()
         self.clips = b = clips
@@ -111,6 +118,7 @@ class LvdStep:
             if self.real_flow is None:
                 self.real_flow = 0.05 * torch.randn(b, t, 2, h, w, generator=g, device=device)
             self.leaves = list(self.net.parameters())
+            self.optimizer = optim.resolve(optimizer, self.leaves, "LvdStep")
 
     def _network_step(self):
         """The forward of synthesizer.py:810-841 through the networks; returns decode_output's tuple and obj_pose."""
@@ -153,6 +161,8 @@ class LvdStep:
         else:
             loss = out[0].square().mean() + out[1].square().mean() + out[3].mean()
         loss.backward()
+        if self.optimizer is not None:
+            self.optimizer.step(loss.detach())
         return loss
 
     def grads_finite(self):

@@ -18,11 +18,14 @@ times it.  ``WifStep(..., unet="reference")`` puts the real network there (``WIF
 ``ii_depth 6``, ``ii_embed_dim 512``); ``act_dtype`` runs it with 16-bit activations (``UNet.act_dtype``).  ``WifStep(..., objective="recipe")`` runs the recipe's full objective,
 ``--s_vid_inpainting_losses "sharp_vid" "lpips_vid"`` with both lambdas 1 (synthesizer.py:587-600): the L1 term plus
 ``LPIPS("vgg")`` of the predicted frames against the real ones (``nets.lpips``; random weights unless a module is passed).
+With ``unet="reference"``, ``optimizer="adam"`` / ``"adamw"`` / an ``optim.Adam`` ends the step as the reference does
+(synthesizer.py:619-631) with ``optimizer.step(loss)`` on the device (``waldo_amd.optim``); None stops at the gradients.
 """
 import torch
 import torch.nn as nn
 
 from .. import functional as WF
+from .. import optim
 from ..nets import LPIPS, WIF, Warper, decode_output, estimate_alpha_grid_occ, flp
 from ..nets.lvd import decoder_tail
 from . import demo
@@ -31,9 +34,10 @@ from .pipeline import synthetic_clip
 
 def wif_opt(**over):
     """The option fields the path reads, at the Cityscapes WIF recipe (train_wif.sh:12-16, 25-37)."""
-    return demo.demo_opt(dim=128, aspect_ratio=2.0, num_obj=16, num_lyt=20, load_dim=512, latent_shape=[8, 16],
-                         obj_shape=[4, 4], patch_size=16, scale_factor=1, min_cls=0.1, use_lyt_opacity=True,
-                         pad_obj_alpha=3, **dict(dict(ii_depth=6), **over))
+    d = dict(dim=128, aspect_ratio=2.0, num_obj=16, num_lyt=20, load_dim=512, latent_shape=[8, 16], obj_shape=[4, 4],
+             patch_size=16, scale_factor=1, min_cls=0.1, use_lyt_opacity=True, pad_obj_alpha=3, ii_depth=6)
+    d.update(over)
+    return demo.demo_opt(**d)
 
 
 class WifStep:
@@ -41,12 +45,17 @@ class WifStep:
     loss and its backward once and returns the loss (the stand-in network's ``.grad`` hold the gradients).
     ``objective``: ``"sharp"``, the `sharp_vid` L1 term alone, or ``"recipe"``, `sharp_vid` + `lpips_vid` as train_wif.sh
     trains; ``lpips``: the ``LPIPS`` module of the latter (a seeded random-weight ``LPIPS("vgg")`` when None).  After a
-    call ``terms`` holds the detached terms of the loss by the reference's names."""
+    call ``terms`` holds the detached terms of the loss by the reference's names.  ``opt_over``: option fields that differ
+    from the recipe's (a smaller UNet: ``ii_embed_dim``, ``ii_depth``; smaller frames: ``load_dim``).  ``optimizer`` (with ``unet="reference"``): None,
+    "adam", "adamw" or an ``optim.Adam`` over the UNet's parameters; the step then ends in ``optimizer.step(loss)``, and
+    ``step.optimizer`` is it."""
 
     frames, ctx_len = 5, 4
 
     def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in", act_dtype=None, objective="sharp",
-                 lpips=None):
+                 lpips=None, optimizer=None, opt_over=None):
+        if optimizer is not None and unet != "reference":
+            raise ValueError("WifStep: optimizer= needs unet='reference' (the stand-in is not the network that trains)")
         if objective not in ("sharp", "recipe"):
             raise ValueError(f"WifStep: objective must be 'sharp' or 'recipe', got {objective!r}")
         if lpips is not None and objective != "recipe":
@@ -57,7 +66,7 @@ class WifStep:
             raise ValueError(f"WifStep: unet must be 'stand-in' or 'reference', got {unet!r}")
         if act_dtype is not None and unet != "reference":
             raise ValueError("WifStep: act_dtype needs unet='reference' (the stand-in has no activations to store)")
-        self.opt = o = wif_opt()
+        self.opt = o = wif_opt(**(opt_over or {}))
         self.clips, self.device = clips, device
         self.warper = Warper(o).to(device)
         torch.manual_seed(seed)
@@ -67,6 +76,7 @@ class WifStep:
         else:
             self.unet = nn.Conv2d(3 + o.num_lyt + o.num_obj + 1, 5, 1).to(device)
             self.wif = WIF(o, unet=self.unet).to(device)
+        self.optimizer = optim.resolve(optimizer, list(self.unet.parameters()), "WifStep")
         self.net = demo.synthetic_network_outputs(o, clips, self.frames, self.ctx_len, seed=seed, device=device,
                                                   motion=motion)
         self.vid, self.lyt = synthetic_clip(o, clips, self.frames, seed, device)
@@ -117,6 +127,8 @@ class WifStep:
             self.terms["lpips_vid"] = lp.detach()
             loss = loss + lp
         loss.backward()                                                     # synthesizer.py:631
+        if self.optimizer is not None:
+            self.optimizer.step(loss.detach())
         return loss
 
     def grads_finite(self):
