@@ -1104,6 +1104,30 @@ int waldo_token_attention_bwd(const float* q, int64_t qs_b, int64_t qs_n, const 
                               float* grad_v1, float* grad_k2, float* grad_v2, float scale, int64_t B, int H, int D,
                               int Nq, int Nk1, int Nk2, waldo_stream_t stream);
 
+/* Token attention on 16-bit operands, the forward: waldo_token_attention_fwd_dt is waldo_token_attention_fwd and
+ * waldo_token_attention_clips_fwd_dt is waldo_token_attention_clips_fwd (next section) with q, k, v and out of ONE
+ * 16-bit element type, dtype = WALDO_DTYPE_F16 or WALDO_DTYPE_BF16, passed as void*.  Strides are in ELEMENTS and are
+ * multiples of 8 (rows are read in 16-byte pieces of 8 values); every pointer is on a 16-byte boundary; D is 16, 32 or
+ * 64; the tiles are the fp32 kernel's (waldo_token_attention_dt_limits reports them as waldo_token_attention_limits
+ * does).  Both products run on the 16-bit matrix instruction with fp32 accumulation:
+ *   a score is an fp32 sum of exact 16-bit products; scale, mask, the running maximum and the running sum l are fp32,
+ *   and l sums the unrounded p; p is rounded to the element type only as the operand of the second product; o is
+ *   accumulated and rescaled in fp32; one rounding (nearest even; a NaN stays a NaN) at the store.
+ * No score matrix, no workspace, no atomics: the same bits from run to run; the caller's stream; capturable in a graph.
+ * A clip with queries and no keys gets NaN rows.  There is no _lse form and no backward on 16-bit operands.
+ * Refusals: WALDO_DTYPE_F32 ("is served by" the fp32 entry point, which the message names) and an unknown code
+ * ("unknown dtype") before anything else; then the fp32 entry point's, in its order and words, with "a multiple of 8
+ * values" for the strides. */
+int waldo_token_attention_dt_limits(int* out, int n);
+int waldo_token_attention_fwd_dt(const void* q, int64_t qs_b, int64_t qs_n, const void* k1, int64_t k1s_b, int64_t k1s_n,
+                                 const void* v1, int64_t v1s_b, int64_t v1s_n, const void* k2, int64_t k2s_b,
+                                 int64_t k2s_n, const void* v2, int64_t v2s_b, int64_t v2s_n, void* out, float scale,
+                                 int64_t B, int H, int D, int Nq, int Nk1, int Nk2, int dtype, waldo_stream_t stream);
+int waldo_token_attention_clips_fwd_dt(const void* q, int64_t qs_n, const void* k, int64_t ks_n, const void* v,
+                                       int64_t vs_n, const int* q_off, const int* k_off, void* out, float scale,
+                                       int64_t B, int H, int D, int64_t Rq, int64_t Rk, int max_q_len, int max_k_len,
+                                       int dtype, waldo_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Token attention over clips: the attention of the future layer predictor's blocks (the reference's
  * models/modules/transform.py FullAttention / CrossAttention with ctx_mask: from_ctx -> attention over all T N keys

@@ -94,11 +94,45 @@ class reference_attention:
         return False
 
 
+def main_16bit(args, net, forward):
+    dtype = {"bf16": torch.bfloat16, "fp16": torch.float16}[args.dtype]
+    out = args.out if os.path.basename(args.out) != "flp_nets.json" else os.path.join(ROOT, "profiles", "flp_nets_16bit.json")
+
+    def route(fused, act_dtype):
+        def fn():
+            net.act_dtype = act_dtype
+            return forward(fused)
+        return fn
+
+    doc = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            doc = json.load(fh)
+    with torch.no_grad():
+        ref, got = route(True, None)(), route(True, dtype)()
+        part = dict(shape=dict(clips=B, frames=T, ctx_len=CTX, tokens_per_frame=NO + 1, **OPT),
+                    device=torch.cuda.get_device_name(0), rounds=args.rounds, warmup=args.warmup,
+                    max_abs_act_dtype_minus_fp32=max((a - b).abs().max().item() for a, b in zip(got, ref)))
+        part["forward"] = f = alternate({"fused_act_dtype": route(True, dtype), "fused_fp32": route(True, None),
+                                         "framework_autocast": route(False, dtype)}, args.warmup, args.rounds)
+    part["act_dtype_over_fp32"] = f["fused_act_dtype"]["median_ms"] / f["fused_fp32"]["median_ms"]
+    part["act_dtype_over_framework_autocast"] = f["fused_act_dtype"]["median_ms"] / f["framework_autocast"]["median_ms"]
+    doc[args.dtype] = part
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(doc, fh, indent=1, sort_keys=True)
+    print(json.dumps({k: round(v["median_ms"], 3) for k, v in f.items() if isinstance(v, dict)}), "spread", f["spread"])
+    print(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "flp_nets.json"))
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dtype", choices=("bf16", "fp16"),
+                    help="measure act_dtype instead: the forward with act_dtype fused, in fp32 fused and fused = False "
+                         "under the same autocast; writes profiles/flp_nets_16bit.json")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -117,6 +151,9 @@ def main():
             with reference_attention():
                 return net(*inputs, ctx_mask=plan)
         return net(*inputs, ctx_mask=plan)
+
+    if args.dtype:
+        return main_16bit(args, net, forward)
 
     def step(fused, route="framework", reference=False):
         net.zero_grad(set_to_none=True)

@@ -8,6 +8,18 @@ at the LVD recipe's shapes (scripts/cityscapes/train_lvd.sh: 512 wide, 8 heads, 
     python tools_dev/ab_lvd_nets.py --out profiles/lvd_nets_bwd.json --sections bwd,step [--clips 4]
     python tools_dev/ab_lvd_nets.py --out FILE --sections op,bwd --head-dim 16 --lib tools_dev/_variants/NAME.so
 
+    python tools_dev/ab_lvd_nets.py --dtype bf16        (writes profiles/lvd_nets_16bit.json: sections op16,lvd16,step16)
+
+--dtype bf16 | fp16 measures the 16-bit route (WF.token_attention_16bit_route("kernel"), ``act_dtype``) instead:
+  op16   at the four op shapes, in one process: ``kernel16`` (waldo_token_attention_fwd_dt on the 16-bit operands),
+         ``framework16`` (WF.token_attention_framework on the same operands), ``sdpa16`` and ``kernel32`` (the fp32 kernel
+         on fp32 copies).  ``kernel16_beats_kernel32``: by more than the spread -- the condition on the kernel at pose_56
+         and pose_112; the sdpa comparison is reported without a bar.  With the bound-by figures: matrix FLOP/s and the
+         bytes of the operands and out over the time;
+  lvd16  the whole LVD forward: ``act_dtype`` fused, fp32 fused, and ``fused = False`` under the same autocast;
+  step16 ``LvdStep(--clips, nets="reference")`` with ``act_dtype`` against fp32 and against ``fused = False`` under the same
+         autocast (all with the default backward route).
+
 --lib binds another build of the library (``_lib.use_library``: tools_dev/build_variant.py makes one) for an A/B of two
 builds in two processes; --head-dim D runs ``op`` and ``bwd`` at another head dimension with the same token counts and
 512 / D heads (the width stays 512; the default 64 is the recipe's).
@@ -253,6 +265,122 @@ def section_lvd(device, warmup, rounds, clips=4, frames=14, opt=None):
     return st
 
 
+DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
+PEAK_16BIT_TFLOPS, PEAK_HBM_TBS = 2500.0, 8.0   # MI355X: dense bf16 / fp16 matrix rate, HBM3E bandwidth (data sheet)
+
+
+def section_op16(device, warmup, rounds, dtype):
+    res = {}
+    for name, seqs, nq, nk1, nk2 in OP_SHAPES:
+        ops32 = op_operands(seqs, nq, nk1, nk2, device)
+        # 16-bit operands as the modules hand them over: the slices of packed 16-bit projections
+        ops16 = tuple(None if t is None else t.to(dtype) for t in ops32)
+        if nk2 is None:
+            ops16 = (*torch.stack(ops16[:3], dim=2).unbind(2), None, None)
+        else:
+            ops16 = (ops16[0], *torch.stack(ops16[1:3], dim=2).unbind(2), *torch.stack(ops16[3:], dim=2).unbind(2))
+
+        def kernel16():
+            with WF.token_attention_16bit_route("kernel"):
+                assert WF._token_attention_served_16bit(*ops16) is not None
+                return WF.token_attention(*ops16)
+
+        with torch.no_grad():
+            routes = {"kernel16": kernel16, "framework16": lambda: WF.token_attention_framework(*ops16),
+                      "sdpa16": lambda: sdpa_route(*ops16), "kernel32": lambda: kernel_route(*ops32)}
+            ref = WF.token_attention_framework(*(None if t is None else t.double() for t in ops16))
+            err = {k: float((fn().double() - ref).abs().max()) for k, fn in routes.items() if k != "kernel32"}
+            del ref
+            st = alternate(routes, warmup, rounds)
+            for k, fn in routes.items():
+                st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+        med = {k: st[k]["median_ms"] for k in routes}
+        nk = nk1 + (nk2 or 0)
+        st["kernel16_over_kernel32"] = med["kernel16"] / med["kernel32"]
+        st["kernel16_over_framework16"] = med["kernel16"] / med["framework16"]
+        st["kernel16_over_sdpa16"] = med["kernel16"] / med["sdpa16"]
+        st["kernel16_beats_kernel32"] = bool(med["kernel16"] * (1 + st["spread"]) < med["kernel32"])
+        tflops = op_flops(seqs, nq, nk) / (med["kernel16"] * 1e-3) / 1e12
+        moved = 2.0 * seqs * HEADS * D * (2 * nq + 2 * nk)   # q and out once, k and v once: the least that crosses memory
+        st["bound_by"] = dict(kernel16_tflops=tflops, fraction_of_matrix_peak=tflops / PEAK_16BIT_TFLOPS,
+                              least_bytes=moved, least_bytes_tb_per_s=moved / (med["kernel16"] * 1e-3) / 1e12,
+                              fraction_of_hbm_peak=moved / (med["kernel16"] * 1e-3) / 1e12 / PEAK_HBM_TBS,
+                              flops_per_byte=op_flops(seqs, nq, nk) / moved)
+        st["max_abs_difference_from_fp64_framework"] = err
+        st["shape"] = dict(sequences=seqs, heads=HEADS, head_dim=D, queries=nq, keys=[nk1] + ([nk2] if nk2 else []))
+        res[name] = st
+        print(name, json.dumps({k: round(v, 4) for k, v in med.items()}), "spread", round(st["spread"], 3),
+              "beats fp32 kernel", st["kernel16_beats_kernel32"], "TFLOP/s", round(tflops, 1), flush=True)
+    res["kernel16_beats_kernel32_at_pose_shapes"] = bool(res["pose_56"]["kernel16_beats_kernel32"]
+                                                         and res["pose_112"]["kernel16_beats_kernel32"])
+    return res
+
+
+def section_lvd16(device, warmup, rounds, dtype, clips=4, frames=14):
+    from waldo_amd.nets import LVD
+    from waldo_amd.tools.lvd_step import recipe_net_opt
+    opt = recipe_net_opt()
+    torch.manual_seed(0)
+    net = LVD(opt).to(device).eval()
+    g = torch.Generator(device=device).manual_seed(1)
+    h, w = opt.dim, int(opt.dim * opt.aspect_ratio)
+    inp = torch.randn(clips, frames, opt.num_lyt + 2, h, w, generator=g, device=device)
+
+    def route(fused, act_dtype):
+        def fn():
+            net.fused, net.act_dtype = fused, act_dtype
+            return lvd_forward(net, inp, opt.ctx_len)
+        return fn
+
+    with torch.no_grad():
+        routes = {"fused_act_dtype": route(True, dtype), "fused_fp32": route(True, None),
+                  "framework_autocast": route(False, dtype)}
+        st = alternate(routes, warmup, rounds)
+    st["act_dtype_over_fp32"] = st["fused_act_dtype"]["median_ms"] / st["fused_fp32"]["median_ms"]
+    st["act_dtype_over_framework_autocast"] = st["fused_act_dtype"]["median_ms"] / st["framework_autocast"]["median_ms"]
+    st["shape"] = dict(clips=clips, frames=frames, embed_dim=opt.embed_dim, heads=opt.num_heads, raster=[h, w],
+                       num_obj=opt.num_obj, depths=[opt.oe_depth, opt.pe_depth])
+    print("lvd16", json.dumps({k: round(v["median_ms"], 3) for k, v in st.items() if isinstance(v, dict) and "median_ms" in v}),
+          "spread", round(st["spread"], 3), flush=True)
+    return st
+
+
+def section_step16(device, warmup, rounds, dtype, clips=4):
+    from waldo_amd.tools.lvd_step import LvdStep
+    steps = {"act_dtype": LvdStep(clips, device, nets="reference", act_dtype=dtype),
+             "fp32": LvdStep(clips, device, nets="reference"),
+             "framework_autocast": LvdStep(clips, device, nets="reference", act_dtype=dtype)}
+    steps["framework_autocast"].net.fused = False
+    st = alternate(steps, warmup, rounds)
+    st["act_dtype_over_framework_autocast"] = st["act_dtype"]["median_ms"] / st["framework_autocast"]["median_ms"]
+    st["act_dtype_over_fp32"] = st["act_dtype"]["median_ms"] / st["fp32"]["median_ms"]
+    st["shape"] = dict(clips=clips, frames=LvdStep.frames, nets="reference", mode="eager",
+                       backward_route=WF.get_token_attention_backward_route())
+    print("step16", json.dumps({k: round(v["median_ms"], 3) for k, v in st.items() if isinstance(v, dict) and "median_ms" in v}),
+          "spread", round(st["spread"], 3), flush=True)
+    return st
+
+
+def main_16bit(args, device):
+    dtype = DTYPES[args.dtype]
+    out = args.out16 or os.path.join(ROOT, "profiles", "lvd_nets_16bit.json")
+    doc = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            doc = json.load(fh)
+    part = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, limits=WF.token_attention_16bit_limits(),
+                head_dim=D, method=dict(rounds=args.rounds, warmup=args.warmup, timing="device events, routes alternating"))
+    sections = {"op16": section_op16, "lvd16": section_lvd16,
+                "step16": lambda *a: section_step16(*a, clips=args.clips)}
+    for sec in (args.sections16 or "op16,lvd16,step16").split(","):
+        part[sec] = sections[sec](device, args.warmup, args.rounds, dtype)
+        doc[args.dtype] = part
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as fh:
+            json.dump(doc, fh, indent=1, sort_keys=True)
+    print(out)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lvd_nets.json"))
@@ -262,6 +390,9 @@ def main():
     ap.add_argument("--clips", type=int, default=4, help="clips of the step section")
     ap.add_argument("--lib", help="another build of the library to bind instead of the product's")
     ap.add_argument("--head-dim", type=int, default=64, choices=(16, 32, 64), help="D of the op and bwd sections")
+    ap.add_argument("--dtype", choices=sorted(DTYPES), help="measure the 16-bit route: profiles/lvd_nets_16bit.json")
+    ap.add_argument("--out16", help="with --dtype: the file to write instead")
+    ap.add_argument("--sections16", help="with --dtype: of op16,lvd16,step16 (default: all three)")
     args = ap.parse_args()
     global HEADS, D
     HEADS, D = WIDTH // args.head_dim, args.head_dim
@@ -271,6 +402,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("ab_lvd_nets: no GPU (a measurement does not fall back)")
     device = torch.device("cuda:0")
+    if args.dtype:
+        return main_16bit(args, device)
     doc = {}
     if os.path.exists(args.out):
         with open(args.out) as fh:

@@ -167,6 +167,11 @@ SIGNATURES = {
                                                                             _stream],
     "waldo_token_attention_clips_bwd": [_c_f, _i64] * 3 + [_c_f] * 9 + [_flt, _i64, _int, _int, _i64, _i64, _int, _int,
                                                                         _stream],
+    # the two forwards on 16-bit operands and out: a WALDO_DTYPE_* code before the stream
+    "waldo_token_attention_fwd_dt": [_c_f, _i64, _i64] * 5 + [_c_f, _flt, _i64, _int, _int, _int, _int, _int, _int,
+                                                              _stream],
+    "waldo_token_attention_clips_fwd_dt": [_c_f, _i64] * 3 + [_c_f] * 3 + [_flt, _i64, _int, _int, _i64, _i64, _int, _int,
+                                                                           _int, _stream],
 }
 # workspace size of each *_det entry point (0: no deterministic kernel for the shape)
 DET_QUERIES = {
@@ -193,6 +198,7 @@ PLAIN = {"waldo_version": (_int, []), "waldo_max_layers": (_int, []),
          "waldo_adam_workspace_bytes": (_i64, [_i64, ctypes.POINTER(_i64)]),
          "waldo_token_attention_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_token_attention_bwd_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
+         "waldo_token_attention_dt_limits": (_int, [ctypes.POINTER(ctypes.c_int), _int]),
          "waldo_warp_composite_pts_supported": (_int, [_int, _int, _int, _int]),
          "waldo_last_error_string": (ctypes.c_char_p, []),
          "waldo_set_debug_option": (_int, [_int, _int]),

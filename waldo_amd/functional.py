@@ -2222,6 +2222,80 @@ class token_attention_backward_route:
         return False
 
 
+TOKEN_ATTENTION_16BIT_ROUTES = ("framework", "kernel")
+_token_attention_16bit_route = "framework"
+
+
+def get_token_attention_16bit_route():
+    """The route ``token_attention`` / ``token_attention_clips`` take on bf16 / fp16 operands now."""
+    return _token_attention_16bit_route
+
+
+class token_attention_16bit_route:
+    """``token_attention_16bit_route(route)`` sets what ``token_attention`` and ``token_attention_clips`` do with bf16 /
+    fp16 operands on the GPU: ``"framework"`` (the default) -- ``token_attention_framework`` /
+    ``token_attention_clips_framework``, as before there was a 16-bit kernel -- or ``"kernel"`` --
+    ``waldo_token_attention_fwd_dt`` / ``waldo_token_attention_clips_fwd_dt`` where the operands meet the layout rules
+    (``_token_attention_served_16bit``), also while autocast is enabled.  fp32 operands are not touched by the switch.
+    Used as ``with token_attention_16bit_route(route):`` the earlier setting comes back on exit, also after an
+    exception; nests.  The route is read when the op's forward runs."""
+
+    def __init__(self, route):
+        global _token_attention_16bit_route
+        if route not in TOKEN_ATTENTION_16BIT_ROUTES:
+            raise ValueError(f"token_attention_16bit_route: route must be one of {TOKEN_ATTENTION_16BIT_ROUTES}, "
+                             f"got {route!r}")
+        self.route = route
+        self.prev = _token_attention_16bit_route
+        _token_attention_16bit_route = route
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _token_attention_16bit_route
+        _token_attention_16bit_route = self.prev
+        return False
+
+
+def token_attention_16bit_limits():
+    """``token_attention_limits`` of the 16-bit kernels (``waldo_token_attention_dt_limits``)."""
+    return _token_attention_limits_of("waldo_token_attention_dt_limits")
+
+
+def _same_16bit_on_gpu(ts):
+    return ts[0].dtype in (torch.float16, torch.bfloat16) and all(
+        t.is_cuda and t.dtype == ts[0].dtype and t.device == ts[0].device for t in ts)
+
+
+def _token_view_strides_16bit(t):
+    """``_token_view_strides`` for 16-bit rows: strides in elements, multiples of 8 (16-byte pieces)."""
+    b, n, h, d = t.shape
+    if (d > 1 and t.stride(3) != 1) or (h > 1 and t.stride(2) != d) or t.data_ptr() % 16:
+        return None
+    sb, sn = (t.stride(0) if b > 1 else 0), (t.stride(1) if n > 1 else 0)
+    if sb % 8 or sn % 8 or sb < 0 or sn < 0:
+        return None
+    return sb, sn
+
+
+def _token_attention_served_16bit(q, k, v, k2, v2):
+    """The strides of the operands if the 16-bit kernel serves them as they lie under the route set now, else None:
+    bf16 or fp16 tensors of one type on one GPU, the route ``"kernel"``, D in the kernel's head dimensions, a unit inner
+    stride, heads D apart, rows on 16-byte boundaries.  Autocast does not matter: the operands already are 16-bit."""
+    if _token_attention_16bit_route != "kernel":
+        return None
+    ts = [t for t in (q, k, v, k2, v2) if t is not None]
+    if not _same_16bit_on_gpu(ts):
+        return None
+    if q.shape[3] not in token_attention_16bit_limits()["head_dims"] or q.numel() == 0:
+        return None
+    if k2 is not None and k2.shape[1] == 0:
+        return None
+    strides = [_token_view_strides_16bit(t) for t in ts]
+    return None if any(s is None for s in strides) else strides
+
+
 class _TokenAttention(torch.autograd.Function):
     """Forward: the kernel on the views as they lie; no score tensor is kept.  Backward, by the route read in the
     forward (``token_attention_backward_route``): ``"kernel"`` -- the forward ran ``waldo_token_attention_fwd_lse`` and
@@ -2284,6 +2358,34 @@ class _TokenAttention(torch.autograd.Function):
         return (None, None, None, *res, *([None] * (5 - len(res))))
 
 
+class _TokenAttention16(torch.autograd.Function):
+    """``_TokenAttention`` on bf16 / fp16 operands: the forward is ``waldo_token_attention_fwd_dt`` on the views as they
+    lie, ``out`` of the operands' type.  The backward is ALWAYS the ``"framework"`` one of ``_TokenAttention`` --
+    ``token_attention_framework`` recomputed from the saved views and differentiated -- whatever
+    ``token_attention_backward_route`` says: there is no 16-bit backward kernel."""
+
+    @staticmethod
+    def forward(ctx, scale, strides, code, q, k, v, k2, v2):
+        b, nq, h, d = q.shape
+        out = torch.empty(b, nq, h * d, dtype=q.dtype, device=q.device)
+        flat = []
+        for t, s in zip((q, k, v), strides):
+            flat += [t, s[0], s[1]]
+        if k2 is not None:
+            flat += [k2, strides[3][0], strides[3][1], v2, strides[4][0], strides[4][1]]
+        else:
+            flat += [None, 0, 0, None, 0, 0]
+        _lib.launch("waldo_token_attention_fwd_dt", q.device, *flat, out, float(scale), b, h, d, nq, k.shape[1],
+                    0 if k2 is None else k2.shape[1], code)
+        ctx.route, ctx.scale, ctx.two = "framework", scale, k2 is not None
+        ctx.save_for_backward(*((q, k, v, k2, v2) if ctx.two else (q, k, v)))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _TokenAttention.backward(ctx, grad_out)
+
+
 def token_attention(q, k, v, k2=None, v2=None, scale=None):
     """``softmax(scale q k^T) v`` per head over the keys of (k, v) followed by those of (k2, v2): q (B, Nq, H, D) and
     k / v (B, Nk, H, D), k2 / v2 (B, Nk2, H, D) or None -> (B, Nq, H D), the layout the output projection takes.
@@ -2296,12 +2398,20 @@ def token_attention(q, k, v, k2=None, v2=None, scale=None):
     set by ``token_attention_backward_route``: ``"kernel"`` is ``waldo_token_attention_bwd`` (the forward then also
     stores its row statistics, ``waldo_token_attention_fwd_lse``; no score tensor, no atomics, only the wanted
     gradients), ``"framework"`` recomputes ``token_attention_framework`` from the saved views and differentiates that.
-    Everything else -- CPU tensors, another D, another dtype (16-bit inputs, autocast), another layout -- IS
-    ``token_attention_framework`` end to end."""
+    bf16 / fp16 tensors on the GPU run ``waldo_token_attention_fwd_dt`` -- both products on the 16-bit matrix
+    instruction with fp32 accumulation, the softmax in fp32, ``out`` of the operands' type -- ONLY under
+    ``token_attention_16bit_route("kernel")``, then also while autocast is enabled; their strides are multiples of 8
+    elements.  Such a call differentiates by the ``"framework"`` route whatever ``token_attention_backward_route``
+    says: a 16-bit backward kernel is out of scope.
+    Everything else -- CPU tensors, another D, another dtype (16-bit inputs under the default 16-bit route, autocast),
+    another layout -- IS ``token_attention_framework`` end to end."""
     _token_attention_check(q, k, v, k2, v2)
     scale = q.shape[3] ** -0.5 if scale is None else float(scale)
     strides = _token_attention_served(q, k, v, k2, v2)
     if strides is None:
+        strides = _token_attention_served_16bit(q, k, v, k2, v2)
+        if strides is not None:
+            return _TokenAttention16.apply(scale, strides, _DTYPE_CODE[q.dtype], q, k, v, k2, v2)
         return token_attention_framework(q, k, v, k2, v2, scale)
     # the route travels with the node; a call that records no node (no gradient wanted) needs no row statistics
     route = _token_attention_backward_route
@@ -2385,6 +2495,25 @@ def _token_attention_clips_served(q, k, v, q_offsets, k_offsets):
     return None if any(s is None for s in strides) else strides
 
 
+def _token_attention_clips_served_16bit(q, k, v, q_offsets, k_offsets):
+    """``_token_attention_served_16bit`` for the packed operands of ``token_attention_clips``: their token strides, or
+    None."""
+    if _token_attention_16bit_route != "kernel" or not _same_16bit_on_gpu((q, k, v)):
+        return None
+    if q.shape[2] not in token_attention_16bit_limits()["head_dims"] or q.numel() == 0 or k.numel() == 0:
+        return None
+    if not (q_offsets.is_contiguous() and k_offsets.is_contiguous()):
+        return None
+    strides = []
+    for t in (q, k, v):
+        r, h, d = t.shape
+        sn = t.stride(0) if r > 1 else 0
+        if (d > 1 and t.stride(2) != 1) or (h > 1 and t.stride(1) != d) or t.data_ptr() % 16 or sn % 8 or sn < 0:
+            return None
+        strides.append(sn)
+    return strides
+
+
 class _TokenAttentionClips(torch.autograd.Function):
     """``_TokenAttention`` for per-clip segments: the kernel on the packed views as they lie; the backward by the route
     read in the forward -- ``"kernel"``: ``waldo_token_attention_clips_bwd`` from the saved ``out`` and ``lse``;
@@ -2432,6 +2561,26 @@ class _TokenAttentionClips(torch.autograd.Function):
         return (None, None, None, None, *[next(grads) if n else None for n in need], None, None)
 
 
+class _TokenAttentionClips16(torch.autograd.Function):
+    """``_TokenAttentionClips`` on bf16 / fp16 operands: ``waldo_token_attention_clips_fwd_dt`` forward, and always the
+    ``"framework"`` backward of ``_TokenAttentionClips`` (no 16-bit backward kernel)."""
+
+    @staticmethod
+    def forward(ctx, scale, strides, code, bounds, q, k, v, q_offsets, k_offsets):
+        rq, h, d = q.shape
+        out = torch.empty(rq, h * d, dtype=q.dtype, device=q.device)
+        shape = (q_offsets.numel() - 1, h, d, rq, k.shape[0], int(bounds[0]), int(bounds[1]))
+        ctx.route, ctx.scale, ctx.strides, ctx.shape = "framework", scale, strides, shape
+        _lib.launch("waldo_token_attention_clips_fwd_dt", q.device, q, strides[0], k, strides[1], v, strides[2],
+                    q_offsets, k_offsets, out, float(scale), *shape, code)
+        ctx.save_for_backward(q, k, v, q_offsets, k_offsets)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _TokenAttentionClips.backward(ctx, grad_out)
+
+
 def token_attention_clips(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, scale=None):
     """``softmax(scale q k^T) v`` per head within each clip of PACKED rows: q (Rq, H, D) and k / v (Rk, H, D) hold the
     rows of all clips one after the other, clip b's queries are the rows ``[q_offsets[b], q_offsets[b + 1])`` and its
@@ -2447,12 +2596,17 @@ def token_attention_clips(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, s
 
     fp32 tensors on the GPU that ``waldo_token_attention_clips_fwd`` serves (as ``token_attention``: D in
     ``token_attention_limits()["head_dims"]``, unit inner stride, heads D apart, rows on 16-byte boundaries, Rk > 0)
-    run the kernel, with the backward set by ``token_attention_backward_route``; everything else IS
-    ``token_attention_clips_framework``."""
+    run the kernel, with the backward set by ``token_attention_backward_route``; bf16 / fp16 tensors run
+    ``waldo_token_attention_clips_fwd_dt`` under ``token_attention_16bit_route("kernel")`` (as ``token_attention``:
+    forward only, the ``"framework"`` backward); everything else IS ``token_attention_clips_framework``."""
     _token_attention_clips_check(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len)
     scale = q.shape[2] ** -0.5 if scale is None else float(scale)
     strides = _token_attention_clips_served(q, k, v, q_offsets, k_offsets)
     if strides is None:
+        strides = _token_attention_clips_served_16bit(q, k, v, q_offsets, k_offsets)
+        if strides is not None:
+            return _TokenAttentionClips16.apply(scale, strides, _DTYPE_CODE[q.dtype], (int(max_q_len), int(max_k_len)),
+                                                q, k, v, q_offsets, k_offsets)
         return token_attention_clips_framework(q, k, v, q_offsets, k_offsets, max_q_len, max_k_len, scale)
     route = _token_attention_backward_route
     if route == "kernel" and not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))):

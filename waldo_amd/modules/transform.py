@@ -9,6 +9,9 @@ matmul -> scale -> softmax -> matmul with the permutes of the packed projections
 sets and the transpose in front of ``proj`` -- is one hand-written kernel, ``WF.token_attention``, which reads the
 slices of ``qkv`` / ``kv`` where they lie.  ``fused = False`` (an attribute of every attention module; ``MultiBlocks``
 and ``Block`` pass an assignment on) runs the reference's sequence of framework ops instead, and is the route on the CPU.
+Under autocast the slices are 16-bit and take the framework route too, unless the caller has set
+``WF.token_attention_16bit_route("kernel")`` -- as the networks' ``act_dtype`` does (nets/lvd.py ``_Net``) -- which
+serves them with the 16-bit forward kernels.
 
 With ``ctx_mask`` -- the future layer predictor's clips, of which a (B, T) mask selects the frames -- the tokens stay
 PACKED, (B', N, C) over the selected frames as the reference's ``to_ctx`` leaves them, and the attention is

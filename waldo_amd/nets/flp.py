@@ -247,12 +247,14 @@ class PoseDecoder(_Net):
         blocks, pred = plan.blocks, plan.pred_blocks
         x_ctx, x_pred = _select(x, blocks.index), _select(x, blocks.rest)
         z_cond = torch.randn([x_pred.size(0), 1, c], device=x.device, dtype=x.dtype) if self.modulate_noise else None
-        for self_block, cross_block in zip(self.self_blocks, self.cross_blocks):
-            x_pred = self_block(x_pred, ctx_mask=pred, z_cond=z_cond)
-            x_pred = cross_block(x_pred, x_ctx=x_ctx, ctx_mask=blocks)
-        x_pred = self.norm(x_pred)
-        x_obj = self.obj_head(x_pred[:, 1:]).view(-1, no, 6 + 2 * lo + 1)
-        x_bg = self.bg_head(x_pred[:, :1]).view(-1, 1, 6 + 2 * l)
+        with self._act_region(x):
+            for self_block, cross_block in zip(self.self_blocks, self.cross_blocks):
+                x_pred = self_block(x_pred, ctx_mask=pred, z_cond=z_cond)
+                x_pred = cross_block(x_pred, x_ctx=x_ctx, ctx_mask=blocks)
+            x_pred = self.norm(x_pred)
+            x_obj = self.obj_head(x_pred[:, 1:]).view(-1, no, 6 + 2 * lo + 1)
+            x_bg = self.bg_head(x_pred[:, :1]).view(-1, 1, 6 + 2 * l)
+        x_obj, x_bg = self._fp32(x_obj, x_bg)   # poses and occlusion scores: the warp path's
         pred_obj, pred_occ, pred_bg = x_obj[:, :, :-1].tanh(), x_obj[:, :, -1], x_bg.tanh()
         if self.use_last:
             pred_obj = pred_obj + last_obj.index_select(0, plan.rest_clip)
@@ -265,7 +267,9 @@ class PoseDecoder(_Net):
 
 
 class FLP(_Net):
-    """flp.py:8-29.  ``ctx_mask``: a boolean (B, T) tensor, as in the reference, or a ``FlpPlan``."""
+    """flp.py:8-29.  ``ctx_mask``: a boolean (B, T) tensor, as in the reference, or a ``FlpPlan``.  ``act_dtype``
+    (``_Net.act_dtype``): the compressor, the encoder and the decoder's blocks and heads under autocast with the 16-bit
+    attention kernel; the predicted poses and occlusion scores leave in fp32."""
 
     def __init__(self, opt):
         super().__init__()
@@ -284,6 +288,7 @@ class FLP(_Net):
         if ctx_mask is None:
             raise ValueError("FLP: ctx_mask is required")
         plan = FlpPlan.of(ctx_mask, self.num_obj + 1, self.cat_z)
-        z = torch.cat([self.compress(x_bg.unsqueeze(1)), self.compress(x_obj)], dim=1)
-        x = self.encode(obj_pose, bg_pose, occ_score, z, plan)
+        with self._act_region(x_obj):
+            z = torch.cat([self.compress(x_bg.unsqueeze(1)), self.compress(x_obj)], dim=1)
+            x = self.encode(obj_pose, bg_pose, occ_score, z, plan)
         return self.decode(obj_pose, bg_pose, occ_score, x, plan, last_obj, last_bg)

@@ -21,6 +21,8 @@ The occlusion products never materialise the reference's (L, L, h, w) broadcast,
 The networks in front of the path -- ``ImageEncoder``, ``LayerEstimator``, ``PoseEstimator``, ``ImageDecoder`` and the
 ``LVD`` module that holds them with the ``Warper`` -- follow at the end of the file.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -818,11 +820,12 @@ def _set_fused(module, value):
 
 class _Net(nn.Module):
     """A network with the ``fused`` switch: True (default) the hand-written kernels where they exist, False framework
-    ops only.  Setting it sets every sub-module's."""
+    ops only.  Setting it sets every sub-module's.  ``act_dtype``: see the property."""
 
     def __init__(self):
         super().__init__()
         self._fused = True
+        self._act_dtype = None
 
     @property
     def fused(self):
@@ -832,6 +835,41 @@ class _Net(nn.Module):
     def fused(self, value):
         self._fused = bool(value)
         _set_fused(self, value)
+
+    @property
+    def act_dtype(self):
+        """None: the caller's precision.  torch.bfloat16 / torch.float16: the network's layers -- its projections, its
+        transformer blocks and its heads -- run inside ``torch.autocast(device, dtype=act_dtype)`` with fp32 master
+        weights, and the blocks' attention on the 16-bit slices of ``qkv`` / ``kv`` is the 16-bit kernel
+        (``WF.token_attention_16bit_route("kernel")`` for the duration; ``fused = False``: the framework's chain under
+        the same autocast).  What a network hands to the warp path -- poses, occlusion scores, alpha images, class
+        weights -- is cast to fp32 where the region ends.  Setting it sets every sub-network's."""
+        return self._act_dtype
+
+    @act_dtype.setter
+    def act_dtype(self, dtype):
+        if dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError(f"{type(self).__name__}: act_dtype must be None, torch.bfloat16 or torch.float16, "
+                             f"got {dtype!r}")
+        for m in self.modules():
+            if isinstance(m, _Net):
+                m._act_dtype = dtype
+
+    @contextlib.contextmanager
+    def _act_region(self, like):
+        """The region ``act_dtype`` describes, on the device of the tensor ``like``; nothing at all without it."""
+        if self._act_dtype is None:
+            yield
+            return
+        with torch.autocast(like.device.type, dtype=self._act_dtype), WF.token_attention_16bit_route("kernel"):
+            yield
+
+    def _fp32(self, *tensors):
+        """Where the region ends: ``tensors`` in fp32 (as they are without ``act_dtype``; None stays None)."""
+        if self._act_dtype is None:
+            return tensors if len(tensors) > 1 else tensors[0]
+        out = tuple(None if t is None else t.float() for t in tensors)
+        return out if len(out) > 1 else out[0]
 
 
 class ImageEncoder(_Net):
@@ -848,7 +886,8 @@ class ImageEncoder(_Net):
         """vid (..., C, H, W) -> tokens (..., L, embed) (``return_list``: the pyramid of the flattened batch)."""
         lead = vid.shape[:-3]
         img = scale(vid.reshape(-1, *vid.shape[-3:]), 1 / self.scale_factor)
-        x = self.from_img(img, return_list=return_list)
+        with self._act_region(img):
+            x = self.from_img(img, return_list=return_list)
         return x if return_list else x.reshape(*lead, *x.shape[1:])
 
 
@@ -884,7 +923,10 @@ class ImageDecoder(_Net):
             skip = skip.reshape(-1, *skip.shape[-3:])
         if fuse_m is not None and fuse_m.ndim == 5:
             fuse_m = fuse_m.reshape(-1, *fuse_m.shape[2:])
-        img = self.to_img(self.norm(x), latent_shape=self.latent_shape[x.size(1)], x_list=x_list, fuse_m=fuse_m, skip=skip)
+        with self._act_region(x):
+            img = self.to_img(self.norm(x), latent_shape=self.latent_shape[x.size(1)], x_list=x_list, fuse_m=fuse_m,
+                              skip=skip)
+        img = self._fp32(img)   # the alpha image: the warp path's
         if self.fused and img.is_cuda and float(self.scale_factor) == int(self.scale_factor):
             img = decoder_tail(img, circle=self.circle if self.use_prior else None, init_bias=float(self.init_bias),
                                scale_factor=int(self.scale_factor), has_alpha=self.has_alpha, use_prior=self.use_prior,
@@ -1051,9 +1093,11 @@ class PoseEstimator(_Net):
         no, lo = x_obj.shape[1:3]
         nbg = l if self.has_bg else 0
         per_clip = lambda v: v.reshape(b, t, *v.shape[1:])
-        tokens = self.blocks(self._sequence(x, x_obj, x_bg))[:, :nbg + no * lo]   # the layers' tokens, background first
         own_bg = self.has_bg and not self.fix_bg
-        out = self.head(self.norm(tokens if own_bg else tokens[:, nbg:]))
+        with self._act_region(x):
+            tokens = self.blocks(self._sequence(x, x_obj, x_bg))[:, :nbg + no * lo]   # the layers' tokens, background first
+            out = self.head(self.norm(tokens if own_bg else tokens[:, nbg:]))
+        out = self._fp32(out)   # poses and occlusion scores: the warp path's
         pose, scl, occ = out.split([self.pose_size, self.scale_size, self.occ_size], dim=2)
         bg = pose[:, :l] if own_bg else None
         pose, scl, occ = (v[:, -no * lo:] for v in (pose, scl, occ))
@@ -1121,6 +1165,11 @@ class LayerEstimator(_Net):
     def forward(self, x):
         """x (B, T, L, C), the context frames' tokens -> (x_obj (B, No, Lo, C), x_bg (B, L, C) or None, cls (B, No, Nl)
         or None)."""
+        with self._act_region(x):
+            x_obj, x_bg, cls = self._forward(x)
+        return x_obj, x_bg, self._fp32(cls)
+
+    def _forward(self, x):
         b, t, l, c = x.shape
         no, lo = self.num_obj, self.latent_obj_size
         x = (x + self.pos_embed + self.time_embed[:, :t]).reshape(b, t, l, c)
@@ -1140,7 +1189,10 @@ class LayerEstimator(_Net):
 class LVD(_Net):
     """lvd.py:11-155, the modes a reconstruction runs: ``encode_input``, ``estimate_layer``, ``estimate_pose``,
     ``estimate_alpha_grid_occ`` and ``decode_output``.  The refiners, the edge filter and ``time_dropout`` belong to
-    training variants the recipe does not use and are refused in the constructor; ``decode_layer`` is not served."""
+    training variants the recipe does not use and are refused in the constructor; ``decode_layer`` is not served.
+    ``act_dtype`` (``_Net.act_dtype``): the encoder, the two estimators and the decoder's projection run under autocast
+    with the 16-bit attention kernel; the ``Warper`` and everything ``estimate_alpha_grid_occ`` / ``decode_output`` hand
+    it stay fp32."""
 
     def __init__(self, opt):
         super().__init__()

@@ -897,12 +897,15 @@ def predict_future(opt, lvd, flp, wif, real_vid, real_lyt, real_flow, ctx_len):
 
 
 def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj=3, num_lyt=20, frames=6, ctx_len=4,
-            device="cuda:0", lvd_over=None, wif_ckpt=None, ii_depth=4, ii_embed_dim=512, flp_ckpt=None, flp_over=None):
+            device="cuda:0", lvd_over=None, wif_ckpt=None, ii_depth=4, ii_embed_dim=512, flp_ckpt=None, flp_over=None,
+            nets_dtype=None):
     """``--lvd-ckpt``: the clip through ``reconstruct`` with a reference ``pe`` checkpoint; ``rec_vid`` and
     ``inp_rec_vid`` written by the writers ``run`` uses.  ``lvd_over``: the checkpoint's training options where they
     differ from ``lvd_demo_opt(demo_opt(...))`` (``--lvd-opt FILE``: a JSON object).  ``flp_ckpt`` (``--flp-ckpt``): a
     reference ``pg`` checkpoint too -- the frames after ``ctx_len`` through ``predict_future`` as well (``pred_vid``,
-    ``fused_pred_vid``); ``flp_over``: its training options where they differ from ``flp_demo_opt`` (``--flp-opt``)."""
+    ``fused_pred_vid``); ``flp_over``: its training options where they differ from ``flp_demo_opt`` (``--flp-opt``).
+    ``nets_dtype`` (``--nets-dtype``; torch.bfloat16 / torch.float16): the ``act_dtype`` of the LVD and FLP networks --
+    under autocast with the 16-bit attention kernel; the warp path stays fp32."""
     from ..nets.flp import FLP
     from ..nets.lvd import LVD
     opt = demo_opt(dim, aspect_ratio, num_obj, num_lyt, ctx_len=ctx_len, ii_depth=ii_depth, ii_embed_dim=ii_embed_dim)
@@ -916,6 +919,7 @@ def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj
             raise ValueError(f"run_lvd: the networks take the flow as input and {clip_dir} has no flow files next to it")
         flow = torch.nn.functional.interpolate(clip["flow"].to(dev), size=vid.shape[-2:], mode="bilinear").unsqueeze(0)
     lvd = load_lvd_checkpoint(LVD(nopt), lvd_ckpt).to(dev).eval()
+    lvd.act_dtype = nets_dtype
     if wif_ckpt is not None:
         wif = load_wif_checkpoint(WIF.with_unet(opt), wif_ckpt).to(dev).eval()
     else:
@@ -924,6 +928,7 @@ def run_lvd(clip_dir, lvd_ckpt, out_dir=None, dim=128, aspect_ratio=1.0, num_obj
     keys = ("rec_vid", "inp_rec_vid")
     if flp_ckpt is not None:
         flp = load_flp_checkpoint(FLP(flp_demo_opt(nopt, **(flp_over or {}))), flp_ckpt).to(dev).eval()
+        flp.act_dtype = nets_dtype
         future = predict_future(nopt, lvd, flp, wif, vid, lyt, flow, ctx_len)
         res.update(pred_vid=future["pred_vid"], fused_pred_vid=future["fused_pred_vid"])
         keys += ("pred_vid", "fused_pred_vid")
@@ -1015,7 +1020,12 @@ def main():
     ap.add_argument("--flp-opt", default=None, metavar="FILE",
                     help="with --flp-ckpt: a JSON object of the checkpoint's training options (pg_enc_depth, "
                          "pg_num_timesteps, cat_z, ...) where they differ from the defaults")
+    ap.add_argument("--nets-dtype", choices=sorted(RAW_DTYPES), default="fp32",
+                    help="with --lvd-ckpt: the element type of the LVD / FLP networks' activations (bf16 / fp16: under "
+                         "autocast, with the 16-bit token attention kernel; poses, grids and the warp path stay fp32)")
     args = ap.parse_args()
+    if args.nets_dtype != "fp32" and args.lvd_ckpt is None:
+        ap.error("--nets-dtype needs --lvd-ckpt: the seeded stand-ins have no networks")
     if args.flp_ckpt is not None and args.lvd_ckpt is None:
         ap.error("--flp-ckpt needs --lvd-ckpt: FLP predicts the poses the LVD networks estimate")
     if args.lvd_ckpt is not None:
@@ -1027,7 +1037,8 @@ def main():
                     over[name] = json.load(fh)
         res = run_lvd(args.clip, args.lvd_ckpt, args.out, args.dim, args.aspect_ratio, args.num_obj, frames=args.frames,
                       ctx_len=args.ctx_len, lvd_over=over.get("lvd_opt"), wif_ckpt=args.wif_ckpt, ii_depth=args.ii_depth,
-                      ii_embed_dim=args.ii_embed_dim, flp_ckpt=args.flp_ckpt, flp_over=over.get("flp_opt"))
+                      ii_embed_dim=args.ii_embed_dim, flp_ckpt=args.flp_ckpt, flp_over=over.get("flp_opt"),
+                      nets_dtype=RAW_DTYPES[args.nets_dtype])
         for k, v in res.items():
             if v is not None:
                 print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "

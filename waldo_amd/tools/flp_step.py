@@ -58,12 +58,13 @@ class FlpStep:
     graph's inputs (new data written into them is a new step), the returned loss, ``terms`` and the gradients its
     outputs, overwritten by every replay.  ``optimizer``: None, "adam", "adamw" (the reference's defaults) or an
     ``optim.Adam`` over FLP's parameters; the step then ends in ``optimizer.step(loss)`` (in the graph too: a replay
-    trains), and ``step.optimizer`` is it."""
+    trains), and ``step.optimizer`` is it.  ``act_dtype``: the ``act_dtype`` of both networks (torch.bfloat16 /
+    torch.float16: under autocast with the 16-bit attention kernel; the poses stay fp32)."""
 
     num_lyt = 20
 
     def __init__(self, clips, device, seed=0, frames=14, ctx_len=4, objective="kernel", graph=False, lvd_over=None,
-                 flp_over=None, dim=128, aspect_ratio=2, optimizer=None):
+                 flp_over=None, dim=128, aspect_ratio=2, optimizer=None, act_dtype=None):
         if objective not in OBJECTIVES:
             raise ValueError(f"FlpStep: objective must be one of {OBJECTIVES}, got {objective!r}")
         if not 0 < ctx_len < frames:
@@ -87,6 +88,7 @@ class FlpStep:
             torch.manual_seed(seed)
             self.lvd = LVD(self.lvd_opt).to(device).eval()
             self.flp = FLP(self.flp_opt).to(device)
+        self.lvd.act_dtype = self.flp.act_dtype = act_dtype
         for p in self.lvd.parameters():
             p.requires_grad_(False)
         self.leaves = list(self.flp.parameters())

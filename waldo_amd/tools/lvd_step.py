@@ -67,11 +67,14 @@ class LvdStep:
     """``clips`` clips of 5 frames resident on ``device``; ``__call__`` runs forward, loss and backward once and
     returns the loss (the leaves' ``.grad`` hold the gradients).  ``optimizer`` (with ``nets="reference"``): None, "adam",
     "adamw" or an ``optim.Adam`` over the networks' parameters; the step then ends in ``optimizer.step(loss)``, and
-    ``step.optimizer`` is it."""
+    ``step.optimizer`` is it.  ``act_dtype`` (with ``nets="reference"``): the networks' ``act_dtype`` -- torch.bfloat16
+    or torch.float16: they run under autocast with the 16-bit attention kernel, the warp path stays fp32."""
 
     frames, num_lyt = 5, 20
 
-    def __init__(self, clips, device, seed=0, objective="stand-in", nets="stand-in", optimizer=None):
+    def __init__(self, clips, device, seed=0, objective="stand-in", nets="stand-in", optimizer=None, act_dtype=None):
+        if act_dtype is not None and nets != "reference":
+            raise ValueError("LvdStep: act_dtype needs nets='reference' (the stand-in step has no networks)")
         if objective not in OBJECTIVES:
             raise ValueError(f"LvdStep: objective must be one of {OBJECTIVES}, got {objective!r}")
         if nets not in NETS:
@@ -115,6 +118,7 @@ class LvdStep:
             with torch.random.fork_rng(devices=[]):
                 torch.manual_seed(seed)
                 self.net = LVD(recipe_net_opt()).to(device)
+            self.net.act_dtype = act_dtype
             if self.real_flow is None:
                 self.real_flow = 0.05 * torch.randn(b, t, 2, h, w, generator=g, device=device)
             self.leaves = list(self.net.parameters())
