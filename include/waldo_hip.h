@@ -1104,7 +1104,7 @@ int waldo_token_attention_bwd(const float* q, int64_t qs_b, int64_t qs_n, const 
                               float* grad_v1, float* grad_k2, float* grad_v2, float scale, int64_t B, int H, int D,
                               int Nq, int Nk1, int Nk2, waldo_stream_t stream);
 
-/* Token attention on 16-bit operands, the forward: waldo_token_attention_fwd_dt is waldo_token_attention_fwd and
+/* Token attention on 16-bit operands: waldo_token_attention_fwd_dt is waldo_token_attention_fwd and
  * waldo_token_attention_clips_fwd_dt is waldo_token_attention_clips_fwd (next section) with q, k, v and out of ONE
  * 16-bit element type, dtype = WALDO_DTYPE_F16 or WALDO_DTYPE_BF16, passed as void*.  Strides are in ELEMENTS and are
  * multiples of 8 (rows are read in 16-byte pieces of 8 values); every pointer is on a 16-byte boundary; D is 16, 32 or
@@ -1114,15 +1114,44 @@ int waldo_token_attention_bwd(const float* q, int64_t qs_b, int64_t qs_n, const 
  *   and l sums the unrounded p; p is rounded to the element type only as the operand of the second product; o is
  *   accumulated and rescaled in fp32; one rounding (nearest even; a NaN stays a NaN) at the store.
  * No score matrix, no workspace, no atomics: the same bits from run to run; the caller's stream; capturable in a graph.
- * A clip with queries and no keys gets NaN rows.  There is no _lse form and no backward on 16-bit operands.
+ * A clip with queries and no keys gets NaN rows.
+ *
+ * The dense form has a backward.  waldo_token_attention_fwd_lse_dt is waldo_token_attention_fwd_dt with one more
+ * output after out: lse (B, H, Nq) contiguous FP32, the row's m + log(l) of the scaled scores; out has the bits of
+ * waldo_token_attention_fwd_dt's.  waldo_token_attention_bwd_dt is waldo_token_attention_bwd on such operands: the
+ * views, out (the forward's STORED 16-bit out), grad_out (B, Nq, H D) contiguous and the five gradients -- contiguous
+ * (B, N, H, D) tensors of the element type, OVERWRITTEN, NULL: not wanted -- are void*; lse and delta (B, H, Nq, the
+ * call's only workspace) are float*.  One call makes three launches at the most (the delta pass, the dQ kernel unless
+ * grad_q is NULL, the dK/dV kernel unless its four gradients are); no score-sized memory, no atomics -- every gradient
+ * element is summed by one lane in one order.  Its arithmetic:
+ *   delta[b, h, i] = sum_d dO[i, d] O[i, d], one fp32 fma chain over d; a recomputed score and dP = dO V^T are fp32
+ *   sums of exact 16-bit products; P = exp(scale S - lse) and dS = P o (dP - delta) are fp32; dS and P are rounded to
+ *   the element type ONLY as operands of dQ = dS K, dK = dS^T Q and of dV = P^T dO, which are accumulated in fp32;
+ *   scale multiplies the fp32 accumulators of dQ and dK once, after the sum; one rounding (nearest even) at the store.
+ * A batch stride of 0 is read as it is: gradients are per batch element.  All five gradients NULL, B == 0 or Nq == 0
+ * return WALDO_OK without a launch.
+ * The per-clip form has neither: there is no _lse form and no backward on 16-bit operands for
+ * waldo_token_attention_clips_fwd_dt (its callers differentiate by recomputing in framework ops; the future layer
+ * predictor's shapes are launch-bound and gain nothing from 16-bit kernels).
  * Refusals: WALDO_DTYPE_F32 ("is served by" the fp32 entry point, which the message names) and an unknown code
  * ("unknown dtype") before anything else; then the fp32 entry point's, in its order and words, with "a multiple of 8
- * values" for the strides. */
+ * values" for the strides ("null pointer" covers out, grad_out, lse and delta; "not aligned" every non-NULL pointer). */
 int waldo_token_attention_dt_limits(int* out, int n);
 int waldo_token_attention_fwd_dt(const void* q, int64_t qs_b, int64_t qs_n, const void* k1, int64_t k1s_b, int64_t k1s_n,
                                  const void* v1, int64_t v1s_b, int64_t v1s_n, const void* k2, int64_t k2s_b,
                                  int64_t k2s_n, const void* v2, int64_t v2s_b, int64_t v2s_n, void* out, float scale,
                                  int64_t B, int H, int D, int Nq, int Nk1, int Nk2, int dtype, waldo_stream_t stream);
+int waldo_token_attention_fwd_lse_dt(const void* q, int64_t qs_b, int64_t qs_n, const void* k1, int64_t k1s_b,
+                                     int64_t k1s_n, const void* v1, int64_t v1s_b, int64_t v1s_n, const void* k2,
+                                     int64_t k2s_b, int64_t k2s_n, const void* v2, int64_t v2s_b, int64_t v2s_n, void* out,
+                                     float* lse, float scale, int64_t B, int H, int D, int Nq, int Nk1, int Nk2, int dtype,
+                                     waldo_stream_t stream);
+int waldo_token_attention_bwd_dt(const void* q, int64_t qs_b, int64_t qs_n, const void* k1, int64_t k1s_b, int64_t k1s_n,
+                                 const void* v1, int64_t v1s_b, int64_t v1s_n, const void* k2, int64_t k2s_b,
+                                 int64_t k2s_n, const void* v2, int64_t v2s_b, int64_t v2s_n, const void* out,
+                                 const void* grad_out, const float* lse, float* delta, void* grad_q, void* grad_k1,
+                                 void* grad_v1, void* grad_k2, void* grad_v2, float scale, int64_t B, int H, int D,
+                                 int Nq, int Nk1, int Nk2, int dtype, waldo_stream_t stream);
 int waldo_token_attention_clips_fwd_dt(const void* q, int64_t qs_n, const void* k, int64_t ks_n, const void* v,
                                        int64_t vs_n, const int* q_off, const int* k_off, void* out, float scale,
                                        int64_t B, int H, int D, int64_t Rq, int64_t Rk, int max_q_len, int max_k_len,

@@ -9,6 +9,7 @@ at the LVD recipe's shapes (scripts/cityscapes/train_lvd.sh: 512 wide, 8 heads, 
     python tools_dev/ab_lvd_nets.py --out FILE --sections op,bwd --head-dim 16 --lib tools_dev/_variants/NAME.so
 
     python tools_dev/ab_lvd_nets.py --dtype bf16        (writes profiles/lvd_nets_16bit.json: sections op16,lvd16,step16)
+    python tools_dev/ab_lvd_nets.py --dtype bf16 --sections16 bwd16,step16      (writes profiles/lvd_nets_16bit_bwd.json)
 
 --dtype bf16 | fp16 measures the 16-bit route (WF.token_attention_16bit_route("kernel"), ``act_dtype``) instead:
   op16   at the four op shapes, in one process: ``kernel16`` (waldo_token_attention_fwd_dt on the 16-bit operands),
@@ -18,7 +19,13 @@ at the LVD recipe's shapes (scripts/cityscapes/train_lvd.sh: 512 wide, 8 heads, 
          bytes of the operands and out over the time;
   lvd16  the whole LVD forward: ``act_dtype`` fused, fp32 fused, and ``fused = False`` under the same autocast;
   step16 ``LvdStep(--clips, nets="reference")`` with ``act_dtype`` against fp32 and against ``fused = False`` under the same
-         autocast (all with the default backward route).
+         autocast (all with the default backward route), and with ``act_dtype`` under
+         WF.token_attention_16bit_backward_route("kernel") (``act_dtype_kernel_backward``);
+  bwd16  forward + backward of the op at the four op shapes, the gradient of a fixed ``grad_out`` in every operand:
+         ``kernel16`` (both 16-bit switches on "kernel": waldo_token_attention_fwd_lse_dt + waldo_token_attention_bwd_dt),
+         ``recompute16`` (the 16-bit forward kernel, the backward recomputing WF.token_attention_framework in 16 bits:
+         the route before the 16-bit backward), ``kernel32`` (the fp32 kernels on fp32 copies) and ``sdpa16`` with its
+         own backward in the same type; ms and peak bytes each.  ``kernel16_beats_recompute16``: by more than the spread.
 
 --lib binds another build of the library (``_lib.use_library``: tools_dev/build_variant.py makes one) for an A/B of two
 builds in two processes; --head-dim D runs ``op`` and ``bwd`` at another head dimension with the same token counts and
@@ -273,12 +280,7 @@ def section_op16(device, warmup, rounds, dtype):
     res = {}
     for name, seqs, nq, nk1, nk2 in OP_SHAPES:
         ops32 = op_operands(seqs, nq, nk1, nk2, device)
-        # 16-bit operands as the modules hand them over: the slices of packed 16-bit projections
-        ops16 = tuple(None if t is None else t.to(dtype) for t in ops32)
-        if nk2 is None:
-            ops16 = (*torch.stack(ops16[:3], dim=2).unbind(2), None, None)
-        else:
-            ops16 = (ops16[0], *torch.stack(ops16[1:3], dim=2).unbind(2), *torch.stack(ops16[3:], dim=2).unbind(2))
+        ops16 = packed16(ops32, dtype)
 
         def kernel16():
             with WF.token_attention_16bit_route("kernel"):
@@ -313,6 +315,62 @@ def section_op16(device, warmup, rounds, dtype):
               "beats fp32 kernel", st["kernel16_beats_kernel32"], "TFLOP/s", round(tflops, 1), flush=True)
     res["kernel16_beats_kernel32_at_pose_shapes"] = bool(res["pose_56"]["kernel16_beats_kernel32"]
                                                          and res["pose_112"]["kernel16_beats_kernel32"])
+    return res
+
+
+def packed16(ops32, dtype):
+    """16-bit operands as the modules hand them over: the slices of packed 16-bit projections."""
+    ops16 = tuple(None if t is None else t.to(dtype) for t in ops32)
+    if ops16[3] is None:
+        return (*torch.stack(ops16[:3], dim=2).unbind(2), None, None)
+    return (ops16[0], *torch.stack(ops16[1:3], dim=2).unbind(2), *torch.stack(ops16[3:], dim=2).unbind(2))
+
+
+def section_bwd16(device, warmup, rounds, dtype):
+    res = {}
+    for name, seqs, nq, nk1, nk2 in OP_SHAPES:
+        ops32 = op_operands(seqs, nq, nk1, nk2, device)
+        go32 = torch.randn(seqs, nq, HEADS * D, generator=torch.Generator(device=device).manual_seed(1), device=device)
+        go16 = go32.to(dtype)
+        leaves16 = [None if t is None else t.detach().requires_grad_() for t in packed16(ops32, dtype)]
+        leaves32 = [None if t is None else t.detach().requires_grad_() for t in ops32]
+        wanted16, wanted32 = [t for t in leaves16 if t is not None], [t for t in leaves32 if t is not None]
+
+        def kernel16(bwd_route):
+            def run():
+                with WF.token_attention_16bit_route("kernel"), WF.token_attention_16bit_backward_route(bwd_route):
+                    assert WF._token_attention_served_16bit(*leaves16) is not None
+                    out = WF.token_attention(*leaves16)
+                return torch.autograd.grad(out, wanted16, go16)
+            return run
+
+        def kernel32():
+            with WF.token_attention_backward_route("kernel"):
+                out = kernel_route(*leaves32)
+            return torch.autograd.grad(out, wanted32, go32)
+
+        routes = {"kernel16": kernel16("kernel"), "recompute16": kernel16("framework"), "kernel32": kernel32,
+                  "sdpa16": lambda: torch.autograd.grad(sdpa_route(*leaves16), wanted16, go16)}
+        ref = routes["kernel32"]()
+        err = {k: max(float((a.float() - b).abs().max() / b.abs().max()) for a, b in zip(fn(), ref))
+               for k, fn in routes.items() if k != "kernel32"}
+        del ref
+        st = alternate(routes, warmup, rounds)
+        for k, fn in routes.items():
+            st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+        med = {k: st[k]["median_ms"] for k in routes}
+        for other in ("recompute16", "kernel32", "sdpa16"):
+            st[f"kernel16_over_{other}"] = med["kernel16"] / med[other]
+            st[f"kernel16_beats_{other}"] = bool(med["kernel16"] * (1 + st["spread"]) < med[other])
+        st["kernel16_tflops_of_the_mathematics"] = 3.5 * op_flops(seqs, nq, nk1 + (nk2 or 0)) / (med["kernel16"] * 1e-3) / 1e12
+        st["max_relative_gradient_difference_from_kernel32"] = err
+        st["shape"] = dict(sequences=seqs, heads=HEADS, head_dim=D, queries=nq, keys=[nk1] + ([nk2] if nk2 else []))
+        res[name] = st
+        print(name, json.dumps({k: (round(v["median_ms"], 4), v["peak_bytes_above_inputs"] >> 20) for k, v in st.items()
+                                if isinstance(v, dict) and "median_ms" in v}), "spread", round(st["spread"], 3),
+              "beats recompute16", st["kernel16_beats_recompute16"], flush=True)
+    res["kernel16_beats_recompute16_everywhere"] = all(v["kernel16_beats_recompute16"] for v in res.values())
+    res["not_measured"] = ["D = 16 and D = 32", "hardware counters", "the step replayed from a graph", "fp16 unless run"]
     return res
 
 
@@ -351,7 +409,19 @@ def section_step16(device, warmup, rounds, dtype, clips=4):
              "fp32": LvdStep(clips, device, nets="reference"),
              "framework_autocast": LvdStep(clips, device, nets="reference", act_dtype=dtype)}
     steps["framework_autocast"].net.fused = False
+    kernel_backward = LvdStep(clips, device, nets="reference", act_dtype=dtype)
+
+    def act_dtype_kernel_backward():
+        with WF.token_attention_16bit_backward_route("kernel"):
+            return kernel_backward()
+
+    steps["act_dtype_kernel_backward"] = act_dtype_kernel_backward
     st = alternate(steps, warmup, rounds)
+    for k, fn in steps.items():
+        st[k]["peak_bytes_above_inputs"] = peak_above_inputs(fn)
+    st["kernel_backward_over_act_dtype"] = st["act_dtype_kernel_backward"]["median_ms"] / st["act_dtype"]["median_ms"]
+    st["kernel_backward_beats_act_dtype"] = bool(st["act_dtype_kernel_backward"]["median_ms"] * (1 + st["spread"])
+                                                 < st["act_dtype"]["median_ms"])
     st["act_dtype_over_framework_autocast"] = st["act_dtype"]["median_ms"] / st["framework_autocast"]["median_ms"]
     st["act_dtype_over_fp32"] = st["act_dtype"]["median_ms"] / st["fp32"]["median_ms"]
     st["shape"] = dict(clips=clips, frames=LvdStep.frames, nets="reference", mode="eager",
@@ -363,16 +433,17 @@ def section_step16(device, warmup, rounds, dtype, clips=4):
 
 def main_16bit(args, device):
     dtype = DTYPES[args.dtype]
-    out = args.out16 or os.path.join(ROOT, "profiles", "lvd_nets_16bit.json")
+    names = (args.sections16 or "op16,lvd16,step16").split(",")
+    out = args.out16 or os.path.join(ROOT, "profiles", "lvd_nets_16bit_bwd.json" if "bwd16" in names else "lvd_nets_16bit.json")
     doc = {}
     if os.path.exists(out):
         with open(out) as fh:
             doc = json.load(fh)
     part = dict(device=torch.cuda.get_device_name(0), torch=torch.__version__, limits=WF.token_attention_16bit_limits(),
                 head_dim=D, method=dict(rounds=args.rounds, warmup=args.warmup, timing="device events, routes alternating"))
-    sections = {"op16": section_op16, "lvd16": section_lvd16,
+    sections = {"op16": section_op16, "lvd16": section_lvd16, "bwd16": section_bwd16,
                 "step16": lambda *a: section_step16(*a, clips=args.clips)}
-    for sec in (args.sections16 or "op16,lvd16,step16").split(","):
+    for sec in names:
         part[sec] = sections[sec](device, args.warmup, args.rounds, dtype)
         doc[args.dtype] = part
         os.makedirs(os.path.dirname(out), exist_ok=True)
@@ -392,7 +463,8 @@ def main():
     ap.add_argument("--head-dim", type=int, default=64, choices=(16, 32, 64), help="D of the op and bwd sections")
     ap.add_argument("--dtype", choices=sorted(DTYPES), help="measure the 16-bit route: profiles/lvd_nets_16bit.json")
     ap.add_argument("--out16", help="with --dtype: the file to write instead")
-    ap.add_argument("--sections16", help="with --dtype: of op16,lvd16,step16 (default: all three)")
+    ap.add_argument("--sections16", help="with --dtype: of op16,lvd16,step16,bwd16 (default: the first three; with bwd16 "
+                                         "the file is profiles/lvd_nets_16bit_bwd.json)")
     args = ap.parse_args()
     global HEADS, D
     HEADS, D = WIDTH // args.head_dim, args.head_dim

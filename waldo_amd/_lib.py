@@ -170,6 +170,11 @@ SIGNATURES = {
     # the two forwards on 16-bit operands and out: a WALDO_DTYPE_* code before the stream
     "waldo_token_attention_fwd_dt": [_c_f, _i64, _i64] * 5 + [_c_f, _flt, _i64, _int, _int, _int, _int, _int, _int,
                                                               _stream],
+    # the dense form's forward with lse (fp32) after out, and its backward: waldo_token_attention_bwd's arguments
+    "waldo_token_attention_fwd_lse_dt": [_c_f, _i64, _i64] * 5 + [_c_f, _c_f, _flt, _i64, _int, _int, _int, _int, _int,
+                                                                  _int, _stream],
+    "waldo_token_attention_bwd_dt": [_c_f, _i64, _i64] * 5 + [_c_f] * 9 + [_flt, _i64, _int, _int, _int, _int, _int, _int,
+                                                                          _stream],
     "waldo_token_attention_clips_fwd_dt": [_c_f, _i64] * 3 + [_c_f] * 3 + [_flt, _i64, _int, _int, _i64, _i64, _int, _int,
                                                                            _int, _stream],
 }

@@ -1,14 +1,19 @@
 // Token attention on bf16 / fp16 operands (include/waldo_hip.h "Token attention", the _dt entry points): the forward of
 // token_attention.hip -- the same workgroup (one (b, h), 64 query rows, 16 per wavefront), the same 64-key tiles, the
 // same two TRANSPOSED products that let a lane own one query row from the scores to the store, the same online softmax
-// -- on the 16-bit matrix instructions with fp32 accumulation (token_attention_16.hip.h).  Forward only.
+// -- on the 16-bit matrix instructions with fp32 accumulation (token_attention_16.hip.h).  The backward of the dense form
+// is token_attention_16_bwd.hip.
 //
 // The arithmetic: a score is an fp32 sum of exact 16-bit products; scale, mask, the running maximum and the running sum
 // l are fp32, and l sums the UNROUNDED p; p is rounded to the operand type only as the operand of the second product; o
 // is accumulated and rescaled in fp32; one rounding to the operand type at the store.  Rows past the last key are
 // zeros in LDS and their scores -inf.  No atomics, no workspace: the same bits from run to run.
 //
-// The per-clip entry point is the same template with CLIPS (TaClips, ta_segment), as in the fp32 kernel.
+// The _lse entry point is the same template with LSE: one more store, the row's m + log(l) of the scaled scores in
+// fp32, from which the backward rebuilds the probabilities; out has the bits of the plain instance.
+//
+// The per-clip entry point is the same template with CLIPS (TaClips, ta_segment), as in the fp32 kernel; it has no _lse
+// form (its backward stays the framework's recompute).
 #include "token_attention_16.hip.h"
 
 namespace waldo {
@@ -16,12 +21,13 @@ namespace waldo {
 struct TokenAttention16Args {
   Ta16Views v;
   uint16_t* out;
+  float* lse;  // LSE: (B, H, Nq)
   float scale;
   int H, Nq, Nk1, Nk, qblocks;  // Nk = Nk1 + Nk2
   TaClips clips;                // CLIPS: the lengths are the clip's own, Nq / Nk1 / Nk are not read
 };
 
-template <int D, bool BF, bool CLIPS>
+template <int D, bool BF, bool CLIPS, bool LSE>
 __global__ __launch_bounds__(kBlock) void token_attention_16_fwd_kernel(TokenAttention16Args a) {
   constexpr int KLD = Ta16Tile<D>::KLD, VLD = Ta16Tile<D>::VLD, PER = Ta16Tile<D>::PER, JB = Ta16Tile<D>::JB,
                 DB = Ta16Tile<D>::DB, QW = Ta16Tile<D>::QW;
@@ -107,57 +113,40 @@ __global__ __launch_bounds__(kBlock) void token_attention_16_fwd_kernel(TokenAtt
       const ta_u32x2 w = {Ta16Type<BF>::round2(x[0], x[1]), Ta16Type<BF>::round2(x[2], x[3])};
       *reinterpret_cast<ta_u32x2*>(op + 16 * d) = w;
     }
+    if constexpr (LSE) {
+      if (c.g == 0) a.lse[(c.b * a.H + c.h) * Nq + (q0 + c.row)] = m + logf(l);
+    }
   }
 }
 
 namespace {
 
-// The dtype's refusals, before anything else: the fp32 code names the fp32 entry point.
-int ta16_check_dtype(const char* fn, const char* fp32_fn, int dtype) {
-  if (dtype == WALDO_DTYPE_F32) {
-    set_error("%s: dtype WALDO_DTYPE_F32 is served by %s", fn, fp32_fn);
-    return WALDO_EINVAL;
-  }
-  if (dtype != WALDO_DTYPE_F16 && dtype != WALDO_DTYPE_BF16) {
-    set_error("%s: unknown dtype %d", fn, dtype);
-    return WALDO_EINVAL;
-  }
-  return WALDO_OK;
-}
-
-// ta_check_strides for 16-bit rows: 16-byte pieces are 8 values.
-int ta16_check_strides(const char* fn, const int64_t* strides, int nstr) {
-  for (int i = 0; i < nstr; ++i)
-    if (strides[i] < 0) {
-      set_error("%s: negative stride", fn);
-      return WALDO_EINVAL;
-    }
-  for (int i = 0; i < nstr; ++i)
-    if (strides[i] % 8 != 0) {
-      if (i & 1)
-        set_error("%s: bad token stride %lld: rows are D consecutive 16-bit values a multiple of 8 values apart (a view "
-                  "with a non-unit inner stride is not served)", fn, (long long)strides[i]);
-      else
-        set_error("%s: bad batch stride %lld: a multiple of 8 values (rows on 16-byte boundaries)", fn,
-                  (long long)strides[i]);
-      return WALDO_EINVAL;
-    }
-  return WALDO_OK;
-}
-
-// The views as the shared pointer check takes them (it looks at the addresses only).
-TaViews ta16_as_checked(const Ta16Views& v) {
-  auto f = [](const Ta16View& x) { return TaView{reinterpret_cast<const float*>(x.p), x.sb, x.sn}; };
-  return {f(v.q), f(v.k1), f(v.v1), f(v.k2), f(v.v2)};
-}
-
-template <bool CLIPS, class Grid>
+template <bool CLIPS, bool LSE, class Grid>
 void ta16_launch(int D, int dtype, Grid grid, hipStream_t st, const TokenAttention16Args& a) {
   ta_for_head_dim(D, [&](auto d) {
     constexpr int DD = decltype(d)::value;
-    if (dtype == WALDO_DTYPE_BF16) token_attention_16_fwd_kernel<DD, true, CLIPS><<<grid, dim3(kBlock), 0, st>>>(a);
-    else token_attention_16_fwd_kernel<DD, false, CLIPS><<<grid, dim3(kBlock), 0, st>>>(a);
+    if (dtype == WALDO_DTYPE_BF16) token_attention_16_fwd_kernel<DD, true, CLIPS, LSE><<<grid, dim3(kBlock), 0, st>>>(a);
+    else token_attention_16_fwd_kernel<DD, false, CLIPS, LSE><<<grid, dim3(kBlock), 0, st>>>(a);
   });
+}
+
+// The dense forward's host half, with or without the row statistics.
+template <bool LSE>
+int ta16_fwd_host(const char* fn, const char* fp32_fn, Ta16Views v, void* out, float* lse, float scale, int64_t B, int H,
+                  int D, int Nq, int Nk1, int Nk2, int dtype, waldo_stream_t stream) {
+  if (ta16_check_dtype(fn, fp32_fn, dtype) != WALDO_OK) return WALDO_EINVAL;
+  const int64_t qblocks = ((int64_t)Nq + kTaQ - 1) / kTaQ;
+  if (ta16_check_shape(fn, v, scale, B, H, D, Nq, Nk1, Nk2, qblocks) != WALDO_OK) return WALDO_EINVAL;
+  if (B == 0 || Nq == 0) return WALDO_OK;
+  TaViews chk = ta16_as_checked(v);
+  if (ta_check_pointers(fn, chk, Nk2, out != nullptr && (!LSE || lse != nullptr), {out, lse}) != WALDO_OK)
+    return WALDO_EINVAL;
+  if (Nk2 == 0) v.k2 = v.v2 = {nullptr, 0, 0};
+  TokenAttention16Args a{};
+  a.v = v, a.out = static_cast<uint16_t*>(out), a.lse = lse;
+  a.scale = scale, a.H = H, a.Nq = Nq, a.Nk1 = Nk1, a.Nk = Nk1 + Nk2, a.qblocks = (int)qblocks;
+  ta16_launch<false, LSE>(D, dtype, dim3((unsigned)(B * H * qblocks)), (hipStream_t)stream, a);
+  return launch_status(fn);
 }
 
 }  // namespace
@@ -173,34 +162,24 @@ extern "C" int waldo_token_attention_fwd_dt(const void* q, int64_t qs_b, int64_t
                                             int64_t k2s_b, int64_t k2s_n, const void* v2, int64_t v2s_b, int64_t v2s_n,
                                             void* out, float scale, int64_t B, int H, int D, int Nq, int Nk1, int Nk2,
                                             int dtype, waldo_stream_t stream) {
-  const char* fn = "waldo_token_attention_fwd_dt";
-  if (ta16_check_dtype(fn, "waldo_token_attention_fwd", dtype) != WALDO_OK) return WALDO_EINVAL;
   auto u = [](const void* p) { return static_cast<const uint16_t*>(p); };
-  Ta16Views v{{u(q), qs_b, qs_n}, {u(k1), k1s_b, k1s_n}, {u(v1), v1s_b, v1s_n}, {u(k2), k2s_b, k2s_n},
-              {u(v2), v2s_b, v2s_n}};
-  const int64_t qblocks = ((int64_t)Nq + kTaQ - 1) / kTaQ;
-  if (B < 0 || H < 1 || Nq < 0 || Nk1 < 1 || Nk2 < 0) {
-    set_error("%s: bad shape B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (B, Nq, Nk2 >= 0; H, Nk1 >= 1)", fn, (long long)B, H, Nq,
-              Nk1, Nk2);
-    return WALDO_EINVAL;
-  }
-  if (ta_check_head_scale(fn, D, scale) != WALDO_OK) return WALDO_EINVAL;
-  if ((int64_t)Nk1 + Nk2 > INT32_MAX - kTaK || B * H > INT32_MAX || B * H * qblocks > INT32_MAX) {
-    set_error("%s: too large: B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (Nk1 + Nk2 and the %d-row query blocks of all (b, h) stay "
-              "below 2^31)", fn, (long long)B, H, Nq, Nk1, Nk2, kTaQ);
-    return WALDO_EINVAL;
-  }
-  const int64_t strides[10] = {qs_b, qs_n, k1s_b, k1s_n, v1s_b, v1s_n, k2s_b, k2s_n, v2s_b, v2s_n};
-  if (ta16_check_strides(fn, strides, Nk2 > 0 ? 10 : 6) != WALDO_OK) return WALDO_EINVAL;
-  if (B == 0 || Nq == 0) return WALDO_OK;
-  TaViews chk = ta16_as_checked(v);
-  if (ta_check_pointers(fn, chk, Nk2, out != nullptr, {out}) != WALDO_OK) return WALDO_EINVAL;
-  if (Nk2 == 0) v.k2 = v.v2 = {nullptr, 0, 0};
-  TokenAttention16Args a{};
-  a.v = v, a.out = static_cast<uint16_t*>(out);
-  a.scale = scale, a.H = H, a.Nq = Nq, a.Nk1 = Nk1, a.Nk = Nk1 + Nk2, a.qblocks = (int)qblocks;
-  ta16_launch<false>(D, dtype, dim3((unsigned)(B * H * qblocks)), (hipStream_t)stream, a);
-  return launch_status(fn);
+  return ta16_fwd_host<false>("waldo_token_attention_fwd_dt", "waldo_token_attention_fwd",
+                              {{u(q), qs_b, qs_n}, {u(k1), k1s_b, k1s_n}, {u(v1), v1s_b, v1s_n}, {u(k2), k2s_b, k2s_n},
+                               {u(v2), v2s_b, v2s_n}},
+                              out, nullptr, scale, B, H, D, Nq, Nk1, Nk2, dtype, stream);
+}
+
+extern "C" int waldo_token_attention_fwd_lse_dt(const void* q, int64_t qs_b, int64_t qs_n, const void* k1, int64_t k1s_b,
+                                                int64_t k1s_n, const void* v1, int64_t v1s_b, int64_t v1s_n,
+                                                const void* k2, int64_t k2s_b, int64_t k2s_n, const void* v2,
+                                                int64_t v2s_b, int64_t v2s_n, void* out, float* lse, float scale,
+                                                int64_t B, int H, int D, int Nq, int Nk1, int Nk2, int dtype,
+                                                waldo_stream_t stream) {
+  auto u = [](const void* p) { return static_cast<const uint16_t*>(p); };
+  return ta16_fwd_host<true>("waldo_token_attention_fwd_lse_dt", "waldo_token_attention_fwd_lse",
+                             {{u(q), qs_b, qs_n}, {u(k1), k1s_b, k1s_n}, {u(v1), v1s_b, v1s_n}, {u(k2), k2s_b, k2s_n},
+                              {u(v2), v2s_b, v2s_n}},
+                             out, lse, scale, B, H, D, Nq, Nk1, Nk2, dtype, stream);
 }
 
 extern "C" int waldo_token_attention_clips_fwd_dt(const void* q, int64_t qs_n, const void* k, int64_t ks_n, const void* v,
@@ -240,6 +219,6 @@ extern "C" int waldo_token_attention_clips_fwd_dt(const void* q, int64_t qs_n, c
   a.v = vw, a.out = static_cast<uint16_t*>(out);
   a.scale = scale, a.H = H, a.qblocks = (int)qblocks;
   a.clips = {q_off, k_off, (int)Rq, (int)Rk};
-  ta16_launch<true>(D, dtype, dim3((unsigned)(B * H * qblocks)), (hipStream_t)stream, a);
+  ta16_launch<true, false>(D, dtype, dim3((unsigned)(B * H * qblocks)), (hipStream_t)stream, a);
   return launch_status(fn);
 }

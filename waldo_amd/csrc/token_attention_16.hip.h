@@ -220,4 +220,158 @@ __device__ __forceinline__ void ta16_values(const uint16_t* vblk, const ta_f32x4
   }
 }
 
+// ---------------------------------------------------------------- the backward (token_attention_16_bwd.hip)
+//
+// The two matrix kernels of the backward read BOTH staged tiles row-wise (S and dP are rows products) and one of them
+// also column-wise (dQ: K; dK/dV: Q and dO), so both tiles take one row stride, Ta16BwdTile<D>::LD, which is the
+// forward's K stride (KLD: 40 / 24 / 12 dwords).  Banks, in the terms of the analysis at the top:
+//   row reads: the forward's K row reads at that stride -- conflict-free at all three D (the forward's unpadded V
+//     stride of D = 16, 8 dwords, would be 2-way here).
+//   transposed reads: D = 64, stride 40 and D = 32, stride 24 are the forward's V strides -- conflict-free.
+//     D = 16, stride 12: the 8 rows of a half start at banks 0 12 24 36 48 60 8 20, runs of 8: the runs of the rows
+//     0 / 5, 1 / 6 and 2 / 7 share 4 banks each (0-3, 12-15, 24-27) -- a 2-way conflict on 12 of the 64 banks.  No
+//     stride serves both reads of 16-value rows without one: the transposed read wants 8 x odd dwords (8, 24, 40),
+//     at which the 8-byte row reads of the rows r and r + 8 meet.  A D = 16 tile step makes 8 row reads (dQ) for 4
+//     transposed ones, so the stride is the row reads'.
+template <int D>
+struct Ta16BwdTile {
+  static constexpr int LD = Ta16Tile<D>::KLD;  // LDS row of either tile, in values (48 / 96 / 160 bytes)
+  static_assert(LD % 8 == 0, "16-byte stage writes and row reads, 8-byte transposed reads");
+};
+
+// One 16-bit value as it is in fp32 (exact).
+template <bool BF>
+__device__ __forceinline__ float ta16_widen(uint32_t bits16) {
+  if constexpr (BF) return __builtin_bit_cast(float, bits16 << 16);
+  else return (float)__builtin_bit_cast(_Float16, (uint16_t)bits16);
+}
+
+// ta16_stage with the backward's stride for both tiles.
+template <int D>
+__device__ __forceinline__ void ta16_stage_bwd(uint16_t* s0, uint16_t* s1, const ta_u32x4 (&r0)[Ta16Tile<D>::PER],
+                                               const ta_u32x4 (&r1)[Ta16Tile<D>::PER]) {
+#pragma unroll
+  for (int i = 0; i < Ta16Tile<D>::PER; ++i) {
+    int row, c8;
+    bool mine;
+    ta16_piece<D>(i, row, c8, mine);
+    if (mine) {
+      *reinterpret_cast<ta_u32x4*>(s0 + row * Ta16BwdTile<D>::LD + c8) = r0[i];
+      *reinterpret_cast<ta_u32x4*>(s1 + row * Ta16BwdTile<D>::LD + c8) = r1[i];
+    }
+  }
+}
+
+// The rows product, ta16_scores at the backward's stride: acc[j][r] += tile row (16 j + 4 g + r) . the lane's own
+// register row `bf` (ta16_load_q's layout); `rows` is the tile's row (lane & 15) at the lane's first column.
+template <int D, bool BF>
+__device__ __forceinline__ void ta16_rows_product(const uint16_t* rows, const uint32_t (&bf)[Ta16Tile<D>::QW],
+                                                  ta_f32x4 (&acc)[Ta16Tile<D>::JB]) {
+  constexpr int JB = Ta16Tile<D>::JB, LD = Ta16BwdTile<D>::LD;
+  if constexpr (D == 16) {
+    const ta_u32x2 b = {bf[0], bf[1]};
+#pragma unroll
+    for (int j = 0; j < JB; ++j)
+      acc[j] = Ta16Type<BF>::mfma16(*reinterpret_cast<const ta_u32x2*>(rows + 16 * j * LD), b, acc[j]);
+  } else {
+#pragma unroll
+    for (int t = 0; t < D / 32; ++t) {
+      const ta_u32x4 b = {bf[4 * t], bf[4 * t + 1], bf[4 * t + 2], bf[4 * t + 3]};
+      ta_u32x4 a[JB];
+#pragma unroll
+      for (int j = 0; j < JB; ++j) a[j] = *reinterpret_cast<const ta_u32x4*>(rows + 16 * j * LD + 32 * t);
+#pragma unroll
+      for (int j = 0; j < JB; ++j) acc[j] = Ta16Type<BF>::mfma32(a[j], b, acc[j]);
+    }
+  }
+}
+
+// The columns product, ta16_values at the backward's stride: acc[d][r] += sum over the tile rows 16 j + 4 g' + r' of
+// tile[row][16 d + 4 g + r] p[row], p[j][r] being the lane's fp32 weight of the row 16 j + 4 g + r, rounded here to the
+// operand type; `blk` is the lane's transposed-read address (the block of the rows 4 g ... of row block 0).
+template <int D, bool BF>
+__device__ __forceinline__ void ta16_cols_product(const uint16_t* blk, const ta_f32x4 (&p)[Ta16Tile<D>::JB],
+                                                  ta_f32x4 (&acc)[Ta16Tile<D>::DB]) {
+  constexpr int JB = Ta16Tile<D>::JB, DB = Ta16Tile<D>::DB, LD = Ta16BwdTile<D>::LD;
+#pragma unroll
+  for (int s = 0; s < JB / 2; ++s) {
+    const ta_u32x4 b = {Ta16Type<BF>::round2(p[2 * s][0], p[2 * s][1]), Ta16Type<BF>::round2(p[2 * s][2], p[2 * s][3]),
+                        Ta16Type<BF>::round2(p[2 * s + 1][0], p[2 * s + 1][1]),
+                        Ta16Type<BF>::round2(p[2 * s + 1][2], p[2 * s + 1][3])};
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+      const ta_u32x2 lo = ta16_read_tr(blk + 16 * (2 * s) * LD + 16 * d);
+      const ta_u32x2 hi = ta16_read_tr(blk + 16 * (2 * s + 1) * LD + 16 * d);
+      const ta_u32x4 a = {lo[0], lo[1], hi[0], hi[1]};
+      acc[d] = Ta16Type<BF>::mfma32(a, b, acc[d]);
+    }
+  }
+}
+
+// One 8-byte store of four fp32 values rounded to the operand type.
+template <bool BF>
+__device__ __forceinline__ void ta16_store4(uint16_t* p, const ta_f32x4& x) {
+  const ta_u32x2 w = {Ta16Type<BF>::round2(x[0], x[1]), Ta16Type<BF>::round2(x[2], x[3])};
+  *reinterpret_cast<ta_u32x2*>(p) = w;
+}
+
+// ---------------------------------------------------------------- host: what the _dt entry points share
+
+// The dtype's refusals, before anything else: the fp32 code names the fp32 entry point.
+inline int ta16_check_dtype(const char* fn, const char* fp32_fn, int dtype) {
+  if (dtype == WALDO_DTYPE_F32) {
+    set_error("%s: dtype WALDO_DTYPE_F32 is served by %s", fn, fp32_fn);
+    return WALDO_EINVAL;
+  }
+  if (dtype != WALDO_DTYPE_F16 && dtype != WALDO_DTYPE_BF16) {
+    set_error("%s: unknown dtype %d", fn, dtype);
+    return WALDO_EINVAL;
+  }
+  return WALDO_OK;
+}
+
+// ta_check_strides for 16-bit rows: 16-byte pieces are 8 values.
+inline int ta16_check_strides(const char* fn, const int64_t* strides, int nstr) {
+  for (int i = 0; i < nstr; ++i)
+    if (strides[i] < 0) {
+      set_error("%s: negative stride", fn);
+      return WALDO_EINVAL;
+    }
+  for (int i = 0; i < nstr; ++i)
+    if (strides[i] % 8 != 0) {
+      if (i & 1)
+        set_error("%s: bad token stride %lld: rows are D consecutive 16-bit values a multiple of 8 values apart (a view "
+                  "with a non-unit inner stride is not served)", fn, (long long)strides[i]);
+      else
+        set_error("%s: bad batch stride %lld: a multiple of 8 values (rows on 16-byte boundaries)", fn,
+                  (long long)strides[i]);
+      return WALDO_EINVAL;
+    }
+  return WALDO_OK;
+}
+
+// ta_check_shape for the dense 16-bit entry points: its refusals in its order and words, the strides held to 8 values.
+inline int ta16_check_shape(const char* fn, const Ta16Views& v, float scale, int64_t B, int H, int D, int Nq, int Nk1,
+                            int Nk2, int64_t blocks) {
+  if (B < 0 || H < 1 || Nq < 0 || Nk1 < 1 || Nk2 < 0) {
+    set_error("%s: bad shape B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (B, Nq, Nk2 >= 0; H, Nk1 >= 1)", fn, (long long)B, H, Nq,
+              Nk1, Nk2);
+    return WALDO_EINVAL;
+  }
+  if (ta_check_head_scale(fn, D, scale) != WALDO_OK) return WALDO_EINVAL;
+  if ((int64_t)Nk1 + Nk2 > INT32_MAX - kTaK || B * H > INT32_MAX || B * H * blocks > INT32_MAX) {
+    set_error("%s: too large: B=%lld H=%d Nq=%d Nk1=%d Nk2=%d (Nk1 + Nk2 and the %d-row query blocks of all (b, h) stay "
+              "below 2^31)", fn, (long long)B, H, Nq, Nk1, Nk2, kTaQ);
+    return WALDO_EINVAL;
+  }
+  const int64_t strides[10] = {v.q.sb, v.q.sn, v.k1.sb, v.k1.sn, v.v1.sb, v.v1.sn, v.k2.sb, v.k2.sn, v.v2.sb, v.v2.sn};
+  return ta16_check_strides(fn, strides, Nk2 > 0 ? 10 : 6);
+}
+
+// The views as the shared pointer check takes them (it looks at the addresses only).
+inline TaViews ta16_as_checked(const Ta16Views& v) {
+  auto f = [](const Ta16View& x) { return TaView{reinterpret_cast<const float*>(x.p), x.sb, x.sn}; };
+  return {f(v.q), f(v.k1), f(v.v1), f(v.k2), f(v.v2)};
+}
+
 }  // namespace waldo

@@ -2258,6 +2258,45 @@ class token_attention_16bit_route:
         return False
 
 
+TOKEN_ATTENTION_16BIT_BACKWARD_ROUTES = ("framework", "kernel")
+_token_attention_16bit_backward_route = "framework"
+
+
+def get_token_attention_16bit_backward_route():
+    """The route the backward of a 16-bit kernel ``token_attention`` whose forward runs now will take."""
+    return _token_attention_16bit_backward_route
+
+
+class token_attention_16bit_backward_route:
+    """``token_attention_16bit_backward_route(route)`` sets how a ``token_attention`` call that the 16-bit kernel serves
+    (bf16 / fp16 operands under ``token_attention_16bit_route("kernel")``) differentiates: ``"framework"`` (the
+    default) -- ``token_attention_framework`` recomputed from the saved views and differentiated, as before there was a
+    16-bit backward -- or ``"kernel"`` -- the forward runs ``waldo_token_attention_fwd_lse_dt`` and saves ``out`` and
+    ``lse`` with the views, and ONE ``waldo_token_attention_bwd_dt`` call computes only the wanted gradients (no score
+    tensor, no atomics).  A switch of its own: ``token_attention_backward_route`` does not reach 16-bit calls.  It has
+    no effect on the CPU, on fp32 operands, under the default 16-bit route and on ``token_attention_clips`` (whose
+    16-bit backward stays the recompute).  Used as ``with token_attention_16bit_backward_route(route):`` the earlier
+    setting comes back on exit, also after an exception; nests.  The route is read when the op's FORWARD runs and
+    travels with the autograd node."""
+
+    def __init__(self, route):
+        global _token_attention_16bit_backward_route
+        if route not in TOKEN_ATTENTION_16BIT_BACKWARD_ROUTES:
+            raise ValueError(f"token_attention_16bit_backward_route: route must be one of "
+                             f"{TOKEN_ATTENTION_16BIT_BACKWARD_ROUTES}, got {route!r}")
+        self.route = route
+        self.prev = _token_attention_16bit_backward_route
+        _token_attention_16bit_backward_route = route
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        global _token_attention_16bit_backward_route
+        _token_attention_16bit_backward_route = self.prev
+        return False
+
+
 def token_attention_16bit_limits():
     """``token_attention_limits`` of the 16-bit kernels (``waldo_token_attention_dt_limits``)."""
     return _token_attention_limits_of("waldo_token_attention_dt_limits")
@@ -2359,13 +2398,16 @@ class _TokenAttention(torch.autograd.Function):
 
 
 class _TokenAttention16(torch.autograd.Function):
-    """``_TokenAttention`` on bf16 / fp16 operands: the forward is ``waldo_token_attention_fwd_dt`` on the views as they
-    lie, ``out`` of the operands' type.  The backward is ALWAYS the ``"framework"`` one of ``_TokenAttention`` --
-    ``token_attention_framework`` recomputed from the saved views and differentiated -- whatever
-    ``token_attention_backward_route`` says: there is no 16-bit backward kernel."""
+    """``_TokenAttention`` on bf16 / fp16 operands, ``out`` of the operands' type, by the route read in the forward
+    (``token_attention_16bit_backward_route``; ``token_attention_backward_route`` does not reach here).
+    ``"framework"``: the forward is ``waldo_token_attention_fwd_dt`` on the views as they lie and the backward the
+    ``"framework"`` one of ``_TokenAttention`` -- ``token_attention_framework`` recomputed from the saved views and
+    differentiated.  ``"kernel"``: the forward is ``waldo_token_attention_fwd_lse_dt`` and saves ``out`` and the fp32
+    ``lse`` with the views; the backward allocates ``delta`` and the wanted gradients and makes one
+    ``waldo_token_attention_bwd_dt`` call."""
 
     @staticmethod
-    def forward(ctx, scale, strides, code, q, k, v, k2, v2):
+    def forward(ctx, scale, strides, code, route, q, k, v, k2, v2):
         b, nq, h, d = q.shape
         out = torch.empty(b, nq, h * d, dtype=q.dtype, device=q.device)
         flat = []
@@ -2375,15 +2417,46 @@ class _TokenAttention16(torch.autograd.Function):
             flat += [k2, strides[3][0], strides[3][1], v2, strides[4][0], strides[4][1]]
         else:
             flat += [None, 0, 0, None, 0, 0]
-        _lib.launch("waldo_token_attention_fwd_dt", q.device, *flat, out, float(scale), b, h, d, nq, k.shape[1],
-                    0 if k2 is None else k2.shape[1], code)
-        ctx.route, ctx.scale, ctx.two = "framework", scale, k2 is not None
-        ctx.save_for_backward(*((q, k, v, k2, v2) if ctx.two else (q, k, v)))
+        shape = (b, h, d, nq, k.shape[1], 0 if k2 is None else k2.shape[1], code)
+        ctx.route, ctx.scale, ctx.two = route, scale, k2 is not None
+        views = (q, k, v, k2, v2) if ctx.two else (q, k, v)
+        if route == "kernel":
+            lse = torch.empty(b, h, nq, dtype=torch.float32, device=q.device)
+            _lib.launch("waldo_token_attention_fwd_lse_dt", q.device, *flat, out, lse, float(scale), *shape)
+            ctx.flat, ctx.shape = [a if type(a) is int else None for a in flat], shape
+            ctx.save_for_backward(*views, out, lse)
+        else:
+            _lib.launch("waldo_token_attention_fwd_dt", q.device, *flat, out, float(scale), *shape)
+            ctx.save_for_backward(*views)
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        return _TokenAttention.backward(ctx, grad_out)
+        nv = 5 if ctx.two else 3
+        need = ctx.needs_input_grad[4:4 + nv]
+        if ctx.route != "kernel":
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(n) for t, n in zip(ctx.saved_tensors, need)]
+                out = token_attention_framework(*leaves, scale=ctx.scale)
+                wanted = [t for t, n in zip(leaves, need) if n]
+                grads = iter(torch.autograd.grad(out, wanted, grad_out)) if wanted else iter(())
+            res = [next(grads) if n else None for n in need]
+            return (None, None, None, None, *res, *([None] * (5 - len(res))))
+        *views, out, lse = ctx.saved_tensors
+        dev = out.device
+        grads = [torch.empty(t.shape, dtype=out.dtype, device=dev) if n else None for t, n in zip(views, need)]
+        flat = list(ctx.flat)
+        flat[0:nv * 3:3] = views
+        delta = torch.empty_like(lse)
+        # dense rows of the operands' type in 16-byte pieces (see _TokenAttention.backward): one copy otherwise
+        if grad_out.dtype != out.dtype:
+            grad_out = grad_out.to(out.dtype, memory_format=torch.contiguous_format)
+        if not grad_out.is_contiguous() or grad_out.data_ptr() % 16:
+            grad_out = grad_out.clone(memory_format=torch.contiguous_format)
+        _lib.launch("waldo_token_attention_bwd_dt", dev, *flat, out, grad_out, lse, delta, *grads,
+                    *([None] * (5 - nv)), float(ctx.scale), *ctx.shape)
+        return (None, None, None, None, *grads, *([None] * (5 - nv)))
 
 
 def token_attention(q, k, v, k2=None, v2=None, scale=None):
@@ -2402,7 +2475,8 @@ def token_attention(q, k, v, k2=None, v2=None, scale=None):
     instruction with fp32 accumulation, the softmax in fp32, ``out`` of the operands' type -- ONLY under
     ``token_attention_16bit_route("kernel")``, then also while autocast is enabled; their strides are multiples of 8
     elements.  Such a call differentiates by the ``"framework"`` route whatever ``token_attention_backward_route``
-    says: a 16-bit backward kernel is out of scope.
+    says; its own switch, ``token_attention_16bit_backward_route("kernel")``, gives it ``waldo_token_attention_bwd_dt``
+    (the forward then is ``waldo_token_attention_fwd_lse_dt``; gradients of the operands' type).
     Everything else -- CPU tensors, another D, another dtype (16-bit inputs under the default 16-bit route, autocast),
     another layout -- IS ``token_attention_framework`` end to end."""
     _token_attention_check(q, k, v, k2, v2)
@@ -2411,7 +2485,12 @@ def token_attention(q, k, v, k2=None, v2=None, scale=None):
     if strides is None:
         strides = _token_attention_served_16bit(q, k, v, k2, v2)
         if strides is not None:
-            return _TokenAttention16.apply(scale, strides, _DTYPE_CODE[q.dtype], q, k, v, k2, v2)
+            # (as below: the route travels with the node, and a call that records no node needs no row statistics)
+            route = _token_attention_16bit_backward_route
+            if route == "kernel" and not (torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                                                          for t in (q, k, v, k2, v2))):
+                route = "framework"
+            return _TokenAttention16.apply(scale, strides, _DTYPE_CODE[q.dtype], route, q, k, v, k2, v2)
         return token_attention_framework(q, k, v, k2, v2, scale)
     # the route travels with the node; a call that records no node (no gradient wanted) needs no row statistics
     route = _token_attention_backward_route

@@ -11,7 +11,9 @@ slices of ``qkv`` / ``kv`` where they lie.  ``fused = False`` (an attribute of e
 and ``Block`` pass an assignment on) runs the reference's sequence of framework ops instead, and is the route on the CPU.
 Under autocast the slices are 16-bit and take the framework route too, unless the caller has set
 ``WF.token_attention_16bit_route("kernel")`` -- as the networks' ``act_dtype`` does (nets/lvd.py ``_Net``) -- which
-serves them with the 16-bit forward kernels.
+serves them with the 16-bit forward kernels.  Their backward is the framework's recompute unless the training code has
+also set ``WF.token_attention_16bit_backward_route("kernel")`` around the step: the dense attention then differentiates
+by ``waldo_token_attention_bwd_dt`` (the per-clip form below keeps the recompute).
 
 With ``ctx_mask`` -- the future layer predictor's clips, of which a (B, T) mask selects the frames -- the tokens stay
 PACKED, (B', N, C) over the selected frames as the reference's ``to_ctx`` leaves them, and the attention is

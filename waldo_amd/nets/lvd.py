@@ -843,7 +843,10 @@ class _Net(nn.Module):
         weights, and the blocks' attention on the 16-bit slices of ``qkv`` / ``kv`` is the 16-bit kernel
         (``WF.token_attention_16bit_route("kernel")`` for the duration; ``fused = False``: the framework's chain under
         the same autocast).  What a network hands to the warp path -- poses, occlusion scores, alpha images, class
-        weights -- is cast to fp32 where the region ends.  Setting it sets every sub-network's."""
+        weights -- is cast to fp32 where the region ends.  Setting it sets every sub-network's.  The attention's
+        BACKWARD stays the framework's recompute unless training code opts in with
+        ``with WF.token_attention_16bit_backward_route("kernel"):`` around the step (``waldo_token_attention_bwd_dt``;
+        the per-clip attention of FLP keeps the recompute either way)."""
         return self._act_dtype
 
     @act_dtype.setter

@@ -68,7 +68,9 @@ class LvdStep:
     returns the loss (the leaves' ``.grad`` hold the gradients).  ``optimizer`` (with ``nets="reference"``): None, "adam",
     "adamw" or an ``optim.Adam`` over the networks' parameters; the step then ends in ``optimizer.step(loss)``, and
     ``step.optimizer`` is it.  ``act_dtype`` (with ``nets="reference"``): the networks' ``act_dtype`` -- torch.bfloat16
-    or torch.float16: they run under autocast with the 16-bit attention kernel, the warp path stays fp32."""
+    or torch.float16: they run under autocast with the 16-bit attention kernel, the warp path stays fp32.  The
+    attention's backward is then the framework's recompute; ``with WF.token_attention_16bit_backward_route("kernel"):``
+    around the call makes it the 16-bit backward kernel (``waldo_token_attention_bwd_dt``)."""
 
     frames, num_lyt = 5, 20
 
