@@ -1298,6 +1298,34 @@ int waldo_lpips_level_bwd(const float* f0, const float* f1, const float* w, cons
                           float* grad_f0, int64_t N, int64_t C, int64_t P, waldo_stream_t stream);
 
 /* -------------------------------------------------------------------------------------
+ * LPIPS level distance in 16 bits: the two entry points above for maps stored in 16 bits, which is what a backbone
+ * under autocast hands over.  f0, f1 and grad_f0 are `dtype` = WALDO_DTYPE_BF16 or WALDO_DTYPE_F16, dense (N, C, P);
+ * w, out, saved (N, 3, P), the workspace's partials and grad_out stay fp32, and ALL arithmetic is fp32 on the exactly
+ * widened elements.  The contract is the one above, word for word where it does not speak of the storage: the two-walk
+ * form with e = f0 / m0 - f1 / m1, eps AFTER the square root, NO ATOMICS (the partials are added in a fixed order: the
+ * same bits from run to run and in a graph replay), equal operands give exact zeros in the value and the gradient, a
+ * pixel with n0[p] == 0 gets EXACT 0 on every channel (saved 1 / m0 = 0 marks it), eps == 0 is served on ragged
+ * tiles, no limit on C beyond C P <= 2^31 - 1.
+ *   Alignment: a lane reads ONE 2-byte element per channel.  Nothing assumes more than 2-byte alignment of f0, f1 or
+ *   grad_f0, or an even P: odd planes (AlexNet's 127 x 255 taps) and views that start on an odd element are served by
+ *   the same kernels as everything else.  There is one kernel form per dtype; nothing is chosen from the pointers.
+ *   The tile is the fp32 kernels' 64 pixels: waldo_lpips_level_workspace_bytes and waldo_lpips_level_saved_bytes size
+ *   the workspace and `saved` of these entry points too.
+ *   Rounding: grad_f0[c, p] is the fp32 expression 2 g (w[c] e[c] / m0 - f0[c, p] q) rounded ONCE to nearest-even in
+ *   `dtype`; for fp16 that includes the subnormals (no flush, no truncation).  The gradient of a mean over 2^19
+ *   pixels is small: fp16 TRAINING NEEDS A SCALED LOSS (waldo_amd.optim's scaler), or most of grad_f0 rounds to
+ *   subnormals and zeros.  bf16 has fp32's exponent range and needs none.
+ * WALDO_EINVAL with a message before any launch: WALDO_DTYPE_F32 is refused with the name of the fp32 entry point
+ * that serves it, any other code with "unknown dtype"; then "null pointer", "bad shape", "too large" and "workspace"
+ * as above.
+ * ------------------------------------------------------------------------------------- */
+int waldo_lpips_level_fwd_dt(const void* f0, const void* f1, const float* w, float* out, float* saved, void* workspace,
+                             int64_t workspace_bytes, int64_t N, int64_t C, int64_t P, float eps, int dtype,
+                             waldo_stream_t stream);
+int waldo_lpips_level_bwd_dt(const void* f0, const void* f1, const float* w, const float* saved, const float* grad_out,
+                             void* grad_f0, int64_t N, int64_t C, int64_t P, int dtype, waldo_stream_t stream);
+
+/* -------------------------------------------------------------------------------------
  * Clip augmentation (waldo_amd.augment; the reference's data/base_dataset.py:113-165 parameters, :330-370 transforms,
  * :173-208 layout and flow).  A training sample from a packed clip ("Packed clip" above) in ONE launch: crop, bilinear
  * resize, flips, colour jitter and normalisation of the frames, the resized layout logits, and the flow through its

@@ -102,6 +102,9 @@ SIGNATURES = {
     # N, C, P, eps; the backward: f0, f1, w, saved, grad_out, grad_f0, N, C, P
     "waldo_lpips_level_fwd": [_c_f] * 6 + [_i64] * 4 + [_flt, _stream],
     "waldo_lpips_level_bwd": [_c_f] * 6 + [_i64] * 3 + [_stream],
+    # the same with 16-bit f0, f1 and grad_f0 (w, out, saved, grad_out stay fp32): a WALDO_DTYPE_* code before the stream
+    "waldo_lpips_level_fwd_dt": [_c_f] * 6 + [_i64] * 4 + [_flt, _int, _stream],
+    "waldo_lpips_level_bwd_dt": [_c_f] * 6 + [_i64] * 3 + [_int, _stream],
     # clip augmentation (include/waldo_hip.h "Clip augmentation"): clip, flow, the five tables, out, flow_out, B, T, Nl,
     # Hd, Wd, Hf, Wf, Ho, Wo
     "waldo_augment_clip_fwd": [_c_f] * 9 + [_int] * 9 + [_stream],

@@ -2705,7 +2705,7 @@ def lpips_level_framework(f0, f1, w, eps=1e-10):
 
 
 def _lpips_level_call(f0, f1, w, eps, want_saved):
-    """One forward call on dense operands: (out (N,), saved or None)."""
+    """One forward call on dense operands (fp32, or 16-bit maps with an fp32 ``w``): (out (N,), saved or None)."""
     n, c, h, wd = f0.shape
     p, dev = h * wd, f0.device
     nbytes = _lib.query("waldo_lpips_level_workspace_bytes", n, c, p)
@@ -2716,14 +2716,16 @@ def _lpips_level_call(f0, f1, w, eps, want_saved):
     saved = None
     if want_saved:
         saved = torch.empty(_lib.query("waldo_lpips_level_saved_bytes", n, c, p) // 4, dtype=torch.float32, device=dev)
-    _lib.launch("waldo_lpips_level_fwd", dev, f0, f1, w, out, saved, ws, nbytes, n, c, p, float(eps))
+    name, codes = _dt_entry("waldo_lpips_level_fwd", f0.dtype)
+    _lib.launch(name, dev, f0, f1, w, out, saved, ws, nbytes, n, c, p, float(eps), *codes)
     return out, saved
 
 
 class _LpipsLevel(torch.autograd.Function):
-    """``waldo_lpips_level_fwd`` with the per-pixel values its backward needs kept only when ``f0`` asks for a gradient;
-    ``grad_f1`` is the same pair of calls with the operands exchanged (the distance is symmetric), its forward run in
-    the backward: the loss differentiates the prediction alone."""
+    """``waldo_lpips_level_fwd`` (``_fwd_dt`` for 16-bit maps) with the per-pixel values its backward needs kept only when
+    ``f0`` asks for a gradient; ``grad_f1`` is the same pair of calls with the operands exchanged (the distance is
+    symmetric), its forward run in the backward: the loss differentiates the prediction alone.  ``out`` and ``grad_out``
+    are fp32; the gradients have the maps' type."""
 
     @staticmethod
     def forward(ctx, eps, f0, f1, w):
@@ -2739,6 +2741,7 @@ class _LpipsLevel(torch.autograd.Function):
         f0, f1, w, saved = ctx.saved_tensors
         grad_out = grad_out.contiguous()
         n, c, h, wd = f0.shape
+        name, codes = _dt_entry("waldo_lpips_level_bwd", f0.dtype)
         grads = [None, None]
         for i, (a, b) in enumerate(((f0, f1), (f1, f0))):
             if not ctx.needs_input_grad[1 + i]:
@@ -2746,8 +2749,12 @@ class _LpipsLevel(torch.autograd.Function):
             if i == 1:
                 _, saved = _lpips_level_call(a, b, w, ctx.eps, True)
             grads[i] = torch.empty_like(a)
-            _lib.launch("waldo_lpips_level_bwd", a.device, a, b, w, saved, grad_out, grads[i], n, c, h * wd)
+            _lib.launch(name, a.device, a, b, w, saved, grad_out, grads[i], n, c, h * wd, *codes)
         return (None, grads[0], grads[1], None)
+
+
+def _lpips_level_mixed(f0, w):
+    return f0.dtype in (torch.bfloat16, torch.float16) and w.dtype == torch.float32
 
 
 def _lpips_level_check(f0, f1, w):
@@ -2760,8 +2767,10 @@ def _lpips_level_check(f0, f1, w):
                          f"{tuple(f1.shape)} on {f1.device}")
     if f0.numel() == 0:
         raise ValueError(f"lpips_level: the operands {tuple(f0.shape)} are empty")
-    if not torch.is_tensor(w) or w.numel() != f0.shape[1] or w.dtype != f0.dtype or w.device != f0.device:
-        raise ValueError(f"lpips_level: w must hold C = {f0.shape[1]} {f0.dtype} weights on {f0.device}, got "
+    mixed = torch.is_tensor(w) and _lpips_level_mixed(f0, w)  # 16-bit maps with an fp32 w: what autocast produces
+    if not torch.is_tensor(w) or w.numel() != f0.shape[1] or not (w.dtype == f0.dtype or mixed) or w.device != f0.device:
+        raise ValueError(f"lpips_level: w must hold C = {f0.shape[1]} {f0.dtype} weights on {f0.device}"
+                         f"{' (or float32 ones)' if f0.dtype in (torch.bfloat16, torch.float16) else ''}, got "
                          f"{getattr(w, 'dtype', type(w).__name__)} {tuple(getattr(w, 'shape', ()))}"
                          + (f" on {w.device}" if torch.is_tensor(w) else ""))
 
@@ -2772,13 +2781,26 @@ def lpips_level(f0, f1, w, eps=1e-10):
 
         u = f / (sqrt(sum_c f^2) + eps);   out[n] = mean over pixels of sum_c w[c] (u0 - u1)^2
 
-    fp32 operands on the GPU with a ``w`` that needs no gradient run ``waldo_lpips_level_fwd`` / ``_bwd``
-    (include/waldo_hip.h "LPIPS level distance"): the two maps are read, one float per image is written; no atomics --
-    the same bits from run to run; ``f1 == f0`` gives exact zeros, value and gradient; a pixel of ``f0`` that is zero on
-    every channel gets an exact 0 gradient (the framework chain: NaN from the square root's backward, which the ReLU
-    behind every LPIPS tap turns into 0 as well).  Operands that are not contiguous are made so.  Everything else (CPU,
-    fp64, 16-bit, ``w.requires_grad``) IS ``lpips_level_framework``."""
+    The kernels (include/waldo_hip.h "LPIPS level distance"): the two maps are read, one float per image is written; no
+    atomics -- the same bits from run to run; ``f1 == f0`` gives exact zeros, value and gradient; a pixel of ``f0`` that
+    is zero on every channel gets an exact 0 gradient (the framework chain: NaN from the square root's backward, which
+    the ReLU behind every LPIPS tap turns into 0 as well).  Operands that are not contiguous are made so.  The routes:
+
+    ===================================================  ===========================================================
+    fp32 maps and ``w`` on the GPU, ``w`` needs no grad  ``waldo_lpips_level_fwd`` / ``_bwd``
+    bf16 / fp16 maps with an FP32 ``w`` (what autocast   ``waldo_lpips_level_fwd_dt`` / ``_bwd_dt``: fp32 arithmetic on
+    hands over) on the GPU, ``w`` needs no grad          the widened maps; ``out`` is fp32, the gradients have the
+                                                         maps' type, rounded once (fp16: scale the loss)
+    the same maps on the CPU, or ``w.requires_grad``     ``lpips_level_framework`` on the maps widened to fp32:
+                                                         ``out`` fp32, gradients of the maps' type
+    everything else (CPU, fp64, ``w.requires_grad``,     IS ``lpips_level_framework`` in the operands' type
+    16-bit maps with a ``w`` of the SAME 16-bit type)
+    ===================================================  ==========================================================="""
     _lpips_level_check(f0, f1, w)
+    if _lpips_level_mixed(f0, w):
+        if f0.is_cuda and not w.requires_grad:
+            return _LpipsLevel.apply(float(eps), f0, f1, w.detach().reshape(-1))
+        return lpips_level_framework(f0.float(), f1.float(), w, eps)
     if f0.is_cuda and f0.dtype == torch.float32 and not w.requires_grad:
         return _LpipsLevel.apply(float(eps), f0, f1, w.detach().reshape(-1))
     return lpips_level_framework(f0, f1, w, eps)

@@ -94,10 +94,20 @@ class LPIPS(nn.Module):
     ``chunk`` image pairs go through the backbone at a time; the per-image results do not depend on it.  Always in eval
     mode with frozen parameters: gradients reach the inputs only.  A new module holds RANDOM weights (He-normal
     convolutions, non-negative lin weights) drawn from ``generator`` (a ``torch.Generator``; the global one when None):
-    ``LPIPS.load`` builds one from files."""
+    ``LPIPS.load`` builds one from files.
 
-    def __init__(self, net="vgg", fused=True, chunk=8, spatial=False, generator=None):
+    ``act_dtype`` (None, ``torch.bfloat16`` or ``torch.float16``): the backbone's activations in 16 bits.  The scaling
+    layer stays fp32, the backbone slices run under ``torch.autocast`` of that type (fp32 parameters, 16-bit taps), and
+    each tap goes -- outside the autocast region -- to ``WF.lpips_level`` with the fp32 lin weights: the 16-bit level
+    kernels (fp32 arithmetic, fp32 level sums, an fp32 result).  With ``fused=False`` the taps are widened to fp32 for
+    ``WF.lpips_level_framework``.  fp16 gradients of a mean over many pixels are small: scale the loss.  None: the fp32
+    module."""
+
+    def __init__(self, net="vgg", fused=True, chunk=8, spatial=False, generator=None, act_dtype=None):
         super().__init__()
+        if act_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError(f"LPIPS: act_dtype must be None, torch.bfloat16 or torch.float16, got {act_dtype!r}")
+        self.act_dtype = act_dtype
         if net not in NETS:
             raise ValueError(f"LPIPS: net must be one of {tuple(NETS)}, got {net!r} (the squeeze backbone is not served)")
         if spatial:
@@ -179,8 +189,13 @@ class LPIPS(nn.Module):
         total = None
         for k in range(5):
             piece = getattr(self.net, f"slice{k + 1}")
-            a, b = piece(a), piece(b)
-            d = level(a, b, self.lin(k))
+            if self.act_dtype is None:
+                a, b = piece(a), piece(b)
+                d = level(a, b, self.lin(k))
+            else:
+                with torch.autocast(in0.device.type, dtype=self.act_dtype):
+                    a, b = piece(a), piece(b)
+                d = level(a, b, self.lin(k)) if self.fused else level(a.float(), b.float(), self.lin(k))
             total = d if total is None else total + d
         return total
 

@@ -998,7 +998,7 @@ def main():
                          "colours of the object layers)")
     ap.add_argument("--eval", action="store_true",
                     help="score rec_vid and inp_pred_vid against the real frames (PSNR, SSIM, MS-SSIM from 161x161)")
-    from .evaluate import add_lpips_arguments, lpips_module
+    from .evaluate import LPIPS_DTYPES, add_lpips_arguments, lpips_module
     add_lpips_arguments(ap)  # (with --eval, and not with --packed: LPIPS takes dense clips)
     ap.add_argument("--wif-ckpt", default=None, metavar="FILE",
                     help="a reference `ii` checkpoint (state dict): run the reference's UNet (WIF.with_unet) in place of "
@@ -1049,8 +1049,8 @@ def main():
               ctx_len=args.ctx_len, seed=args.seed, raw_dtype=RAW_DTYPES[args.raw_dtype], packed=args.packed,
               eval=args.eval, out_bytes=args.out_bytes, render=args.render, palette=palette, wif_ckpt=args.wif_ckpt,
               ii_depth=args.ii_depth, ii_embed_dim=args.ii_embed_dim, unet_dtype=RAW_DTYPES[args.unet_dtype],
-              lpips=lpips_module(args.lpips_net, args.lpips_state, args.lpips_backbone, args.lpips_lin) if args.eval
-              else None)
+              lpips=lpips_module(args.lpips_net, args.lpips_state, args.lpips_backbone, args.lpips_lin,
+                                 act_dtype=LPIPS_DTYPES[args.lpips_dtype]) if args.eval else None)
     scores = res.pop("metrics", None)
     for k, v in res.items():
         print(f"{k}: {tuple(v.shape)} range [{v.min().item():.3f}, {v.max().item():.3f}] "

@@ -3,6 +3,7 @@
     python -m waldo_amd.tools.evaluate REAL FAKE VID_LENGTH VID_CONTEXT [--metrics psnr ssim msssim lpips]
                                        [--batch-size 16] [--drop-last] [--json PATH]
                                        [--lpips-net alex|vgg] [--lpips-state FILE | --lpips-backbone FILE --lpips-lin FILE]
+                                       [--lpips-dtype bf16|fp16]
 
 Step 2 of the reference's evaluation (tools/eval/metrics.py, README "Metrics").  REAL and FAKE are directories of
 clips as ``tools.io.dump_video`` writes them: one sub-directory of PNG frames, or one APNG / WebP / GIF file, per clip.
@@ -55,12 +56,16 @@ def load_batch(paths, vid_length):
     return torch.stack(clips)
 
 
-def lpips_module(net="alex", state=None, backbone=None, lin=None, device="cuda:0"):
-    """The ``LPIPS`` module of the ``--lpips-*`` arguments on ``device``, or None when no file is given."""
+LPIPS_DTYPES = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}  # --lpips-dtype
+
+
+def lpips_module(net="alex", state=None, backbone=None, lin=None, device="cuda:0", act_dtype=None):
+    """The ``LPIPS`` module of the ``--lpips-*`` arguments on ``device``, or None when no file is given.  ``act_dtype``:
+    ``LPIPS.act_dtype`` (the backbone under autocast, the 16-bit level kernels)."""
     if state is None and backbone is None and lin is None:
         return None
     from ..nets import LPIPS
-    return LPIPS.load(net, state=state, backbone=backbone, lin=lin).to(torch.device(device))
+    return LPIPS.load(net, state=state, backbone=backbone, lin=lin, act_dtype=act_dtype).to(torch.device(device))
 
 
 def evaluate(real_dir, fake_dir, vid_length, vid_context, metrics=M.METRICS, batch_size=16, drop_last=False,
@@ -102,6 +107,8 @@ def add_lpips_arguments(ap):
     ap.add_argument("--lpips-state", default=None, help="a saved lpips.LPIPS state dict")
     ap.add_argument("--lpips-backbone", default=None, help="torchvision's alexnet / vgg16 state dict (with --lpips-lin)")
     ap.add_argument("--lpips-lin", default=None, help="the lpips package's lin-layer file (with --lpips-backbone)")
+    ap.add_argument("--lpips-dtype", choices=sorted(LPIPS_DTYPES), default="fp32",
+                    help="bf16 / fp16: the LPIPS backbone under autocast and the 16-bit level kernels (LPIPS.act_dtype)")
 
 
 def main(argv=None):
@@ -121,7 +128,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.batch_size < 1:
         ap.error("--batch-size must be >= 1")
-    lpips = lpips_module(args.lpips_net, args.lpips_state, args.lpips_backbone, args.lpips_lin, args.device)
+    lpips = lpips_module(args.lpips_net, args.lpips_state, args.lpips_backbone, args.lpips_lin, args.device,
+                         act_dtype=LPIPS_DTYPES[args.lpips_dtype])
     _, summary = evaluate(args.real, args.fake, args.vid_length, args.vid_context, metrics=tuple(args.metrics),
                           batch_size=args.batch_size, drop_last=args.drop_last, device=args.device, lpips=lpips)
     if args.json:

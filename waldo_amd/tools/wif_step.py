@@ -44,7 +44,9 @@ class WifStep:
     """``clips`` clips of 5 frames resident on ``device``; ``__call__`` runs the no-grad decode, ``WIF.forward``, the
     loss and its backward once and returns the loss (the stand-in network's ``.grad`` hold the gradients).
     ``objective``: ``"sharp"``, the `sharp_vid` L1 term alone, or ``"recipe"``, `sharp_vid` + `lpips_vid` as train_wif.sh
-    trains; ``lpips``: the ``LPIPS`` module of the latter (a seeded random-weight ``LPIPS("vgg")`` when None).  After a
+    trains; ``lpips``: the ``LPIPS`` module of the latter (a seeded random-weight ``LPIPS("vgg")`` when None);
+    ``lpips_dtype``: that module's ``act_dtype`` (bf16 / fp16 backbone activations and the 16-bit level kernels; a given
+    ``lpips`` must agree with it).  After a
     call ``terms`` holds the detached terms of the loss by the reference's names.  ``opt_over``: option fields that differ
     from the recipe's (a smaller UNet: ``ii_embed_dim``, ``ii_depth``; smaller frames: ``load_dim``).  ``optimizer`` (with ``unet="reference"``): None,
     "adam", "adamw" or an ``optim.Adam`` over the UNet's parameters; the step then ends in ``optimizer.step(loss)``, and
@@ -53,7 +55,7 @@ class WifStep:
     frames, ctx_len = 5, 4
 
     def __init__(self, clips, device, seed=0, motion="calibrated", unet="stand-in", act_dtype=None, objective="sharp",
-                 lpips=None, optimizer=None, opt_over=None):
+                 lpips=None, optimizer=None, opt_over=None, lpips_dtype=None):
         if optimizer is not None and unet != "reference":
             raise ValueError("WifStep: optimizer= needs unet='reference' (the stand-in is not the network that trains)")
         if objective not in ("sharp", "recipe"):
@@ -62,6 +64,11 @@ class WifStep:
             raise ValueError("WifStep: lpips= needs objective='recipe' (the 'sharp' objective has no LPIPS term)")
         if lpips is not None and not isinstance(lpips, LPIPS):
             raise ValueError(f"WifStep: lpips must be an LPIPS module, got {type(lpips).__name__}")
+        if lpips_dtype is not None and objective != "recipe":
+            raise ValueError("WifStep: lpips_dtype= needs objective='recipe' (the 'sharp' objective has no LPIPS term)")
+        if lpips_dtype is not None and lpips is not None and lpips.act_dtype != lpips_dtype:
+            raise ValueError(f"WifStep: lpips_dtype={lpips_dtype} disagrees with the given module's act_dtype="
+                             f"{lpips.act_dtype}")
         if unet not in ("stand-in", "reference"):
             raise ValueError(f"WifStep: unet must be 'stand-in' or 'reference', got {unet!r}")
         if act_dtype is not None and unet != "reference":
@@ -88,7 +95,8 @@ class WifStep:
         self.objective, self.terms, self.lpips = objective, {}, None
         if objective == "recipe":
             if lpips is None:
-                lpips = LPIPS("vgg", generator=torch.Generator().manual_seed(seed))  # (no global generator is touched)
+                # (no global generator is touched; a bad lpips_dtype is LPIPS's ValueError)
+                lpips = LPIPS("vgg", generator=torch.Generator().manual_seed(seed), act_dtype=lpips_dtype)
             self.lpips = lpips.to(device)
 
     def decode(self):
